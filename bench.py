@@ -14,13 +14,17 @@ N>1: one process per GPU, one sample per rank (weak scaling), RCCL all-reduce of
     the worst child status.  `--share-gpu` lets the ranks share devices when the box has fewer than N (gloo instead of
     RCCL, which refuses two ranks on one device): a functional check of the N>1 path, not a scaling number.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run
+sets up, warms up, times --steps steps and prints that line; `--dump-outputs DIR` also writes what the last timed step computed as
+DIR/<name>.npy.  `--full` adds what takes runs or processes of its own:
+  "also":           the other BASELINE configurations, each with its own timed region (configs[2] / configs[4] at N=1, configs[3] at N>1)
   "roofline":       dominant kernel (by summed time in the timed region), measured live with HIP events on the launch stream; its
                     `traffic` from the newest committed PMC capture of the same configuration (scripts/round_profile.sh ->
                     profiles/rNN*_pmc_traffic{,_bf16_b8,_infer_f16}.json), read bytes from the request-size counters
   "step_rooflines": SURVEY 8(d)'s algorithmic FLOPs / bytes of the whole step over the measured step time, and the HBM bytes all
                     kernels of a step moved in that capture over the algorithmic bytes (wasted-traffic ratio)
   "cpu_baseline":   the oracle's identical 128^3 step on the host cores (rank 0, N=1 only)
+  "oracle_agreement": the engine's first step next to that oracle step from the same weights and draws
 """
 import argparse
 import json
@@ -301,6 +305,28 @@ def active_overrides():
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith('BTS_') and not k.startswith('BTS_BENCH_')}
 
 
+DUMP_SAMPLE = 1 << 22      # --dump-outputs: an output of more elements is written as its values at this many fixed (seeded) positions
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per output of the timed path's last step, flattened, float32 (float64 where the output is
+    float64 or a host scalar).  Positions of a sampled output depend only on its size, so two builds compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        if isinstance(v, float):
+            np.save(os.path.join(dirname, name + '.npy'), np.array([v], dtype=np.float64))
+            continue
+        t = v.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(1234)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(dirname, name + '.npy'), t.cpu().numpy())
+
+
 def _free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -364,10 +390,10 @@ INFER_ALGORITHMIC_GFLOP = 3984.7   # 160x192x160 forward without th
 INFER_ALGORITHMIC_GB = {'f16': 8.7, 'bf16': 8.7, 'f32': 17.25}   # 8.55 GB of 16-bit activations + 149 MB weights
 
 
-def measure_infer(args, world, rank, dev, overrides, dtype=None, shape=None, batch=None, steps=None, warmup=None):
+def measure_infer(args, world, rank, dev, overrides, dtype=None, shape=None, batch=None, steps=None, warmup=None, dump=None):
     """BASELINE configs[4]: 2ch x 155x190x147 zero-padded to 160x192x160 (test.py:164-178), inference=True (VAE skipped,
     model.py:67-68), CLI-default model, batch 1 per GPU.  A step = one forward.  N > 1: independent replicas (the path has no
-    exchange step).  Returns the result dict on rank 0 (None elsewhere)."""
+    exchange step).  `dump`: directory for the last forward's output (rank 0).  Returns the result dict on rank 0 (None elsewhere)."""
     import torch
     from bts_amd import lowp, ops, parallel
     from bts_amd.model import Model
@@ -417,10 +443,12 @@ def measure_infer(args, world, rank, dev, overrides, dtype=None, shape=None, bat
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         torch.distributed.all_reduce(one, op=torch.distributed.ReduceOp.SUM)
         dts, ranks_seen = float(tt.item()), int(round(float(one.item())))
+    if dump and rank == 0:
+        dump_outputs(dump, {'y_pred': y})
     # per-kernel pass AFTER the timed region (the HIP-event hooks cost a few percent of a 7-ms forward): `roofline` / `kernel_breakdown`
     prof = None
     prof_steps = min(steps, 5)
-    if not args.no_profile and rank == 0:
+    if args.full and not args.no_profile and rank == 0:
         ops.enable_side_streams(False)      # (one stream: a launch that shares the chip with the gate stream has no duration of its own)
         y = fwd()
         torch.cuda.synchronize()
@@ -449,7 +477,7 @@ def measure_infer(args, world, rank, dev, overrides, dtype=None, shape=None, bat
                    'parallelism': 'replicas%d' % world},
         'y_pred_mean': float(y.mean()),
     }
-    if canonical:      # whole-forward rooflines (SURVEY 8d figures): both terms, the larger one bounds the forward
+    if canonical and args.full:      # whole-forward rooflines (SURVEY 8d figures): both terms, the larger one bounds the forward
         out['forward_rooflines'] = {
             'algorithmic_gflop': INFER_ALGORITHMIC_GFLOP, 'algorithmic_gb': INFER_ALGORITHMIC_GB[dt],
             'mfma_frac': INFER_ALGORITHMIC_GFLOP / 1e3 / sec / (PEAK_F32_MFMA_TFLOPS if dt == 'f32' else PEAK_F16_MFMA_TFLOPS),
@@ -523,9 +551,11 @@ def _roofline_from_records(prof, steps_p, dt_p, traffic_of, measured):
     return {'roofline': roof, 'kernel_breakdown': brk}
 
 
-def measure_train(args, world, rank, dev, overrides, dtype=None, batch=None, steps=None, warmup=None, shared=None, agreement_dir=None):
+def measure_train(args, world, rank, dev, overrides, dtype=None, batch=None, steps=None, warmup=None, shared=None, agreement_dir=None,
+                  dump=None):
     """one training configuration -> result dict on rank 0 (None elsewhere).  dtype f32: BASELINE configs[1] (the headline);
-    bf16 / f16: the 16-bit STORAGE step of BASELINE configs[2] (bts_amd.lowp_train)."""
+    bf16 / f16: the 16-bit STORAGE step of BASELINE configs[2] (bts_amd.lowp_train).  `dump`: directory for what the last timed
+    step computed (rank 0): loss, Dice, label map and the updated parameters."""
     import torch
     from bts_amd import ops, parallel
     from bts_amd.data import synthetic_batch
@@ -617,12 +647,15 @@ def measure_train(args, world, rank, dev, overrides, dtype=None, batch=None, ste
         torch.distributed.all_reduce(one, op=torch.distributed.ReduceOp.SUM)
         dt = float(tt.item())
         ranks_seen = int(round(float(one.item())))
+    if dump and rank == 0:
+        dump_outputs(dump, {'loss': float(loss), 'macro_dice': float(macro), 'micro_dice': float(micro), 'labels': dice_fn.last_labels,
+                            'params': torch.cat([p.t.detach().reshape(-1).float() for p in model.trainable_variables])})
     # Per-kernel pass, after the timed region: the step runs its weight gradients and gate branches on side streams, so inside
     # the timed region a kernel shares the chip with other streams' kernels and the HIP events around its launch measure that
     # sharing, not the kernel.  Launch durations (the `roofline` object, `kernel_breakdown`) are therefore taken from PROF_STEPS
     # further steps of the same workload on ONE stream, HIP events on the launch stream around every conv / weight-gradient launch
     # (`bench.py --serial-streams` under rocprofv3 is the capture these averages must agree with).
-    do_prof = (not args.no_profile) and rank == 0
+    do_prof = args.full and (not args.no_profile) and rank == 0
     prof = None
     prof_steps = min(steps, 5)
     loss_v, macro_v = float(loss), float(macro)
@@ -673,7 +706,7 @@ def measure_train(args, world, rank, dev, overrides, dtype=None, batch=None, ste
     if overrides:
         out['overrides'] = overrides
     sfx = '' if (tdt == 'f32' and nb == 1) else ('_%s_b%d' % (tdt, nb))
-    if args.crop == 128:
+    if args.full and args.crop == 128:
         out['step_rooflines'] = step_rooflines(TRAIN_ALGORITHMIC_TFLOP_PER_VOLUME * nb, TRAIN_ALGORITHMIC_GB_PER_VOLUME[tdt] * nb,
                                                dt / steps, tdt, sfx)
     if do_prof and prof:
@@ -737,7 +770,7 @@ def _sig(v, n=5):
 def _compact(out, top):
     """the printed form of one result: the contract keys and `roofline` unchanged in meaning, `kernel_breakdown` cut to the `top`
     kernels by time (ms, executed fraction of the matrix peak, HBM fraction, bound), the counter read-outs behind `traffic`, the
-    per-step byte sums and the long notes left to the detail file (gpurun_out/bench_detail.json, same content as round 4's line)"""
+    per-step byte sums and the long notes left to the detail file (--detail-file, same content as round 4's line)"""
     c = {k: v for k, v in out.items() if k not in ('kernel_breakdown', 'also', 'overrides_note')}
     if 'roofline' in c:
         r = dict(c['roofline'])
@@ -785,9 +818,15 @@ def main():
     ap.add_argument('--dtype', default=None, help="storage type: training f32 (default) | bf16 | f16; --infer f16 (default) | bf16 | f32")
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--agreement-dir', default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the other BASELINE configurations ("also"), the per-kernel pass (roofline, kernel_breakdown), '
+                         'step_rooflines, the CPU baseline and the oracle agreement; a plain run times the headline only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)')
     ap.add_argument('--full-line', action='store_true',
-                    help='print the complete record (every kernel, counter read-outs, notes) instead of the tail-safe compact line; '
-                         'the complete record is always written to gpurun_out/bench_detail.json')
+                    help='print the complete record (every kernel, counter read-outs, notes) instead of the tail-safe compact line')
+    ap.add_argument('--detail-file', default=os.path.join(ROOT, 'bench_detail.json'),
+                    help='--full: where the complete record is written as JSON (default: bench_detail.json in the repository root)')
     args = ap.parse_args()
     if args.cpu_baseline_worker:
         _cpu_baseline_worker(args.crop, args.agreement_dir)
@@ -826,15 +865,15 @@ def main():
     import tempfile
     agreement_dir = None
     if args.infer:
-        out = measure_infer(args, world, rank, dev, overrides)
+        out = measure_infer(args, world, rank, dev, overrides, dump=args.dump_outputs)
     else:
         headline = args.dtype in (None, 'f32', 'fp32', 'float32') and args.batch == 1 and args.crop == 128
-        want_cpu = world == 1 and not parallel.active() and not args.no_cpu_baseline
+        want_cpu = args.full and world == 1 and not parallel.active() and not args.no_cpu_baseline
         if want_cpu and args.dtype in (None, 'f32', 'fp32', 'float32') and args.batch == 1 and args.cpu_baseline_crop == args.crop:
             agreement_dir = tempfile.mkdtemp(prefix='bts_bench_')
-        out = measure_train(args, world, rank, dev, overrides, shared=shared, agreement_dir=agreement_dir)
+        out = measure_train(args, world, rank, dev, overrides, shared=shared, agreement_dir=agreement_dir, dump=args.dump_outputs)
         first = out.pop('_first_step', None) if out is not None else None
-        if headline and world == 1 and not parallel.active() and not args.no_also and out is not None:
+        if args.full and headline and world == 1 and not parallel.active() and not args.no_also and out is not None:
             # The two secondary BASELINE configurations, measured in this same process right after the (untouched) headline and
             # nested under "also": driver-witnessed numbers for the 16-bit engine.  Each is its own workload with its own timed
             # region (warm-up, then steps bracketed by synchronize); none of it is inside the headline's timed region.
@@ -853,7 +892,7 @@ def main():
             except Exception as e:   # the headline stands on its own; a failure here is reported, not hidden
                 also['error'] = '%s: %s' % (type(e).__name__, str(e)[:300])
             out['also'] = also
-        if world > 1 and args.dtype in (None, 'f32', 'fp32', 'float32') and args.batch == 1 and not args.no_also:
+        if args.full and world > 1 and args.dtype in (None, 'f32', 'fp32', 'float32') and args.batch == 1 and not args.no_also:
             # N > 1 (the driver's scaling run: `bench.py --gpus N` with its default arguments): after the fp32 weak-scaling headline, whose
             # N = 1 value is the single-GPU line, BASELINE configs[3] itself -- configs[2]'s step (bf16 storage, batch 8 per GPU) on every
             # rank with the gradient buckets all-reduced from inside the backward -- nested under "also" with its own `ranks_seen`,
@@ -870,7 +909,7 @@ def main():
                 also['error'] = '%s: %s' % (type(e).__name__, str(e)[:300])
             if out is not None:
                 out['also'] = also
-        if world == 1 and not args.no_cpu_baseline and out is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and out is not None:
             out['cpu_baseline'] = cpu_baseline(args.cpu_baseline_crop, agreement_dir=agreement_dir)
             if agreement_dir:
                 try:
@@ -895,13 +934,14 @@ def main():
         full = dict(out)
         full['summary'] = summary
         detail = None
-        try:       # the complete record (what round 4 printed) goes to a file; gpurun merges gpurun_out/ back
-            os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
-            detail = os.path.join('gpurun_out', 'bench_detail.json')
-            with open(os.path.join(ROOT, detail), 'w') as f:
-                json.dump(full, f)
-        except OSError:
-            detail = None
+        if args.full:
+            try:       # the complete record (what round 4 printed) goes to a file
+                detail = os.path.relpath(os.path.abspath(args.detail_file), ROOT)
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail_file)), exist_ok=True)
+                with open(args.detail_file, 'w') as f:
+                    json.dump(full, f)
+            except OSError:
+                detail = None
         if args.full_line:
             line = full
         else:
@@ -918,7 +958,8 @@ def main():
                             (v.get('roofline') or {}).pop(k, None)
             if isinstance(line.get('oracle_agreement'), dict):
                 line['oracle_agreement'] = {k: v for k, v in line['oracle_agreement'].items() if k != 'what'}
-            line['detail'] = detail
+            if args.full:
+                line['detail'] = detail
             line['summary'] = summary
             line = _sig(line)
         print(json.dumps(line), flush=True)

@@ -15,7 +15,7 @@ O=$R/gpurun_out
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 
-python3 "$R/bench.py" --steps 10 --warmup 3 > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
+python3 "$R/bench.py" --full --detail-file "$O/bench_detail.json" --steps 10 --warmup 3 > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
 test -s "$O/${TAG}_bench.json" || { echo "bench.py printed nothing"; tail -5 "$O/${TAG}_bench.err"; exit 1; }
 cut -c1-400 "$O/${TAG}_bench.json"
 cp "$O/bench_detail.json" "$O/${TAG}_bench_detail.json"     # the complete record behind the compact line (every kernel, counter read-outs)
@@ -41,9 +41,9 @@ cp "$(need "$O/prof_${TAG}_ms" bench_kernel_stats.csv)" "$O/${TAG}_bench_multist
 
 # the 16-bit configurations (BASELINE configs[2]: bf16 storage, batch 8; configs[4]: fp16 full-volume inference): their own bench
 # lines and one-stream kernel tables
-python3 "$R/bench.py" --dtype bf16 --batch 8 --steps 5 --warmup 2 --no-cpu-baseline --no-also > "$O/${TAG}_train_bf16_b8.json" 2> "$O/${TAG}_train_bf16_b8.err"
+python3 "$R/bench.py" --full --dtype bf16 --batch 8 --steps 5 --warmup 2 --no-cpu-baseline --no-also > "$O/${TAG}_train_bf16_b8.json" 2> "$O/${TAG}_train_bf16_b8.err"
 cut -c1-300 "$O/${TAG}_train_bf16_b8.json"
-python3 "$R/bench.py" --infer --dtype f16 --steps 10 --warmup 3 --no-cpu-baseline --no-also > "$O/${TAG}_infer_f16.json" 2> "$O/${TAG}_infer_f16.err"
+python3 "$R/bench.py" --full --infer --dtype f16 --steps 10 --warmup 3 --no-cpu-baseline --no-also > "$O/${TAG}_infer_f16.json" 2> "$O/${TAG}_infer_f16.err"
 cut -c1-300 "$O/${TAG}_infer_f16.json"
 rm -rf "$O/prof_${TAG}_bf16"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_${TAG}_bf16" -o bench -- \

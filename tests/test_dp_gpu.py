@@ -126,7 +126,8 @@ def test_bench_launcher_starts_the_ranks(tmp_path):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--share-gpu', '--crop', '32',
-                        '--steps', '2', '--warmup', '1', '--no-cpu-baseline'], env=env, cwd=ROOT, capture_output=True,
+                        '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--full',
+                        '--detail-file', str(tmp_path / 'bench_detail.json')], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]

@@ -293,3 +293,25 @@ def test_pmc_aggregate_takes_the_last_full_step(tmp_path):
     steady = (128.0 * (30 + 100 + 10) * 8.0) + (30 + 100 + 10) / 4.0 * kib        # request-counter reads + WRITE_SIZE writes of one step
     assert abs(sr['measured_hbm_gb_per_step'] * 1e9 - steady) < 1e-3 * steady, (sr, steady)
     assert sr['outside_the_step_loop_gb'] > 0
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path):
+    """bench.py --dump-outputs: one <name>.npy per output, float32 (float64 for host scalars / fp64 tensors); an output larger than
+    DUMP_SAMPLE is written at fixed positions, the same in every run"""
+    import importlib.util
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod3', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    arrays = {'loss': 1.25, 'labels': torch.tensor([[0, 1], [2, 3]], dtype=torch.uint8), 'params': big}
+    bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    loss, labels, params = (np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in ('loss', 'labels', 'params'))
+    assert loss.dtype == np.float64 and loss.tolist() == [1.25]
+    assert labels.dtype == np.float32 and labels.tolist() == [0, 1, 2, 3]
+    assert params.dtype == np.float32 and params.size == bench.DUMP_SAMPLE and np.all(np.diff(params) >= 0)
+    assert np.array_equal(params, np.load(str(tmp_path / 'b' / 'params.npy')))
+    r = _bench(['--help'], {})
+    assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout

@@ -22,9 +22,29 @@ def _global_reference(cfg, P, x, y, mask, eps):
     return loss.detach(), torch.cat([t.reshape(-1) for t in g])
 
 
+def _local_rank(rank):
+    """the device parallel.init_from_env binds where a GPU is visible: the ranks share the devices there are (the compute here is torch-CPU,
+    and a box with one GPU has no device 1)"""
+    return str(rank % max(1, torch.cuda.device_count()))
+
+
+def _get(q, procs, timeout):
+    """the next result of the workers; fails at once when a worker has exited without delivering one"""
+    import queue
+    import time
+    end = time.time() + timeout
+    while True:
+        try:
+            return q.get(timeout=2)
+        except queue.Empty:
+            assert all(p.exitcode in (None, 0) for p in procs), 'worker exit codes %s' % [p.exitcode for p in procs]
+            if time.time() > end:
+                raise
+
+
 def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=_local_rank(rank))
     import bts_amd  # noqa: F401
     from bts_amd import parallel
     from oracle import torch_ref as R
@@ -72,7 +92,7 @@ def test_two_rank_data_parallel_equals_global_batch():
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    res = q.get(timeout=600)
+    res = _get(q, procs, 600)
     for p in procs:
         p.join(timeout=600)
         assert p.exitcode == 0
@@ -86,7 +106,7 @@ def _ckpt_worker(rank, world, port, folder, q):
     back its own augmentation generator and its own dropout / reparameterisation counters (all ranks used to
     resume with rank 0's)"""
     sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=_local_rank(rank))
     import bts_amd  # noqa: F401
     from bts_amd import data as D, parallel, train as T
     from bts_amd.model import Model
@@ -122,7 +142,7 @@ def test_checkpoint_keeps_per_rank_random_state(tmp_path):
     procs = [ctx.Process(target=_ckpt_worker, args=(r, 2, port, str(tmp_path), q)) for r in range(2)]
     for p in procs:
         p.start()
-    res = sorted(q.get(timeout=300) for _ in range(2))
+    res = sorted(_get(q, procs, 300) for _ in range(2))
     for p in procs:
         p.join(timeout=300)
         assert p.exitcode == 0
@@ -134,7 +154,7 @@ def _fit_worker(rank, world, port, folder, q):
     """fit() with a metric that is NOT all-reduced (rank 1 sees a worse validation Dice) and a save_folder on rank 0 only: the
     round-3 advisor's hang.  Both ranks must take rank 0's save / stop decisions and finish"""
     sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=_local_rank(rank))
     import bts_amd  # noqa: F401
     from bts_amd import parallel, train as T
     from bts_amd.model import Model
@@ -172,7 +192,7 @@ def test_fit_takes_rank_identical_save_and_stop_decisions(tmp_path):
     procs = [ctx.Process(target=_fit_worker, args=(r, 2, port, str(tmp_path), q)) for r in range(2)]
     for p in procs:
         p.start()
-    res = sorted(q.get(timeout=300) for _ in range(2))
+    res = sorted(_get(q, procs, 300) for _ in range(2))
     for p in procs:
         p.join(timeout=300)
         assert p.exitcode == 0

@@ -1,5 +1,6 @@
-"""CPU, build container only: the REFERENCE's own Python (model.py, layers/*.py, util.py under /root/reference) imported over the
-`tensorflow` stand-in of oracle/tf_standin and run against oracle/torch_ref.py (round-3 verdict, item 8).
+"""CPU: the REFERENCE's own Python (model.py, layers/*.py, util.py) against oracle/torch_ref.py (round-3 verdict, item 8), through what
+it computed when imported over the `tensorflow` stand-in of oracle/tf_standin: tests/golden/ref_wiring_*.npz, recorded by
+tests/golden/make_ref_wiring.py from a checkout of the reference (see its header).
 
 What this checks: the restatement's WIRING -- block / level / concat order (encoder.py:69-101 incl. the duplicated dense concat,
 decoder.py:65-83, vae.py:114-143), the GroupNormalization reshape sequence as written (group_norm.py:83-124: the channels_last
@@ -8,22 +9,20 @@ regulariser (sum(model.losses), train.py:146), the Keras tracking order of the v
 promises (vae.unproj last), the learning-rate schedule and one Adam step.  What it does NOT check: TensorFlow's arithmetic -- the
 stand-in's primitives are this repository's reading of it (conv / transposed-conv literally the oracle's).  Parity stays UNPINNED.
 
-Skipped where /root/reference does not exist (the GPU box)."""
-import importlib
+The recorded gradients are kept as three seeded projections and the largest magnitude per variable (the full tensors would not be
+small): a gradient within 1e-9 of the reference's elementwise meets both, so the bounds below are necessary conditions of that one.
+The checks execute in a CHILD interpreter (minimal environment, read-only scratch working directory) started by
+test_reference_wiring_in_a_child_process, so that they see nothing but the repository; in the parent they are skipped."""
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
-HAVE_REF = os.path.exists(os.path.join(REF, 'model.py'))
-# /root/reference is untrusted public content: its import-time code never runs inside the pytest process that runs the other tests.
-# The checks below execute in a CHILD interpreter (minimal environment, read-only scratch working directory) started by
-# test_reference_wiring_in_a_child_process; in the parent they are skipped.
+GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 IN_CHILD = os.environ.get('BTS_REF_WIRING_CHILD') == '1'
-pytestmark = pytest.mark.skipif(not HAVE_REF, reason='the reference is mounted in the build container only')
 child_only = pytest.mark.skipif(not IN_CHILD, reason='runs in the child process of test_reference_wiring_in_a_child_process')
 
 
@@ -47,126 +46,143 @@ def test_reference_wiring_in_a_child_process():
         os.rmdir(scratch)
 
 
-@pytest.fixture(scope='module')
-def ref():
-    """the reference's modules, imported over the stand-in; sys.path / sys.modules are restored afterwards"""
-    saved_path, saved_mods = list(sys.path), dict(sys.modules)
-    for k in [k for k in sys.modules if k == 'tensorflow' or k.startswith('tensorflow.') or k in ('model', 'util', 'layers') or k.startswith('layers.')]:
-        del sys.modules[k]
-    sys.path.insert(0, os.path.join(ROOT, 'oracle', 'tf_standin'))
-    sys.path.insert(0, REF)
-    try:
-        tf = importlib.import_module('tensorflow')
-        assert 'STAND-IN' in (tf.__doc__ or ''), 'a real tensorflow is importable: this test is for images without one'
-        mods = {'tf': tf, 'model': importlib.import_module('model'), 'util': importlib.import_module('util')}
-        assert mods['model'].__file__.startswith(REF) and mods['util'].__file__.startswith(REF)
-        yield mods
-    finally:
-        for k in [k for k in sys.modules if k not in saved_mods]:
-            del sys.modules[k]
-        sys.modules.update(saved_mods)      # (the product's own `layers` / `model` packages live under bts_amd.*, never under these names)
-        sys.path[:] = saved_path
-
-
 CASES = [
     dict(base_filters=4, groups=2, reduction=2, depth=2),                                         # SURVEY 8c "micro"
     dict(base_filters=8, groups=4, reduction=2, depth=3),                                         # dense concat of three blocks
     dict(base_filters=8, groups=4, reduction=2, depth=3, data_format='channels_first'),           # true channel groups, per-class Dice
     dict(base_filters=8, groups=4, reduction=2, depth=3, downsampling='max', upsampling='linear'),
 ]
+N_PROJ = 3
+
+
+def case_id(kw):
+    return '-'.join('%s' % v for v in kw.values())
+
+
+def fixture_path(kw):
+    return os.path.join(GOLDEN, 'ref_wiring_%s.npz' % case_id(kw).replace('_', ''))
+
+
+def case_inputs(kw):
+    """the volume, labels, dropout mask and eps of one case (channels_first: permuted to NCDHW), fp64"""
+    from oracle import torch_ref as R
+    cfg = R.default_config(**kw)
+    crop = (8, 8, 8) if cfg['depth'] == 2 else (16, 16, 16)
+    latent = cfg['base_filters'] * 2 ** (cfg['depth'] - 2)
+    x, y, mask, eps = R.synthetic_batch(2, crop, latent=latent, seed=21, dtype=torch.float64)
+    if cfg['data_format'] == 'channels_first':
+        x, y, mask = (t.permute(0, 4, 1, 2, 3).contiguous() for t in (x, y, mask))
+    return cfg, crop, x, y, mask, eps
+
+
+def draw_values(names, shapes):
+    """the value of every variable, in tracking order: gamma ~ 1 + N(0, 0.25), beta ~ N(0, 0.25) (gamma_2 = 0 at init would hide every
+    block's conv branch), kernels ~ N(0, 1 / fan_in), biases ~ N(0, 0.01)"""
+    g = torch.Generator().manual_seed(5)
+    out = []
+    for name, shape in zip(names, shapes):
+        t = torch.randn(tuple(shape), dtype=torch.float64, generator=g)
+        if name == 'gamma':
+            t = t * 0.5 + 1.0
+        elif name == 'beta':
+            t = t * 0.5
+        elif len(shape) >= 2:
+            t = t / float(np.prod(shape[:-1])) ** 0.5
+        else:
+            t = t * 0.1
+        out.append(t)
+    return out
+
+
+def projections(i, numel):
+    """the N_PROJ fixed vectors the gradient of variable i is projected on"""
+    g = torch.Generator().manual_seed(1000 + i)
+    return torch.randn((N_PROJ, numel), dtype=torch.float64, generator=g)
+
+
+def load_case(kw):
+    z = np.load(fixture_path(kw))
+    nd = z['var_ndim']
+    flat = list(z['var_shape_flat'])
+    shapes, k = [], 0
+    for n in nd:
+        shapes.append(tuple(int(v) for v in flat[k:k + n]))
+        k += n
+    return z, [str(s) for s in z['var_names']], shapes
 
 
 @child_only
-@pytest.mark.parametrize('kw', CASES, ids=lambda k: '-'.join('%s' % v for v in k.values()))
-def test_reference_python_on_the_standin_equals_the_oracle(ref, kw):
+@pytest.mark.parametrize('kw', CASES, ids=case_id)
+def test_reference_python_on_the_standin_equals_the_oracle(kw):
     import bts_amd  # noqa: F401
     from bts_amd.model import Model as ProductModel
     from oracle import torch_ref as R
-    tf = ref['tf']
-    cfg = R.default_config(**kw)
-    cf = cfg['data_format'] == 'channels_first'
-    crop = (8, 8, 8) if cfg['depth'] == 2 else (16, 16, 16)
-    n = 2
-    latent = cfg['base_filters'] * 2 ** (cfg['depth'] - 2)
-    x, y, mask, eps = R.synthetic_batch(n, crop, latent=latent, seed=21, dtype=torch.float64)
-    if cf:
-        x, y, mask = (t.permute(0, 4, 1, 2, 3).contiguous() for t in (x, y, mask))
-    # ---- the reference's Model, built the way train.py:94-96 does: one call on zeros ----
-    tf.INJECT['gen'].manual_seed(5)
-    tf.INJECT['dropout_mask'] = tf.INJECT['eps'] = None
-    rm = ref['model'].Model(**kw)
-    rm(torch.zeros_like(x))
-    rvars = rm.trainable_variables
-    for w in rvars:                      # gamma_2 = 0 at init hides every block's conv branch (SURVEY F6): randomise the norms
-        if w._standin['name'] in ('gamma', 'beta'):
-            with torch.no_grad():
-                w.copy_(torch.randn(w.shape, dtype=torch.float64, generator=tf.INJECT['gen']) * 0.5 + (1.0 if w._standin['name'] == 'gamma' else 0.0))
+    z, rnames, rshapes = load_case(kw)
+    cfg, crop, x, y, mask, eps = case_inputs(kw)
+    n = x.shape[0]
+    rvals = draw_values(rnames, rshapes)
     # ---- variable order: what the product promises for Model.get_weights() (Keras tracking order) ----
     pm = ProductModel(**kw)
     pm.build((n,) + crop + (2,))        # (the engine's memory is NDHWC whatever the public layout)
     pvars = pm.trainable_variables
-    assert len(pvars) == len(rvars), (len(pvars), len(rvars))
+    assert len(pvars) == len(rshapes), (len(pvars), len(rshapes))
     P = R.ParamSet()
     ref_l2 = R.build_params(cfg, crop, seed=0).l2
-    for pv, rv in zip(pvars, rvars):
-        assert tuple(pv.t.shape) == tuple(rv.shape), (pv.name, tuple(pv.t.shape), tuple(rv.shape))
-        P[pm.oracle_name(pv)] = rv.detach().clone()
+    for pv, shape, val in zip(pvars, rshapes, rvals):
+        assert tuple(pv.t.shape) == shape, (pv.name, tuple(pv.t.shape), shape)
+        P[pm.oracle_name(pv)] = val.clone()
     P.l2.update(ref_l2)
     assert set(P) == set(ref_l2), set(P) ^ set(ref_l2)
     last = [pm.oracle_name(v) for v in pvars[-2:]]
     assert last == ['vae/unproj_k', 'vae/unproj_b'], last            # vae.py:105: created in build(), tracked last
     # ---- forward, training mode, identical draws ----
-    tf.INJECT['dropout_mask'], tf.INJECT['eps'] = mask, eps
-    yp_r, yv_r, zm_r, zl_r = rm(x, training=True, inference=False)
     yp_o, yv_o, zm_o, zl_o = R.model(x, P, cfg, training=True, inference=False, mask=mask, eps=eps)
-    for a, b, name in ((yp_r, yp_o, 'y_pred'), (yv_r, yv_o, 'y_vae'), (zm_r, zm_o, 'z_mean'), (zl_r, zl_o, 'z_logvar')):
+    for b, name in ((yp_o, 'y_pred'), (yv_o, 'y_vae'), (zm_o, 'z_mean'), (zl_o, 'z_logvar')):
+        a = torch.from_numpy(z[name])
         assert tuple(a.shape) == tuple(b.shape), name
-        a, b = a.detach(), b.detach()
+        b = b.detach()
         assert float((a - b).abs().max()) <= 1e-10 * max(1.0, float(b.abs().max())), (name, float((a - b).abs().max()))
     # ---- loss (util.py:13-24), regularisers (train.py:146), metric (util.py:35-57) ----
     df = cfg['data_format']
-    loss_r = ref['util'].DiceVAELoss(data_format=df)(x, y, yp_r, yv_r, zm_r, zl_r)
-    reg_r = sum(rm.losses)
-    loss_o = R.dice_vae_loss(x, y, yp_o, yv_o, zm_o, zl_o, data_format=df)
-    reg_o = R.l2_regularisation(P)
-    assert abs(float(loss_r.detach()) - float(loss_o.detach())) <= 1e-12 * max(1.0, abs(float(loss_o.detach())))
-    assert abs(float(reg_r.detach()) - float(reg_o.detach())) <= 1e-12 * max(1e-6, abs(float(reg_o.detach()))), (float(reg_r.detach()), float(reg_o.detach()))
-    mac_r, mic_r = ref['util'].DiceCoefficient(data_format=df)(y, yp_r.detach())
+    loss_r, reg_r, mac_r, mic_r = (float(z[k]) for k in ('loss', 'reg', 'macro', 'micro'))
+    loss_o = float(R.dice_vae_loss(x, y, yp_o, yv_o, zm_o, zl_o, data_format=df).detach())
+    reg_o = float(R.l2_regularisation(P).detach())
+    assert abs(loss_r - loss_o) <= 1e-12 * max(1.0, abs(loss_o))
+    assert abs(reg_r - reg_o) <= 1e-12 * max(1e-6, abs(reg_o)), (reg_r, reg_o)
     mac_o, mic_o, _ = R.dice_coefficient(y, yp_o.detach(), data_format=df)
-    assert abs(float(mac_r) - float(mac_o)) <= 1e-12 and abs(float(mic_r) - float(mic_o)) <= 1e-12
+    assert abs(mac_r - float(mac_o)) <= 1e-12 and abs(mic_r - float(mic_o)) <= 1e-12
     # ---- gradients of the reference's graph (torch autograd through the stand-in) against the oracle's ----
-    g_r = torch.autograd.grad(loss_r + reg_r, rvars)
     leaves = R.ParamSet()
     leaves.update({k: v.clone().requires_grad_(True) for k, v in P.items()})
     leaves.l2 = P.l2
     out = R.model(x, leaves, cfg, training=True, inference=False, mask=mask, eps=eps)
     g_o = torch.autograd.grad(R.dice_vae_loss(x, y, *out, data_format=df) + R.l2_regularisation(leaves), [leaves[pm.oracle_name(v)] for v in pvars])
-    for pv, a, b in zip(pvars, g_r, g_o):
-        assert float((a - b).abs().max()) <= 1e-9 * max(1e-9, float(b.abs().max())), pv.name
+    for i, (pv, b) in enumerate(zip(pvars, g_o)):
+        # (floor 1e-15: a gradient that is zero in exact arithmetic -- a bias ahead of a GroupNorm -- is left with ~1e-17 of
+        # rounding, which differs between the machine that recorded the file and this one)
+        tol = 1e-9 * max(1e-6, float(b.abs().max()))
+        r = projections(i, b.numel())
+        assert np.all(np.abs(z['grad_proj'][i] - (r @ b.reshape(-1)).numpy()) <= tol * r.abs().sum(dim=1).numpy()), pv.name
+        assert abs(float(z['grad_absmax'][i]) - float(b.abs().max())) <= tol, pv.name
     # ---- inference mode: VAE branch skipped (model.py:63-68) ----
-    out_inf = rm(x, training=False, inference=True)
-    assert out_inf[1] is None and out_inf[2] is None and out_inf[3] is None
+    assert bool(z['inference_vae_outputs_none'])
     yp_inf = R.model(x, P, cfg, training=False, inference=True)[0]
-    assert float((out_inf[0].detach() - yp_inf.detach()).abs().max()) <= 1e-10
-    with pytest.raises(AssertionError):
-        rm(x, training=True, inference=True)
+    assert float((torch.from_numpy(z['y_pred_inference']) - yp_inf.detach()).abs().max()) <= 1e-10
+    assert bool(z['training_and_inference_raises'])
 
 
 @child_only
-def test_reference_schedule_and_adam_step_equal_the_oracle(ref):
+def test_reference_schedule_and_adam_step_equal_the_oracle():
     """util.py:60-84: ScheduledOptim.__call__(epoch) and one apply_gradients against oracle.scheduled_lr / adam_tf_step"""
     from oracle import torch_ref as R
-    opt = ref['util'].ScheduledOptim(learning_rate=1e-4)
-    for epoch in (0, 1, 150, 299):
-        opt(epoch=epoch)
-        assert abs(float(opt._get_hyper('learning_rate')) - R.scheduled_lr(1e-4, epoch)) <= 1e-18
+    z = np.load(os.path.join(GOLDEN, 'ref_wiring_adam.npz'))
+    for epoch, lr_r in zip(z['epochs'], z['lr']):
+        assert abs(float(lr_r) - R.scheduled_lr(1e-4, int(epoch))) <= 1e-18
     g = torch.Generator().manual_seed(3)
-    w = torch.randn(50, dtype=torch.float64, generator=g).requires_grad_(True)
+    w = torch.randn(50, dtype=torch.float64, generator=g)
     gr = torch.randn(50, dtype=torch.float64, generator=g) * torch.logspace(-8, 0, 50, dtype=torch.float64)
-    p, m, v = w.detach().clone(), torch.zeros(50, dtype=torch.float64), torch.zeros(50, dtype=torch.float64)
-    opt(epoch=3)
+    p, m, v = w.clone(), torch.zeros(50, dtype=torch.float64), torch.zeros(50, dtype=torch.float64)
     lr = R.scheduled_lr(1e-4, 3)
     for t in (1, 2, 3):
-        opt.apply_gradients([(gr, w)])
         p, m, v = R.adam_tf_step(p, gr, m, v, t, lr)
-        assert float((w.detach() - p).abs().max()) <= 1e-15
+        assert float((torch.from_numpy(z['w_after'][t - 1]) - p).abs().max()) <= 1e-15

@@ -132,7 +132,8 @@ def test_checkpoint_container_round_trip(tmp_path):
     opt = ScheduledOptim(1e-4)
     opt.iterations = 41
     opt(epoch=7)
-    mom = (torch.randn(m.flat_params.shape, generator=g), torch.rand(m.flat_params.shape, generator=g))
+    dev = m.flat_params.device          # (the Adam moments live where the parameters do: cuda:0 where a GPU is visible)
+    mom = (torch.randn(m.flat_params.shape, generator=g).to(dev), torch.rand(m.flat_params.shape, generator=g).to(dev))
     opt._state[id(m.flat_params)] = mom
     meta = T.save_checkpoint(str(tmp_path), m, opt)
     assert meta['epoch'] == 7 and meta['n_params'] == m.n_params
