@@ -73,7 +73,6 @@ struct IgemmParams {
   float* part;
   long ws_bytes, ws_need;  // host-side planning only
   int plan_only;
-  int dbg;  // profiling aid (BTS_IGEMM_DBG): 1 = skip the MFMA sweep, 2 = skip re-staging after the first stage
   // fused GroupNorm statistics of the output (slab semantics: group = z-slab of D/G planes, whole tiles per group):
   // every workgroup writes (sum, sum of squares) of its tile to gnp[((n*G+g)*gn_B + b)*2], b = tile index inside the group
   double* gnp;
@@ -205,10 +204,7 @@ __device__ __forceinline__ void stage_taps(const IgemmParams& p, const int* tlp,
 #define IG_TRI(MS, NS, KGS, FUSE2, FIXG) ((MS) == 2 && (NS) == 1 && (KGS) == 1 && !(FUSE2) && (FIXG))
 template <int MS, int NS, int WM, int WN, int KGS, bool FUSE2 = false, bool FIXG = false, bool T27 = false>
 __global__ __launch_bounds__(256, IG_TRI(MS, NS, KGS, FUSE2, FIXG) ? 3 : 2) void igemm_kernel(const IgemmParams p) {
-  // MS == 4 (512-voxel tile, 16 MFMAs per tap for 32-cout layers): its 59 KB halo tile is single-buffered so that two
-  // workgroups still fit a CU; the partner workgroup covers the (short) LDS refill between stages
-  constexpr int NSLOT = (MS == 4) ? 10 : MAXSLOT;
-  constexpr bool SINGLE = (MS == 4) || IG_TRI(MS, NS, KGS, FUSE2, FIXG);
+  constexpr bool SINGLE = IG_TRI(MS, NS, KGS, FUSE2, FIXG);
   constexpr int S = KGS * 8 + 4;  // dwords per staged voxel (pad 4: 16B-odd stride)
   constexpr int QPV = KGS * 2;    // float4 slots per voxel
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -242,11 +238,11 @@ __global__ __launch_bounds__(256, IG_TRI(MS, NS, KGS, FUSE2, FIXG) ? 3 : 2) void
   //      is kept per slot (-1 = zero padding); LDS offset and channel quad are recomputed from e (QPV is a constant).
   const int nslots = tileVox * QPV;
   const float* xbase = p.x + ((((long)n * p.Di + iz0) * p.Hi + iy0) * p.Wi + ix0) * (long)p.ldx;  // wave-uniform
-  int goff[NSLOT];
+  int goff[MAXSLOT];
   const int IYX = p.IY * p.IX;
   const float invIX = 1.0f / (float)p.IX, invIYX = 1.0f / (float)IYX;
 #pragma unroll
-  for (int i = 0; i < NSLOT; ++i) {
+  for (int i = 0; i < MAXSLOT; ++i) {
     const int e = tid + i * 256;
     goff[i] = -1;
     if (e < nslots) {
@@ -321,11 +317,11 @@ __global__ __launch_bounds__(256, IG_TRI(MS, NS, KGS, FUSE2, FIXG) ? 3 : 2) void
   const int nstages = (kgEnd - kgBeg + KGS - 1) / KGS;
   const bool vecin = (p.flags & IG_FLAG_VECIN) != 0;
 
-  f32x4 pre[NSLOT];
+  f32x4 pre[MAXSLOT];
   auto fetch = [&](int st) {
     const int c0 = (stBeg + st) * KGS * 8;
 #pragma unroll
-    for (int i = 0; i < NSLOT; ++i) {
+    for (int i = 0; i < MAXSLOT; ++i) {
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (goff[i] >= 0) {
         const int c = c0 + ((tid + i * 256) % QPV) * 4;
@@ -344,7 +340,7 @@ __global__ __launch_bounds__(256, IG_TRI(MS, NS, KGS, FUSE2, FIXG) ? 3 : 2) void
   };
   auto commit = [&](float* buf) {
 #pragma unroll
-    for (int i = 0; i < NSLOT; ++i) {
+    for (int i = 0; i < MAXSLOT; ++i) {
       const int e = tid + i * 256;
       if (e < nslots) *reinterpret_cast<f32x4*>(buf + (e / QPV) * S + (e % QPV) * 4) = pre[i];
     }
@@ -358,15 +354,14 @@ __global__ __launch_bounds__(256, IG_TRI(MS, NS, KGS, FUSE2, FIXG) ? 3 : 2) void
     const float* cur = SINGLE ? lds : lds + (st & 1) * bufDw;
     float* nxt = SINGLE ? lds : lds + ((st + 1) & 1) * bufDw;
     const bool more = (st + 1) < nstages;
-    if (more && BTS_DBG(p) != 2) fetch(st + 1);
+    if (more) fetch(st + 1);
 
     // k-groups of this stage x taps: fully unrolled tap sequence (tables hoisted to SGPRs), weight fragments
     // prefetched two taps ahead and input fragments one tap ahead so their latencies sit under the MFMAs
     const int kg0 = (stBeg + st) * KGS;
     int nkg = kgEnd - kg0;
     if (nkg > KGS) nkg = KGS;
-    if (BTS_DBG(p) == 1) {
-    } else if constexpr (FIXG || T27 || FUSE2) {  // 27-tap form known at compile time (fixed geometry, the fused pair, or
+    if constexpr (FIXG || T27 || FUSE2) {  // 27-tap form known at compile time (fixed geometry, the fused pair, or
       // the launcher's T27 instantiation for k3s1 / stride-2 convs): no runtime tap-count dispatch, so the accumulators
       // are not shuffled between register sets around a switch
       stage_taps<27, MS, NS, FUSE2, FIXG>(p, tlp, twp, cur, bbase, lane_woff, kg0, nkg, acc, acc2, x2row, have_x2);
@@ -382,7 +377,7 @@ __global__ __launch_bounds__(256, IG_TRI(MS, NS, KGS, FUSE2, FIXG) ? 3 : 2) void
       stage_taps<1, MS, NS>(p, tlp, twp, cur, bbase, lane_woff, kg0, nkg, acc, nullptr, x2row, false);
     }
     if (SINGLE) __syncthreads();  // every wave has finished reading the tile before it is overwritten
-    if (more && BTS_DBG(p) != 2) commit(nxt);
+    if (more) commit(nxt);
     __syncthreads();
   }
 
@@ -1070,7 +1065,7 @@ static int plan_upm(UpmParams& p, int N, int Di, int Hi, int Wi, int Cin, int Co
   p.ksplit = 1; p.kg_per = p.KG;
   if (wgs < min_wgs) {
     // too few workgroups to fill the chip: split the contraction (deterministic two-stage reduction) when it is long
-    if (p.KG < 8 || getenv("BTS_IGEMM_UPM_NOSPLIT") != nullptr) return 0;
+    if (p.KG < 8) return 0;
     int ks = (int)((512 + wgs - 1) / wgs);
     if (ks > p.KG / 4) ks = p.KG / 4;
     if (ks > 16) ks = 16;
@@ -1086,7 +1081,6 @@ static int plan_upm(UpmParams& p, int N, int Di, int Hi, int Wi, int Cin, int Co
 // returns BTS_OK when the merged-class kernel took the launch, 1 when the shape is left to the per-class path
 static int launch_upm(const float* x, const float* wp, const float* bias, float* y, int N, int Di, int Hi, int Wi, int Cin,
                       int ldx, int Cout, int ldy, int flags, void* ws, long ws_bytes, hipStream_t stream) {
-  if (getenv("BTS_IGEMM_NOUPM") != nullptr) return 1;
   if ((ldx & 3) || (ldy & 3) || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return 1;
   UpmParams p;
   long need = 0;
@@ -1233,7 +1227,6 @@ __global__ __launch_bounds__(256, 4) void k1s_kernel(const K1sParams p) {
 // returns BTS_OK when taken, 1 when the shape is left to the staged igemm path
 static int launch_k1s(const float* x, const float* wp, const float* bias, float* y, long nvox, int Cin, int ldx, int Cout, int ldy,
                       int flags, hipStream_t stream) {
-  if (getenv("BTS_IGEMM_NOK1S") != nullptr) return 1;
   if ((Cin & 7) || (ldx & 3) || (((uintptr_t)x) & 15)) return 1;  // whole k-groups, 16-byte row quads
   const long min_vox = getenv("BTS_IGEMM_K1S_MIN") ? atol(getenv("BTS_IGEMM_K1S_MIN")) : 256 * 256;  // (tests force 1)
   if (nvox < min_vox) return 1;  // small grids (deep levels): too few workgroups, keep the split-K capable path
@@ -1368,7 +1361,6 @@ __global__ __launch_bounds__(256, 4) void dsc_kernel(const DscParams p) {
 // returns BTS_OK when taken, 1 when the shape is left to the MFMA path
 static int launch_dsc(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin, int ldx,
                       int Cout, int ldy, int flags, hipStream_t stream) {
-  if (getenv("BTS_IGEMM_NODSC") != nullptr) return 1;
   if (Cout > 4 || (Cin & 7) || (ldx & 3) || (((uintptr_t)x) & 15)) return 1;
   const long tiles = (long)N * ((D + 1) / 2) * ((H + 3) / 4) * ((W + 31) / 32);
   const long min_tiles = getenv("BTS_IGEMM_DSC_MIN") ? atol(getenv("BTS_IGEMM_DSC_MIN")) : 1024;  // (tests force 1)
@@ -1525,7 +1517,6 @@ __global__ __launch_bounds__(256, 2) void c2_kernel(const C2Params p) {
 static int launch_c2(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin, int ldx,
                      int Cout, int ldy, int flags, const float* wp2, const float* bias2, float* y2, int ldy2, double* gnp, int gnG,
                      long* gn_B, hipStream_t stream) {
-  if (getenv("BTS_IGEMM_NOC2") != nullptr) return 1;
   if (Cin != 2 || Cout > 32 || Cout % 4 != 0 || ldy % 4 != 0 || (((uintptr_t)y) & 15)) return 1;
   if (flags & (IG_FLAG_ACCUM | IG_FLAG_SIGMOID)) return 1;
   if (y2 != nullptr && (ldy2 % 4 != 0 || (((uintptr_t)y2) & 15))) return 1;
@@ -1561,11 +1552,11 @@ template <int MS, int NS, int WM, int WN, int KGS, bool FUSE2 = false, bool FIXG
 static int launch_cfg(IgemmParams& p, hipStream_t stream) {
   constexpr int S = KGS * 8 + 4;
   const int tileVox = p.IZ * p.IY * p.IX;
-  if (tileVox * KGS * 2 > 256 * ((MS == 4) ? 10 : MAXSLOT)) return BTS_ERR_SHAPE;
+  if (tileVox * KGS * 2 > 256 * MAXSLOT) return BTS_ERR_SHAPE;
   // a single stage (all channels fit one staging pass, e.g. the 1x1x1 convs with Cin <= 32) needs no second buffer:
   // half the LDS -> twice the resident workgroups to hide the (then un-overlapped) staging latency
   const int nstages_all = (p.KG + KGS - 1) / KGS;
-  const size_t shmem = (size_t)((nstages_all > 1 && MS != 4 && !IG_TRI(MS, NS, KGS, FUSE2, FIXG)) ? 2 : 1) * tileVox * S * sizeof(float);
+  const size_t shmem = (size_t)((nstages_all > 1 && !IG_TRI(MS, NS, KGS, FUSE2, FIXG)) ? 2 : 1) * tileVox * S * sizeof(float);
   auto kern = igemm_kernel<MS, NS, WM, WN, KGS, FUSE2, FIXG, T27>;
   static bool attr_done = false;
   if (!attr_done && !p.plan_only) {
@@ -1607,7 +1598,7 @@ static int launch_cfg(IgemmParams& p, hipStream_t stream) {
   if (p.plan_only) return BTS_OK;
   const bool prof = bts_prof_on();
   if (prof) {
-    constexpr int cfgid = (MS == 4) ? 5 : (MS == 2 && NS == 1) ? 0 : (MS == 2 && NS == 2) ? 1 : (MS == 1 && NS == 2) ? 2 : (WN == 2) ? 3 : 4;
+    constexpr int cfgid = (MS == 2 && NS == 1) ? 0 : (MS == 2 && NS == 2) ? 1 : (MS == 1 && NS == 2) ? 2 : (WN == 2) ? 3 : 4;
     const double taps = (p.ncls > 1) ? 27.0 : (double)p.ntaps;
     bts_prof_begin(cfgid + (KGS == 4 ? 8 : 0), 2.0 * taps * p.Cin * p.Cout * (double)p.N * p.Do * p.Ho * p.Wo, stream);
   }
@@ -1637,9 +1628,7 @@ static int choose_cfg(int geo, int N, int Do, int Ho, int Wo, int Npad, int* Mou
   } else {
     const long wg256 = (long)N * ((vox + 255) / 256) * ((Npad + 63) / 64);
     if (Npad <= 32) {
-      if (geo == GEO_S1 && Wo >= 32 && Ho >= 4 && Do >= 4 && (long)N * ((vox + 511) / 512) >= 1024 &&
-          getenv("BTS_IGEMM_M512") != nullptr) { M = 512; cfg = 5; }  // measured equal to M=256 on MI355X: opt-in only
-      else if ((long)N * ((vox + 255) / 256) >= 512) { M = 256; cfg = 0; }
+      if ((long)N * ((vox + 255) / 256) >= 512) { M = 256; cfg = 0; }
       else { M = 128; cfg = 4; }
     } else if (wg256 >= 512) { M = 256; cfg = 1; }
     else {
@@ -1718,11 +1707,6 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
   p.part = reinterpret_cast<float*>(ws);
   p.ws_bytes = ws_bytes;
   p.plan_only = need_out != nullptr;
-#ifdef BTS_TIMING_EXPERIMENTS
-  { const char* e = getenv("BTS_IGEMM_DBG"); p.dbg = e ? atoi(e) : 0; }
-#else
-  p.dbg = 0;
-#endif
   p.ws_need = 0;
   p.x = x; p.wp = wp; p.bias = bias; p.y = y;
   p.N = N; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.ldx = ldx;
@@ -1779,7 +1763,6 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
   const int k1 = (geo == GEO_K1);
   int M;  // voxels per workgroup tile
   int cfg = choose_cfg(geo, (geo == GEO_UP && pz < 0) ? 8 * N : N, Do, Ho, Wo, p.Npad, &M);
-  if (p.y2 != nullptr && cfg == 5) { cfg = 0; M = 256; }  // the fused pair needs the registers of the 256-voxel tiling
   // tile dims (powers of two in x,y)
   int TX = 32;
   while (TX > 4 && TX / 2 >= Wo) TX /= 2;  // smallest pow2 >= Wo, capped at 32
@@ -1832,13 +1815,12 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
 
   int rc;
   const bool fixg = (geo == GEO_S1) && p.IX == 34 && p.IY == 6;
-  if (fixg && !k1 && (cfg == 0 || cfg == 1 || cfg == 5)) {
+  if (fixg && !k1 && (cfg == 0 || cfg == 1)) {
     if (p.y2 != nullptr) {
       if (cfg == 0) rc = launch_cfg<2, 1, 4, 1, 1, true, true>(p, stream);
       else rc = BTS_ERR_UNSUPPORTED;
     } else {
       if (cfg == 0) rc = launch_cfg<2, 1, 4, 1, 1, false, true>(p, stream);
-      else if (cfg == 5) rc = launch_cfg<4, 1, 4, 1, 1, false, true>(p, stream);
       else rc = launch_cfg<2, 2, 4, 1, 1, false, true>(p, stream);
     }
   } else if (k1) {
@@ -1852,7 +1834,6 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
   } else if (p.y2 != nullptr) {  // fused shortcut conv: every tiling but the 64-accumulator one has the registers
     switch (cfg) {
       case 0: rc = launch_cfg<2, 1, 4, 1, 1, true>(p, stream); break;
-      case 5: rc = BTS_ERR_UNSUPPORTED; break;  // M=512 tiling exists only with the compile-time halo geometry
       case 2: rc = launch_cfg<1, 2, 2, 2, 1, true>(p, stream); break;
       case 3: rc = launch_cfg<1, 1, 2, 2, 1, true>(p, stream); break;
       case 4: rc = launch_cfg<1, 1, 4, 1, 1, true>(p, stream); break;
@@ -1861,7 +1842,6 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
   } else if (p.ntaps == 27 && p.ncls <= 1) {
     switch (cfg) {
       case 0: rc = launch_cfg<2, 1, 4, 1, 1, false, false, true>(p, stream); break;
-      case 5: rc = BTS_ERR_UNSUPPORTED; break;
       case 1: rc = launch_cfg<2, 2, 4, 1, 1, false, false, true>(p, stream); break;
       case 2: rc = launch_cfg<1, 2, 2, 2, 1, false, false, true>(p, stream); break;
       case 3: rc = launch_cfg<1, 1, 2, 2, 1, false, false, true>(p, stream); break;
@@ -1870,7 +1850,6 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
   } else {
     switch (cfg) {
       case 0: rc = launch_cfg<2, 1, 4, 1, 1>(p, stream); break;
-      case 5: rc = BTS_ERR_UNSUPPORTED; break;
       case 1: rc = launch_cfg<2, 2, 4, 1, 1>(p, stream); break;
       case 2: rc = launch_cfg<1, 2, 2, 2, 1>(p, stream); break;
       case 3: rc = launch_cfg<1, 1, 2, 2, 1>(p, stream); break;

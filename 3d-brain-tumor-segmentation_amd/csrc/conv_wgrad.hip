@@ -47,7 +47,6 @@ struct WgradParams {
   int want_bias;
   int fixg;  // 1/2: the sub-tile is the unclamped 16x4x2 (stride 1) / 8x4x1 (stride 2) 27-tap geometry -> fixed sweep
   int fastf;  // fixed geometry AND whole tiles / whole 32-channel groups: per-lane staging offsets are precomputed once
-  int dbg;  // profiling aid (BTS_WGRAD_DBG), see the sub-tile loop
   int tap_vox[27];  // voxel offset of each tap inside the P halo tile
 };
 
@@ -486,11 +485,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_kernel(const WgradParams 
     const float* bp = lds + cur * bufDw;
     const float* bq = bp + pRegion;
     const bool more = (sub + 1) < sub1;
-    // BTS_WGRAD_DBG (timing only, results are wrong): 1 skip the sweep, 2 no re-staging, 3 = 2 + no barriers,
-    // 4 = 2 + at most 3 row-tiles per wave, 5 stage but keep reading buffer 0, 7 = always stage the first sub-tile
-    const bool dofetch = more && (BTS_DBG(p) < 2 || BTS_DBG(p) >= 5);
     if constexpr (FIXG == 0) {
-      if (dofetch) {
+      if (more) {
         if constexpr (GLDS) fetch_glds(sub + 1, lds + (cur ^ 1) * bufDw);
         else fetch(sub + 1);
       }
@@ -510,11 +506,11 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_kernel(const WgradParams 
       auto stage = [&](auto kc) {
         constexpr int K = decltype(kc)::value;
         if constexpr (K == 0) {
-          if (dofetch) fast_prep(BTS_DBG(p) == 7 ? sub0 : sub + 1, lds + (cur ^ 1) * bufDw);
+          if (more) fast_prep(sub + 1, lds + (cur ^ 1) * bufDw);
         } else if constexpr (K >= P0 && K < Q0 && (K - P0) % PD == 0) {
-          if (dofetch) fast_slot_p(IC<(K - P0) / PD>{});
+          if (more) fast_slot_p(IC<(K - P0) / PD>{});
         } else if constexpr (K >= Q0 && K <= Q0 + 3 * QD && (K - Q0) % QD == 0) {
-          if (dofetch) fast_slot_q(IC<(K - Q0) / QD>{});
+          if (more) fast_slot_q(IC<(K - Q0) / QD>{});
         }
       };
       const unsigned bpb = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)bp;
@@ -522,28 +518,24 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_kernel(const WgradParams 
       unsigned vp[WG_MAXT];
 #pragma unroll
       for (int i = 0; i < WG_MAXT; ++i) vp[i] = bpb + 4u * (unsigned)(rowoff[i] + ((h * p.s) << 5));
-      if (BTS_DBG(p) == 1) {
-        if (dofetch) fetch_fast(sub + 1, lds + (cur ^ 1) * bufDw);
-      } else {
-        // 27 row-tiles over 8 waves: every wave owns tiles w, w+8, w+16 for the whole sub-tile and 1/8 of the voxel pairs
-        // of the three left-over tiles 24..26 (its own x-row for stride 1, half a row for stride 2) in a second, short
-        // sweep -> 216 MFMAs per wave and sub-tile on every wave instead of 256 / 192 (the barrier waits for the slowest)
-        using GX = typename std::conditional<FIXG == 1, WgGeo<1, 16, 1, 1>, WgGeo<2, 4, 1, 1>>::type;   // NS = 8 / 2 steps
-        static_assert(GX::NS * WG_WAVES == G::NS, "the left-over tiles' steps must split evenly over the waves");
-        const int k0 = wave * GX::NS;                       // first step of this wave's slice (wave-uniform)
-        const int r0 = k0 / G::JR, j0 = k0 % G::JR;         // its x-row (z-major) and position inside the row
-        const int pb0 = (((r0 >> 2) * p.s * p.IY + (r0 & 3) * p.s) * p.IX + 2 * j0 * p.s) * 128;   // = G::p_b(k0), TY = 4
-        unsigned vpx[WG_MAXT];
+      // 27 row-tiles over 8 waves: every wave owns tiles w, w+8, w+16 for the whole sub-tile and 1/8 of the voxel pairs
+      // of the three left-over tiles 24..26 (its own x-row for stride 1, half a row for stride 2) in a second, short
+      // sweep -> 216 MFMAs per wave and sub-tile on every wave instead of 256 / 192 (the barrier waits for the slowest)
+      using GX = typename std::conditional<FIXG == 1, WgGeo<1, 16, 1, 1>, WgGeo<2, 4, 1, 1>>::type;   // NS = 8 / 2 steps
+      static_assert(GX::NS * WG_WAVES == G::NS, "the left-over tiles' steps must split evenly over the waves");
+      const int k0 = wave * GX::NS;                       // first step of this wave's slice (wave-uniform)
+      const int r0 = k0 / G::JR, j0 = k0 % G::JR;         // its x-row (z-major) and position inside the row
+      const int pb0 = (((r0 >> 2) * p.s * p.IY + (r0 & 3) * p.s) * p.IX + 2 * j0 * p.s) * 128;   // = G::p_b(k0), TY = 4
+      unsigned vpx[WG_MAXT];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) vpx[i] = bpb + 4u * (unsigned)(rowoffx[i] + ((h * p.s) << 5)) + (unsigned)pb0;
-        vpx[3] = vpx[2];
-        auto nostage = [](auto) {};
-        wgrad_sweep_fixed<3, GX>(vpx, vq + (unsigned)(k0 * 256), accx, nostage);
-        wgrad_sweep_fixed<3, G>(vp, vq, acc, stage);
-      }
+      for (int i = 0; i < 3; ++i) vpx[i] = bpb + 4u * (unsigned)(rowoffx[i] + ((h * p.s) << 5)) + (unsigned)pb0;
+      vpx[3] = vpx[2];
+      auto nostage = [](auto) {};
+      wgrad_sweep_fixed<3, GX>(vpx, vq + (unsigned)(k0 * 256), accx, nostage);
+      wgrad_sweep_fixed<3, G>(vp, vq, acc, stage);
     } else {
       const int st0 = ksplit ? wave : 0, stinc = ksplit ? WG_WAVES : 1;
-      if (BTS_DBG(p) != 1) switch ((BTS_DBG(p) == 4 && ntw > 3) ? 3 : ntw) {  // wave-uniform: row-tiles this wave owns -> branch-free MFMA bodies
+      switch (ntw) {  // wave-uniform: row-tiles this wave owns -> branch-free MFMA bodies
         case 4: wgrad_steps<4>(p, bp, bq, rowoff, acc, st0, stinc, nsteps, h, l32); break;
         case 3: wgrad_steps<3>(p, bp, bq, rowoff, acc, st0, stinc, nsteps, h, l32); break;
         case 2: wgrad_steps<2>(p, bp, bq, rowoff, acc, st0, stinc, nsteps, h, l32); break;
@@ -551,12 +543,12 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_kernel(const WgradParams 
         default: break;
       }
     }
-    if (dofetch) {
+    if (more) {
       if constexpr (GLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else commit(lds + (cur ^ 1) * bufDw);
     }
-    if (BTS_DBG(p) != 3) __syncthreads();
-    if (BTS_DBG(p) < 2) cur ^= 1;
+    __syncthreads();
+    cur ^= 1;
   }
 
   // ---- write partials ----
@@ -816,13 +808,12 @@ static int plan_wgrad(WgradPlan& pl, int ntaps, int s, int neg, int N, int Dp, i
       p.tap_vox[t] = ((oz - lo) * p.IY + (oy - lo)) * p.IX + (ox - lo);
     }
   p.fixg = 0;
-  if (ntaps == 27 && cpad == 32 && !neg && getenv("BTS_WGRAD_NOFIX") == nullptr) {
+  if (ntaps == 27 && cpad == 32 && !neg) {
     if (s == 1 && TX == 16 && TY == 4 && TZ == 2) p.fixg = 1;
     if (s == 2 && TX == 8 && TY == 4 && TZ == 1) p.fixg = 2;
   }
   p.fastf = 0;
-  if (p.fixg && Wq % TX == 0 && Hq % TY == 0 && Dq % TZ == 0 && Cp % 32 == 0 && Cq % 32 == 0 &&
-      getenv("BTS_WGRAD_NOFASTF") == nullptr)
+  if (p.fixg && Wq % TX == 0 && Hq % TY == 0 && Dq % TZ == 0 && Cp % 32 == 0 && Cq % 32 == 0)
     p.fastf = 1;  // (the 32-bit staging offsets are range-checked where the leading dimensions are known)
   if (!p.fastf) p.fixg = 0;  // the fixed sweep only ships together with the fast staging
   p.nsub = N * p.ntz * p.nty * p.ntx;
@@ -833,25 +824,19 @@ static int plan_wgrad(WgradPlan& pl, int ntaps, int s, int neg, int N, int Dp, i
   // write/combine traffic (~0.0023 per workgroup).  Smallest cost wins, ties go to fewer partials.
   {
     const long pairs = (long)pl.npct * pl.nqct;
-    const char* ov = getenv("BTS_WGRAD_WGS");  // experiment override: target workgroup count
     long best = 1;
-    if (ov) {
-      best = atol(ov) / pairs;
-    } else {
-      double bestc = 1e30;
-      long maxn = 2048 / pairs;
-      if (maxn < 1) maxn = 1;
-      if (maxn > p.nsub) maxn = p.nsub;
-      for (long n = 1; n <= maxn; ++n) {
-        const long spw = (p.nsub + n - 1) / n;
-        const long ne = (p.nsub + spw - 1) / spw;
-        if (ne != n) continue;
-        const long rounds = (ne * pairs + 255) / 256;
-        const double c = (double)rounds * ((double)spw + 0.5) + 0.0023 * (double)(ne * pairs);
-        if (c < bestc - 1e-9) { bestc = c; best = n; }
-      }
+    double bestc = 1e30;
+    long maxn = 2048 / pairs;
+    if (maxn < 1) maxn = 1;
+    if (maxn > p.nsub) maxn = p.nsub;
+    for (long n = 1; n <= maxn; ++n) {
+      const long spw = (p.nsub + n - 1) / n;
+      const long ne = (p.nsub + spw - 1) / spw;
+      if (ne != n) continue;
+      const long rounds = (ne * pairs + 255) / 256;
+      const double c = (double)rounds * ((double)spw + 0.5) + 0.0023 * (double)(ne * pairs);
+      if (c < bestc - 1e-9) { bestc = c; best = n; }
     }
-    if (best < 1) best = 1;
     if (best > p.nsub) best = p.nsub;
     p.sub_per_wg = (int)((p.nsub + best - 1) / best);
     pl.nsp = (p.nsub + p.sub_per_wg - 1) / p.sub_per_wg;
@@ -1310,11 +1295,6 @@ extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, 
   p.partial_b = reinterpret_cast<double*>(pb);
   // bias gradient = column sums of dy: dy is Q in the plain form only
   p.want_bias = (db != nullptr && !pIsDy) ? 1 : 0;
-#ifdef BTS_TIMING_EXPERIMENTS
-  { const char* e = getenv("BTS_WGRAD_DBG"); p.dbg = e ? atoi(e) : 0; }
-#else
-  p.dbg = 0;
-#endif
   typedef void (*WgKernel)(const WgradParams);
   static const WgKernel kernels[4] = {wgrad_kernel<0, 0>, wgrad_kernel<1, 0>, wgrad_kernel<2, 1>, wgrad_kernel<2, 2>};
   static bool attr_done = false;
@@ -1329,7 +1309,7 @@ extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, 
   char* ztail = reinterpret_cast<char*>(workspace) + ((need - 64) & ~15L);
   p.zeros = reinterpret_cast<const float*>(ztail);
   const bool glds = (p.ldp % 4 == 0) && (p.Cp % 4 == 0) && ((((uintptr_t)p.p) & 15) == 0) && (p.ldq % 4 == 0) &&
-                    (p.Cq % 4 == 0) && ((((uintptr_t)p.q) & 15) == 0) && getenv("BTS_WGRAD_NOGLDS") == nullptr;
+                    (p.Cq % 4 == 0) && ((((uintptr_t)p.q) & 15) == 0);
   if (p.fastf && ((double)p.IZ * p.Hp * p.Wp * p.ldp * 4.0 >= 4.0e9 || (double)p.TZ * p.Hq * p.Wq * p.ldq * 4.0 >= 4.0e9 || !glds))
     p.fastf = p.fixg = 0;
   const bool prof = bts_prof_on();

@@ -20,7 +20,6 @@
 //
 // Rounding: the transforms add fp32 values before the multiply, so results differ from the direct form in the last bits
 // (measured max |err| 5e-6 at |y| ~ 3, K = 864); the summation order is fixed (deterministic).
-#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
@@ -29,19 +28,6 @@
 int bts_prof_on();
 void bts_prof_begin(int sym, double flops, hipStream_t stream);
 void bts_prof_end(hipStream_t stream);
-
-#ifdef BTS_WINO_STAMPS   // experiment builds only (scripts/wino_timeline.py): per-item clock stamps of wave 0
-__device__ long long g_wino_stamps[1 << 20];
-extern "C" int bts_wino_stamps_copy_(long long* dst, long n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wino_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#define WSTAMP(slot)                                                                              \
-  do {                                                                                            \
-    if (tid == 0) g_wino_stamps[((long)blockIdx.x * p.T + it) * 16 + (slot)] = wall_clock64();    \
-  } while (0)
-#else
-#define WSTAMP(slot) do { } while (0)
-#endif
 
 #include "wino_util.h"
 
@@ -414,18 +400,6 @@ __global__ __launch_bounds__(256, 1) void wino_kernel(const WinoParams p) {
   for (int it = 0; it < p.T; ++it) {
     const bool have_next = (it + 1 < p.T) && (seq0 + it + 1 < items_here);
     const Item out = cur;
-    WSTAMP(0);
-#ifdef BTS_WINO_STAMPS
-    if (tid == 0) {
-      unsigned hwid;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-      unsigned xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      g_wino_stamps[((long)blockIdx.x * p.T + it) * 16 + 6] = ((long long)xcc << 32) | hwid;
-      g_wino_stamps[((long)blockIdx.x * p.T + it) * 16 + 7] = clock64();
-    }
-#endif
-    WSTAMP(1);
     // from an item's last stage on, the input-side state is the successor's (the item's own last halo tile is in LDS by then)
     auto enter = [&](int st) {
       const bool chain = (st + 1 == st1) && have_next;
@@ -442,17 +416,13 @@ __global__ __launch_bounds__(256, 1) void wino_kernel(const WinoParams p) {
       stage(std::true_type{}, st0, par, st0 + 1 < st1, chain, (it + 1) & 1);
       par ^= 1;
     }
-    WSTAMP(2);
     for (int st = st0 + 1; st < st1; ++st) {
       const bool chain = enter(st);
       stage(std::false_type{}, st, par, st + 1 < st1, chain, (it + 1) & 1);
       par ^= 1;
     }
-    WSTAMP(3);
     if (have_next) wr = wr_n;
-    WSTAMP(4);
     finish(out, it & 1);
-    WSTAMP(5);
     if (!have_next) break;
   }
 }
@@ -546,10 +516,6 @@ int bts_wino_launch_(const float* x, const float* up, const float* bias, float* 
   if (q.ksplit > 1 && (ws == nullptr || ws_bytes < q.need || (((uintptr_t)ws) & 15))) { q.ksplit = 1; q.kg_per = Cin / 8; }
   int min_wgs = 192;
   { const char* e = getenv("BTS_WINO_MIN_WGS"); if (e) min_wgs = atoi(e); }
-  if (getenv("BTS_WINO_LOG"))
-    fprintf(stderr, "wino %s N=%d D=%d H=%d W=%d Cin=%d Cout=%d ldx=%d ldy=%d accum=%d gn=%d xw=%d wgs=%ld ksplit=%d ws=%ld\n",
-            q.wgs * q.ksplit < min_wgs ? "declined" : "taken", N, D, H, W, Cin, Cout, ldx, ldy, accum, gnp != nullptr, q.xw, q.wgs,
-            q.ksplit, ws_bytes);
   if (q.wgs * q.ksplit < min_wgs) return 1;
   WinoParams p;
   p.x = x; p.up = up; p.bias = bias; p.y = y;
@@ -562,8 +528,6 @@ int bts_wino_launch_(const float* x, const float* up, const float* bias, float* 
   {
     const long per_cu = ((long)p.tiles_per_xcd * q.nb) / 32;
     p.T = q.ksplit > 1 ? 1 : (per_cu >= 8 ? 4 : per_cu >= 4 ? 2 : 1);
-    const char* e = getenv("BTS_WINO_T");   // A/B aid
-    if (e && q.ksplit == 1) p.T = atoi(e) > 0 ? atoi(e) : 1;
   }
   p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1;
   if (q.ksplit == 1 && gnp != nullptr && gnG > 0 && D % gnG == 0 && (D / gnG) % 4 == 0 && getenv("BTS_IGEMM_NOGNFUSE") == nullptr) {

@@ -36,19 +36,6 @@ int bts_prof_on();
 void bts_prof_begin(int sym, double flops, hipStream_t stream);
 void bts_prof_end(hipStream_t stream);
 
-#ifdef BTS_WINO_STAMPS   // experiment builds only (scripts/w3_timeline.py): clock stamps of wave 0, one row per workgroup
-__device__ long long g_w3_stamps[1 << 20];
-extern "C" int bts_w3_stamps_copy_(long long* dst, long n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_w3_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#define W3STAMP(slot)                                                                     \
-  do {                                                                                    \
-    if (tid == 0 && blockIdx.z == 0) g_w3_stamps[(long)blockIdx.x * 16 + (slot)] = wall_clock64(); \
-  } while (0)
-#else
-#define W3STAMP(slot) do { } while (0)
-#endif
-
 struct W3Params {
   const float* x;
   const float* up;
@@ -180,22 +167,12 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
   // U fragments of group G = 4*stage + gi live in aw[gi]; the groups of a stage run xi_y = 1, 2, 0, 3
   f32x4 aw[4][4];
   auto wload = [&](f32x4 (&dst)[4], const __amdgpu_buffer_rsrc_t d, int st, int b) {
-#ifdef W3_EXP_SAMEU   // timing experiment (wrong results): every fragment request hits the same 16 KB
-    const unsigned so = (unsigned)(b * 4096) + wwave + 0u * st;
-#else
     const unsigned so = (unsigned)(st * (64 * 1024) + b * 4096) + wwave;
-#endif
-#ifdef W3_EXP_NOW     // timing experiment (wrong results): no weight fragment requests
-    return;
-#endif
 #pragma unroll
     for (int e = 0; e < 4; ++e) dst[e] = bufload(d, wlane + e * 1024, so);
   };
   f32x4 c[4][4], v[2][4], t[4];
   auto rd_row = [&](const float* lb, int j) {   // row j of the lane's patch: 4 voxels x 4 channels, already z-combined
-#ifdef W3_EXP_NOLDS   // timing experiment (wrong results): no operand reads from LDS
-    return;
-#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) c[j][k] = *reinterpret_cast<const f32x4*>(lb + offP + W3OFF(j, k));
   };
@@ -244,14 +221,8 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
       __builtin_amdgcn_sched_barrier(0);
       commit(lds + (par ^ 1) * W3BUF);
       if (FIRST && tid < 32) bsh[bslot * 32 + tid] = bias_v;
-#ifndef W3_EXP_NOBAR   // timing experiment (wrong results): no stage barrier
       __syncthreads();
-#endif
-#ifdef W3_EXP_NOFETCH  // timing experiment (wrong results): no halo traffic after the first tile
-      fetch(0x80000000u);
-#else
       fetch(f_soff);
-#endif
     }
     {  // MFMA xi_y = 3 ; read rows 1, 2 of the NEXT stage and form its xi_y = 1 : c1 + c2
       wload(aw[1], wt, stn, 2);
@@ -299,7 +270,6 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
-    W3STAMP(4);
     f32x2 gn_s2 = {0.f, 0.f}, gn_q2 = {0.f, 0.f};
     const bool gn_on = p.gnp != nullptr;
     {
@@ -367,16 +337,6 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
     }
   };
 
-  W3STAMP(0);
-#ifdef BTS_WINO_STAMPS
-  if (tid == 0 && blockIdx.z == 0) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    g_w3_stamps[(long)blockIdx.x * 16 + 6] = ((long long)xcc << 32) | hwid;
-    g_w3_stamps[(long)blockIdx.x * 16 + 7] = clock64();
-  }
-#endif
   // ---- prologue: first halo tile, first operands of the workgroup's first item ----
   Item cur = decode(seq0), nxt = cur;
   setup_x(cur);
@@ -406,7 +366,6 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
   wino_yt(t, v[0]);
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_nop 3" ::: "memory");
-  W3STAMP(1);
 
   int par = 0;
   for (int it = 0; it < p.T; ++it) {
@@ -428,19 +387,13 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
       par ^= 1;
     };
     run(std::true_type{}, st0);
-    if (it == 0) W3STAMP(2);
     for (int st = st0 + 1; st < st1; ++st) run(std::false_type{}, st);
-    if (it == 0) W3STAMP(3);
     finish(out, it & 1);
     if (!have_next) break;
     cur = nxt;
     wr = wr_n;
     bias_v = bias_n;
   }
-  W3STAMP(5);
-#ifdef BTS_WINO_STAMPS
-  if (tid == 0 && blockIdx.z == 0) g_w3_stamps[(long)blockIdx.x * 16 + 8] = clock64();
-#endif
 }
 
 static int w3_enabled() {  // BTS_WINO=0: no Winograd form at all; BTS_W3=0: this one off, conv_wino.hip's F(2x2,3x3) x direct form stays

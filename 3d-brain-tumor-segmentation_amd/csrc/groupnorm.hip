@@ -428,7 +428,7 @@ extern "C" int bts_gn_apply(const float* x, float* y, const float* gamma, const 
     return BTS_OK;
   }
   if (ldy < C || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return BTS_ERR_ALIGN;
-  if (mode == BTS_GN_SLAB && g.L % 1024 == 0 && 1024 % C == 0 && getenv("BTS_GN_NOSTREAM") == nullptr) {
+  if (mode == BTS_GN_SLAB && g.L % 1024 == 0 && 1024 % C == 0) {
     // NOTE: results differ from gn_apply_kernel in the last bit ((x - m) * rs * gamma + beta is evaluated as
     // fma(x - m, rs*gamma, beta)); both are within the element-wise tolerance of the oracle
     const long cpu = g.L / 1024;
@@ -766,7 +766,7 @@ extern "C" int bts_gn_bwd(const float* x, const float* dy, float* dx, const floa
                        (double)g.L, accumulate_params);
     BTS_LAUNCH_CHECK();
   }
-  if (slab && g.L % 1024 == 0 && 1024 % C == 0 && getenv("BTS_GN_NOSTREAM") == nullptr) {
+  if (slab && g.L % 1024 == 0 && 1024 % C == 0) {
     const long cpu = g.L / 1024;
     const int cpb = gn_stream_cpb(cpu);
     const long nblk = (long)N * G * cpu / cpb;

@@ -549,8 +549,6 @@ __global__ __launch_bounds__(256) void lp_splitk_reduce_gn_kernel(const float* p
 // partial slots per (n, group) the kernel above leaves (0 = it does not take the shape)
 long bts_lp_splitk_gn_B_(int N, long V, int Cout, int G) {
   if (G <= 0 || Cout % 32 != 0 || Cout % G != 0 || (V * Cout) % G != 0 || ((V * Cout) / G) % 8 != 0) return 0;
-  static const bool off = [] { const char* e = getenv("BTS_LP_SPLIT_GN"); return e && atoi(e) == 0; }();      // A/B: the separate statistics pass
-  if (off) return 0;
   // (many short workgroups -- one or two 2048-element steps each: the tensor is small and the pass is latency-bound; < 512 partials per
   // unit keeps the finalize on its one-wave-per-unit form)
   long b = (V * Cout / G + 2047) / 2048;
@@ -1138,27 +1136,9 @@ extern "C" long bts_lp_conv3d_fwd_gn_workspace(int N, int D, int H, int W, int C
   const long stats = bts_lp_gn_workspace(N, (long)D * H * W, Cout, G);
   return conv + (fused > stats ? fused : stats) + 64;
 }
-static int lp_conv3d_fwd_gn_impl(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd,
-                                 void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G,
-                                 float eps, int accum, hipStream_t stream);
 extern "C" int bts_lp_conv3d_fwd_gn(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd,
                                     void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G,
                                     float eps, hipStream_t stream) {
-  return lp_conv3d_fwd_gn_impl(dtype, x, wp, bias, y, mean, rstd, workspace, workspace_bytes, N, D, H, W, Cin, ldx, Cout, G, eps, 0, stream);
-}
-// The same, ADDING the convolution to what y already holds (accumulate != 0), the statistics taken of the final sums: a contraction
-// split over its input channels whose parts become available at different times -- the decoder's conv1 over [skip | up-sampled]
-// (decoder.py:75, resnet.py:134): the skip part (with the bias) can run as soon as the encoder level is done, the up-sampled part adds to
-// it later (pass bias = NULL then).  The partial sum passes through the storage type once (as in the two-pass form of lowp_s1z.hip).
-extern "C" int bts_lp_conv3d_fwd_gn_acc(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd,
-                                        void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G,
-                                        float eps, int accumulate, hipStream_t stream) {
-  return lp_conv3d_fwd_gn_impl(dtype, x, wp, bias, y, mean, rstd, workspace, workspace_bytes, N, D, H, W, Cin, ldx, Cout, G, eps, accumulate ? 1 : 0,
-                               stream);
-}
-static int lp_conv3d_fwd_gn_impl(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd,
-                                 void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G,
-                                 float eps, int accum, hipStream_t stream) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0) return BTS_ERR_SHAPE;
   if (workspace == nullptr || workspace_bytes < bts_lp_conv3d_fwd_gn_workspace(N, D, H, W, Cin, Cout, G) || (((uintptr_t)workspace) & 15))
     return BTS_ERR_WORKSPACE;
@@ -1166,16 +1146,13 @@ static int lp_conv3d_fwd_gn_impl(int dtype, const void* x, const void* wp, const
   char* tail = reinterpret_cast<char*>(workspace) + conv_ws;
   const long V = (long)D * H * W;
   long B = 0;
-  // (accumulating: the split-K finish writes y from its partial sums and cannot add to it with statistics -- such grids take the
-  // statistics from the stored result)
-  const bool split = bts_lp_s1z_gn_B_(N, D, H, W, Cin, Cout, 1) <= 0 && bts_lp_s1d_workspace_(N, D, H, W, Cin, Cout) > 0;
-  if (!(accum && split) && lp_s1_gn_plan(N, D, H, W, Cin, Cout, G, &B)) {
+  if (lp_s1_gn_plan(N, D, H, W, Cin, Cout, G, &B)) {
     double* part = reinterpret_cast<double*>(tail);
-    const int r = lp_conv_run(1, dtype, x, wp, bias, y, workspace, conv_ws, N, D, H, W, Cin, ldx, Cout, Cout, accum, stream, nullptr, part, G);
+    const int r = lp_conv_run(1, dtype, x, wp, bias, y, workspace, conv_ws, N, D, H, W, Cin, ldx, Cout, Cout, 0, stream, nullptr, part, G);
     if (r != BTS_OK) return r;
     return bts_gn_finalize_partials_(part, mean, rstd, N * G, B, (double)(V * Cout / G), eps, stream);
   }
-  const int r = lp_conv_run(1, dtype, x, wp, bias, y, workspace, conv_ws, N, D, H, W, Cin, ldx, Cout, Cout, accum, stream);
+  const int r = lp_conv_run(1, dtype, x, wp, bias, y, workspace, conv_ws, N, D, H, W, Cin, ldx, Cout, Cout, 0, stream);
   if (r != BTS_OK) return r;
   return bts_lp_gn_stats(dtype, y, mean, rstd, tail, workspace_bytes - conv_ws, N, V, Cout, G, BTS_GN_SLAB, eps, stream);
 }
@@ -1190,8 +1167,7 @@ __global__ __launch_bounds__(256) void lp_colsum_finalize_kernel(const double* p
 extern "C" long bts_lp_conv3d_fwd_gn_shortcut_workspace(int N, int D, int H, int W, int Cin, int ldx, int Cout, int G) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0 || D % G != 0 || Cin % 16 != 0) return -1;
   static const bool off = [] { const char* e = getenv("BTS_LP_FS"); return e && atoi(e) == 0; }();
-  static const bool off64 = [] { const char* e = getenv("BTS_LP_FS_PAIR"); return e && atoi(e) == 0; }();      // BTS_LP_FS_PAIR=0: not on the two-pass 64-channel form (A/B)
-  if (off || (off64 && Cin == 64)) return -1;
+  if (off) return -1;
   // (two dense 32-channel operands -- voxel stride 32 under 64 channels: the two-pass form at any size, planned like one of its passes)
   const long Bg = bts_lp_s1z_gn_B_(N, D, H, W, (Cin == 64 && ldx < 64) ? 32 : Cin, Cout, G), Bf = bts_lp_s1z_fs_B_(N, D, H, W, Cin, ldx, Cout, Cout);
   if (Bg <= 0 || Bf <= 0) return -1;
@@ -1230,8 +1206,7 @@ extern "C" int bts_lp_conv3d_fwd_gn_shortcut(int dtype, const void* x, long x_sp
 // streaming kernel does not take the shape in this form (the caller runs bts_lp_gn_apply + bts_lp_conv3d_fwd_gn).
 extern "C" long bts_lp_conv3d_gnin_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int in_G, int G) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0 || in_G <= 0 || Cin % in_G != 0) return -1;
-  static const bool off = [] { const char* e = getenv("BTS_LP_GNA"); return e && atoi(e) == 0; }();      // A/B: the separate apply pass
-  if (off || !bts_lp_s1z_gna_ok_(N, D, H, W, Cin, Cin, Cout, Cout, in_G)) return -1;
+  if (!bts_lp_s1z_gna_ok_(N, D, H, W, Cin, Cin, Cout, Cout, in_G)) return -1;
   const long B = bts_lp_s1z_gn_B_(N, D, H, W, Cin, Cout, G);
   if (B <= 0) return -1;
   return (long)N * G * B * 16 + 128;
@@ -1290,21 +1265,8 @@ extern "C" long bts_lp_conv1_gap_workspace(int N, long V, int Cout) {
   const long b = bts_lp_colsum_workspace(N, V, Cout);
   return a > b ? a : b;
 }
-static int lp_conv1_gap_impl(int dtype, const void* x, const void* wp, const float* bias, void* res, float* gap, void* workspace,
-                             long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldres, int accum, hipStream_t stream);
 extern "C" int bts_lp_conv1_gap(int dtype, const void* x, const void* wp, const float* bias, void* res, float* gap, void* workspace,
                                 long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldres, hipStream_t stream) {
-  return lp_conv1_gap_impl(dtype, x, wp, bias, res, gap, workspace, workspace_bytes, N, D, H, W, Cin, ldx, Cout, ldres, 0, stream);
-}
-// The same, ADDING to what res already holds (the shortcut over [skip | up-sampled], the skip part computed earlier: see
-// bts_lp_conv3d_fwd_gn_acc); gap = mean of the final sums
-extern "C" int bts_lp_conv1_gap_acc(int dtype, const void* x, const void* wp, const float* bias, void* res, float* gap, void* workspace,
-                                    long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldres, int accumulate,
-                                    hipStream_t stream) {
-  return lp_conv1_gap_impl(dtype, x, wp, bias, res, gap, workspace, workspace_bytes, N, D, H, W, Cin, ldx, Cout, ldres, accumulate ? 1 : 0, stream);
-}
-static int lp_conv1_gap_impl(int dtype, const void* x, const void* wp, const float* bias, void* res, float* gap, void* workspace,
-                             long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldres, int accum, hipStream_t stream) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0) return BTS_ERR_SHAPE;
   const long V = (long)D * H * W;
   if (workspace == nullptr || workspace_bytes < bts_lp_conv1_gap_workspace(N, V, Cout) || (((uintptr_t)workspace) & 15)) return BTS_ERR_WORKSPACE;
@@ -1316,7 +1278,7 @@ static int lp_conv1_gap_impl(int dtype, const void* x, const void* wp, const flo
     if (kb == 0 && N == 1 && bts_lp_k1_gap_block_(V, 256, Cin, Cout) > 0) kb = 256;
     if (kb > 0 && (V % kb == 0 || N == 1) && ldres == Cout) {
       double* part = reinterpret_cast<double*>(workspace);
-      const int r = bts_lp_k1_launch_(dtype, x, wp, bias, res, (long)N * V, Cin, ldx, Cout, ldres, accum, part, kb, stream);
+      const int r = bts_lp_k1_launch_(dtype, x, wp, bias, res, (long)N * V, Cin, ldx, Cout, ldres, 0, part, kb, stream);
       if (r == BTS_OK) {
         hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * Cout + 3) / 4), dim3(256), 0, stream, part, gap, N, Cout, (int)((V + kb - 1) / kb), 1.0 / (double)V);
         BTS_LAUNCH_CHECK();
@@ -1326,14 +1288,14 @@ static int lp_conv1_gap_impl(int dtype, const void* x, const void* wp, const flo
     }
   }
   const long ppb = 128L * lp_gather_vb((long)N * V, NB);     // positions per block
-  if (accum || V % ppb != 0 || ldres != Cout) {      // (the gather kernel's fused column sums do not see the old values: sums of the stored result)
-    const int r = lp_conv_run(0, dtype, x, wp, bias, res, nullptr, 0, N, D, H, W, Cin, ldx, Cout, ldres, accum, stream);
+  if (V % ppb != 0 || ldres != Cout) {
+    const int r = lp_conv_run(0, dtype, x, wp, bias, res, nullptr, 0, N, D, H, W, Cin, ldx, Cout, ldres, 0, stream);
     if (r != BTS_OK) return r;
     if (ldres != Cout) return BTS_ERR_UNSUPPORTED;
     return bts_lp_colsum(dtype, res, gap, workspace, workspace_bytes, N, V, Cout, (float)(1.0 / (double)V), stream);
   }
   double* part = reinterpret_cast<double*>(workspace);
-  const int r = lp_conv_run(0, dtype, x, wp, bias, res, nullptr, 0, N, D, H, W, Cin, ldx, Cout, ldres, accum, stream, part);
+  const int r = lp_conv_run(0, dtype, x, wp, bias, res, nullptr, 0, N, D, H, W, Cin, ldx, Cout, ldres, 0, stream, part);
   if (r != BTS_OK) return r;
   hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * Cout + 3) / 4), dim3(256), 0, stream, part, gap, N, Cout, (int)(V / ppb),
                      1.0 / (double)V);
@@ -1377,8 +1339,7 @@ extern "C" long bts_lp_conv3d_bwd_data_sc_workspace(int N, int D, int H, int W, 
 }
 extern "C" int bts_lp_conv3d_bwd_data_sc_split_ok(int N, int D, int H, int W, int Cin, int Cout) {
   static const bool off = [] { const char* e = getenv("BTS_LP_SC"); return e && atoi(e) == 0; }();
-  static const bool off2 = [] { const char* e = getenv("BTS_LP_SC_SPLIT"); return e && atoi(e) == 0; }();      // BTS_LP_SC_SPLIT=0: never (A/B)
-  if (off || off2 || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cout % 16 != 0) return 0;
+  if (off || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cout % 16 != 0) return 0;
   return bts_lp_s1d_sc_split_ok_(N, D, H, W, Cout, Cin) ? 1 : 0;
 }
 extern "C" int bts_lp_conv3d_bwd_data_sc(int dtype, const void* dy, const void* wp_bwd, const void* dy2, const void* wp2_bwd, void* dx,
@@ -1713,7 +1674,7 @@ extern "C" int bts_lp_gn_apply(int dtype, const void* x, void* y, const float* g
   {
     const int slab = mode == BTS_GN_SLAB;
     const long Lu = slab ? L : E;
-    if (2048 % C == 0 && Lu % 2048 == 0 && !getenv("BTS_LP_ELEM_OLD")) {
+    if (2048 % C == 0 && Lu % 2048 == 0) {
       const int upn = slab ? G : 1;
       int B;
       const long per = lp_chunk_per(Lu, (long)N * upn, &B);
@@ -1916,7 +1877,7 @@ extern "C" int bts_lp_block_epilogue(int dtype, const void* res, const void* c2,
   {
     const int slab = mode == BTS_GN_SLAB;
     const long Lu = slab ? L : E;
-    if (2048 % C == 0 && Lu % 2048 == 0 && !getenv("BTS_LP_ELEM_OLD")) {
+    if (2048 % C == 0 && Lu % 2048 == 0) {
       const int upn = slab ? G : 1;
       int B;
       const long per = lp_chunk_per(Lu, (long)N * upn, &B);
@@ -3375,10 +3336,9 @@ extern "C" int bts_lp_conv3d_bwd_weight(int kind, int dtype, const void* x, cons
 // wave fed by planes of dy1 that ride in the Q-ring slots the 3x3x3 contraction no longer needs (its older planes live in registers).
 // The 1x1x1 weight-gradient launch -- HBM-bound, its own read of the Cin-wide x -- goes away.  db3 (may be NULL; dy3 dense then) (+)= sum dy3.
 // Same conventions as bts_lp_conv3d_bwd_weight (dup_start / dup_shift fold both kernels alike).  The workspace query returns -1 and the
-// call 1 (nothing launched) where the streaming kernel does not take the shape: run bts_lp_conv3d_bwd_weight twice.  BTS_LP_WPAIR=0: never.
+// call 1 (nothing launched) where the streaming kernel does not take the shape: run bts_lp_conv3d_bwd_weight twice.
 extern "C" long bts_lp_conv3d_bwd_weight_pair_workspace(int N, int D, int H, int W, int Cin, int Cout) {
-  static const bool off = [] { const char* e = getenv("BTS_LP_WPAIR"); return e && atoi(e) == 0; }();
-  if (off || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || Cout % 8 != 0) return -1;
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || Cout % 8 != 0) return -1;
   const long alt = bts_lp_wgd_workspace_(N, D, H, W, Cin, Cout);
   if (alt <= 0) return -1;
   const long part = ((alt / 27 * 28 + 255) & ~255L);
@@ -3764,42 +3724,19 @@ extern "C" int bts_lp_block_bwd(int dtype, const void* dout, int lddo, const voi
   double* dbp1 = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(scratch + (long)N * F + (long)N * R) + 63) & ~(uintptr_t)63);
   double* dbp2 = dbp1 + (N * (long)G > 2048 ? N * (long)G : 2048L) * F + 8;
   (void)hipGetLastError();
-  // BTS_LP_FUSE_BLOCK_BWD_REDUCE=0 (A/B): the two light reduce passes of the separate routes, then the fused apply pass
-  const char* fr = getenv("BTS_LP_FUSE_BLOCK_BWD_REDUCE");
-  int Bse = G * B;
-  if (fr && atoi(fr) == 0) {
-    long vspan;
-    Bse = lp_se_blocks(V, N, F, &vspan);
-    if (dtype == LP_F16) {
-      hipLaunchKernelGGL(lp_gn_bwd_reduce_kernel<TF16>, dim3(B, N * G), dim3(256), 0, stream, (const unsigned short*)c2x, (const unsigned short*)dout, gamma, beta, mean, rstd, partial, E, L, span, F, G, cg, lddo, 1);
-      hipLaunchKernelGGL(lp_se_bwd_reduce_kernel<TF16>, dim3(Bse, N), dim3(256), 0, stream, (const unsigned short*)dout, (const unsigned short*)res, sp, ds, sep, V, F, lddo, vspan);
-    } else {
-      hipLaunchKernelGGL(lp_gn_bwd_reduce_kernel<TBF16>, dim3(B, N * G), dim3(256), 0, stream, (const unsigned short*)c2x, (const unsigned short*)dout, gamma, beta, mean, rstd, partial, E, L, span, F, G, cg, lddo, 1);
-      hipLaunchKernelGGL(lp_se_bwd_reduce_kernel<TBF16>, dim3(Bse, N), dim3(256), 0, stream, (const unsigned short*)dout, (const unsigned short*)res, sp, ds, sep, V, F, lddo, vspan);
-    }
-  } else {
 #define LP_BB_R(TT) hipLaunchKernelGGL(lp_blk_bwd_reduce_kernel<TT>, dim3(B, N * G), dim3(256), 0, stream, (const unsigned short*)c2x, (const unsigned short*)dout, (const unsigned short*)res, sp, gamma, beta, mean, rstd, partial, sep, ds, E, L, span, F, G, cg, lddo)
-    if (dtype == LP_F16) LP_BB_R(TF16); else LP_BB_R(TBF16);
+  if (dtype == LP_F16) LP_BB_R(TF16); else LP_BB_R(TBF16);
 #undef LP_BB_R
-  }
   BTS_LAUNCH_CHECK();
   // Between the reduce and the apply pass (review: ~100 launches of 5-10 us on this chain per step): ONE launch for the two finalizes that
   // only need the reduce pass's partials (GroupNorm class sums -> dgamma / dbeta / c1 / c2; gate partials -> per-(n, c) sums), then the
   // per-sample SE-MLP backward (dgap: the apply pass needs it).  The sums over the samples (dW1, dW2, dw_sp) and the two bias-gradient
-  // finalizes wait for the tail launch behind the apply pass: nothing on the chain reads them.  BTS_LP_BLK_BWD_MERGE=0: the six launches (A/B).
-  static const bool merge = [] { const char* e = getenv("BTS_LP_BLK_BWD_MERGE"); return !(e && atoi(e) == 0); }();
-  if (merge) {
-    hipLaunchKernelGGL(lp_blk_bwd_middle_kernel, dim3(G + (N * F + 3) / 4), dim3(256), 0, stream, partial, gamma, dgamma, dbeta, c1, c2, sep, red, N, G, B, cg,
-                       (double)L, Bse, F);
-    BTS_LAUNCH_CHECK();
-    const int r = bts_se_mlp_bwd_sample_(red, scratch, h, ch, w1, w2, dgap, N, V, F, R, stream);
-    if (r != BTS_OK) return r;
-  } else {
-    hipLaunchKernelGGL(lp_gn_bwd_finalize_kernel, dim3(G), dim3(256), 0, stream, partial, gamma, dgamma, dbeta, c1, c2, N, G, B, cg, (double)L, 1);
-    BTS_LAUNCH_CHECK();
-    const int r = bts_se_bwd_middle_(sep, red, scratch, gap, h, ch, w1, w2, dw1, dw2, dwsp, dgap, N, Bse, V, F, R, 1, stream);
-    if (r != BTS_OK) return r;
-  }
+  // finalizes wait for the tail launch behind the apply pass: nothing on the chain reads them.
+  hipLaunchKernelGGL(lp_blk_bwd_middle_kernel, dim3(G + (N * F + 3) / 4), dim3(256), 0, stream, partial, gamma, dgamma, dbeta, c1, c2, sep, red, N, G, B, cg,
+                     (double)L, G * B, F);
+  BTS_LAUNCH_CHECK();
+  const int r = bts_se_mlp_bwd_sample_(red, scratch, h, ch, w1, w2, dgap, N, V, F, R, stream);
+  if (r != BTS_OK) return r;
   int Ba;
   const long per = lp_chunk_per(L, (long)N * G, &Ba, 2048);
   const long blocks = (long)N * G * Ba;
@@ -3807,21 +3744,10 @@ extern "C" int bts_lp_block_bwd(int dtype, const void* dout, int lddo, const voi
   if (dtype == LP_F16) LP_BB_A(TF16); else LP_BB_A(TBF16);
 #undef LP_BB_A
   BTS_LAUNCH_CHECK();
-  if (merge) {
-    const int np = (R * F + 255) / 256;
-    hipLaunchKernelGGL(lp_blk_bwd_tail_kernel, dim3(np + (dbias_c2 ? F : 0) + (dbias_pt ? F : 0)), dim3(256), 0, stream, red, gap, h, dw1, dw2, dwsp, scratch,
-                       N, F, R, np, dbias_c2 ? dbp1 : (const double*)nullptr, dbias_c2, dbias_pt ? dbp2 : (const double*)nullptr, dbias_pt, (int)blocks);
-    BTS_LAUNCH_CHECK();
-    return BTS_OK;
-  }
-  if (dbias_c2 != nullptr) {
-    hipLaunchKernelGGL(lp_dbias_finalize_kernel, dim3(F), dim3(256), 0, stream, dbp1, dbias_c2, (int)blocks, F, 1);
-    BTS_LAUNCH_CHECK();
-  }
-  if (dbias_pt != nullptr) {
-    hipLaunchKernelGGL(lp_dbias_finalize_kernel, dim3(F), dim3(256), 0, stream, dbp2, dbias_pt, (int)blocks, F, 1);
-    BTS_LAUNCH_CHECK();
-  }
+  const int np = (R * F + 255) / 256;
+  hipLaunchKernelGGL(lp_blk_bwd_tail_kernel, dim3(np + (dbias_c2 ? F : 0) + (dbias_pt ? F : 0)), dim3(256), 0, stream, red, gap, h, dw1, dw2, dwsp, scratch,
+                     N, F, R, np, dbias_c2 ? dbp1 : (const double*)nullptr, dbias_c2, dbias_pt ? dbp2 : (const double*)nullptr, dbias_pt, (int)blocks);
+  BTS_LAUNCH_CHECK();
   return BTS_OK;
 }
 

@@ -358,8 +358,7 @@ int bts_lp_k1_launch_(int dtype, const void* x, const void* wp, const float* bia
   p.ncg = (p.NB + cb - 1) / cb;
   if (blocks * p.ncg > 0x7fffffffL) return 1;
   const dim3 grid((unsigned)(blocks * p.ncg));
-  static const bool lf_on = !(getenv("BTS_LP_K1F") && atoi(getenv("BTS_LP_K1F")) == 0);
-  const bool lf = lf_on && Cin % 64 == 0;      // whole 128-byte row pieces per load instruction
+  const bool lf = Cin % 64 == 0;      // whole 128-byte row pieces per load instruction
   const bool gp = gap_part != nullptr;
 #define K1_GO(KERN, T_) do {                                                                                                          \
     if (cb == 2) { if (gp) hipLaunchKernelGGL((KERN<T_, 2, true>), grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL((KERN<T_, 2, false>), grid, dim3(256), 0, stream, p); } \

@@ -50,8 +50,6 @@ struct LpS1dParams {
   // item order: cout group fastest, then the tiles of a block of bx x by x bz tiles (x fastest), then the blocks (x fastest), then
   // the samples -- a block is what the 32 workgroups of an XCD hold at a time, so the halo voxels its tiles share are fetched from
   // HBM once and found in that XCD's L2 by the neighbours.  Divisions by run-time constants as multiply-high + shift.
-  int dbg;          // timing experiments (builds with -DBTS_TIMING_EXPERIMENTS only): 1 no output stores, 2 no halo traffic, 4 no matrix instructions,
-                    // 8 no fragment reads from LDS, 16 no weight traffic
   int bx, by, bz_;
   unsigned bvol_, nbx_, nby_, nbz_;
   unsigned dv_mul[7], dv_sh[7];    // divisors: ncg, bx*by*bz, bx, by, ntx/bx, nty/by, ntz/bz
@@ -182,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void lp_s1d_kernel(const LpS1dParams p) {
   auto dma_item = [&](const Item& t, bool live) {   // halo origin + per-chunk offsets of the item the NEXT k-step belongs to
     const unsigned short* xorg = p.x + ((((long)t.n * p.D + (t.oz0 - 1)) * p.H + (t.oy0 - 1)) * p.W + (t.ox0 - 1)) * (long)p.ldx;
     xr = __builtin_amdgcn_make_buffer_rsrc((void*)xorg, 0, 0x7fffffff, 0x00020000);
-    const int zb = (live && !(BTS_DBG(p) & 2)) ? t.oz0 - 1 : 0x100000;       // no next item: every voxel out of range (zeros, no traffic)
+    const int zb = live ? t.oz0 - 1 : 0x100000;       // no next item: every voxel out of range (zeros, no traffic)
 #pragma unroll
     for (int r = 0; r < NH; ++r) {
       const int vx = hcrd[r] & 0xff, vy = (hcrd[r] >> 8) & 0xff, vz = hcrd[r] >> 16;
@@ -208,7 +206,6 @@ __global__ __launch_bounds__(512, 2) void lp_s1d_kernel(const LpS1dParams p) {
     wdst[r] = c < G::NWC ? G::OFF_W + c * 1024 : G::OFF_SCR;
   }
   auto w_soff = [&](int cg, int ks, int dz, bool live) -> unsigned {
-    if (BTS_DBG(p) & 16) return 0x80000000u;
     return live ? (unsigned)((((cg * p.KS + ks) * 3) + dz) * G::WSTAGE) : 0x80000000u;    // (no next item: nothing to fetch)
   };
   auto issue_w1 = [&](int r, unsigned soff, int dz) {
@@ -265,13 +262,11 @@ __global__ __launch_bounds__(512, 2) void lp_s1d_kernel(const LpS1dParams p) {
   u32x4 Bc[6], Ac[3], Bn[6], An[3];
   auto ldB = [&](u32x4 (&B)[6], const unsigned char* hb, auto dzc, auto dxc) {     // hb = the halo buffer of this k-step
     constexpr int DZ = decltype(dzc)::value, DX = decltype(dxc)::value;
-    if (BTS_DBG(p) & 8) { asm volatile("" : "+v"(B[0]), "+v"(B[1]), "+v"(B[2]), "+v"(B[3]), "+v"(B[4]), "+v"(B[5])); return; }
 #pragma unroll
     for (int j = 0; j < 6; ++j) B[j] = *reinterpret_cast<const u32x4*>(hb + hbB[DX] + ((DZ * PS) + j * SX) * 32);
   };
   auto ldA = [&](u32x4 (&A)[3], auto dzc, auto dxc) {
     constexpr int DZ = decltype(dzc)::value, DX = decltype(dxc)::value;
-    if (BTS_DBG(p) & 8) { asm volatile("" : "+v"(A[0]), "+v"(A[1]), "+v"(A[2])); return; }
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) A[dy] = *reinterpret_cast<const u32x4*>(lds + wbA + DZ * G::WSTAGE + (dy * 3 + DX) * G::WTAP);
   };
@@ -280,13 +275,8 @@ __global__ __launch_bounds__(512, 2) void lp_s1d_kernel(const LpS1dParams p) {
   auto mm = [&](const u32x4 (&A)[3], const u32x4 (&B)[6], auto&& hook) {
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      if (!(BTS_DBG(p) & 4)) {
 #pragma unroll
-        for (int v = 0; v < 4; ++v) acc[v] = T::mfma(A[dy], B[v + dy], acc[v]);
-      } else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) asm volatile("" ::"v"(A[dy]), "v"(B[v + dy]));
-      }
+      for (int v = 0; v < 4; ++v) acc[v] = T::mfma(A[dy], B[v + dy], acc[v]);
       hook(dy);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -324,7 +314,7 @@ __global__ __launch_bounds__(512, 2) void lp_s1d_kernel(const LpS1dParams p) {
       // ---- stage 0 (dz = 0): requests W(ks, 2) then the first half of the next k-step's halo tile ----
       // (SC: the centre-tap pair of THIS k-step, requested after the second group of the stage 1 before, may still be in flight here -- it
       // sits behind every request this stage needs and ahead of W(ks, 1), so the stage-1 wait below covers it)
-#ifdef S1D_SC_LATE      // A/B build (make variantf FILE=lowp_s1d NAME=sclate EXTRA=-DS1D_SC_LATE): the pair requested in stage 2, as first built
+#ifdef S1D_SC_LATE      // A/B build (make alt NAME=sclate EXTRA=-DS1D_SC_LATE): the pair requested in stage 2, as first built
       constexpr int NSC = 0;
 #else
       constexpr int NSC = SC ? 5 : 0;
@@ -375,10 +365,8 @@ __global__ __launch_bounds__(512, 2) void lp_s1d_kernel(const LpS1dParams p) {
       __builtin_amdgcn_sched_barrier(0);
       mm(Ac, Bc, [&](int i) { hook1(i + 3); });
       if constexpr (SC) {      // the shortcut's k-step: centre tap only
-        if (!(BTS_DBG(p) & 4)) {
 #pragma unroll
-          for (int v = 0; v < 4; ++v) acc[v] = T::mfma(A2, B2[v], acc[v]);
-        }
+        for (int v = 0; v < 4; ++v) acc[v] = T::mfma(A2, B2[v], acc[v]);
         __builtin_amdgcn_sched_barrier(0);
         // ... and the NEXT k-step's pair right away, into the registers just read: behind all of this stage's requests (they went out with
         // the first two groups), a stage ahead of W(next, 1) -- two and a third stages of flight time before the matrix pipe asks for it
@@ -448,7 +436,7 @@ __global__ __launch_bounds__(512, 2) void lp_s1d_kernel(const LpS1dParams p) {
           for (int v = 0; v < 4; ++v) {
             const bool oks = oz < p.D && oy + v < p.H && ox < p.W;
             const bool ok = co < p.Cout && oks;
-            const unsigned off = (ok && !(BTS_DBG(p) & 1)) ? (unsigned)((((oz * p.H + oy + v) * p.W + ox) * p.ldy + cb_col + 16 * qp + 8 * h) * 2) : 0x80000000u;
+            const unsigned off = ok ? (unsigned)((((oz * p.H + oy + v) * p.W + ox) * p.ldy + cb_col + 16 * qp + 8 * h) * 2) : 0x80000000u;
             float f[4], g2[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { f[j] = acc[v][8 * qp + j]; g2[j] = acc[v][8 * qp + 4 + j]; }
@@ -592,23 +580,21 @@ static double s1d_plan_shape(int N, int D, int H, int W, int Cin, int Cout, int 
   auto cost = [&](int per, int split) { return ((double)((pl.nitems * split + 255) / 256) + 0.1 * (double)(pl.nitems * split) / 256.0) * (per + 1.5); };
   pl.ksplit = 1; pl.ks_per = KS;
   double best = cost(KS, 1);
-  { const char* e = getenv("BTS_LP_S1D_SPLIT_ITEMS"); if (pl.nitems < (e ? atol(e) : 160) && KS >= 4) {
+  if (pl.nitems < 160 && KS >= 4) {
     for (int ks = 2; ks <= KS / 2 && ks <= 16; ++ks) {
       const int per = (KS + ks - 1) / ks, split = (KS + per - 1) / per;
       const double c = cost(per, split) + 0.5 * split;      // (+ the reduce pass grows with the split)
       if (c < best - 1e-9) { best = c; pl.ks_per = per; pl.ksplit = split; }
     }
-  } }
+  }
   return best;
 }
 static bool s1d_plan(int N, int D, int H, int W, int Cin, int Cout, S1dPlan& pl) {
   if (!s1d_enabled() || Cin % 16 != 0 || Cout % 8 != 0 || W < 12) return false;
-  { const char* fl = getenv("BTS_LP_S1D_FLOOR"); if ((long)N * D * H * W < (fl ? atol(fl) : 4096)) return false; }
+  if ((long)N * D * H * W < 4096) return false;
   // x extent of a tile: 32, or 16 with two z planes per fragment -- whichever wastes less of the 256 CUs on this grid (20x24x20, the
   // deepest level of the full inference volume: 32 wide gives 120 items = one round at split 2, 16 wide 144 items = two rounds;
   // 80x96x80: 16 wide tiles it exactly, 1200 items against 1440, 118 us against 136)
-  const char* e = getenv("BTS_LP_S1D_TXL");
-  if (e) return s1d_plan_shape(N, D, H, W, Cin, Cout, atoi(e) == 4 ? 4 : 5, pl) >= 0.0;
   S1dPlan a, b;
   const double ca = s1d_plan_shape(N, D, H, W, Cin, Cout, 5, a), cb = s1d_plan_shape(N, D, H, W, Cin, Cout, 4, b);
   if (ca < 0.0 && cb < 0.0) return false;
@@ -689,10 +675,6 @@ int bts_lp_s1d_launch_(int dtype, const void* x, const void* wp_dma, const float
     if (gnp != nullptr) return BTS_ERR_WORKSPACE;      // (the caller sized the partial array for the split plan)
     p.ksplit = 1; p.ks_per = p.KS;
   }
-  p.dbg = 0;
-#ifdef BTS_TIMING_EXPERIMENTS
-  { const char* e = getenv("BTS_S1D_DBG"); if (e) p.dbg = atoi(e); }
-#endif
   p.x2 = (const unsigned short*)x2; p.wp2 = (const unsigned short*)wp2; p.ldx2 = ldx2;
   p.ysplit = ysplit; p.ycol = ysplit ? 0 : 32;
   p.gnp = gnp; p.gn_G = gn_G; p.gn_zt = gn_G > 0 ? D / gn_G : 1;

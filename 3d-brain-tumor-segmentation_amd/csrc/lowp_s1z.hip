@@ -82,13 +82,8 @@ __global__ __launch_bounds__(512, 1) void lp_s1z_kernel(const LpS1zParams p) {
   constexpr int OFF_P = WB, OFF_BIAS = WB + 2 * PLB, OFF_SCR = OFF_BIAS + 256;
   constexpr int OFF_BIAS2 = OFF_BIAS + 128;   // FS: the shortcut's bias (32 floats)
   constexpr int OFF_GB = OFF_SCR + 1024;      // GNB: gamma'[32] | beta'[32] | mean[32] | rstd[32] of the current sample (floats); GNA: gamma | beta | mean | rstd
-#ifdef S1Z_EXP_2ISSUE   // timing experiment: two waves issue all plane requests of a stage (is request back-pressure what stalls the others?)
-  constexpr int NREQ = NCHK * KS, NR = NREQ / 2;
-#define S1Z_ID(j) ((wave < 2) ? (wave * NR + (j)) : 0x7fff)
-#else
   constexpr int NREQ = NCHK * KS, NR = (NREQ + 7) / 8;       // plane requests per stage / per wave
 #define S1Z_ID(j) ((j) * 8 + wave)
-#endif
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -167,9 +162,6 @@ __global__ __launch_bounds__(512, 1) void lp_s1z_kernel(const LpS1zParams p) {
 #pragma unroll
     for (int i = 0; i < NSL; ++i)
       if (tid + 512 * i < NSLOT) raw[i] = *reinterpret_cast<const u32x4*>(lds + OFF_P + buf * PLB + (tid + 512 * i) * 16);
-#ifdef S1Z_EXP_GNA_NOLDS      // timing experiment (wrong results): the transform without its arithmetic and stores
-    return;
-#endif
 #pragma unroll
     for (int i = 0; i < NSL; ++i) {
       if (tid + 512 * i < NSLOT) {
@@ -417,9 +409,6 @@ __global__ __launch_bounds__(512, 1) void lp_s1z_kernel(const LpS1zParams p) {
         unsigned d0 = pack2<T>(f[0], f[1]), d1 = pack2<T>(f[2], f[3]), d2 = pack2<T>(g2[0], g2[1]), d3 = pack2<T>(g2[2], g2[3]);
         asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\tv_nop"
                      : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
-#ifdef S1Z_EXP_NOSTORE   // timing experiment (wrong results)
-        if (z == -12345)
-#endif
         __builtin_amdgcn_raw_buffer_store_b128(u32x4{d0, d1, d2, d3}, yr, off, 0, LP_OUT_STORE_AUX);
         if constexpr (GNB) {      // (after the exchange: the STORED couts co .. co + 7 of voxel l32, as a reduce pass would read them)
           dst_ = u32x4{d0, d1, d2, d3};
@@ -500,17 +489,7 @@ __global__ __launch_bounds__(512, 1) void lp_s1z_kernel(const LpS1zParams p) {
         ldA(A[(g + 1) & 1], g + 1);
         if ((g + 1) % 3 == 0) ldB(B[bs ^ 1], g + 1);
       }
-#ifdef S1Z_EXP_NODMA     // timing experiment (wrong results)
-      if (g < NR) issue_filler();
-#else
-#ifdef S1Z_EXP_2ISSUE
-      if (g == 0 && wave < 2) {
-        for (int j = 0; j < NR; ++j) { if (more) issue1(j, zp + 1, buf ^ 1); else issue_filler(); }
-      }
-#else
       if (g < NR) { if (more) issue1(g, zp + 1, buf ^ 1); else issue_filler(); }
-#endif
-#endif
       if constexpr (GNB) {
         if (g == (NR < NG ? NR : NG - 1)) gnb_request(zp - 1);       // (after this stage's plane requests)
       }
@@ -527,21 +506,12 @@ __global__ __launch_bounds__(512, 1) void lp_s1z_kernel(const LpS1zParams p) {
       }
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
-#ifdef S1Z_EXP_NOMFMA   // timing experiment (wrong results)
-        if (ky) { asm volatile("" ::"v"(A[g & 1][ky]), "v"(B[bs][ky + 1])); continue; }
-#endif
         acc[s][0] = T::mfma(A[g & 1][ky], B[bs][ky], acc[s][0]);
         acc[s][1] = T::mfma(A[g & 1][ky], B[bs][ky + 1], acc[s][1]);
-#ifdef S1Z_EXP_MFMA2     // timing experiment (wrong results): twice the matrix work per stage
-        acc[s][0] = T::mfma(A[g & 1][ky], B[bs][ky], acc[s][0]);
-        acc[s][1] = T::mfma(A[g & 1][ky], B[bs][ky + 1], acc[s][1]);
-#endif
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-#ifndef S1Z_EXP_2ISSUE
     static_assert(NR <= NG, "a stage has one request slot per group");
-#endif
   };
 
   xplane = (unsigned)(p.H * p.W * p.ldx * 2);

@@ -232,9 +232,6 @@ __global__ __launch_bounds__(512, 1) void lp_wgd_kernel(const LpWgdParams p) {
     return r;
   };
   auto issue1 = [&](const StageReq& r, int j) {
-#ifdef WGD_EXP_NODMA    // timing experiment (wrong results): no requests after the prologue
-    if (r.qslot >= 0) return;
-#endif
     if (kind_of(j) == 1) {
       wgd_dma16(qr, lds0 + (unsigned)(WGD_QBASE + r.qslot * WGD_QPL + dst_of(j)), r.qok ? voff[j] : 0x80000000u, r.qso);
     } else {
@@ -278,9 +275,6 @@ __global__ __launch_bounds__(512, 1) void lp_wgd_kernel(const LpWgdParams p) {
     qoff[h] = (unsigned)(WGD_QBASE + (4 * hv) * WGD_QROW + xl * 64 + ps * 16 + (c4 & 1) * 8);
   }
   auto trd = [&](const unsigned char* a) -> u32x2 {
-#ifdef WGD_EXP_NOREAD   // timing experiment (wrong results): no operand reads from LDS
-    return u32x2{(unsigned)(uintptr_t)a, 1u};
-#endif
     return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a)));
   };
   f32x4 acc[27];
@@ -323,12 +317,7 @@ __global__ __launch_bounds__(512, 1) void lp_wgd_kernel(const LpWgdParams p) {
     rdq(0);
     pf[0] = rdp(0);
     pf[1] = rdp(1);
-#ifdef WGD_EXP_DMA_FIRST   // timing experiment: all six requests at the start of the stage
-#pragma unroll
-    for (int j = 0; j < 6; ++j) issue1(rq, j);
-#else
     issue1(rq, 0);
-#endif
     rdq(1);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -337,12 +326,7 @@ __global__ __launch_bounds__(512, 1) void lp_wgd_kernel(const LpWgdParams p) {
       if (st + 2 < 18) pf[(st + 2) % 3] = rdp(st + 2);
       if (st == 2) rdq(2);
       if (st == 5) rdq(3);
-#ifdef WGD_EXP_DMA_STAGGER   // timing experiment: the two row halves (SIMD partners) issue in different thirds of the stage
-      if (hv == 0 ? (st == 1 || st == 2 || st == 3 || st == 4 || st == 5) : (st == 9 || st == 10 || st == 11 || st == 12 || st == 13))
-        issue1(rq, hv == 0 ? st : st - 8);
-#elif !defined(WGD_EXP_DMA_FIRST)
       if (st == 1 || st == 4 || st == 7 || st == 10 || st == 13) issue1(rq, (st + 2) / 3);
-#endif
       const u32x4 a = pf[st % 3];
       if constexpr (K1F) {      // centre tap (ky = 1, kx = 1) of the 1x1x1 conv: P row prow against Q2 row prow - 1 of the same plane
         if (kx == 0 && prow >= 1 && prow <= 4) q2f = rdq2(prow - 1);        // (read one step ahead of its use)
@@ -355,9 +339,6 @@ __global__ __launch_bounds__(512, 1) void lp_wgd_kernel(const LpWgdParams p) {
         for (int ky = 0; ky < 3; ++ky) {
           const int qrow = prow - ky;
           if (qrow < 0 || qrow > 3) continue;
-#ifdef WGD_EXP_NOMFMA   // timing experiment (wrong results): one matrix instruction per step keeps the reads alive
-          if (kz != 0 || ky != (prow > 3 ? prow - 3 : 0)) continue;
-#endif
           acc[(kz * 3 + ky) * 3 + kx] = Mfma16<T>::run(a, qfp[(kz + R) % 3][qrow], acc[(kz * 3 + ky) * 3 + kx]);
         }
       __builtin_amdgcn_sched_barrier(0);
@@ -400,9 +381,7 @@ __global__ __launch_bounds__(512, 1) void lp_wgd_kernel(const LpWgdParams p) {
 #pragma unroll
       for (int qrow = 0; qrow < 4; ++qrow) { qfp[2][qrow] = qfp[1][qrow]; qfp[1][qrow] = qfp[0][qrow]; }
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // the next stage's planes have landed; this stage's requests stay in flight
-#ifndef WGD_EXP_NOBAR   // timing experiment (wrong results): no stage barrier
       __builtin_amdgcn_s_barrier();
-#endif
       asm volatile("" ::: "memory");
       if constexpr (GNA) {      // the next stage's P plane (zp + 1) has landed: normalise it before anyone reads it
         if (zp < zhi) { ga_apply(pb_i + 1 == WGD_NPB ? 0 : pb_i + 1, zp + 1); }

@@ -36,9 +36,6 @@ __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
 }
 // y transform of one z-combined row set
 __device__ __forceinline__ void wino_yt(const f32x4 (&c)[4], f32x4 (&v)[4]) {
-#ifdef W3_EXP_NOXF    // timing experiment (wrong results): no transforms
-  return;
-#endif
   v[0] = sub4(c[0], c[2]);
   v[1] = add4(c[1], c[2]);
   v[2] = sub4(c[2], c[1]);

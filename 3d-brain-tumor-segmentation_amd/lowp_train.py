@@ -90,21 +90,9 @@ class LowPrecisionTrainer(object):
         self._packs = {}
         self._pads = {}
         self._pack_table = lowp.PackTable()
-        # gate + GroupNorm-2 backward of a block in one pair of passes (bts_lp_block_bwd): 89.4 -> 87.5 ms per batch-8 step measured by
-        # interleaved rounds inside one process (scripts/lp_fuse_ab.py; A/B between processes drowns in the pool's run-to-run spread).
-        # BTS_LP_FUSE_BLOCK_BWD=0: the two separate routes
-        self.fuse_block_bwd = os.environ.get('BTS_LP_FUSE_BLOCK_BWD', '1') != '0'
-        # conv2's data gradient + GroupNorm-1's backward through bts_lp_conv3d_bwd_data_gn_bwd (class sums from the conv's epilogue where
-        # the streaming kernel runs the layer); BTS_LP_FUSE_GN1_BWD=0: the two separate calls (A/B)
-        self.fuse_gn1_bwd = os.environ.get('BTS_LP_FUSE_GN1_BWD', '1') != '0'
         # GroupNorm-1 + ReLU applied inside conv2's forward and weight-gradient kernels where both can (the normalised tensor is never
         # written); BTS_LP_FUSE_GN1_APPLY=0: the separate apply pass everywhere (A/B)
         self.fuse_gn1_apply = os.environ.get('BTS_LP_FUSE_GN1_APPLY', '1') != '0'
-        # conv1 + shortcut + squeeze from one pass over the block input (bts_lp_conv3d_fwd_gn_shortcut); BTS_LP_FS=0 in the library's
-        # environment is the A/B switch
-        self.fuse_shortcut_fwd = True
-        # level 0's [skip | up-sampled] as two dense operands (see step()); BTS_LP_FWD_SPLIT=0: the 64-wide slab (A/B)
-        self.split_level0 = os.environ.get('BTS_LP_FWD_SPLIT', '1') != '0'
         self.last_labels = None
         self._clock = None
 
@@ -220,7 +208,7 @@ class LowPrecisionTrainer(object):
 
     def _level0_split_ok(self, n, d, h, w, nb, f, spare, dec):
         """level 0 as two dense 32-channel operands: only where EVERY reader of the pair takes the list (there is no single-tensor fallback)"""
-        if not self.split_level0 or nb != 1 or f != 32 or spare != 32 or not dec.levels or not self.fuse_shortcut_fwd:
+        if nb != 1 or f != 32 or spare != 32 or not dec.levels:
             return False
         up, blk = dec.levels[-1]
         from ._lib import lib
@@ -258,7 +246,7 @@ class LowPrecisionTrainer(object):
         # conv1 (+ the statistics of its output) and the shortcut conv (+ the gate's squeeze) from ONE pass over x where the z-marching
         # kernel takes the layer (round 6: the shortcut is a second set of output columns at the centre tap); else the shortcut conv +
         # squeeze in one pass of their own.  Then the SE-MLP (main stream: see lowp.gate_branch)
-        both = lowp.conv_gn_shortcut(code, tdt, x, wp_c1, blk.conv1_b.t, f, blk.norm1, wp_pt, blk.ptwise_b.t) if self.fuse_shortcut_fwd else None
+        both = lowp.conv_gn_shortcut(code, tdt, x, wp_c1, blk.conv1_b.t, f, blk.norm1, wp_pt, blk.ptwise_b.t)
         if both is not None:
             c1, m1, r1, res, gap = both
             hbuf, ch = ops.se_mlp_fwd(gap, blk.se_w1.t, blk.se_w2.t)
@@ -308,8 +296,9 @@ class LowPrecisionTrainer(object):
         lp1 = lowp.wgrad_supported(ops.K3S1, xc, f)
         # conv branch: GN2 (+ReLU) -> conv2 -> GN1 (+ReLU) -> conv1
         # gate backward and GroupNorm-2 backward both read dout: one pair of passes where the fused kernels' tiling fits
+        # (bts_lp_block_bwd: 89.4 -> 87.5 ms per batch-8 step)
         fused = None
-        if lp2 and lp1 and n2._mode == ops.GN_SLAB and self.fuse_block_bwd:
+        if lp2 and lp1 and n2._mode == ops.GN_SLAB:
             fused = lowp.block_bwd(code, self.tdt, dout, s['res'], s['c2'], s['sp'], s['gap'], s['hbuf'], s['ch'], blk.se_w1.t, blk.se_w2.t,
                                    blk.spatial_k.t.reshape(-1), n2.gamma.t, n2.beta.t, s['m2'], s['r2'], n2.groups, self._gslot(blk.se_w1),
                                    self._gslot(blk.se_w2), self._gslot(blk.spatial_k).reshape(-1), self._gslot(n2.gamma), self._gslot(n2.beta),
@@ -335,7 +324,7 @@ class LowPrecisionTrainer(object):
                                                              accumulate=True))
         wp_c2b = self._pk((key, 'c2b'), ops.K3S1, blk.conv2_k, f, f, role=ops.ROLE_BWD)
         both = None
-        if self.fuse_gn1_bwd and n1._mode == ops.GN_SLAB and dc2_16.shape[-1] == f:
+        if n1._mode == ops.GN_SLAB and dc2_16.shape[-1] == f:
             # conv2's data gradient and GroupNorm-1's backward as one library call: on the layers the z-marching conv takes, the class
             # sums of GroupNorm's backward leave the conv's epilogue (no reduce pass over da and c1)
             both = lowp.conv_bwd_data_gn_bwd(code, self.tdt, dc2_16, wp_c2b, s['c1'], n1.gamma.t, n1.beta.t, s['m1'], s['r1'], self._gslot(n1.gamma),

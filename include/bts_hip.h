@@ -291,8 +291,7 @@ int bts_lp_conv3d_bwd_data(int kind, int dtype, const void* dy, const void* wp_b
  * dx_split (elements; 0 = dx is one (N,D,H,W,Cin) view): columns [32 b, 32 b + 32) go to dx + b * dx_split, every block a tensor of its
  * own with voxel stride lddx -- the gradient of the decoder's concat of 32-channel tensors (decoder.py:75) leaves as DENSE tensors whose
  * readers fetch whole 128-byte lines.  Only the fused tiled kernel writes that form: bts_lp_conv3d_bwd_data_sc_split_ok (1 / 0) says
- * whether it takes the shape; BTS_ERR_UNSUPPORTED otherwise.  BTS_LP_SC=0 in the environment: always the two launches, BTS_LP_SC_SPLIT=0:
- * _split_ok answers 0 (A/B aids) */
+ * whether it takes the shape; BTS_ERR_UNSUPPORTED otherwise.  BTS_LP_SC=0 in the environment: always the two launches (A/B aid) */
 long bts_lp_conv3d_bwd_data_sc_workspace(int N, int D, int H, int W, int Cin, int Cout);
 int bts_lp_conv3d_bwd_data_sc_split_ok(int N, int D, int H, int W, int Cin, int Cout);
 int bts_lp_conv3d_bwd_data_sc(int dtype, const void* dy, const void* wp_bwd, const void* dy2, const void* wp2_bwd, void* dx, long dx_split,
@@ -304,7 +303,7 @@ int bts_lp_conv3d_bwd_data_sc(int dtype, const void* dy, const void* wp_bwd, con
  * the HBM-bound 1x1x1 weight-gradient launch and its own read of the Cin-wide x go away.  db3 (may be NULL; dy3 dense then) (+)= sum dy3.
  * dup_start / dup_shift fold both kernels alike.  x_split (elements; 0 = one tensor): x as a list of Cin / 32 dense 32-channel tensors x +
  * b * x_split with voxel stride ldx (the operands of a concat; no fold then).  Workspace query -1 / return value 1 (nothing launched) outside the streaming kernel's
- * shapes (W % 32, H % 8, large volumes): run bts_lp_conv3d_bwd_weight twice.  BTS_LP_WPAIR=0 in the environment: never (A/B aid) */
+ * shapes (W % 32, H % 8, large volumes): run bts_lp_conv3d_bwd_weight twice. */
 long bts_lp_conv3d_bwd_weight_pair_workspace(int N, int D, int H, int W, int Cin, int Cout);
 int bts_lp_conv3d_bwd_weight_pair(int dtype, const void* x, long x_split, const void* dy3, const void* dy1, float* dw3, float* dw1, float* db3,
                                   void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy3,
@@ -387,17 +386,6 @@ long bts_lp_conv3d_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cou
 int bts_lp_conv3d_fwd_gn(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd, void* workspace,
                          long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G, float eps,
                          bts_stream_t stream);
-/* bts_lp_conv3d_fwd_gn / bts_lp_conv1_gap ADDING to what y / res already hold (accumulate != 0), statistics / squeeze of the final sums: a
- * contraction split over its input channels whose parts become available at different times -- the decoder block's conv1 and shortcut over
- * [skip | up-sampled] (decoder.py:75; resnet.py:118,134): the skip part (with the bias) can run as soon as the encoder level is done, next
- * to the under-filled deep levels, the up-sampled part adds to it later (bias = NULL then).  The partial sum passes through the storage type
- * once.  Workspaces: bts_lp_conv3d_fwd_gn_workspace / bts_lp_conv1_gap_workspace */
-int bts_lp_conv3d_fwd_gn_acc(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd, void* workspace,
-                             long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G, float eps, int accumulate,
-                             bts_stream_t stream);
-int bts_lp_conv1_gap_acc(int dtype, const void* x, const void* wp, const float* bias, void* res, float* gap, void* workspace,
-                         long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldres, int accumulate,
-                         bts_stream_t stream);
 /* conv1 AND the shortcut of a ResnetBlock from ONE pass over the block input (resnet.py:118 and resnet.py:134 read the same `inputs`):
  * y = conv3x3x3(x) + bias with GroupNorm G's statistics of y (as bts_lp_conv3d_fwd_gn), res = conv1x1x1(x) + bias_pt and gap[n][c] = mean
  * over the voxels of the unrounded res (as bts_lp_conv1_gap).  The shortcut is a second set of output columns at the centre tap of the
@@ -407,7 +395,7 @@ int bts_lp_conv1_gap_acc(int dtype, const void* x, const void* wp, const float* 
  * operands of a concat (decoder.py:75) never materialised side by side, each read in whole lines (virtual concat as a list of
  * (ptr, C) segments); the two passes at any volume size (pass ldx = 32 to the workspace query).  Workspace query -1 / return value 1 (nothing
  * launched) outside the kernel's shapes: run bts_lp_conv1_gap +
- * bts_lp_conv3d_fwd_gn.  BTS_LP_FS=0 in the environment: never, BTS_LP_FS_PAIR=0: not on the two-pass form (A/B aids) */
+ * bts_lp_conv3d_fwd_gn.  BTS_LP_FS=0 in the environment: never (A/B aid) */
 long bts_lp_conv3d_fwd_gn_shortcut_workspace(int N, int D, int H, int W, int Cin, int ldx, int Cout, int G);
 int bts_lp_conv3d_fwd_gn_shortcut(int dtype, const void* x, long x_split, const void* wp, const float* bias, void* y, float* mean, float* rstd,
                                   const void* wp_pt, const float* bias_pt, void* res, float* gap, void* workspace, long workspace_bytes,

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""fp32 train step (CLI model, 128^3, batch 1): main chain on a HIGH-priority stream or the default one, weight-gradient kernels with
-their planned workgroup count or more, shorter workgroups (BTS_WGRAD_WGS) -- does finer-grained weight-gradient work let the main
-chain's HBM-bound passes in sooner?  ms per step, wall clock over `--steps` steps."""
+"""fp32 train step (CLI model, 128^3, batch 1): main chain on a HIGH-priority stream or the default one -- does priority let the main
+chain's HBM-bound passes in sooner than the weight-gradient kernels?  ms per step, wall clock over `--steps` steps."""
 import argparse
 import os
 import sys
@@ -38,7 +37,7 @@ def main():
         for _ in range(a.steps):
             train_step(m, opt, lf, df, x, y)
         torch.cuda.synchronize()
-    print('high=%d BTS_WGRAD_WGS=%s: %.3f ms per step' % (a.high, os.environ.get('BTS_WGRAD_WGS', '-'), (time.perf_counter() - t0) / a.steps * 1e3))
+    print('high=%d: %.3f ms per step' % (a.high, (time.perf_counter() - t0) / a.steps * 1e3))
 
 
 if __name__ == '__main__':
