@@ -31,21 +31,9 @@ void bts_prof_end(hipStream_t stream);
 #include "lowp_common.h"
 #include "finalize_parts.h"
 
-// lowp_s1d.hip: LDS-DMA staged stride-1 3x3x3 kernel (offered first; 1 = declined) and its part of the K3S1 image
+// lowp_s1d.hip: the DMA part of a K3S1 image (the stride-1 kernels' plans and launchers: lowp_common.h)
 long bts_lp_s1d_image_bytes_(int K, int N);
 int bts_lp_s1d_pack_(int dtype, const LpPackParams& p, void* dst, hipStream_t stream);
-long bts_lp_s1d_workspace_(int N, int D, int H, int W, int Cin, int Cout);
-long bts_lp_s1d_gn_B_(int N, int D, int H, int W, int Cin, int Cout, int Gn);
-// lowp_s1z.hip: z-marching stride-1 3x3x3 kernel for few channels (offered first; 1 = declined)
-long bts_lp_s1z_gn_B_(int N, int D, int H, int W, int Cin, int Cout, int Gn);
-int bts_lp_s1z_launch_(int dtype, const void* x, const void* wp, const float* bias, void* y, int N, int D, int H, int W, int Cin, int ldx,
-                       int Cout, int ldy, int accum, double* gn_part, int gn_G, hipStream_t stream, const LpGnbFuse* gb = nullptr,
-                       const LpGnaFuse* ga = nullptr, const void* x2 = nullptr, const void* wp2 = nullptr, int ldx2 = 0, void* y2 = nullptr,
-                       const float* bias2 = nullptr, double* gap_part = nullptr, int ldy2 = 0, int Cout2 = 0, int accum2 = 0,
-                       const void* xb = nullptr, int ldxb = 0);
-long bts_lp_s1z_fs_B_(int N, int D, int H, int W, int Cin, int ldx, int Cout, int Cout2);
-bool bts_lp_s1z_gna_ok_(int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int in_G);
-long bts_lp_s1z_gnb_B_(int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int Gn);
 // lowp_k1.hip: streaming 1x1x1 kernel (offered first; 1 = declined); gap partials per block of bts_lp_k1_gap_block_ positions
 int bts_lp_k1_gap_block_(long npos, long V, int Cin, int Cout);
 int bts_lp_s2t_launch_(int dtype, const void* x, const void* wp, const float* bias, void* y, int N, int D, int H, int W, int Cin, int ldx,
@@ -56,10 +44,6 @@ int bts_lp_k1_launch_(int dtype, const void* x, const void* wp, const float* bia
 int bts_lp_up_launch_(int dtype, const void* x, const void* wp_dma, const float* bias, void* y, int N, int D, int H, int W, int Cin, int ldx,
                       int Cout, int ldy, int accum, hipStream_t stream, double* gnp = nullptr, int gn_G = 0);
 long bts_lp_up_gn_B_(int N, int D, int H, int W, int Cin, int Cout, int Gn);
-int bts_lp_s1d_launch_(int dtype, const void* x, const void* wp_dma, const float* bias, void* y, void* ws, long ws_bytes, int N, int D, int H,
-                       int W, int Cin, int ldx, int Cout, int ldy, int accum, double* gnp, int gn_G, hipStream_t stream,
-                       const void* x2 = nullptr, const void* wp2 = nullptr, int ldx2 = 0, long ysplit = 0);
-bool bts_lp_s1d_sc_split_ok_(int N, int D, int H, int W, int K, int Ncols);
 
 // =====================================================================================================================
 // weight packing: Keras layout fp32 -> [tap][k-step of 16 cin][cout block of 32][h][32 couts][8 cin] 16-bit
@@ -596,24 +580,10 @@ static int lp_s1_ksplit(long wgs, int KS) {
 }
 
 template <typename T, int VB, int CB, int TXL>
-static int lp_s1_launch(LpS1Params p, void* ws, long ws_bytes, hipStream_t stream) {
+static int lp_s1_launch(const LpS1Params& p, hipStream_t stream) {
   constexpr int TX = 1 << TXL, R = 32 / TX, TY = VB * R, TZ = 4;
-  p.ntx = (p.W + TX - 1) / TX; p.nty = (p.H + TY - 1) / TY; p.ntz = (p.D + TZ - 1) / TZ;
-  p.ncg = (p.NB + CB - 1) / CB;
-  const long wgs = (long)p.N * p.ntz * p.nty * p.ntx * p.ncg;
-  if (wgs > 0x7fffffffL) return BTS_ERR_SHAPE;
-  p.ksplit = lp_s1_ksplit(wgs, p.KS);
-  p.ks_per = p.KS;
-  p.part = reinterpret_cast<float*>(ws);
   const long nvox = (long)p.N * p.D * p.H * p.W;
-  if (p.ksplit > 1) {
-    p.ks_per = (p.KS + p.ksplit - 1) / p.ksplit;
-    p.ksplit = (p.KS + p.ks_per - 1) / p.ks_per;
-    if (ws == nullptr || ws_bytes < (long)p.ksplit * nvox * p.NB * 32 * 4 || (((uintptr_t)ws) & 15)) { p.ksplit = 1; p.ks_per = p.KS; }
-  }
-  if (p.gnp != nullptr && p.ksplit > 1) return BTS_ERR_UNSUPPORTED;   // (bts_lp_conv3d_fwd_gn plans with the same rule: not reached)
   const size_t shmem = (size_t)(TX + 2) * (TY + 2) * (TZ + 2) * LPS * 2 + 32 * CB * 4;   // halo tile + the tile's bias values
-  if ((long)p.D * p.H * p.W * (long)p.ldy * 2 >= 0x7fffff00L) return BTS_ERR_SHAPE;   // 31-bit output offsets inside one sample
   auto kern = lp_conv_s1_kernel<T, VB, CB, TXL>;
   static bool attr_done = false;
   if (!attr_done) {
@@ -622,8 +592,7 @@ static int lp_s1_launch(LpS1Params p, void* ws, long ws_bytes, hipStream_t strea
     attr_done = true;
   }
   (void)hipGetLastError();
-  p.ntiles = wgs;
-  const long grid = wgs < 1024 ? wgs : 1024;   // <= 4 workgroups per CU in flight or queued
+  const long grid = p.ntiles < 1024 ? p.ntiles : 1024;   // <= 4 workgroups per CU in flight or queued
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(30, 2.0 * 27.0 * 16.0 * p.KS * p.Cout * (double)nvox, stream);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid, p.ksplit), dim3(256), shmem, stream, p);
@@ -639,7 +608,7 @@ static int lp_s1_launch(LpS1Params p, void* ws, long ws_bytes, hipStream_t strea
   return BTS_OK;
 }
 
-// (VB, CB, TXL) of a stride-1 call; shared by the launcher and the workspace query
+// (VB, CB, TXL) of a stride-1 call
 static void lp_s1_shape(int N, int D, int H, int W, int NB, int& vb, int& cb, int& txl) {
   // x extent of a wave's 32 columns: the widest power of two that wastes no more columns than a narrower one would
   txl = (W >= 24) ? 5 : (W >= 12 ? 4 : 3);
@@ -650,16 +619,38 @@ static void lp_s1_shape(int N, int D, int H, int W, int NB, int& vb, int& cb, in
   vb = vox >= 4096 ? 4 : (vox >= 1024 ? 2 : 1);
   if (vb == 4 && txl == 5) cb = 1;   // 4 x 2 tiles (128 accumulators + weight ring + halo prefetch) spill at two waves per SIMD
 }
-static long lp_s1_wgs(int N, int D, int H, int W, int NB, int vb, int cb, int txl) {
-  const int TX = 1 << txl, TY = vb * (32 / TX);
-  return (long)N * ((D + 3) / 4) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX) * ((NB + cb - 1) / cb);
+bool lp_s1_accept(const LpS1Call& c, LpS1Choice& ch) {
+  LpS1Shape& s = ch.s;
+  const int NB = (c.Cout + 31) / 32, KS = c.Cin / 16;
+  lp_s1_shape(c.N, c.D, c.H, c.W, NB, s.vb, s.cb, s.txl);
+  const int TX = 1 << s.txl, TY = s.vb * (32 / TX);
+  s.ntx = (c.W + TX - 1) / TX; s.nty = (c.H + TY - 1) / TY; s.ntz = (c.D + 3) / 4; s.ncg = (NB + s.cb - 1) / s.cb;
+  s.wgs = (long)c.N * s.ntz * s.nty * s.ntx * s.ncg;
+  if (s.wgs > 0x7fffffffL) return false;
+  if ((long)c.D * c.H * c.W * (long)c.ldy * 2 >= 0x7fffff00L) return false;   // 31-bit output offsets inside one sample
+  const int ks = lp_s1_ksplit(s.wgs, KS);
+  s.ks_per = (KS + ks - 1) / ks;
+  s.ksplit = (KS + s.ks_per - 1) / s.ks_per;
+  ch.ws = ks > 1 ? (long)ks * c.N * c.D * c.H * c.W * NB * 32 * 4 : 0;      // (sized for the split before rounding, as it always was)
+  // GroupNorm partials from the epilogue: no split-K, whole planes per group, four-cout stores
+  ch.B = (c.G > 0 && !c.gnb_G && s.ksplit == 1 && c.D % c.G == 0 && c.Cout % 4 == 0) ? (long)(c.D / c.G) * s.nty * s.ntx * s.ncg : 0;
+  return true;
 }
 
 template <typename T>
-static int lp_s1_dispatch(const LpS1Params& p, void* ws, long ws_bytes, hipStream_t stream) {
-  int vb, cb, txl;
-  lp_s1_shape(p.N, p.D, p.H, p.W, p.NB, vb, cb, txl);
-#define LP_S1_CASE(VB_, CB_, TXL_) if (vb == VB_ && cb == CB_ && txl == TXL_) return lp_s1_launch<T, VB_, CB_, TXL_>(p, ws, ws_bytes, stream);
+static int lp_s1_dispatch(const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream) {
+  const LpS1Shape& s = ch.s;
+  LpS1Params p;
+  p.x = (const unsigned short*)q.x; p.wp = (const unsigned short*)q.wp; p.bias = q.bias; p.y = (unsigned short*)q.y;
+  p.N = c.N; p.D = c.D; p.H = c.H; p.W = c.W; p.ldx = c.ldx; p.ldy = c.ldy; p.Cout = c.Cout; p.KS = c.Cin / 16; p.NB = (c.Cout + 31) / 32;
+  p.accum = c.accum;
+  p.gnp = q.gnp; p.gn_G = q.gnp != nullptr ? c.G : 0; p.gn_zt = p.gn_G > 0 ? c.D / p.gn_G : 1;
+  p.ntx = s.ntx; p.nty = s.nty; p.ntz = s.ntz; p.ncg = s.ncg; p.ntiles = s.wgs;
+  p.ksplit = s.ksplit; p.ks_per = s.ks_per;
+  p.part = reinterpret_cast<float*>(q.ws);
+  const long nvox = (long)c.N * c.D * c.H * c.W;
+  if (p.ksplit > 1 && (q.ws == nullptr || q.ws_bytes < (long)p.ksplit * nvox * p.NB * 32 * 4 || (((uintptr_t)q.ws) & 15))) { p.ksplit = 1; p.ks_per = p.KS; }
+#define LP_S1_CASE(VB_, CB_, TXL_) if (s.vb == VB_ && s.cb == CB_ && s.txl == TXL_) return lp_s1_launch<T, VB_, CB_, TXL_>(p, stream);
   LP_S1_CASE(4, 1, 5) LP_S1_CASE(4, 2, 5) LP_S1_CASE(2, 1, 5) LP_S1_CASE(2, 2, 5) LP_S1_CASE(1, 1, 5) LP_S1_CASE(1, 2, 5)
   LP_S1_CASE(4, 1, 4) LP_S1_CASE(4, 2, 4) LP_S1_CASE(2, 1, 4) LP_S1_CASE(2, 2, 4) LP_S1_CASE(1, 1, 4) LP_S1_CASE(1, 2, 4)
   LP_S1_CASE(4, 1, 3) LP_S1_CASE(4, 2, 3) LP_S1_CASE(2, 1, 3) LP_S1_CASE(2, 2, 3) LP_S1_CASE(1, 1, 3) LP_S1_CASE(1, 2, 3)
@@ -994,38 +985,73 @@ static int lp_gather_launch(LpGatherParams p, hipStream_t stream) {
   return BTS_OK;
 }
 
-// geometry-driven core of both entry points below.  geo: 0 = 1x1x1, 1 = 3x3x3 stride 1, 2 = stride-2 gather (out = ceil(in/2),
-// in = 2o + k - pad), 3 = 8 output-parity classes of the transposed form (out = 2 in; even outputs take (i, k=0) and (i-1, k=2),
-// odd ones (i, k=1)).  (D,H,W) are the dims of `x`, the tensor the taps read; Cin its channels (the contraction).
-static int lp_conv_run(int geo, int dtype, const void* x, const void* wp, const float* bias, void* y, void* workspace, long workspace_bytes,
-                       int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int accum, hipStream_t stream,
-                       double* gap_part = nullptr, double* gn_part = nullptr, int gn_G = 0, const LpGnbFuse* gnb = nullptr,
-                       const LpGnaFuse* gna = nullptr) {
+// The stride-1 kernel of a call: the z-marching kernel (lowp_s1z.hip) for few channels on a big volume, then the LDS-DMA tiled one
+// (lowp_s1d.hip), then the register-staged one.  Forms: GroupNorm-backward class sums (gnb), GroupNorm applied to the input (gna),
+// FS and a second input tensor (ldxb) only on the first, a split output only on the second, SC on the first two.  G and gnb are
+// epilogues: the kernel that takes the plain call writes them, or nobody does (B = 0).
+int lp_s1_choose(const LpS1Call& c, LpS1Choice& ch) {
+  ch = LpS1Choice{};
+  if (c.N <= 0 || c.D <= 0 || c.H <= 0 || c.W <= 0 || c.Cin <= 0 || c.Cout <= 0) return BTS_ERR_SHAPE;
+  if (c.Cin % 16 != 0 || c.ldx % 8 != 0 || c.ldx < (c.ldxb ? 32 : c.Cin) || c.ldy < (c.ysplit ? 32 : c.Cout) || (c.Cout >= 4 && c.ldy % 4 != 0))
+    return BTS_ERR_ALIGN;
+  if (((long)(c.D + 2) * c.H * c.W + 64) * (long)c.ldx * 2 >= 0x7fffffffL) return BTS_ERR_SHAPE;   // 31-bit offsets inside one volume
+  // BTS_LP_SC=0 / BTS_LP_FS=0: never the SC / FS form (A/B; read once)
+  static const bool sc_off = [] { const char* e = getenv("BTS_LP_SC"); return e && atoi(e) == 0; }();
+  static const bool fs_off = [] { const char* e = getenv("BTS_LP_FS"); return e && atoi(e) == 0; }();
+  const bool z_only = c.gna_G || c.Cout2 || c.ldxb;
+  if (!(c.ldx2 && sc_off) && !(c.Cout2 && fs_off)) {
+    if (!c.ysplit && lp_s1z_accept(c, ch)) { ch.kernel = LP_S1Z; return BTS_OK; }
+    if (!z_only && lp_s1d_accept(c, ch)) { ch.kernel = LP_S1D; return BTS_OK; }
+    if (!z_only && !c.ysplit && !c.ldx2 && lp_s1_accept(c, ch)) { ch.kernel = LP_S1; return BTS_OK; }
+  }
+  if (!(z_only || c.ysplit || c.ldx2)) return BTS_ERR_SHAPE;
+  LpS1Call plain = c;
+  plain.gna_G = plain.ldx2 = plain.Cout2 = plain.ldy2 = plain.ldxb = 0;
+  plain.ysplit = 0;
+  const int r = lp_s1_choose(plain, ch);
+  return r == BTS_OK ? 1 : r;
+}
+static bool lp_s1_same(const LpS1Choice& a, const LpS1Choice& b) { return a.kernel == b.kernel && a.ws == b.ws && a.B == b.B; }
+static bool lp_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// the query's view of a call: dense strides, aligned operands
+static LpS1Call lp_s1_call(int N, int D, int H, int W, int Cin, int Cout) {
+  LpS1Call c{};
+  c.N = N; c.D = D; c.H = H; c.W = W; c.Cin = Cin; c.ldx = Cin; c.Cout = Cout; c.ldy = Cout;
+  c.aligned = 1;
+  return c;
+}
+static int lp_s1_run(int dtype, const LpS1Call& c, const LpS1Choice& ch, LpS1Ptrs q, hipStream_t stream) {
+  if (ch.kernel == LP_S1) return dtype == LP_F16 ? lp_s1_dispatch<TF16>(c, ch, q, stream) : lp_s1_dispatch<TBF16>(c, ch, q, stream);
+  q.wp = reinterpret_cast<const char*>(q.wp) + lp_s1d_part_offset(c.Cin, c.Cout);      // (the DMA part of the image)
+  return ch.kernel == LP_S1Z ? bts_lp_s1z_launch_(dtype, c, ch, q, stream) : bts_lp_s1d_launch_(dtype, c, ch, q, stream);
+}
+
+// what every conv launch checks before it looks at the geometry
+static int lp_conv_check(int dtype, const void* x, const void* wp, const void* y, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BTS_ERR_SHAPE;
   // (results are stored four couts = 8 bytes at a time; a head with fewer than four output channels stores them one by one)
   const bool vec_out = Cout >= 4;
   if (Cin % 16 != 0 || ldx % 8 != 0 || (vec_out && ldy % 4 != 0) || ldx < Cin || ldy < Cout) return BTS_ERR_ALIGN;
-  if ((((uintptr_t)x) & 15) || (((uintptr_t)y) & (vec_out ? 7 : 1)) || (((uintptr_t)wp) & 15)) return BTS_ERR_ALIGN;
+  if (!lp_al16(x) || (((uintptr_t)y) & (vec_out ? 7 : 1)) || !lp_al16(wp)) return BTS_ERR_ALIGN;
+  return BTS_OK;
+}
+// geometry-driven core of both entry points below.  geo: 0 = 1x1x1, 1 = 3x3x3 stride 1, 2 = stride-2 gather (out = ceil(in/2),
+// in = 2o + k - pad), 3 = 8 output-parity classes of the transposed form (out = 2 in; even outputs take (i, k=0) and (i-1, k=2),
+// odd ones (i, k=1)).  (D,H,W) are the dims of `x`, the tensor the taps read; Cin its channels (the contraction).
+static int lp_conv_run(int geo, int dtype, const void* x, const void* wp, const float* bias, void* y, void* workspace, long workspace_bytes,
+                       int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int accum, hipStream_t stream,
+                       double* gap_part = nullptr, double* gn_part = nullptr, int gn_G = 0) {
+  const int chk = lp_conv_check(dtype, x, wp, y, N, D, H, W, Cin, ldx, Cout, ldy);
+  if (chk != BTS_OK) return chk;
   const int KS = Cin / 16, NB = (Cout + 31) / 32;
   if (geo == 1) {
-    if (((long)(D + 2) * H * W + 64) * (long)ldx * 2 >= 0x7fffffffL) return BTS_ERR_SHAPE;   // 31-bit offsets inside one volume
-    {   // few channels on a big volume: the z-marching streaming kernel (lowp_s1z.hip); same image part as the tiled DMA kernel
-      const int r = bts_lp_s1z_launch_(dtype, x, reinterpret_cast<const char*>(wp) + lp_s1d_part_offset(Cin, Cout), bias, y, N, D, H, W, Cin, ldx,
-                                       Cout, ldy, accum, gn_part, gn_G, stream, gnb, gna);
-      if (r != 1) return r;
-    }
-    if (gnb != nullptr || gna != nullptr) return 1;      // (only the streaming kernel has these epilogue / prologue forms: nothing was launched)
-    {
-      const int r = bts_lp_s1d_launch_(dtype, x, reinterpret_cast<const char*>(wp) + lp_s1d_part_offset(Cin, Cout), bias, y, workspace,
-                                       workspace_bytes, N, D, H, W, Cin, ldx, Cout, ldy, accum, gn_part, gn_G, stream);
-      if (r != 1) return r;
-    }
-    LpS1Params p;
-    p.x = (const unsigned short*)x; p.wp = (const unsigned short*)wp; p.bias = bias; p.y = (unsigned short*)y;
-    p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = ldx; p.ldy = ldy; p.Cout = Cout; p.KS = KS; p.NB = NB; p.accum = accum;
-    p.gnp = gn_part; p.gn_G = gn_G; p.gn_zt = gn_G > 0 ? D / gn_G : 1;
-    return dtype == LP_F16 ? lp_s1_dispatch<TF16>(p, workspace, workspace_bytes, stream) : lp_s1_dispatch<TBF16>(p, workspace, workspace_bytes, stream);
+    LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+    c.ldx = ldx; c.ldy = ldy; c.accum = accum; c.aligned = lp_al16(x) && lp_al16(y) && lp_al16(wp);
+    LpS1Choice ch;
+    const int r = lp_s1_choose(c, ch);
+    if (r != BTS_OK) return r;
+    return lp_s1_run(dtype, c, ch, LpS1Ptrs{x, wp, bias, y, workspace, workspace_bytes}, stream);
   }
   LpGatherParams g;
   g.x = (const unsigned short*)x; g.wp = (const unsigned short*)wp; g.bias = bias; g.y = (unsigned short*)y;
@@ -1081,16 +1107,8 @@ static int lp_conv_run(int geo, int dtype, const void* x, const void* wp, const 
 }
 
 static long lp_s1_workspace(int N, int D, int H, int W, int Cin, int Cout) {
-  if (Cin % 16 != 0) return 0;
-  {
-    const long d = bts_lp_s1d_workspace_(N, D, H, W, Cin, Cout);
-    if (d >= 0) return d;
-  }
-  const int NB = (Cout + 31) / 32;
-  int vb, cb, txl;
-  lp_s1_shape(N, D, H, W, NB, vb, cb, txl);
-  const int ks = lp_s1_ksplit(lp_s1_wgs(N, D, H, W, NB, vb, cb, txl), Cin / 16);
-  return ks > 1 ? (long)ks * N * D * H * W * NB * 32 * 4 : 0;
+  LpS1Choice ch;
+  return lp_s1_choose(lp_s1_call(N, D, H, W, Cin, Cout), ch) == BTS_OK ? ch.ws : 0;
 }
 extern "C" long bts_lp_conv3d_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout) {
   return kind == BTS_CONV_K3S1 ? lp_s1_workspace(N, D, H, W, Cin, Cout) : 0;
@@ -1106,53 +1124,44 @@ extern "C" int bts_lp_conv3d_fwd(int kind, int dtype, const void* x, const void*
 // reference runs it on channels_last data: resnet.py:80-93 conv -> GroupNormalization) in one pass: (sum, sumsq) partials leave the
 // conv's epilogue per (z plane, tile column), bts_gn_finalize_partials_ turns them into mean / rstd.  Grids that split the input
 // channels, z-slabs that are not whole planes (D % G != 0) and heads with Cout % 4 != 0 run the conv and bts_lp_gn_stats on the stored y.
-static bool lp_s1_gn_plan(int N, int D, int H, int W, int Cin, int Cout, int G, long* B) {
-  if (Cin % 16 != 0 || Cout % 4 != 0 || G <= 0) return false;
-  if (D % G != 0) {      // slabs that are not whole planes: only the split-K finish of the DMA kernel counts them
-    const bool s1z_takes_it = bts_lp_s1z_gn_B_(N, D, H, W, Cin, Cout, 1) > 0;      // (offered first by lp_conv_run)
-    const bool splits = bts_lp_s1d_workspace_(N, D, H, W, Cin, Cout) > 0;
-    *B = (!s1z_takes_it && splits) ? bts_lp_s1d_gn_B_(N, D, H, W, Cin, Cout, G) : 0;
-    return *B > 0;
-  }
-  *B = bts_lp_s1z_gn_B_(N, D, H, W, Cin, Cout, G);          // the streaming kernel takes this shape: its partial layout
-  if (*B > 0) return true;
-  if (bts_lp_s1d_workspace_(N, D, H, W, Cin, Cout) >= 0) {      // the DMA kernel takes this shape: its partial layout
-    *B = bts_lp_s1d_gn_B_(N, D, H, W, Cin, Cout, G);
-    return *B > 0;
-  }
-  const int NB = (Cout + 31) / 32;
-  int vb, cb, txl;
-  lp_s1_shape(N, D, H, W, NB, vb, cb, txl);
-  if (lp_s1_ksplit(lp_s1_wgs(N, D, H, W, NB, vb, cb, txl), Cin / 16) > 1) return false;
-  const int TX = 1 << txl, TY = vb * (32 / TX);
-  *B = (long)(D / G) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX) * ((NB + cb - 1) / cb);
-  return true;
-}
-extern "C" long bts_lp_conv3d_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int G) {
+static long lp_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int G, LpS1Choice& ch) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0) return -1;
-  long B = 0;
-  const long fused = lp_s1_gn_plan(N, D, H, W, Cin, Cout, G, &B) ? (long)N * G * B * 16 + 64 : 0;
-  const long conv = ((lp_s1_workspace(N, D, H, W, Cin, Cout) + 63) / 64) * 64;
+  LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+  c.G = G;
+  lp_s1_choose(c, ch);
+  const long fused = ch.B > 0 ? (long)N * G * ch.B * 16 + 64 : 0;
+  const long conv = ((ch.ws + 63) / 64) * 64;
   const long stats = bts_lp_gn_workspace(N, (long)D * H * W, Cout, G);
   return conv + (fused > stats ? fused : stats) + 64;
+}
+extern "C" long bts_lp_conv3d_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int G) {
+  LpS1Choice ch;
+  return lp_fwd_gn_workspace(N, D, H, W, Cin, Cout, G, ch);
 }
 extern "C" int bts_lp_conv3d_fwd_gn(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd,
                                     void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G,
                                     float eps, hipStream_t stream) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0) return BTS_ERR_SHAPE;
-  if (workspace == nullptr || workspace_bytes < bts_lp_conv3d_fwd_gn_workspace(N, D, H, W, Cin, Cout, G) || (((uintptr_t)workspace) & 15))
+  LpS1Choice sized, ch;
+  if (workspace == nullptr || workspace_bytes < lp_fwd_gn_workspace(N, D, H, W, Cin, Cout, G, sized) || (((uintptr_t)workspace) & 15))
     return BTS_ERR_WORKSPACE;
-  const long conv_ws = ((lp_s1_workspace(N, D, H, W, Cin, Cout) + 63) / 64) * 64;
+  int r = lp_conv_check(dtype, x, wp, y, N, D, H, W, Cin, ldx, Cout, Cout);
+  if (r != BTS_OK) return r;
+  LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+  c.ldx = ldx; c.G = G; c.aligned = lp_al16(x) && lp_al16(y) && lp_al16(wp);
+  r = lp_s1_choose(c, ch);
+  if (r != BTS_OK) return r;
+  const long conv_ws = ((sized.ws + 63) / 64) * 64;
   char* tail = reinterpret_cast<char*>(workspace) + conv_ws;
   const long V = (long)D * H * W;
-  long B = 0;
-  if (lp_s1_gn_plan(N, D, H, W, Cin, Cout, G, &B)) {
-    double* part = reinterpret_cast<double*>(tail);
-    const int r = lp_conv_run(1, dtype, x, wp, bias, y, workspace, conv_ws, N, D, H, W, Cin, ldx, Cout, Cout, 0, stream, nullptr, part, G);
+  LpS1Ptrs q{x, wp, bias, y, workspace, conv_ws};
+  if (ch.B > 0 && lp_s1_same(ch, sized)) {
+    q.gnp = reinterpret_cast<double*>(tail);
+    r = lp_s1_run(dtype, c, ch, q, stream);
     if (r != BTS_OK) return r;
-    return bts_gn_finalize_partials_(part, mean, rstd, N * G, B, (double)(V * Cout / G), eps, stream);
+    return bts_gn_finalize_partials_(q.gnp, mean, rstd, N * G, ch.B, (double)(V * Cout / G), eps, stream);
   }
-  const int r = lp_conv_run(1, dtype, x, wp, bias, y, workspace, conv_ws, N, D, H, W, Cin, ldx, Cout, Cout, 0, stream);
+  r = lp_s1_run(dtype, c, ch, q, stream);
   if (r != BTS_OK) return r;
   return bts_lp_gn_stats(dtype, y, mean, rstd, tail, workspace_bytes - conv_ws, N, V, Cout, G, BTS_GN_SLAB, eps, stream);
 }
@@ -1164,39 +1173,48 @@ extern "C" int bts_lp_conv3d_fwd_gn(int dtype, const void* x, const void* wp, co
 // (N,D,H,W,Cout).  The workspace query returns -1 and the call 1 (nothing launched) where the streaming kernel does not take the shape:
 // the caller runs bts_lp_conv1_gap + bts_lp_conv3d_fwd_gn.  BTS_LP_FS=0 in the environment: never (A/B aid).
 __global__ __launch_bounds__(256) void lp_colsum_finalize_kernel(const double* partial, float* out, int N, int C, int B, double scale);
+static long lp_fwd_gn_shortcut_workspace(int N, int D, int H, int W, int Cin, int ldx, int Cout, int G, LpS1Choice& ch) {
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0) return -1;
+  LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+  // (a voxel stride below Cin: the two 32-channel halves are dense tensors of their own -- the two-pass form)
+  c.ldx = ldx; c.ldxb = ldx < Cin ? ldx : 0; c.G = G; c.Cout2 = c.ldy2 = Cout;
+  if (lp_s1_choose(c, ch) != BTS_OK || ch.B <= 0) return -1;
+  return (long)N * G * ch.B * 16 + 64 + (long)N * lp_s1z_fs_B(ch.z) * Cout * 8 + 64;
+}
 extern "C" long bts_lp_conv3d_fwd_gn_shortcut_workspace(int N, int D, int H, int W, int Cin, int ldx, int Cout, int G) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0 || D % G != 0 || Cin % 16 != 0) return -1;
-  static const bool off = [] { const char* e = getenv("BTS_LP_FS"); return e && atoi(e) == 0; }();
-  if (off) return -1;
-  // (two dense 32-channel operands -- voxel stride 32 under 64 channels: the two-pass form at any size, planned like one of its passes)
-  const long Bg = bts_lp_s1z_gn_B_(N, D, H, W, (Cin == 64 && ldx < 64) ? 32 : Cin, Cout, G), Bf = bts_lp_s1z_fs_B_(N, D, H, W, Cin, ldx, Cout, Cout);
-  if (Bg <= 0 || Bf <= 0) return -1;
-  return (long)N * G * Bg * 16 + 64 + (long)N * Bf * Cout * 8 + 64;
+  LpS1Choice ch;
+  return lp_fwd_gn_shortcut_workspace(N, D, H, W, Cin, ldx, Cout, G, ch);
 }
 extern "C" int bts_lp_conv3d_fwd_gn_shortcut(int dtype, const void* x, long x_split, const void* wp, const float* bias, void* y, float* mean,
                                              float* rstd, const void* wp_pt, const float* bias_pt, void* res, float* gap, void* workspace,
                                              long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G, float eps,
                                              hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  const long need = bts_lp_conv3d_fwd_gn_shortcut_workspace(N, D, H, W, Cin, ldx, Cout, G);
+  LpS1Choice sized, ch;
+  const long need = lp_fwd_gn_shortcut_workspace(N, D, H, W, Cin, ldx, Cout, G, sized);
   if (need < 0) return 1;
   if (workspace == nullptr || workspace_bytes < need || (((uintptr_t)workspace) & 15)) return BTS_ERR_WORKSPACE;
   if (x == nullptr || wp == nullptr || wp_pt == nullptr || y == nullptr || res == nullptr || gap == nullptr || mean == nullptr || rstd == nullptr)
     return BTS_ERR_ALIGN;
-  if (ldx % 8 != 0 || ldx < (x_split ? 32 : Cin) || (((uintptr_t)x) & 15) || (((uintptr_t)wp) & 15)) return BTS_ERR_ALIGN;
+  if (ldx % 8 != 0 || ldx < (x_split ? 32 : Cin) || !lp_al16(x) || !lp_al16(wp)) return BTS_ERR_ALIGN;
   if (x_split != 0 && (Cin != 64 || x_split < 0 || x_split % 8 != 0)) return BTS_ERR_SHAPE;      // (two 32-channel operands: the two-pass form)
-  const long Bg = bts_lp_s1z_gn_B_(N, D, H, W, (Cin == 64 && ldx < 64) ? 32 : Cin, Cout, G), Bf = bts_lp_s1z_fs_B_(N, D, H, W, Cin, ldx, Cout, Cout);
-  double* gpart = reinterpret_cast<double*>(workspace);
-  double* fpart = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((long)N * G * Bg * 16 + 63) / 64) * 64);
+  const void* xb = x_split ? static_cast<const void*>(reinterpret_cast<const unsigned short*>(x) + x_split) : nullptr;
+  LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+  c.ldx = ldx; c.ldxb = x_split ? ldx : 0; c.G = G; c.Cout2 = c.ldy2 = Cout;
+  c.aligned = lp_al16(x) && lp_al16(y) && lp_al16(wp) && lp_al16(wp_pt) && lp_al16(res) && lp_al16(xb);
+  if (lp_s1_choose(c, ch) != BTS_OK || !lp_s1_same(ch, sized)) return 1;
+  const long Bg = ch.B, Bf = lp_s1z_fs_B(ch.z);
+  LpS1Ptrs q{x, wp, bias, y};
+  q.gnp = reinterpret_cast<double*>(workspace);
+  q.wp2 = wp_pt; q.y2 = res; q.bias2 = bias_pt; q.xb = xb;
+  q.gap_part = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((long)N * G * Bg * 16 + 63) / 64) * 64);
   const long V = (long)D * H * W;
-  const int r = bts_lp_s1z_launch_(dtype, x, reinterpret_cast<const char*>(wp) + lp_s1d_part_offset(Cin, Cout), bias, y, N, D, H, W, Cin, ldx, Cout,
-                                   Cout, 0, gpart, G, stream, nullptr, nullptr, nullptr, wp_pt, 0, res, bias_pt, fpart, Cout, Cout, 0,
-                                   x_split ? static_cast<const void*>(reinterpret_cast<const unsigned short*>(x) + x_split) : nullptr, x_split ? ldx : 0);
+  const int r = lp_s1_run(dtype, c, ch, q, stream);
   if (r != BTS_OK) return r;
-  const int r2 = bts_gn_finalize_partials_(gpart, mean, rstd, N * G, Bg, (double)(V * Cout / G), eps, stream);
+  const int r2 = bts_gn_finalize_partials_(q.gnp, mean, rstd, N * G, Bg, (double)(V * Cout / G), eps, stream);
   if (r2 != BTS_OK) return r2;
   (void)hipGetLastError();
-  hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * Cout + 3) / 4), dim3(256), 0, stream, fpart, gap, N, Cout, (int)Bf, 1.0 / (double)V);
+  hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * Cout + 3) / 4), dim3(256), 0, stream, q.gap_part, gap, N, Cout, (int)Bf, 1.0 / (double)V);
   BTS_LAUNCH_CHECK();
   return BTS_OK;
 }
@@ -1204,27 +1222,36 @@ extern "C" int bts_lp_conv3d_fwd_gn_shortcut(int dtype, const void* x, long x_sp
 // conv2 of a ResnetBlock reading conv1's raw output (resnet.py:133-136: conv -> GroupNormalization -> relu -> conv) where no backward
 // needs the normalised tensor (inference, test.py:128-151 via Model.call(inference=True)).  The workspace query returns -1 where the
 // streaming kernel does not take the shape in this form (the caller runs bts_lp_gn_apply + bts_lp_conv3d_fwd_gn).
-extern "C" long bts_lp_conv3d_gnin_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int in_G, int G) {
+static long lp_gnin_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int in_G, int G, LpS1Choice& ch) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0 || in_G <= 0 || Cin % in_G != 0) return -1;
-  if (!bts_lp_s1z_gna_ok_(N, D, H, W, Cin, Cin, Cout, Cout, in_G)) return -1;
-  const long B = bts_lp_s1z_gn_B_(N, D, H, W, Cin, Cout, G);
-  if (B <= 0) return -1;
-  return (long)N * G * B * 16 + 128;
+  LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+  c.G = G; c.gna_G = in_G;
+  if (lp_s1_choose(c, ch) != BTS_OK || ch.B <= 0) return -1;
+  return (long)N * G * ch.B * 16 + 128;
+}
+extern "C" long bts_lp_conv3d_gnin_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int in_G, int G) {
+  LpS1Choice ch;
+  return lp_gnin_fwd_gn_workspace(N, D, H, W, Cin, Cout, in_G, G, ch);
 }
 extern "C" int bts_lp_conv3d_gnin_fwd_gn(int dtype, const void* x, const float* in_gamma, const float* in_beta, const float* in_mean,
                                          const float* in_rstd, int in_G, int in_relu, const void* wp, const float* bias, void* y, float* mean,
                                          float* rstd, void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int Cout, int G,
                                          float eps, hipStream_t stream) {
-  const long need = bts_lp_conv3d_gnin_fwd_gn_workspace(N, D, H, W, Cin, Cout, in_G, G);
+  LpS1Choice sized, ch;
+  const long need = lp_gnin_fwd_gn_workspace(N, D, H, W, Cin, Cout, in_G, G, sized);
   if (need < 0 || !in_relu) return BTS_ERR_UNSUPPORTED;      // (the kernel form that exists applies GroupNorm + ReLU)
   if (workspace == nullptr || workspace_bytes < need || (((uintptr_t)workspace) & 15)) return BTS_ERR_WORKSPACE;
-  const long B = bts_lp_s1z_gn_B_(N, D, H, W, Cin, Cout, G);
-  double* part = reinterpret_cast<double*>(workspace);
-  LpGnaFuse ga{in_gamma, in_beta, in_mean, in_rstd, in_G, Cin / in_G};
-  const int r = lp_conv_run(1, dtype, x, wp, bias, y, nullptr, 0, N, D, H, W, Cin, Cin, Cout, Cout, 0, stream, nullptr, part, G, nullptr, &ga);
-  if (r == 1) return BTS_ERR_UNSUPPORTED;
+  const int chk = lp_conv_check(dtype, x, wp, y, N, D, H, W, Cin, Cin, Cout, Cout);
+  if (chk != BTS_OK) return chk;
+  LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+  c.G = G; c.gna_G = in_G; c.aligned = lp_al16(x) && lp_al16(y) && lp_al16(wp);
+  if (lp_s1_choose(c, ch) != BTS_OK || !lp_s1_same(ch, sized)) return BTS_ERR_UNSUPPORTED;
+  const LpGnaFuse ga{in_gamma, in_beta, in_mean, in_rstd, in_G, Cin / in_G};
+  LpS1Ptrs q{x, wp, bias, y};
+  q.gnp = reinterpret_cast<double*>(workspace); q.ga = &ga;
+  const int r = lp_s1_run(dtype, c, ch, q, stream);
   if (r != BTS_OK) return r;
-  return bts_gn_finalize_partials_(part, mean, rstd, N * G, B, (double)((long)D * H * W * Cout / G), eps, stream);
+  return bts_gn_finalize_partials_(q.gnp, mean, rstd, N * G, ch.B, (double)((long)D * H * W * Cout / G), eps, stream);
 }
 // y = Conv3DTranspose(k3, s2, 'same')(x) + bias (dense fine tensor, storage type) AND the slab-mode GroupNorm statistics of y -- ConvUpsample
 // (upsample.py:28-43: conv -> GroupNormalization) without the statistics pass over the fine tensor: (sum, sumsq) partials leave the
@@ -1334,13 +1361,20 @@ extern "C" int bts_lp_conv3d_bwd_data(int kind, int dtype, const void* dy, const
 // dx_split (elements; 0 = dx is one (N,D,H,W,Cin) view): columns [32 b, 32 b + 32) of the result go to dx + b * dx_split, each block a
 // tensor of its own with voxel stride lddx -- the gradient of a concat of 32-channel tensors (decoder.py:75) leaves as dense tensors whose
 // readers fetch whole lines.  Only the fused tiled kernel writes that form: ask bts_lp_conv3d_bwd_data_sc_split_ok first.
+// (role-swapped: the contraction runs over the forward's Cout, the columns are the forward's Cin; the query's view: dense dy, dy2, dx)
+static LpS1Call lp_sc_call(int N, int D, int H, int W, int Cin, int Cout, long dx_split) {
+  LpS1Call c = lp_s1_call(N, D, H, W, Cout, Cin);
+  c.ldx2 = Cout; c.ysplit = dx_split;
+  if (dx_split != 0) c.ldy = 32;
+  return c;
+}
 extern "C" long bts_lp_conv3d_bwd_data_sc_workspace(int N, int D, int H, int W, int Cin, int Cout) {
-  return lp_s1_workspace(N, D, H, W, Cout, Cin);
+  LpS1Choice ch;
+  return lp_s1_choose(lp_sc_call(N, D, H, W, Cin, Cout, 0), ch) >= 0 ? ch.ws : 0;      // (1: the two launches' K3S1 conv)
 }
 extern "C" int bts_lp_conv3d_bwd_data_sc_split_ok(int N, int D, int H, int W, int Cin, int Cout) {
-  static const bool off = [] { const char* e = getenv("BTS_LP_SC"); return e && atoi(e) == 0; }();
-  if (off || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cout % 16 != 0) return 0;
-  return bts_lp_s1d_sc_split_ok_(N, D, H, W, Cout, Cin) ? 1 : 0;
+  LpS1Choice ch;
+  return lp_s1_choose(lp_sc_call(N, D, H, W, Cin, Cout, (long)N * D * H * W * 32), ch) == BTS_OK ? 1 : 0;
 }
 extern "C" int bts_lp_conv3d_bwd_data_sc(int dtype, const void* dy, const void* wp_bwd, const void* dy2, const void* wp2_bwd, void* dx,
                                          long dx_split, void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int lddx,
@@ -1349,27 +1383,22 @@ extern "C" int bts_lp_conv3d_bwd_data_sc(int dtype, const void* dy, const void* 
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BTS_ERR_SHAPE;
   if (dy == nullptr || dy2 == nullptr || wp_bwd == nullptr || wp2_bwd == nullptr || dx == nullptr) return BTS_ERR_ALIGN;
-  // (role-swapped: the contraction runs over the forward's Cout, the columns are the forward's Cin)
-  const int K = Cout, Nc = Cin;
-  static const bool off = [] { const char* e = getenv("BTS_LP_SC"); return e && atoi(e) == 0; }();      // BTS_LP_SC=0: always the two launches (A/B)
-  if (!off && K % 16 == 0 && lddy % 8 == 0 && lddy2 % 8 == 0 && lddy >= K && lddy2 >= K && lddx >= (dx_split ? 32 : Nc) && lddx % 4 == 0 &&
-      !(((uintptr_t)dy) & 15) && !(((uintptr_t)dy2) & 15) && !(((uintptr_t)dx) & 7) && dx_split % 4 == 0 && !(((uintptr_t)wp_bwd) & 15) && !(((uintptr_t)wp2_bwd) & 15) &&
-      ((long)(D + 2) * H * W + 64) * (long)lddy * 2 < 0x7fffffffL) {
-    const char* dma = reinterpret_cast<const char*>(wp_bwd) + lp_s1d_part_offset(K, Nc);
-    int r = 1;
-    if (dx_split == 0)
-      r = bts_lp_s1z_launch_(dtype, dy, dma, nullptr, dx, N, D, H, W, K, lddy, Nc, lddx, accum, nullptr, 0, stream, nullptr, nullptr, dy2, wp2_bwd, lddy2);
-    if (r == 1) r = bts_lp_s1d_launch_(dtype, dy, dma, nullptr, dx, workspace, workspace_bytes, N, D, H, W, K, lddy, Nc, lddx, accum, nullptr, 0, stream,
-                                       dy2, wp2_bwd, lddy2, dx_split);
-    if (r != 1) {
-      if (r == BTS_OK && fused) *fused = 1;
-      return r;
-    }
+  LpS1Choice sized, ch;
+  lp_s1_choose(lp_sc_call(N, D, H, W, Cin, Cout, dx_split), sized);
+  LpS1Call c = lp_sc_call(N, D, H, W, Cin, Cout, dx_split);
+  c.ldx = lddy; c.ldx2 = lddy2; c.ldy = lddx; c.accum = accum;
+  c.aligned = lp_al16(dy) && lp_al16(dy2) && lp_al16(dx) && lp_al16(wp_bwd) && lp_al16(wp2_bwd) && dx_split % 8 == 0;
+  if (lp_s1_choose(c, ch) == BTS_OK && lp_s1_same(ch, sized)) {
+    LpS1Ptrs q{dy, wp_bwd, nullptr, dx, workspace, workspace_bytes};
+    q.x2 = dy2; q.wp2 = wp2_bwd;
+    const int r = lp_s1_run(dtype, c, ch, q, stream);
+    if (r == BTS_OK && fused) *fused = 1;
+    return r;
   }
   if (dx_split != 0) return BTS_ERR_UNSUPPORTED;      // (the two-launch route writes one tensor)
-  const int r = lp_conv_run(1, dtype, dy, wp_bwd, nullptr, dx, workspace, workspace_bytes, N, D, H, W, K, lddy, Nc, lddx, accum, stream);
+  const int r = lp_conv_run(1, dtype, dy, wp_bwd, nullptr, dx, workspace, workspace_bytes, N, D, H, W, Cout, lddy, Cin, lddx, accum, stream);
   if (r != BTS_OK) return r;
-  return lp_conv_run(0, dtype, dy2, wp2_bwd, nullptr, dx, nullptr, 0, N, D, H, W, K, lddy2, Nc, lddx, 1, stream);
+  return lp_conv_run(0, dtype, dy2, wp2_bwd, nullptr, dx, nullptr, 0, N, D, H, W, Cout, lddy2, Cin, lddx, 1, stream);
 }
 
 // =====================================================================================================================
@@ -2656,14 +2685,20 @@ extern "C" int bts_lp_gn_bwd(int dtype, const void* x, const void* dy, void* dx,
 // bts_lp_gn_bwd run back to back: same results up to the order of the fp32 class sums.  (D,H,W): the grid; Cg = GroupNorm channels =
 // the forward conv's INPUT channels, Cdy = dy's channels (row stride lddy); wp_bwd = bts_lp_pack(BTS_CONV_K3S1, BTS_ROLE_BWD_DATA, ...).
 // *fused_out (may be NULL) <- 1 when the epilogue form ran, 0 otherwise.
-extern "C" long bts_lp_conv3d_bwd_data_gn_bwd_workspace(int N, int D, int H, int W, int Cg, int Cdy, int G) {
+static long lp_bwd_data_gn_bwd_workspace(int N, int D, int H, int W, int Cg, int Cdy, int G, LpS1Choice& ch) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cg <= 0 || Cdy <= 0 || G <= 0 || Cg % G != 0) return -1;
-  const long V = (long)D * H * W;
-  const long conv = ((lp_s1_workspace(N, D, H, W, Cdy, Cg) + 63) / 64) * 64;
-  const long plain = bts_lp_gn_bwd_workspace(N, V, Cg, G);
-  const long B = bts_lp_s1z_gnb_B_(N, D, H, W, Cdy, Cdy, Cg, Cg, G);
+  LpS1Call c = lp_s1_call(N, D, H, W, Cdy, Cg);
+  c.gnb_G = G;
+  lp_s1_choose(c, ch);
+  const long conv = ((ch.ws + 63) / 64) * 64;
+  const long plain = bts_lp_gn_bwd_workspace(N, (long)D * H * W, Cg, G);
+  const long B = ch.B;
   const long fused = B > 0 ? (long)N * G * B * (Cg / G) * 2 * 8 + (long)N * G * 2 * 4 + 64 + 16384L * Cg * 8 + 64 : 0;
   return conv + (fused > plain ? fused : plain) + 64;
+}
+extern "C" long bts_lp_conv3d_bwd_data_gn_bwd_workspace(int N, int D, int H, int W, int Cg, int Cdy, int G) {
+  LpS1Choice ch;
+  return lp_bwd_data_gn_bwd_workspace(N, D, H, W, Cg, Cdy, G, ch);
 }
 extern "C" int bts_lp_conv3d_bwd_data_gn_bwd(int dtype, const void* dy, const void* wp_bwd, void* da, const void* c, void* dc, float* dc32,
                                              const float* gamma, const float* beta, const float* mean, const float* rstd, float* dgamma,
@@ -2672,29 +2707,36 @@ extern "C" int bts_lp_conv3d_bwd_data_gn_bwd(int dtype, const void* dy, const vo
                                              hipStream_t stream) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cg <= 0 || Cdy <= 0 || G <= 0 || Cg % G != 0) return BTS_ERR_SHAPE;
   const long V = (long)D * H * W;
-  const int chk = lp_gn_bwd_check(dtype, c, da, dc, dc32, N, V, Cg, Cg, G);
-  if (chk != BTS_OK) return chk;
-  if (workspace == nullptr || workspace_bytes < bts_lp_conv3d_bwd_data_gn_bwd_workspace(N, D, H, W, Cg, Cdy, G) || (((uintptr_t)workspace) & 15))
+  int r = lp_gn_bwd_check(dtype, c, da, dc, dc32, N, V, Cg, Cg, G);
+  if (r != BTS_OK) return r;
+  LpS1Choice sized, ch;
+  if (workspace == nullptr || workspace_bytes < lp_bwd_data_gn_bwd_workspace(N, D, H, W, Cg, Cdy, G, sized) || (((uintptr_t)workspace) & 15))
     return BTS_ERR_WORKSPACE;
-  const long conv_ws = ((lp_s1_workspace(N, D, H, W, Cdy, Cg) + 63) / 64) * 64;
+  const long conv_ws = ((sized.ws + 63) / 64) * 64;
   char* tail = reinterpret_cast<char*>(workspace) + conv_ws;
   const long L = V * Cg / G;
   const int cg = Cg / G;
   if (fused_out) *fused_out = 0;
-  const long B = bts_lp_s1z_gnb_B_(N, D, H, W, Cdy, lddy, Cg, Cg, G);
-  if (B > 0 && B <= 0x7fffffffL && B == bts_lp_s1z_gnb_B_(N, D, H, W, Cdy, Cdy, Cg, Cg, G)) {     // (the workspace was sized for dense dy)
+  r = lp_conv_check(dtype, dy, wp_bwd, da, N, D, H, W, Cdy, lddy, Cg, Cg);
+  if (r != BTS_OK) return r;
+  LpS1Call cl = lp_s1_call(N, D, H, W, Cdy, Cg);
+  cl.ldx = lddy; cl.gnb_G = G; cl.aligned = lp_al16(dy) && lp_al16(da) && lp_al16(wp_bwd) && lp_al16(c);
+  r = lp_s1_choose(cl, ch);
+  if (r != BTS_OK) return r;
+  LpS1Ptrs q{dy, wp_bwd, nullptr, da, workspace, conv_ws};
+  const long B = ch.B;
+  if (B > 0 && B <= 0x7fffffffL && lp_s1_same(ch, sized)) {     // (the workspace was sized for dense dy)
     LpGnbFuse f;
     f.x = (const unsigned short*)c; f.gamma = gamma; f.beta = beta; f.mean = mean; f.rstd = rstd;
     f.part = reinterpret_cast<double*>(tail); f.G = G; f.cg = cg; f.relu = relu; f.B = B;
-    const int r = lp_conv_run(1, dtype, dy, wp_bwd, nullptr, da, nullptr, 0, N, D, H, W, Cdy, lddy, Cg, Cg, 0, stream, nullptr, nullptr, 0, &f);
-    if (r == BTS_OK) {
-      if (fused_out) *fused_out = 1;
-      return lp_gn_bwd_tail(dtype, c, da, dc, dc32, gamma, beta, mean, rstd, dgamma, dbeta, f.part, (int)B,
-                            reinterpret_cast<float*>(f.part + (long)N * G * B * cg * 2), N, L, Cg, Cg, G, relu, accumulate_params, dbias, stream);
-    }
-    if (r != 1) return r;
+    q.gb = &f;
+    r = lp_s1_run(dtype, cl, ch, q, stream);
+    if (r != BTS_OK) return r;
+    if (fused_out) *fused_out = 1;
+    return lp_gn_bwd_tail(dtype, c, da, dc, dc32, gamma, beta, mean, rstd, dgamma, dbeta, f.part, (int)B,
+                          reinterpret_cast<float*>(f.part + (long)N * G * B * cg * 2), N, L, Cg, Cg, G, relu, accumulate_params, dbias, stream);
   }
-  const int r = lp_conv_run(1, dtype, dy, wp_bwd, nullptr, da, workspace, conv_ws, N, D, H, W, Cdy, lddy, Cg, Cg, 0, stream);
+  r = lp_s1_run(dtype, cl, ch, q, stream);
   if (r != BTS_OK) return r;
   return bts_lp_gn_bwd(dtype, c, da, dc, dc32, gamma, beta, mean, rstd, dgamma, dbeta, tail, workspace_bytes - conv_ws, N, V, Cg, Cg, G, relu,
                        accumulate_params, dbias, stream);

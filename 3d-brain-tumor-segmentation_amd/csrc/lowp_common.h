@@ -193,3 +193,62 @@ struct LpGnbFuse {
   int G, cg, relu;
   long B;
 };
+
+// ---- stride-1 3x3x3 convolutions: which of the three kernels takes a call (lowp_s1z.hip, lowp_s1d.hip, lowp.hip's register-staged
+// lp_conv_s1_kernel), decided ONCE per query or launch by lp_s1_choose; the workspace queries and the entry points answer from it ----
+struct LpS1Call {         // shape, strides (elements) and requested form of one call -- no pointers
+  int N, D, H, W, Cin, ldx, Cout, ldy;
+  int accum;
+  int G;                  // GroupNorm partial sums of y, slab mode, G groups (0: none) -- an epilogue: it does not change the choice
+  int gnb_G;              // GroupNorm-backward class sums in the epilogue (LpGnbFuse::G; 0: none) -- likewise
+  int gna_G;              // GroupNorm + ReLU applied to the input planes (LpGnaFuse::G; 0: none)
+  int ldx2;               // SC: voxel stride of the centre-tap second operand (0: none)
+  int Cout2, ldy2;        // FS: shortcut output columns and their voxel stride (0: none)
+  long ysplit;            // split output: elements between the tensors of consecutive 32-column blocks (0: one tensor)
+  int ldxb;               // channels [32, 64) of a 64-channel input as a tensor of their own, voxel stride ldxb (0: none)
+  int aligned;            // every operand sits on a 16-byte boundary
+};
+struct S1zPlan { int ntx, nty, nzc, ZC, nitems, ipw, nwg, xcd, pair; };      // pair: Cin = 64 as two 32-channel passes
+struct S1dPlan {
+  int mode, txl, ntx, nty, ntz, ncg, ksplit, ks_per;
+  int bx, by, bz;
+  long nitems;
+};
+struct LpS1Shape { int vb, cb, txl, ntx, nty, ntz, ncg, ksplit, ks_per; long wgs; };      // the register-staged kernel
+enum { LP_S1Z = 1, LP_S1D, LP_S1 };
+struct LpS1Choice {
+  int kernel;             // LP_S1Z | LP_S1D | LP_S1
+  S1zPlan z;
+  S1dPlan d;
+  LpS1Shape s;
+  long ws;                // conv workspace bytes (split-K partial sums)
+  long B;                 // GroupNorm partial slots per (n, group) the kernel writes for LpS1Call::G / gnb_G; 0: it cannot
+};
+struct LpS1Ptrs {         // the operands of a launch (NULL: absent); wp = the whole K3S1 image
+  const void* x;
+  const void* wp;
+  const float* bias;
+  void* y;
+  void* ws;
+  long ws_bytes;
+  double* gnp;            // [N*G][B][2] (LpS1Call::G)
+  const LpGnbFuse* gb;
+  const LpGnaFuse* ga;
+  const void* x2;         // SC
+  const void* wp2;        // SC / FS: the K1 image
+  void* y2;               // FS
+  const float* bias2;
+  double* gap_part;
+  const void* xb;         // LpS1Call::ldxb
+};
+// true: the kernel takes the call (every shape, stride and form condition of its launcher; which kernel has which form is
+// lp_s1_choose's rule) -- ch's plan, ws and B are filled in, and the launcher does not decline it
+bool lp_s1z_accept(const LpS1Call& c, LpS1Choice& ch);
+bool lp_s1d_accept(const LpS1Call& c, LpS1Choice& ch);
+bool lp_s1_accept(const LpS1Call& c, LpS1Choice& ch);
+// BTS_OK: ch = the call's kernel.  1: no kernel takes the operand form asked for (SC, FS, gna, ysplit, ldxb); ch = the choice of the same
+// call without it.  Otherwise the status of a call no kernel takes.
+int lp_s1_choose(const LpS1Call& c, LpS1Choice& ch);
+inline long lp_s1z_fs_B(const S1zPlan& pl) { return (long)pl.ntx * pl.nty * pl.nzc * 8; }      // FS column-sum rows per sample
+int bts_lp_s1z_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);     // q.wp = the DMA part
+int bts_lp_s1d_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);

@@ -19,7 +19,7 @@
 //   * a three-slot weight ring and a double-buffered halo tile are filled two stages / one k-step ahead; a stage boundary is
 //     `s_waitcnt vmcnt(N)` with N counted (never 0) + one s_barrier; a workgroup walks its items (tile x cout group, XCD-aware
 //     order) as ONE stage stream, the next item's operands in flight under the current item's output side.
-// Declines (caller runs the old kernel): W < 12, fewer than 4096 voxels, Cout % 8 != 0, offsets beyond 31 bits.
+// Takes (lp_s1d_accept; lp_s1_choose offers the register-staged kernel the rest): W >= 12, at least 4096 voxels, Cout % 8 == 0, 31-bit offsets.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -528,11 +528,6 @@ int bts_lp_s1d_pack_(int dtype, const LpPackParams& p0, void* dst, hipStream_t s
 // =====================================================================================================================
 // plan + launch
 // =====================================================================================================================
-struct S1dPlan {
-  int mode, txl, ntx, nty, ntz, ncg, ksplit, ks_per;
-  int bx, by, bz;
-  long nitems;
-};
 // q = n / d for n < 2^31 as (n * mul) >> (32 + sh); mul == 0 means d == 1
 static void s1d_fastdiv(unsigned d, unsigned& mul, unsigned& sh) {
   if (d <= 1) { mul = 0; sh = 0; return; }
@@ -602,25 +597,26 @@ static bool s1d_plan(int N, int D, int H, int W, int Cin, int Cout, S1dPlan& pl)
   pl = wide ? a : b;
   return true;
 }
-long bts_lp_s1d_workspace_(int N, int D, int H, int W, int Cin, int Cout) {
-  S1dPlan pl;
-  if (!s1d_plan(N, D, H, W, Cin, Cout, pl)) return -1;
-  return pl.ksplit > 1 ? (long)pl.ksplit * N * D * H * W * ((Cout + 31) / 32) * 32 * 4 : 0;
-}
-// GroupNorm-partial slots per (n, group) when the conv can emit them (no split-K, whole planes per group); 0 otherwise
-long bts_lp_s1d_gn_B_(int N, int D, int H, int W, int Cin, int Cout, int Gn) {
-  S1dPlan pl;
-  if (Gn <= 0 || !s1d_plan(N, D, H, W, Cin, Cout, pl)) return 0;
-  // (the split-K finish leaves the partials, in its own layout: slabs need not be whole planes there)
-  if (pl.ksplit > 1) return bts_lp_splitk_gn_B_(N, (long)D * H * W, Cout, Gn);
-  if (D % Gn != 0) return 0;
-  return (long)(D / Gn) * pl.nty * pl.ntx * pl.ncg * 2;
-}
-
-// does the SC form with a split output take this shape?  (K contraction channels, Ncols output columns)
-bool bts_lp_s1d_sc_split_ok_(int N, int D, int H, int W, int K, int Ncols) {
-  S1dPlan pl;
-  return s1d_plan(N, D, H, W, K, Ncols, pl) && pl.mode == 1 && pl.ksplit == 1 && Ncols % 32 == 0;
+bool lp_s1d_accept(const LpS1Call& c, LpS1Choice& ch) {
+  S1dPlan& pl = ch.d;
+  if (!s1d_plan(c.N, c.D, c.H, c.W, c.Cin, c.Cout, pl)) return false;
+  const long dhw = (long)c.D * c.H * c.W, npad = (long)((c.Cout + 31) / 32) * 32;
+  const bool sc = c.ldx2 != 0;
+  // split output: the SC form, whole 32-column blocks, no split-K (its finish writes one tensor), 32-bit scalar offsets
+  if (c.ysplit != 0 && (!sc || c.ysplit < 0 || c.Cout % 32 != 0 || c.ldy < 32 || pl.ksplit > 1)) return false;
+  // SC: 64-cout items only (32-cout items have no registers left for the operand pair)
+  if (sc && (pl.mode != 1 || c.ldx2 < c.Cin || c.ldx2 % 8 != 0 || !c.aligned || dhw * (long)c.ldx2 * 2 >= 0x7fffff00L)) return false;
+  if (((long)(c.D + 2) * c.H * c.W + 64) * (long)c.ldx * 2 >= 0x7fffffffL) return false;
+  const long omax = (long)c.ldy > npad * 2 ? c.ldy : npad * 2;
+  if (dhw * omax * 2 >= 0x7fffff00L) return false;
+  ch.ws = pl.ksplit > 1 ? (long)pl.ksplit * c.N * dhw * npad * 4 : 0;
+  // GroupNorm partials: the epilogue's (whole planes per group), or the split-K finish's in its own layout (dense y, no accumulation)
+  ch.B = 0;
+  if (c.G > 0 && !c.gnb_G && c.ysplit == 0) {
+    if (pl.ksplit > 1) ch.B = (c.accum || c.ldy != c.Cout) ? 0 : bts_lp_splitk_gn_B_(c.N, dhw, c.Cout, c.G);
+    else if (c.D % c.G == 0) ch.B = (long)(c.D / c.G) * pl.nty * pl.ntx * pl.ncg * 2;
+  }
+  return true;
 }
 
 template <typename T, int MODE, int TXL, bool SC = false>
@@ -641,26 +637,16 @@ static int s1d_launch_t(const LpS1dParams& p, hipStream_t stream) {
   return BTS_OK;
 }
 
-// BTS_OK = ran, 1 = declined.  wp_dma = the DMA part of the K3S1 image.  gn_B (out, may be NULL): partial slots per (n, group) written.
-// x2 / wp2 / ldx2 (may be NULL): the SC form -- y += x2 . w2 at the centre tap, x2 (N,D,H,W,Cin) with voxel stride ldx2, wp2 the first
-// part of a K1 image with the same K = Cin and N = Cout (64-cout items only: 32-cout items have no registers left for the operand pair)
-int bts_lp_s1d_launch_(int dtype, const void* x, const void* wp_dma, const float* bias, void* y, void* ws, long ws_bytes, int N, int D, int H,
-                       int W, int Cin, int ldx, int Cout, int ldy, int accum, double* gnp, int gn_G, hipStream_t stream, const void* x2,
-                       const void* wp2, int ldx2, long ysplit) {
-  S1dPlan pl;
-  if (!s1d_plan(N, D, H, W, Cin, Cout, pl)) return 1;
-  // split output: whole 32-column blocks, no split-K (its finish writes one tensor), no fused statistics, 32-bit scalar offsets
-  if (ysplit != 0 && (x2 == nullptr || ysplit < 0 || Cout % 32 != 0 || ldy < 32 || pl.ksplit > 1 || gnp != nullptr)) return 1;
-  const bool sc = x2 != nullptr;
-  if (sc && (pl.mode != 1 || wp2 == nullptr || ldx2 < Cin || ldx2 % 8 != 0 || (((uintptr_t)x2) & 15) || (((uintptr_t)wp2) & 15) ||
-             (long)D * H * W * (long)ldx2 * 2 >= 0x7fffff00L))
-    return 1;
-  if (((long)(D + 2) * H * W + 64) * (long)ldx * 2 >= 0x7fffffffL) return 1;
-  const long omax = (long)ldy > (long)((Cout + 31) / 32) * 32 * 2 ? ldy : (long)((Cout + 31) / 32) * 32 * 2;
-  if ((long)D * H * W * omax * 2 >= 0x7fffff00L) return 1;
+// q.wp = the DMA part of the K3S1 image.  SC (q.x2, q.wp2): y += x2 . w2 at the centre tap, x2 (N,D,H,W,Cin) with voxel stride
+// c.ldx2, wp2 the first part of a K1 image with the same K = Cin and N = Cout.
+int bts_lp_s1d_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream) {
+  const S1dPlan& pl = ch.d;
+  const bool sc = q.x2 != nullptr;
+  const int N = c.N, D = c.D, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout;
+  const int gn_G = q.gnp != nullptr ? c.G : 0;
   LpS1dParams p;
-  p.x = (const unsigned short*)x; p.wp = (const unsigned short*)wp_dma; p.bias = bias; p.y = (unsigned short*)y;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = ldx; p.ldy = ldy; p.Cout = Cout; p.KS = Cin / 16; p.NB = (Cout + 31) / 32;
+  p.x = (const unsigned short*)q.x; p.wp = (const unsigned short*)q.wp; p.bias = q.bias; p.y = (unsigned short*)q.y;
+  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = c.ldx; p.ldy = c.ldy; p.Cout = Cout; p.KS = Cin / 16; p.NB = (Cout + 31) / 32;
   p.ntx = pl.ntx; p.nty = pl.nty; p.ntz = pl.ntz; p.ncg = pl.ncg; p.nitems = pl.nitems;
   p.bx = pl.bx; p.by = pl.by; p.bz_ = pl.bz;
   p.bvol_ = (unsigned)(pl.bx * pl.by * pl.bz); p.nbx_ = (unsigned)(pl.ntx / pl.bx); p.nby_ = (unsigned)(pl.nty / pl.by); p.nbz_ = (unsigned)(pl.ntz / pl.bz);
@@ -668,22 +654,19 @@ int bts_lp_s1d_launch_(int dtype, const void* x, const void* wp_dma, const float
     const unsigned dv[7] = {(unsigned)pl.ncg, p.bvol_, (unsigned)pl.bx, (unsigned)pl.by, p.nbx_, p.nby_, p.nbz_};
     for (int k = 0; k < 7; ++k) s1d_fastdiv(dv[k], p.dv_mul[k], p.dv_sh[k]);
   }
-  p.ksplit = pl.ksplit; p.ks_per = pl.ks_per; p.accum = accum;
-  p.part = reinterpret_cast<float*>(ws);
+  p.ksplit = pl.ksplit; p.ks_per = pl.ks_per; p.accum = c.accum;
+  p.part = reinterpret_cast<float*>(q.ws);
   const long nvox = (long)N * D * H * W;
-  if (p.ksplit > 1 && (ws == nullptr || ws_bytes < (long)p.ksplit * nvox * p.NB * 32 * 4 || (((uintptr_t)ws) & 15))) {
-    if (gnp != nullptr) return BTS_ERR_WORKSPACE;      // (the caller sized the partial array for the split plan)
+  if (p.ksplit > 1 && (q.ws == nullptr || q.ws_bytes < ch.ws || (((uintptr_t)q.ws) & 15))) {
+    if (q.gnp != nullptr) return BTS_ERR_WORKSPACE;      // (the caller sized the partial array for the split plan)
     p.ksplit = 1; p.ks_per = p.KS;
   }
-  p.x2 = (const unsigned short*)x2; p.wp2 = (const unsigned short*)wp2; p.ldx2 = ldx2;
-  p.ysplit = ysplit; p.ycol = ysplit ? 0 : 32;
-  p.gnp = gnp; p.gn_G = gn_G; p.gn_zt = gn_G > 0 ? D / gn_G : 1;
+  p.x2 = (const unsigned short*)q.x2; p.wp2 = (const unsigned short*)q.wp2; p.ldx2 = c.ldx2;
+  p.ysplit = c.ysplit; p.ycol = c.ysplit ? 0 : 32;
+  p.gnp = q.gnp; p.gn_G = gn_G; p.gn_zt = gn_G > 0 ? D / gn_G : 1;
   p.gn_B = gn_G > 0 ? (long)p.gn_zt * pl.nty * pl.ntx * pl.ncg * 2 : 0;
-  const bool split_gn = gnp != nullptr && p.ksplit > 1;      // statistics from the split-K finish (dense y, whole 32-cout blocks)
-  if (split_gn) {
-    if (accum || ldy != Cout || bts_lp_splitk_gn_B_(N, (long)D * H * W, Cout, gn_G) <= 0) return BTS_ERR_UNSUPPORTED;
-    p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1; p.gn_B = 0;
-  }
+  const bool split_gn = q.gnp != nullptr && p.ksplit > 1;      // statistics from the split-K finish (dense y, whole 32-cout blocks)
+  if (split_gn) { p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1; p.gn_B = 0; }
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(33 | ((1 + pl.mode * 2 + (pl.txl == 4 ? 1 : 0)) << 16), 2.0 * (sc ? 28.0 : 27.0) * Cin * (double)Cout * (double)nvox, stream);   // (bits 16+: the variant, for bench.py's per-variant table)
   int r;
@@ -698,7 +681,7 @@ int bts_lp_s1d_launch_(int dtype, const void* x, const void* wp_dma, const float
 #undef S1D_CASE
   if (prof) bts_prof_end(stream);
   if (r != BTS_OK) return r;
-  if (split_gn) return bts_lp_splitk_reduce_gn_(dtype, p.part, bias, y, gnp, N, (long)D * H * W, Cout, gn_G, p.ksplit, stream);
-  if (p.ksplit > 1) return bts_lp_splitk_reduce_(dtype, p.part, bias, y, nvox, Cout, p.NB * 32, ldy, p.ksplit, accum, stream);
+  if (split_gn) return bts_lp_splitk_reduce_gn_(dtype, p.part, q.bias, q.y, q.gnp, N, (long)D * H * W, Cout, c.G, p.ksplit, stream);
+  if (p.ksplit > 1) return bts_lp_splitk_reduce_(dtype, p.part, q.bias, q.y, nvox, Cout, p.NB * 32, c.ldy, p.ksplit, c.accum, stream);
   return BTS_OK;
 }

@@ -142,7 +142,7 @@ def conv_bwd_data_sc(code, dy, wp_bwd, dy2, wp2_bwd, dx, accumulate):
 
 def conv_bwd_data_sc_split_ok(n, d, h, w, cin, cout):
     """does the fused launch write its (cin = 32 B)-column result as B dense 32-channel tensors at this shape?"""
-    return cin % 32 == 0 and cin >= 64 and bool(lib().probe('bts_lp_conv3d_bwd_data_sc_split_ok', n, d, h, w, cin, cout))
+    return bool(lib().probe('bts_lp_conv3d_bwd_data_sc_split_ok', n, d, h, w, cin, cout))
 
 
 def conv(kind, code, tdt, x, wp, bias, cout, out=None):

@@ -120,6 +120,14 @@ def test_normalisation_and_gate_workspaces(L, grid):
     assert L._bts_loss_workspace() > 0 and L._bts_l2_workspace() > 0 and L._bts_lp_head_bwd_workspace(32, 3) >= 0
 
 
+
+def test_split_data_gradient_query_matches_the_kernel_bounds(L):
+    """bts_lp_conv3d_bwd_data_sc_split_ok answers from the same choice the launch makes: at 1 x 224^3 (64 -> 32) the split output's
+    offsets leave 31 bits and the launch declines, so the query must say 0 (the trainer then keeps level 0 as one slab)"""
+    assert L._bts_lp_conv3d_bwd_data_sc_split_ok(1, 224, 224, 224, 64, 32) == 0
+    assert L._bts_lp_conv3d_bwd_data_sc_split_ok(1, 192, 192, 192, 64, 32) == 1
+    assert L._bts_lp_conv3d_bwd_data_sc_split_ok(8, 128, 128, 128, 64, 32) == 1
+
 def test_pack_descriptor_tables_are_written_inside_their_bounds(L):
     """bts_conv_pack_desc / bts_lp_pack_desc fill entry `index` of a host table of `*_desc_bytes()` entries: a guard band behind the
     table must stay untouched (the ASan run checks the same thing from the allocator's side)"""
