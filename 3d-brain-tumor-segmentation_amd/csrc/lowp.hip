@@ -2743,717 +2743,6 @@ extern "C" int bts_lp_conv3d_bwd_data_gn_bwd(int dtype, const void* dy, const vo
 }
 
 // =====================================================================================================================
-// Weight gradient of the stride-1 3x3x3 and 1x1x1 convolutions on 16-bit operands (what TF autodiff derives for the Conv3D
-// kernels of resnet.py:30-37,80-87,96-103; train.py:151):  dW[t][c][k] = sum_v P[v + off_t][c] * Q[v][k],  P = the conv's input,
-// Q = the gradient of its output.  The contraction runs over VOXELS, so both matrix operands want 8 consecutive voxels of one
-// channel per lane (v_mfma_f32_32x32x16: A row = input channel, B column = output channel, K = 16 voxels along x) while memory is
-// channel-fastest: the (halo) tiles are staged voxel-major in LDS as they come and every fragment is gathered with eight
-// 2-byte LDS reads -- taps, which shift the 8-voxel window by single voxels, cost nothing extra that way.  A Q fragment serves all
-// of a wave's taps, a P fragment all of its cout blocks.  8 waves: the 27 taps are dealt round-robin (1x1x1: the 32 x-rows of the
-// tile are), persistent workgroups accumulate over their tiles and leave fp32 partials for a fixed-order finalize that also folds
-// the encoder's duplicated slice back onto both copies of the weight (encoder.py:83-87) and adds into the gradient buffer.
-// =====================================================================================================================
-struct LpWgParams {
-  const unsigned short* p;
-  const unsigned short* q;
-  float* part;
-  int N, D, H, W, Cp, ldp, Cq, ldq, ntaps;
-  int ntx, nty, ntz;
-  long ntiles;
-  int ncp, ncqg;
-};
-#define LPW_TX 16
-#define LPW_TY 8
-#define LPW_TZ 4
-
-template <typename T, int NQ, bool K3>
-__global__ __launch_bounds__(512, 1) void lp_wgrad_kernel(const LpWgParams p) {
-  constexpr int TX = LPW_TX, TY = LPW_TY, TZ = LPW_TZ;
-  constexpr int PS = 36, QS = 32 * NQ + 4;          // halves per staged voxel (8-byte aligned rows, bank-skewed)
-  extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, l32 = lane & 31;
-  constexpr bool k3 = K3;
-  constexpr int halo = K3 ? 1 : 0;
-  constexpr int SX = TX + 2 * halo, SY = TY + 2 * halo, SZ = TZ + 2 * halo;
-  constexpr int nvp = SX * SY * SZ;
-  unsigned short* ldsP = lds;
-  unsigned short* ldsQ = lds + (TX + 2) * (TY + 2) * (TZ + 2) * PS;
-  const int cpt = blockIdx.y / p.ncqg, cqg = blockIdx.y % p.ncqg;
-  const int cp0 = cpt * 32, cq0 = cqg * 32 * NQ;
-  f32x16 acc[4][NQ];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int c = 0; c < NQ; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][c][r] = 0.f;
-  auto tile_origin = [&](long tile, int& n, int& x0, int& y0, int& z0) {
-    long b = tile;
-    const int tx = (int)(b % p.ntx); b /= p.ntx;
-    const int ty = (int)(b % p.nty); b /= p.nty;
-    const int tz = (int)(b % p.ntz);
-    n = (int)(b / p.ntz);
-    x0 = tx * TX; y0 = ty * TY; z0 = tz * TZ;
-  };
-
-  if constexpr (K3) {
-    // ---- 3x3x3: LDS tiles with PAIRS of x-neighbours interleaved per channel, [row (z, y)][x pair][channel] dwords (low half = the
-    // even slot).  A matrix operand (8 consecutive voxels of one channel) is then 4 consecutive pair-dwords of a lane's channel: 4 or
-    // 5 ds_read_b32 + 4 v_alignbit (a tap's window starts at an odd slot for kx = 0, 2) instead of eight 2-byte reads and their
-    // packing.  Staging interleaves two voxels' 8-channel chunks with v_perm and writes 32 contiguous bytes.
-    constexpr int NPP = (SX + 2) / 2;            // pairs per P row: slots x = -2 .. SX - 1
-    constexpr int NPQ = TX / 2;
-    constexpr int PU = SZ * SY * NPP * 4, QU = TZ * TY * NPQ * 4 * NQ;    // staging units: (row, pair, channel octet)
-    constexpr int PUS = (PU + 511) / 512, QUS = (QU + 511) / 512;
-    unsigned* const ldsP32 = reinterpret_cast<unsigned*>(lds);
-    unsigned* const ldsQ32 = ldsP32 + SZ * SY * NPP * 32;
-    u32x4 preP[PUS][2], preQ[QUS][2];
-    auto fetch = [&](long tile) {
-      int n, x0, y0, z0;
-      tile_origin(tile, n, x0, y0, z0);
-#pragma unroll
-      for (int i = 0; i < PUS; ++i) {
-        const int e = tid + i * 512;
-        preP[i][0] = preP[i][1] = u32x4{0u, 0u, 0u, 0u};
-        if (e < PU) {
-          const int oct = e & 3, xp = (e >> 2) % NPP, row = (e >> 2) / NPP;
-          const int gz = z0 - 1 + row / SY, gy = y0 - 1 + row % SY;
-          if ((unsigned)gz < (unsigned)p.D && (unsigned)gy < (unsigned)p.H && cp0 + oct * 8 < p.Cp) {
-            const unsigned short* rowp = p.p + (((long)n * p.D + gz) * p.H + gy) * (long)p.W * p.ldp + cp0 + oct * 8;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-              const int slot = 2 * xp + s2, gx = x0 - 2 + slot;   // slots 1 .. SX are the halo tile's columns -1 .. TX
-              if (slot >= 1 && slot <= SX && (unsigned)gx < (unsigned)p.W) preP[i][s2] = *reinterpret_cast<const u32x4*>(rowp + (long)gx * p.ldp);
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < QUS; ++i) {
-        const int e = tid + i * 512;
-        preQ[i][0] = preQ[i][1] = u32x4{0u, 0u, 0u, 0u};
-        if (e < QU) {
-          const int oct = e % (4 * NQ), xp = (e / (4 * NQ)) % NPQ, row = e / (4 * NQ * NPQ);
-          const int gz = z0 + row / TY, gy = y0 + row % TY;
-          if (gz < p.D && gy < p.H && cq0 + oct * 8 < p.Cq) {
-            const unsigned short* rowq = p.q + (((long)n * p.D + gz) * p.H + gy) * (long)p.W * p.ldq + cq0 + oct * 8;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-              const int gx = x0 + 2 * xp + s2;
-              if (gx < p.W) preQ[i][s2] = *reinterpret_cast<const u32x4*>(rowq + (long)gx * p.ldq);
-            }
-          }
-        }
-      }
-    };
-    // (even voxel's channels c, c+1 | odd voxel's c, c+1) x 4 -> channel c: (even, odd), channel c+1: (even, odd)
-    auto weave = [&](const u32x4 ev, const u32x4 od, unsigned* dst) {
-      u32x4 lo, hi;
-      lo[0] = __builtin_amdgcn_perm(od[0], ev[0], 0x05040100u); lo[1] = __builtin_amdgcn_perm(od[0], ev[0], 0x07060302u);
-      lo[2] = __builtin_amdgcn_perm(od[1], ev[1], 0x05040100u); lo[3] = __builtin_amdgcn_perm(od[1], ev[1], 0x07060302u);
-      hi[0] = __builtin_amdgcn_perm(od[2], ev[2], 0x05040100u); hi[1] = __builtin_amdgcn_perm(od[2], ev[2], 0x07060302u);
-      hi[2] = __builtin_amdgcn_perm(od[3], ev[3], 0x05040100u); hi[3] = __builtin_amdgcn_perm(od[3], ev[3], 0x07060302u);
-      reinterpret_cast<u32x4*>(dst)[0] = lo;
-      reinterpret_cast<u32x4*>(dst)[1] = hi;
-    };
-    auto commit = [&]() {
-#pragma unroll
-      for (int i = 0; i < PUS; ++i) {
-        const int e = tid + i * 512;
-        if (e < PU) weave(preP[i][0], preP[i][1], ldsP32 + (e >> 2) * 32 + (e & 3) * 8);
-      }
-#pragma unroll
-      for (int i = 0; i < QUS; ++i) {
-        const int e = tid + i * 512;
-        if (e < QU) weave(preQ[i][0], preQ[i][1], ldsQ32 + (e / (4 * NQ)) * (32 * NQ) + (e % (4 * NQ)) * 8);
-      }
-    };
-    if constexpr (NQ == 1) {
-      // Tap dealing: six compute waves = (dy, half of the tile's y rows); a wave walks the P rows (z', y' = y + dy) of its four y
-      // and uses each row's three x windows (kx = 0, 1, 2: window starts at slots 1, 2, 3 -- six pair reads, five alignbits) for
-      // ALL three dz with the Q rows z = z' - dz, which roll through three fragment registers: 10 LDS reads + 5 vector-ALU
-      // instructions per 9 matrix instructions at full depth.  Nine accumulators (dz, kx) per wave; the two halves of a dy meet in
-      // LDS at the end.  Waves 6, 7 only help staging.
-      const bool cw = wave < 6;
-      const int dy = wave % 3, half = (wave / 3) & 1;
-      const unsigned* pbase = ldsP32 + 4 * h * 32 + l32;
-      const unsigned* qbase = ldsQ32 + 4 * h * 32 + l32;
-      f32x16 a9[3][3];
-  #pragma unroll
-      for (int dz = 0; dz < 3; ++dz)
-  #pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-  #pragma unroll
-          for (int r = 0; r < 16; ++r) a9[dz][kx][r] = 0.f;
-      long tile = blockIdx.x;
-      if (tile < p.ntiles) fetch(tile);
-      for (; tile < p.ntiles; tile += gridDim.x) {
-        __syncthreads();      // every wave is done with the previous tile
-        commit();
-        __syncthreads();
-        if (tile + gridDim.x < p.ntiles) fetch(tile + gridDim.x);
-        if (cw) {
-  #pragma unroll 2
-          for (int yi = 0; yi < TY / 2; ++yi) {
-            const int yq = half * (TY / 2) + yi;
-            const unsigned* prow = pbase + ((yq + dy) * NPP) * 32;
-            const unsigned* qrow = qbase + (yq * NPQ) * 32;
-            u32x4 qf[3];
-  #pragma unroll
-            for (int zp = 0; zp < SZ; ++zp) {
-              if (zp < TZ) {
-                const unsigned* qr = qrow + (zp * TY * NPQ) * 32;
-                qf[zp % 3] = u32x4{qr[0], qr[32], qr[64], qr[96]};
-              }
-              const unsigned* pr = prow + (zp * SY * NPP) * 32;
-              unsigned pp[6], sh[5];
-  #pragma unroll
-              for (int k = 0; k < 6; ++k) pp[k] = pr[k * 32];
-  #pragma unroll
-              for (int k = 0; k < 5; ++k) sh[k] = __builtin_amdgcn_alignbit(pp[k + 1], pp[k], 16);
-              const u32x4 w0 = {sh[0], sh[1], sh[2], sh[3]}, w1 = {pp[1], pp[2], pp[3], pp[4]}, w2 = {sh[1], sh[2], sh[3], sh[4]};
-  #pragma unroll
-              for (int dz = 0; dz < 3; ++dz) {
-                const int z = zp - dz;
-                if (z >= 0 && z < TZ) {
-                  a9[dz][0] = T::mfma(w0, qf[z % 3], a9[dz][0]);
-                  a9[dz][1] = T::mfma(w1, qf[z % 3], a9[dz][1]);
-                  a9[dz][2] = T::mfma(w2, qf[z % 3], a9[dz][2]);
-                }
-              }
-            }
-          }
-        }
-      }
-      // the two halves of a dy: waves 3..5 hand their nine accumulators over through LDS, waves 0..2 add and write the partials
-      __syncthreads();
-      float* xch = reinterpret_cast<float*>(lds);
-      if (wave >= 3 && wave < 6) {
-  #pragma unroll
-        for (int dz = 0; dz < 3; ++dz)
-  #pragma unroll
-          for (int kx = 0; kx < 3; ++kx)
-  #pragma unroll
-            for (int r = 0; r < 16; ++r) xch[((((wave - 3) * 9 + dz * 3 + kx) * 16) + r) * 64 + lane] = a9[dz][kx][r];
-      }
-      __syncthreads();
-      if (wave < 3) {
-        float* pb = p.part + (((long)blockIdx.x * p.ncp + cpt) * p.ncqg + cqg) * (long)27 * 32 * 32;
-  #pragma unroll
-        for (int dz = 0; dz < 3; ++dz)
-  #pragma unroll
-          for (int kx = 0; kx < 3; ++kx) {
-            const int slot = (dz * 3 + dy) * 3 + kx;
-  #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-              pb[((long)slot * 32 + row) * 32 + l32] = a9[dz][kx][r] + xch[(((wave * 9 + dz * 3 + kx) * 16) + r) * 64 + lane];
-            }
-          }
-      }
-      return;
-    } else {
-      // wave w owns taps w, w+8, w+16 (and w+24 for w < 3) and walks all 32 x-rows of the tile; a tap's window starts at slot
-      // kx + 1 (+ 8 for the lanes of the upper K half): pair offset and alignbit shift are wave constants
-      int toff[4], tsh[4];
-  #pragma unroll
-      for (int ti = 0; ti < 4; ++ti) {
-        const int t = wave + 8 * ti;
-        const int tt = t < 27 ? t : 0;
-        const int kx = tt % 3;
-        toff[ti] = ((((tt / 9) * SY + (tt / 3) % 3) * NPP) + ((kx + 1) >> 1)) * 32;
-        tsh[ti] = ((kx + 1) & 1) ? 16 : 0;
-      }
-      const bool t3 = wave + 24 < 27;
-      const unsigned* pbase = ldsP32 + 4 * h * 32 + l32;
-      const unsigned* qbase = ldsQ32 + 4 * h * (32 * NQ) + l32;
-      auto pfrag = [&](const unsigned* prow, int off, int sh) {
-        unsigned pp[5];
-  #pragma unroll
-        for (int k = 0; k < 5; ++k) pp[k] = prow[off + k * 32];
-        return u32x4{__builtin_amdgcn_alignbit(pp[1], pp[0], sh), __builtin_amdgcn_alignbit(pp[2], pp[1], sh),
-                     __builtin_amdgcn_alignbit(pp[3], pp[2], sh), __builtin_amdgcn_alignbit(pp[4], pp[3], sh)};
-      };
-      long tile = blockIdx.x;
-      if (tile < p.ntiles) fetch(tile);
-      for (; tile < p.ntiles; tile += gridDim.x) {
-        __syncthreads();      // every wave is done with the previous tile
-        commit();
-        __syncthreads();
-        if (tile + gridDim.x < p.ntiles) fetch(tile + gridDim.x);
-  #pragma unroll 4
-        for (int kb = 0; kb < TY * TZ; ++kb) {
-          const int z = kb / TY, y = kb % TY;
-          u32x4 bq[NQ];
-  #pragma unroll
-          for (int c = 0; c < NQ; ++c) {
-            const unsigned* qr = qbase + (kb * NPQ) * (32 * NQ) + c * 32;
-            bq[c] = u32x4{qr[0], qr[32 * NQ], qr[2 * 32 * NQ], qr[3 * 32 * NQ]};
-          }
-          const unsigned* prow = pbase + ((z * SY + y) * NPP) * 32;
-  #pragma unroll
-          for (int ti = 0; ti < 3; ++ti) {
-            const u32x4 a = pfrag(prow, toff[ti], tsh[ti]);
-  #pragma unroll
-            for (int c = 0; c < NQ; ++c) acc[ti][c] = T::mfma(a, bq[c], acc[ti][c]);
-          }
-          if (t3) {
-            const u32x4 a = pfrag(prow, toff[3], tsh[3]);
-  #pragma unroll
-            for (int c = 0; c < NQ; ++c) acc[3][c] = T::mfma(a, bq[c], acc[3][c]);
-          }
-        }
-      }
-    }
-  } else {
-    // ---- 1x1x1: voxel-major tiles as they come, every fragment gathered with eight 2-byte LDS reads; wave w takes x-rows w, w+8,
-    // w+16, w+24 (one accumulator per wave; the finalize adds the eight)
-    constexpr int PSLOT = (nvp * 4 + 511) / 512;   // 16-byte chunks of the P tile per thread
-    constexpr int QSLOT = (TX * TY * TZ * 4 * NQ + 511) / 512;
-    u32x4 preP[PSLOT], preQ[QSLOT];
-    auto fetch = [&](long tile) {
-      int n, x0, y0, z0;
-      tile_origin(tile, n, x0, y0, z0);
-#pragma unroll
-      for (int i = 0; i < PSLOT; ++i) {
-        const int e = tid + i * 512;
-        preP[i] = u32x4{0u, 0u, 0u, 0u};
-        if (e < nvp * 4) {
-          const int vox = e >> 2, cq = e & 3;
-          const int vz = vox / (SY * SX), r = vox - vz * (SY * SX), vy = r / SX, vx = r - vy * SX;
-          const int gz = z0 - halo + vz, gy = y0 - halo + vy, gx = x0 - halo + vx;
-          if ((unsigned)gz < (unsigned)p.D && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W && cp0 + cq * 8 < p.Cp)
-            preP[i] = *reinterpret_cast<const u32x4*>(p.p + ((((long)n * p.D + gz) * p.H + gy) * p.W + gx) * (long)p.ldp + cp0 + cq * 8);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < QSLOT; ++i) {
-        const int e = tid + i * 512;
-        preQ[i] = u32x4{0u, 0u, 0u, 0u};
-        if (e < TX * TY * TZ * 4 * NQ) {
-          const int vox = e / (4 * NQ), cq = e % (4 * NQ);
-          const int vz = vox / (TY * TX), r = vox - vz * (TY * TX), vy = r / TX, vx = r - vy * TX;
-          const int gz = z0 + vz, gy = y0 + vy, gx = x0 + vx;
-          if (gz < p.D && gy < p.H && gx < p.W && cq0 + cq * 8 < p.Cq)
-            preQ[i] = *reinterpret_cast<const u32x4*>(p.q + ((((long)n * p.D + gz) * p.H + gy) * p.W + gx) * (long)p.ldq + cq0 + cq * 8);
-        }
-      }
-    };
-    auto commit = [&]() {
-#pragma unroll
-      for (int i = 0; i < PSLOT; ++i) {
-        const int e = tid + i * 512;
-        if (e < nvp * 4) {
-          u32x2* d = reinterpret_cast<u32x2*>(ldsP + (e >> 2) * PS + (e & 3) * 8);
-          d[0] = u32x2{preP[i][0], preP[i][1]};
-          d[1] = u32x2{preP[i][2], preP[i][3]};
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < QSLOT; ++i) {
-        const int e = tid + i * 512;
-        if (e < TX * TY * TZ * 4 * NQ) {
-          u32x2* d = reinterpret_cast<u32x2*>(ldsQ + (e / (4 * NQ)) * QS + (e % (4 * NQ)) * 8);
-          d[0] = u32x2{preQ[i][0], preQ[i][1]};
-          d[1] = u32x2{preQ[i][2], preQ[i][3]};
-        }
-      }
-    };
-    // eight 2-byte reads -> one 16-byte matrix operand (K = 8 consecutive voxels along x of one channel)
-    auto gather = [&](const unsigned short* base, int stride) {
-      unsigned v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = base[j * stride];
-      return u32x4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
-    };
-    long tile = blockIdx.x;
-    if (tile < p.ntiles) fetch(tile);
-    for (; tile < p.ntiles; tile += gridDim.x) {
-      __syncthreads();      // every wave is done with the previous tile
-      commit();
-      __syncthreads();
-      if (tile + gridDim.x < p.ntiles) fetch(tile + gridDim.x);
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti) {
-        const int kb = wave + 8 * ti;
-        const int z = kb / TY, y = kb % TY;
-        const u32x4 a = gather(ldsP + ((z * SY + y) * SX + 8 * h) * PS + l32, PS);
-#pragma unroll
-        for (int c = 0; c < NQ; ++c) {
-          const u32x4 b = gather(ldsQ + ((z * TY + y) * TX + 8 * h) * QS + c * 32 + l32, QS);
-          acc[0][c] = T::mfma(a, b, acc[0][c]);
-        }
-      }
-    }
-  }
-  // partial sums: part[wg][cp tile][cq group][slot][32 cin][32*NQ cout]; slot = tap (3x3x3) or wave (1x1x1)
-  const int nslot = k3 ? 27 : 8;
-  float* pb = p.part + (((long)blockIdx.x * p.ncp + cpt) * p.ncqg + cqg) * (long)nslot * 32 * (32 * NQ);
-#pragma unroll
-  for (int ti = 0; ti < 4; ++ti) {
-    const int slot = k3 ? wave + 8 * ti : wave;
-    if ((k3 && slot < 27) || (!k3 && ti == 0)) {
-#pragma unroll
-      for (int c = 0; c < NQ; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-          pb[((long)slot * 32 + row) * (32 * NQ) + c * 32 + l32] = acc[ti][c][r];
-        }
-    }
-  }
-}
-
-struct LpWfParams {
-  const float* part;
-  float* dw;
-  int nwg, ncp, ncqg, nslot, ntaps, NQ, Cp, Cq, Cin_ref, dup_start, dup_shift, accum;
-};
-// dW[t][c_ref][k] (+)= sum over workgroups (and, for 1x1x1, waves) of the partials, fixed order; a slab channel c is reference
-// channel c + shift and, inside the duplicated slice, ALSO reference channel c - dup_start (both copies get the gradient)
-__global__ __launch_bounds__(256) void lp_wgrad_finalize_kernel(const LpWfParams f) {
-  // 32 consecutive elements x 8 slices of the workgroup list per block: coalesced partial reads, slices combined in fixed order
-  __shared__ double sh[8][32];
-  const long total = (long)f.ntaps * f.Cp * f.Cq;
-  const int el = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  for (long i0 = blockIdx.x * 32L; i0 < total; i0 += (long)gridDim.x * 32) {
-    const long i = i0 + el;
-    double s = 0.0;
-    int k = 0, c = 0, t = 0;
-    if (i < total) {
-      k = (int)(i % f.Cq);
-      const long r = i / f.Cq;
-      c = (int)(r % f.Cp);
-      t = (int)(r / f.Cp);
-      const int cpt = c / 32, row = c % 32, cqg = k / (32 * f.NQ), col = k % (32 * f.NQ);
-      const int s0 = f.ntaps == 27 ? t : 0, s1 = f.ntaps == 27 ? t + 1 : f.nslot;      // (1x1x1: the general kernel's 8 wave slots, the streaming kernel's one)
-      for (int wg = sl; wg < f.nwg; wg += 8) {
-        const float* pb = f.part + (((long)wg * f.ncp + cpt) * f.ncqg + cqg) * (long)f.nslot * 32 * (32 * f.NQ);
-        for (int q = s0; q < s1; ++q) s += pb[((long)q * 32 + row) * (32 * f.NQ) + col];
-      }
-    }
-    __syncthreads();
-    sh[sl][el] = s;
-    __syncthreads();
-    if (sl == 0 && i < total) {
-      double tot = 0.0;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) tot += sh[q][el];
-      const float v = (float)tot;
-      float* d0 = f.dw + ((long)t * f.Cin_ref + c + f.dup_shift) * f.Cq + k;
-      *d0 = f.accum ? *d0 + v : v;
-      if (f.dup_shift > 0 && c >= f.dup_start && c < f.dup_start + f.dup_shift) {
-        float* d1 = f.dw + ((long)t * f.Cin_ref + (c - f.dup_start)) * f.Cq + k;
-        *d1 = f.accum ? *d1 + v : v;
-      }
-    }
-  }
-}
-// The same for the 3x3x3 launches (one slot per tap) with Cq % 4 == 0: a thread owns FOUR consecutive columns (16-byte partial reads:
-// the 4-byte version above read 28 MB in 29 us = 1 TB/s, 1.7 ms of the batch-8 step), 32 threads x 4 = 128 elements x 8 slices per block
-__global__ __launch_bounds__(256) void lp_wgrad_finalize4_kernel(const LpWfParams f) {
-  __shared__ double sh[8][32][4];
-  const long total4 = (long)f.ntaps * f.Cp * f.Cq / 4;
-  const int el = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int W = 32 * f.NQ;
-  for (long i0 = blockIdx.x * 32L; i0 < total4; i0 += (long)gridDim.x * 32) {
-    const long i4 = i0 + el;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    int k = 0, c = 0, t = 0;
-    if (i4 < total4) {
-      const long i = i4 * 4;
-      k = (int)(i % f.Cq);
-      const long r = i / f.Cq;
-      c = (int)(r % f.Cp);
-      t = (int)(r / f.Cp);
-      const int cpt = c / 32, row = c % 32, cqg = k / W, col = k % W;
-      for (int wg = sl; wg < f.nwg; wg += 8) {
-        const float* pb = f.part + (((long)wg * f.ncp + cpt) * f.ncqg + cqg) * (long)f.nslot * 32 * W;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(pb + ((long)t * 32 + row) * W + col);
-        s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[sl][el][j] = s[j];
-    __syncthreads();
-    if (sl == 0 && i4 < total4) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        double tot = 0.0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) tot += sh[q][el][j];
-        const float v = (float)tot;
-        float* d0 = f.dw + ((long)t * f.Cin_ref + c + f.dup_shift) * f.Cq + k + j;
-        *d0 = f.accum ? *d0 + v : v;
-        if (f.dup_shift > 0 && c >= f.dup_start && c < f.dup_start + f.dup_shift) {
-          float* d1 = f.dw + ((long)t * f.Cin_ref + (c - f.dup_start)) * f.Cq + k + j;
-          *d1 = f.accum ? *d1 + v : v;
-        }
-      }
-    }
-  }
-}
-static void lp_wgrad_finalize_launch(const LpWfParams& f, hipStream_t stream) {
-  const long total = (long)f.ntaps * f.Cp * f.Cq;
-  if (f.ntaps == 27 && f.nslot == 27 && f.Cq % 4 == 0 && (((uintptr_t)f.part) & 15) == 0) {
-    long blocks = (total / 4 + 31) / 32;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(lp_wgrad_finalize4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, f);
-    return;
-  }
-  long blocks = (total + 31) / 32;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(lp_wgrad_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, f);
-}
-int bts_lp_wgrad_finalize_(const float* part, float* dw, int nwg, int ncp, int ncqg, int nslot, int ntaps, int NQ, int Cp, int Cq, int Cin_ref,
-                           int dup_start, int dup_shift, int accum, hipStream_t stream) {
-  LpWfParams f;
-  f.part = part; f.dw = dw; f.nwg = nwg; f.ncp = ncp; f.ncqg = ncqg; f.nslot = nslot; f.ntaps = ntaps; f.NQ = NQ;
-  f.Cp = Cp; f.Cq = Cq; f.Cin_ref = Cin_ref; f.dup_start = dup_start; f.dup_shift = dup_shift; f.accum = accum;
-  (void)hipGetLastError();
-  lp_wgrad_finalize_launch(f, stream);
-  BTS_LAUNCH_CHECK();
-  return BTS_OK;
-}
-// lowp_wgs.hip: weight gradient of the strided convolutions (P on the fine grid, Q on the coarse one)
-long bts_lp_wgs_workspace_(int N, int Dc, int Hc, int Wc, int Cp, int Cq);
-int bts_lp_wgs_launch_(int dtype, const void* P, const void* Q, float* dw, void* ws, long ws_bytes, int N, int Df, int Hf, int Wf, int Dc, int Hc,
-                       int Wc, int Cp, int ldp, int Cq, int ldq, int accum, hipStream_t stream);
-// lowp_wgd.hip: the streaming weight-gradient kernel of the stride-1 3x3x3 convolutions with Cout <= 32
-long bts_lp_wgd_workspace_(int N, int D, int H, int W, int Cp, int Cq);
-int bts_lp_wgd_launch_(int dtype, const void* x, const void* dy, float* dw, void* ws, long ws_bytes, int N, int D, int H, int W, int Cp, int ldp,
-                       int Cq, int ldq, int dup_start, int dup_shift, int accum, hipStream_t stream, const LpGnaFuse* ga = nullptr,
-                       const void* dy2 = nullptr, float* dw1 = nullptr, int lddy2 = 0, long psplit = 0);
-bool bts_lp_wgd_gna_ok_(int N, int D, int H, int W, int Cp, int Cq, int in_G);
-// db[k] (+)= sum_n colsum[n][k]
-__global__ void lp_bias_grad_kernel(const float* cs, float* db, int N, int C, int accum) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= C) return;
-  float s = 0.f;
-  for (int n = 0; n < N; ++n) s += cs[n * C + k];
-  db[k] = accum ? db[k] + s : s;
-}
-
-static void lp_wg_plan(int kind, int N, int D, int H, int W, int Cp, int Cq, int& nq, int& nwg, long& ntiles, int& ncp, int& ncqg) {
-  nq = Cq >= 64 ? 2 : 1;
-  ncp = (Cp + 31) / 32;
-  ncqg = (Cq + 32 * nq - 1) / (32 * nq);
-  ntiles = (long)N * ((D + LPW_TZ - 1) / LPW_TZ) * ((H + LPW_TY - 1) / LPW_TY) * ((W + LPW_TX - 1) / LPW_TX);
-  long cap = 256 / ((long)ncp * ncqg);          // one 512-thread workgroup per CU over the whole launch
-  if (cap < 1) cap = 1;
-  nwg = (int)(ntiles < cap ? ntiles : cap);
-}
-// strided kinds: (P channels, Q channels, coarse dims, voxels dy lives on) of a call with forward-input dims (D,H,W)
-static void lp_wgs_roles(int kind, int D, int H, int W, int Cin, int Cout, int& Cp, int& Cq, int& Dc, int& Hc, int& Wc, long& Vdy) {
-  if (kind == BTS_CONV_K3S2) { Cp = Cin; Cq = Cout; Dc = D / 2; Hc = H / 2; Wc = W / 2; Vdy = (long)Dc * Hc * Wc; }
-  else { Cp = Cout; Cq = Cin; Dc = D; Hc = H; Wc = W; Vdy = 8L * D * H * W; }
-}
-extern "C" long bts_lp_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout) {
-  if (kind == BTS_CONV_K3S2 || kind == BTS_CONV_K3S2T) {
-    int Cp, Cq, Dc, Hc, Wc; long Vdy;
-    lp_wgs_roles(kind, D, H, W, Cin, Cout, Cp, Cq, Dc, Hc, Wc, Vdy);
-    const long part = ((bts_lp_wgs_workspace_(N, Dc, Hc, Wc, Cp, Cq) + 255) & ~255L);
-    return part + (long)N * ((Cout + 7) / 8 * 8) * 4 + 256 + bts_lp_colsum_workspace(N, Vdy, (Cout + 7) / 8 * 8) + 256;
-  }
-  if (kind != BTS_CONV_K3S1 && kind != BTS_CONV_K1) return -1;
-  int nq, nwg, ncp, ncqg; long ntiles;
-  lp_wg_plan(kind, N, D, H, W, Cin, Cout, nq, nwg, ntiles, ncp, ncqg);
-  const int nslot = kind == BTS_CONV_K3S1 ? 27 : 8;
-  long part = (long)nwg * ncp * ncqg * nslot * 32 * 32 * nq * 4;
-  if (kind == BTS_CONV_K3S1) {          // (the streaming kernel's slabs sit in the same place; one per workgroup too)
-    const long alt = bts_lp_wgd_workspace_(N, D, H, W, Cin, Cout);
-    if (alt > part) part = alt;
-  }
-  return part + (long)N * ((Cout + 7) / 8 * 8) * 4 + bts_lp_colsum_workspace(N, (long)D * H * W, (Cout + 7) / 8 * 8) + 256;
-}
-// dw (Keras layout (kd,kh,kw,Cin_ref,Cout), fp32) (+)= the weight gradient; db (may be NULL) (+)= sum of dy over voxels and samples.
-// x (N,D,H,W,Cin) stride ldx, dy (N,D,H,W,Cout) DENSE when db is wanted; Cin, Cout multiples of 8.  K3S1 and K1 only (-3 otherwise).
-extern "C" int bts_lp_conv3d_bwd_weight(int kind, int dtype, const void* x, const void* dy, float* dw, float* db, void* workspace,
-                                        long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int dup_start,
-                                        int dup_shift, int accumulate, hipStream_t stream) {
-  if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (kind == BTS_CONV_K3S2 || kind == BTS_CONV_K3S2T) {
-    // strided kinds (lowp_wgs.hip): x lives on the forward-input grid (D,H,W), dy on the half grid (stride-2 conv; TF 'same' with even
-    // sizes pads (0,1): input 2o + t) or the doubled grid (transposed conv: output 2i + k)
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || Cout % 8 != 0 || ldx % 8 != 0 || lddy % 8 != 0) return BTS_ERR_SHAPE;
-    if (kind == BTS_CONV_K3S2 && ((D | H | W) & 1)) return BTS_ERR_UNSUPPORTED;
-    if (dup_shift != 0) return BTS_ERR_UNSUPPORTED;
-    if ((((uintptr_t)x) & 15) || (((uintptr_t)dy) & 15) || (((uintptr_t)workspace) & 15)) return BTS_ERR_ALIGN;
-    if (workspace_bytes < bts_lp_conv3d_bwd_weight_workspace(kind, N, D, H, W, Cin, Cout)) return BTS_ERR_WORKSPACE;
-    int Cp, Cq, Dc, Hc, Wc; long Vdy;
-    lp_wgs_roles(kind, D, H, W, Cin, Cout, Cp, Cq, Dc, Hc, Wc, Vdy);
-    const long part = ((bts_lp_wgs_workspace_(N, Dc, Hc, Wc, Cp, Cq) + 255) & ~255L);
-    int r;
-    if (kind == BTS_CONV_K3S2)
-      r = bts_lp_wgs_launch_(dtype, x, dy, dw, workspace, part, N, D, H, W, Dc, Hc, Wc, Cp, ldx, Cq, lddy, accumulate, stream);
-    else
-      r = bts_lp_wgs_launch_(dtype, dy, x, dw, workspace, part, N, 2 * D, 2 * H, 2 * W, Dc, Hc, Wc, Cp, lddy, Cq, ldx, accumulate, stream);
-    if (r != BTS_OK) return r;
-    if (db != nullptr) {
-      if (lddy != Cout) return BTS_ERR_UNSUPPORTED;
-      char* wsb = reinterpret_cast<char*>(workspace) + part;
-      float* cs = reinterpret_cast<float*>(wsb);
-      void* cws = wsb + (((long)N * Cout * 4 + 255) & ~255L);
-      r = bts_lp_colsum(dtype, dy, cs, cws, bts_lp_colsum_workspace(N, Vdy, Cout), N, Vdy, Cout, 1.0f, stream);
-      if (r != BTS_OK) return r;
-      hipLaunchKernelGGL(lp_bias_grad_kernel, dim3((Cout + 255) / 256), dim3(256), 0, stream, cs, db, N, Cout, accumulate);
-      BTS_LAUNCH_CHECK();
-    }
-    return BTS_OK;
-  }
-  if (kind != BTS_CONV_K3S1 && kind != BTS_CONV_K1) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || Cout % 8 != 0 || ldx % 8 != 0 || lddy % 8 != 0) return BTS_ERR_SHAPE;
-  if ((((uintptr_t)x) & 15) || (((uintptr_t)dy) & 15) || (((uintptr_t)workspace) & 15)) return BTS_ERR_ALIGN;
-  if (dup_shift < 0 || (dup_shift > 0 && dup_start + dup_shift > Cin)) return BTS_ERR_SHAPE;
-  if (workspace_bytes < bts_lp_conv3d_bwd_weight_workspace(kind, N, D, H, W, Cin, Cout)) return BTS_ERR_WORKSPACE;
-  LpWgParams p;
-  int nq, nwg;
-  lp_wg_plan(kind, N, D, H, W, Cin, Cout, nq, nwg, p.ntiles, p.ncp, p.ncqg);
-  long part_bytes = (long)nwg * p.ncp * p.ncqg * (kind == BTS_CONV_K3S1 ? 27 : 8) * 32 * 32 * nq * 4;
-  bool streamed = false;
-  if (kind == BTS_CONV_K3S1) {          // few output channels at a large volume: the streaming kernel (lowp_wgd.hip), else the general one
-    const long alt = bts_lp_wgd_workspace_(N, D, H, W, Cin, Cout);
-    if (alt > 0) {
-      const int r = bts_lp_wgd_launch_(dtype, x, dy, dw, workspace, alt > part_bytes ? alt : part_bytes, N, D, H, W, Cin, ldx, Cout, lddy, dup_start,
-                                       dup_shift, accumulate, stream);
-      if (r < 0) return r;
-      streamed = r == BTS_OK;
-      if (alt > part_bytes) part_bytes = alt;
-    }
-  }
-  if (!streamed) {
-  p.p = (const unsigned short*)x; p.q = (const unsigned short*)dy; p.part = reinterpret_cast<float*>(workspace);
-  p.N = N; p.D = D; p.H = H; p.W = W; p.Cp = Cin; p.ldp = ldx; p.Cq = Cout; p.ldq = lddy; p.ntaps = kind == BTS_CONV_K3S1 ? 27 : 1;
-  p.ntx = (W + LPW_TX - 1) / LPW_TX; p.nty = (H + LPW_TY - 1) / LPW_TY; p.ntz = (D + LPW_TZ - 1) / LPW_TZ;
-  const size_t shmem = ((size_t)(LPW_TX + 2) * (LPW_TY + 2) * (LPW_TZ + 2) * 36 + (size_t)LPW_TX * LPW_TY * LPW_TZ * (32 * nq + 4)) * 2;
-  (void)hipGetLastError();
-#define LPW_LAUNCH(TT, NQ_, K3_)                                                                                                \
-  do {                                                                                                                        \
-    auto kern = lp_wgrad_kernel<TT, NQ_, K3_>;                                                                                \
-    static bool done = false;                                                                                                 \
-    if (!done) {                                                                                                              \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      if (e != hipSuccess) return (int)e;                                                                                     \
-      done = true;                                                                                                            \
-    }                                                                                                                         \
-    hipLaunchKernelGGL(kern, dim3(nwg, p.ncp * p.ncqg), dim3(512), shmem, stream, p);                                         \
-  } while (0)
-  const bool k3 = kind == BTS_CONV_K3S1;
-  const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(32 | ((k3 ? 1 : 2) << 16), 2.0 * p.ntaps * (double)Cin * Cout * (double)N * D * H * W, stream);   // (variant 2: 1x1x1 -- 2 FLOP per operand byte, HBM-bound)
-  if (dtype == LP_F16) {
-    if (k3) { if (nq == 2) LPW_LAUNCH(TF16, 2, true); else LPW_LAUNCH(TF16, 1, true); }
-    else { if (nq == 2) LPW_LAUNCH(TF16, 2, false); else LPW_LAUNCH(TF16, 1, false); }
-  } else {
-    if (k3) { if (nq == 2) LPW_LAUNCH(TBF16, 2, true); else LPW_LAUNCH(TBF16, 1, true); }
-    else { if (nq == 2) LPW_LAUNCH(TBF16, 2, false); else LPW_LAUNCH(TBF16, 1, false); }
-  }
-#undef LPW_LAUNCH
-  if (prof) bts_prof_end(stream);
-  BTS_LAUNCH_CHECK();
-  LpWfParams f;
-  f.part = p.part; f.dw = dw; f.nwg = nwg; f.ncp = p.ncp; f.ncqg = p.ncqg; f.nslot = kind == BTS_CONV_K3S1 ? 27 : 8; f.ntaps = p.ntaps; f.NQ = nq;
-  f.Cp = Cin; f.Cq = Cout; f.Cin_ref = Cin + dup_shift; f.dup_start = dup_start; f.dup_shift = dup_shift; f.accum = accumulate;
-  lp_wgrad_finalize_launch(f, stream);
-  BTS_LAUNCH_CHECK();
-  }
-  if (db != nullptr) {
-    if (lddy != Cout) return BTS_ERR_UNSUPPORTED;
-    char* wsb = reinterpret_cast<char*>(workspace) + part_bytes;
-    float* cs = reinterpret_cast<float*>(wsb);
-    void* cws = wsb + (((long)N * Cout * 4 + 255) & ~255L);
-    const int r = bts_lp_colsum(dtype, dy, cs, cws, bts_lp_colsum_workspace(N, (long)D * H * W, Cout), N, (long)D * H * W, Cout, 1.0f, stream);
-    if (r != BTS_OK) return r;
-    hipLaunchKernelGGL(lp_bias_grad_kernel, dim3((Cout + 255) / 256), dim3(256), 0, stream, cs, db, N, Cout, accumulate);
-    BTS_LAUNCH_CHECK();
-  }
-  return BTS_OK;
-}
-// The weight gradients of the TWO convolutions that read a ResnetBlock's input (resnet.py:134 conv1, 3x3x3; resnet.py:118 shortcut, 1x1x1)
-// from ONE pass over that input: dw3[t][c][k] (+)= sum_v x[v + off_t][c] dy3[v][k] and dw1[c][k] (+)= sum_v x[v][c] dy1[v][k].  The streaming
-// weight-gradient kernel (lowp_wgd.hip) holds a P fragment of the centre tap anyway; the shortcut's gradient is one more accumulator per
-// wave fed by planes of dy1 that ride in the Q-ring slots the 3x3x3 contraction no longer needs (its older planes live in registers).
-// The 1x1x1 weight-gradient launch -- HBM-bound, its own read of the Cin-wide x -- goes away.  db3 (may be NULL; dy3 dense then) (+)= sum dy3.
-// Same conventions as bts_lp_conv3d_bwd_weight (dup_start / dup_shift fold both kernels alike).  The workspace query returns -1 and the
-// call 1 (nothing launched) where the streaming kernel does not take the shape: run bts_lp_conv3d_bwd_weight twice.
-extern "C" long bts_lp_conv3d_bwd_weight_pair_workspace(int N, int D, int H, int W, int Cin, int Cout) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || Cout % 8 != 0) return -1;
-  const long alt = bts_lp_wgd_workspace_(N, D, H, W, Cin, Cout);
-  if (alt <= 0) return -1;
-  const long part = ((alt / 27 * 28 + 255) & ~255L);
-  return part + (long)N * ((Cout + 7) / 8 * 8) * 4 + bts_lp_colsum_workspace(N, (long)D * H * W, (Cout + 7) / 8 * 8) + 512;
-}
-extern "C" int bts_lp_conv3d_bwd_weight_pair(int dtype, const void* x, long x_split, const void* dy3, const void* dy1, float* dw3, float* dw1,
-                                             float* db3, void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx,
-                                             int Cout, int lddy3, int lddy1, int dup_start, int dup_shift, int accumulate, hipStream_t stream) {
-  if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  const long need = bts_lp_conv3d_bwd_weight_pair_workspace(N, D, H, W, Cin, Cout);
-  if (need < 0) return 1;
-  if (x == nullptr || dy3 == nullptr || dy1 == nullptr || dw3 == nullptr || dw1 == nullptr) return BTS_ERR_ALIGN;
-  if (ldx % 8 != 0 || lddy3 % 8 != 0 || lddy1 % 8 != 0 || ldx < (x_split ? 32 : Cin) || lddy3 < Cout || lddy1 < Cout) return BTS_ERR_SHAPE;
-  if (x_split != 0 && (x_split < 0 || x_split % 8 != 0 || Cin % 32 != 0 || dup_shift != 0)) return BTS_ERR_SHAPE;
-  if ((((uintptr_t)x) & 15) || (((uintptr_t)dy3) & 15) || (((uintptr_t)dy1) & 15) || (((uintptr_t)workspace) & 15)) return BTS_ERR_ALIGN;
-  if (dup_shift < 0 || (dup_shift > 0 && dup_start + dup_shift > Cin)) return BTS_ERR_SHAPE;
-  if (workspace == nullptr || workspace_bytes < need) return BTS_ERR_WORKSPACE;
-  if (db3 != nullptr && lddy3 != Cout) return BTS_ERR_UNSUPPORTED;
-  const long part_bytes = ((bts_lp_wgd_workspace_(N, D, H, W, Cin, Cout) / 27 * 28 + 255) & ~255L);
-  const int r = bts_lp_wgd_launch_(dtype, x, dy3, dw3, workspace, part_bytes, N, D, H, W, Cin, ldx, Cout, lddy3, dup_start, dup_shift, accumulate, stream,
-                                   nullptr, dy1, dw1, lddy1, x_split);
-  if (r != BTS_OK) return r;      // (1: declined, nothing launched)
-  if (db3 != nullptr) {
-    char* wsb = reinterpret_cast<char*>(workspace) + part_bytes;
-    float* cs = reinterpret_cast<float*>(wsb);
-    void* cws = wsb + (((long)N * Cout * 4 + 255) & ~255L);
-    const int r2 = bts_lp_colsum(dtype, dy3, cs, cws, bts_lp_colsum_workspace(N, (long)D * H * W, Cout), N, (long)D * H * W, Cout, 1.0f, stream);
-    if (r2 != BTS_OK) return r2;
-    hipLaunchKernelGGL(lp_bias_grad_kernel, dim3((Cout + 255) / 256), dim3(256), 0, stream, cs, db3, N, Cout, accumulate);
-    BTS_LAUNCH_CHECK();
-  }
-  return BTS_OK;
-}
-// conv2 of a ResnetBlock in TRAINING without the normalised tensor: conv2's forward reads conv1's raw output through
-// bts_lp_conv3d_gnin_fwd_gn, and its weight gradient dW[t][c][k] = sum_v a[v + off_t][c] dy[v][k] with a = relu(GN1(x)) is taken from the
-// raw x the same way -- the streaming weight-gradient kernel normalises its P planes in LDS (lowp_wgd.hip, GNA).  a = relu(GN1(c1))
-// (resnet.py:133-134) is then never written: one 1 read + 1 write pass and one activation-sized tensor per block less.
-// bts_lp_conv3d_gnin_train_ok: 1 when BOTH kernels take the shape in this form (ask before the forward), else 0.
-extern "C" int bts_lp_conv3d_gnin_train_ok(int N, int D, int H, int W, int Cin, int Cout, int in_G, int G) {
-  if (bts_lp_conv3d_gnin_fwd_gn_workspace(N, D, H, W, Cin, Cout, in_G, G) < 0) return 0;
-  return bts_lp_wgd_gna_ok_(N, D, H, W, Cin, Cout, in_G) ? 1 : 0;
-}
-// x: the RAW GroupNorm input, dense (N,D,H,W,Cin); in_*: that GroupNorm's parameters and statistics (slab mode; ReLU follows it);
-// dy (N,D,H,W,Cout) rows of lddy; dw (3,3,3,Cin,Cout) fp32 (+)=; db (may be NULL) (+)= column sums of dy (dense dy then).  Workspace:
-// bts_lp_conv3d_bwd_weight_workspace(BTS_CONV_K3S1, ...).  BTS_ERR_UNSUPPORTED where bts_lp_conv3d_gnin_train_ok says 0.
-extern "C" int bts_lp_conv3d_gnin_bwd_weight(int dtype, const void* x, const float* in_gamma, const float* in_beta, const float* in_mean,
-                                             const float* in_rstd, int in_G, const void* dy, float* dw, float* db, void* workspace,
-                                             long workspace_bytes, int N, int D, int H, int W, int Cin, int Cout, int lddy, int accumulate,
-                                             hipStream_t stream) {
-  if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || Cout % 8 != 0 || lddy % 8 != 0 || lddy < Cout) return BTS_ERR_SHAPE;
-  if (!bts_lp_wgd_gna_ok_(N, D, H, W, Cin, Cout, in_G)) return BTS_ERR_UNSUPPORTED;
-  if ((((uintptr_t)x) & 15) || (((uintptr_t)dy) & 15) || (((uintptr_t)workspace) & 15)) return BTS_ERR_ALIGN;
-  if (workspace_bytes < bts_lp_conv3d_bwd_weight_workspace(BTS_CONV_K3S1, N, D, H, W, Cin, Cout)) return BTS_ERR_WORKSPACE;
-  const long part_bytes = bts_lp_wgd_workspace_(N, D, H, W, Cin, Cout);
-  LpGnaFuse ga{in_gamma, in_beta, in_mean, in_rstd, in_G, Cin / in_G};
-  const int r = bts_lp_wgd_launch_(dtype, x, dy, dw, workspace, part_bytes, N, D, H, W, Cin, Cin, Cout, lddy, 0, 0, accumulate, stream, &ga);
-  if (r == 1) return BTS_ERR_UNSUPPORTED;
-  if (r != BTS_OK) return r;
-  if (db != nullptr) {
-    if (lddy != Cout) return BTS_ERR_UNSUPPORTED;
-    char* wsb = reinterpret_cast<char*>(workspace) + ((part_bytes + 255) & ~255L);
-    float* cs = reinterpret_cast<float*>(wsb);
-    void* cws = wsb + (((long)N * Cout * 4 + 255) & ~255L);
-    const int r2 = bts_lp_colsum(dtype, dy, cs, cws, bts_lp_colsum_workspace(N, (long)D * H * W, Cout), N, (long)D * H * W, Cout, 1.0f, stream);
-    if (r2 != BTS_OK) return r2;
-    hipLaunchKernelGGL(lp_bias_grad_kernel, dim3((Cout + 255) / 256), dim3(256), 0, stream, cs, db, N, Cout, accumulate);
-    BTS_LAUNCH_CHECK();
-  }
-  return BTS_OK;
-}
-
-// =====================================================================================================================
 // Gate (squeeze-excitation) backward on 16-bit tensors (resnet.py:121-130 under TF autodiff): with g = dout * res per element,
 //   t_v = sum_c g, ds_v = t_v sp_v (1 - sp_v)            (spatial gate, fp32 per voxel)
 //   Pch[n][c] = sum_v g, Pw[c] = sum_v ds_v res          (per-block partials, fp64, layout of se.hip; stages 2a / 2 are se.hip's)

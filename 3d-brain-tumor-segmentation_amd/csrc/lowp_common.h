@@ -252,3 +252,58 @@ int lp_s1_choose(const LpS1Call& c, LpS1Choice& ch);
 inline long lp_s1z_fs_B(const S1zPlan& pl) { return (long)pl.ntx * pl.nty * pl.nzc * 8; }      // FS column-sum rows per sample
 int bts_lp_s1z_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);     // q.wp = the DMA part
 int bts_lp_s1d_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);
+
+// ---- 16-bit weight gradients: which of the three kernels takes a call (the streaming lp_wgd_kernel of lowp_wgd.hip, the general LDS-tiled
+// lp_wgrad_kernel of lowp_wg.hip, the strided lp_wgs_kernel of lowp_wgs.hip) and where its workspace areas lie, decided ONCE per query or
+// launch by lp_wg_choose; the workspace queries and the entry points answer from it ----
+struct LpWgCall {         // kind, shape, strides (elements) and requested form of one call -- no pointers
+  int kind, N, D, H, W, Cin, ldx, Cout, lddy;      // (D, H, W: the forward-input grid x lives on)
+  int dup_start, dup_shift, accum;
+  int want_db;            // db (+)= the column sums of dy is asked for
+  int gna_G;              // GNA: x is the RAW input of a GroupNorm (+ ReLU) of gna_G groups, applied to the P planes in LDS (0: none)
+  int k1f, lddy1;         // K1F: the 1x1x1 weight gradient of a second conv on the same input, from dy1 with voxel stride lddy1
+  long x_split;           // x as a list of 32-channel tensors x + b * x_split with voxel stride ldx (0: one tensor)
+  int aligned;            // every operand and the workspace sit on a 16-byte boundary
+};
+struct WgdPlan { int ntx, nty, nzc, ZC, nitems, ipw, nwg, ncp, ncq, xcd; };
+struct LpWgPlan { int nq, nwg, ncp, ncqg, ntx, nty, ntz; long ntiles; };      // the general and the strided kernel
+enum { LP_WGD = 1, LP_WG, LP_WGS };
+struct LpWgChoice {
+  int kernel;             // LP_WGD | LP_WG | LP_WGS (0: none)
+  WgdPlan d;
+  LpWgPlan g;
+  long part;              // bytes of the partial-slab area at the head of the workspace (a whole number of 4 KB slabs)
+  long cs_off, cws_off;   // byte offsets of the per-sample column sums of dy and of bts_lp_colsum's workspace behind it
+  long ws;                // the whole workspace
+};
+// the operands of a launch (NULL: absent); ga: LpWgCall::gna_G, dy1 / dw1: LpWgCall::k1f
+struct LpWgPtrs { const void *x, *dy; float* dw; void* ws; const LpGnaFuse* ga; const void* dy1; float* dw1; };
+// the general and the strided kernel: persistent 512-thread workgroups over nz x ny x nx tiles per sample, one per CU over the whole launch
+inline void lp_wg_tiles(LpWgPlan& g, int N, int Cp, int Cq, int nx, int ny, int nz) {
+  g.nq = Cq >= 64 ? 2 : 1;
+  g.ncp = (Cp + 31) / 32;
+  g.ncqg = (Cq + 32 * g.nq - 1) / (32 * g.nq);
+  g.ntx = nx; g.nty = ny; g.ntz = nz;
+  g.ntiles = (long)N * nz * ny * nx;
+  const long per = (long)g.ncp * g.ncqg, cap = per < 256 ? 256 / per : 1;
+  g.nwg = (int)(g.ntiles < cap ? g.ntiles : cap);
+}
+// voxels per sample of the grid dy lives on: the half grid of a stride-2 conv, the doubled grid of a transposed one
+inline long lp_wg_dy_voxels(const LpWgCall& c) {
+  if (c.kind == BTS_CONV_K3S2) return (long)(c.D / 2) * (c.H / 2) * (c.W / 2);
+  return (c.kind == BTS_CONV_K3S2T ? 8L : 1L) * c.D * c.H * c.W;
+}
+// true: the kernel takes the call (every shape, stride, 31-bit offset and form condition of its launcher) -- ch's kernel, plan and part are
+// filled in, and the launcher does not decline it
+bool lp_wgd_accept(const LpWgCall& c, LpWgChoice& ch);      // K3S1, every form
+bool lp_wg_accept(const LpWgCall& c, LpWgChoice& ch);       // K3S1 and K1, no form
+bool lp_wgs_accept(const LpWgCall& c, LpWgChoice& ch);      // K3S2 and K3S2T
+// BTS_OK: ch = the call's kernel and workspace layout, and the launch cannot fail on its arguments any more.  1: the streaming kernel does
+// not take the form asked for (GNA, K1F, x_split).  Otherwise the status of the call; ch is still filled in wherever a kernel could be
+// planned (the sizing query answers for every channel count).
+int lp_wg_choose(const LpWgCall& c, LpWgChoice& ch);
+int bts_lp_wgd_launch_(int dtype, const LpWgCall& c, const LpWgChoice& ch, const LpWgPtrs& q, hipStream_t stream);
+int bts_lp_wgs_launch_(int dtype, const LpWgCall& c, const LpWgChoice& ch, const LpWgPtrs& q, hipStream_t stream);
+// lowp_wg.hip: dw (+)= the partial slabs summed in fixed order (layout [workgroup][cp block][cq group][slot][32][32 * NQ]), fold included
+int bts_lp_wgrad_finalize_(const float* part, float* dw, int nwg, int ncp, int ncqg, int nslot, int ntaps, int NQ, int Cp, int Cq, int Cin_ref,
+                           int dup_start, int dup_shift, int accum, hipStream_t stream);

@@ -3,7 +3,7 @@
 // train.py:142-151:   dW[t][c][k] = sum_v P[v + off_t][c] * Q[v][k],   P = the conv's input, Q = the gradient of its output.
 //
 // At 32 x 32 channels the arithmetic intensity of this contraction (27 taps x 2 x 32 x 32 flops per 128 operand bytes = 432 flop/B)
-// sits just below the machine balance (2.5 PFLOP/s : ~5 TB/s): the layer is bound by reading P and Q ONCE.  lowp.hip's general
+// sits just below the machine balance (2.5 PFLOP/s : ~5 TB/s): the layer is bound by reading P and Q ONCE.  lowp_wg.hip's general
 // kernel (register staging with a 2-byte interleave, 16 x 8 x 4 tiles whose 18 x 10 x 6 halo re-reads P 2.1 times, two idle waves)
 // ran it at 0.79 PFLOP/s = 0.43 of that bound.  This kernel is built to stream:
 //   * a workgroup owns a 32 (x) x 8 (y) column and marches along z: every stage brings ONE plane of P (34 x 10 voxels: the x/y halo is
@@ -19,7 +19,7 @@
 //   * v_mfma_f32_16x16x32: a wave owns ONE 16 x 16 (cin x cout) block of all 27 taps (108 accumulation registers) for half of the
 //     column's rows -- 8 waves = 2 cin halves x 2 cout halves x 2 row halves, every SIMD equally loaded.  A P fragment (one row, one
 //     x tap) meets the 3 x 3 (z, y) neighbourhood of Q fragments: 60 transposing reads per 108 matrix instructions;
-//   * the two row halves meet in LDS at the end: one fp32 partial slab per workgroup in the layout of lowp.hip's fixed-order finalize.
+//   * the two row halves meet in LDS at the end: one fp32 partial slab per workgroup in the layout of lowp_wg.hip's fixed-order finalize.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -31,8 +31,6 @@
 int bts_prof_on();
 void bts_prof_begin(int sym, double flops, hipStream_t stream);
 void bts_prof_end(hipStream_t stream);
-int bts_lp_wgrad_finalize_(const float* part, float* dw, int nwg, int ncp, int ncqg, int nslot, int ntaps, int NQ, int Cp, int Cq, int Cin_ref,
-                           int dup_start, int dup_shift, int accum, hipStream_t stream);
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -429,28 +427,37 @@ __global__ __launch_bounds__(512, 1) void lp_wgd_kernel(const LpWgdParams p) {
 }
 
 // =====================================================================================================================
-// plan + launch (the finalize is lowp.hip's)
+// plan + launch (the finalize is lowp_wg.hip's)
 // =====================================================================================================================
-struct WgdPlan { int ntx, nty, nzc, ZC, nitems, ipw, nwg, ncp, ncq, xcd; };
-static bool wgd_enabled() {   // BTS_LP_WGD=0: these layers back on lowp.hip's general weight-gradient kernel (A/B; read per call)
+static bool wgd_enabled() {   // BTS_LP_WGD=0: these layers back on lowp_wg.hip's general weight-gradient kernel (A/B; read per call)
   const char* e = getenv("BTS_LP_WGD");
   return !(e && atoi(e) == 0);
 }
-static bool wgd_plan(WgdPlan& pl, int N, int D, int H, int W, int Cp, int ldp, int Cq, int ldq) {
-  if (!wgd_enabled() || Cq % 8 != 0 || Cp % 8 != 0 || W % WGD_TX != 0 || H % WGD_TY != 0 || D < 4) return false;
-  if ((long)D * H * W * (long)ldp * 2 >= 0x7fffffffL || (long)D * H * W * (long)ldq * 2 >= 0x7fffffffL) return false;
+// the forms: GNA (GroupNorm + ReLU on the P planes, dense x of <= 32 channels whose classes tile a 16-byte slot, whole z planes per group),
+// K1F (a second gradient dy1; its slab is a 28th tap behind the 27), x_split (P as a list of 32-channel tensors) -- GNA goes with neither
+bool lp_wgd_accept(const LpWgCall& c, LpWgChoice& ch) {
+  const int Cp = c.Cin, Cq = c.Cout;
+  if (c.kind != BTS_CONV_K3S1 || !wgd_enabled() || Cq % 8 != 0 || Cp % 8 != 0 || c.W % WGD_TX != 0 || c.H % WGD_TY != 0 || c.D < 4) return false;
+  const long V = (long)c.D * c.H * c.W;
+  if (V * (long)c.ldx * 2 >= 0x7fffffffL || V * (long)c.lddy * 2 >= 0x7fffffffL) return false;
+  if (c.x_split != 0 && (c.x_split < 0 || c.gna_G != 0 || Cp % 32 != 0 || c.ldx < 32 || c.x_split % 8 != 0)) return false;
+  if (c.gna_G != 0) {
+    const int G = c.gna_G;
+    if (G < 0 || G > 32 || c.D % G != 0 || Cp % G != 0 || Cp > 32 || Cp / G > 8 || 8 % (Cp / G) != 0 || c.ldx != Cp || c.dup_shift != 0) return false;
+  }
+  if (c.k1f && (c.gna_G != 0 || c.lddy1 < Cq || c.lddy1 % 8 != 0 || V * (long)c.lddy1 * 2 >= 0x7fffffffL)) return false;
+  WgdPlan& pl = ch.d;
   pl.ncp = (Cp + 31) / 32;
   pl.ncq = (Cq + 31) / 32;
-  pl.ntx = W / WGD_TX; pl.nty = H / WGD_TY;
-  const long ncol = (long)N * pl.ntx * pl.nty;
-  if (ncol * D < 64) return false;      // (fewer than 64 plane stages: nothing to stream)
+  pl.ntx = c.W / WGD_TX; pl.nty = c.H / WGD_TY;
+  const long ncol = (long)c.N * pl.ntx * pl.nty;
+  if (ncol * c.D < 64) return false;      // (fewer than 64 plane stages: nothing to stream)
   int cus = 256 / (pl.ncp * pl.ncq);
   if (cus < 8) cus = 8;
   int nzc = 1;
-  while (ncol * nzc < 2L * cus && (D + 2 * nzc - 1) / (2 * nzc) >= 8) nzc *= 2;
-  pl.nzc = nzc;
-  pl.ZC = (D + nzc - 1) / nzc;
-  pl.nzc = (D + pl.ZC - 1) / pl.ZC;
+  while (ncol * nzc < 2L * cus && (c.D + 2 * nzc - 1) / (2 * nzc) >= 8) nzc *= 2;
+  pl.ZC = (c.D + nzc - 1) / nzc;
+  pl.nzc = (c.D + pl.ZC - 1) / pl.ZC;
   const long items = ncol * pl.nzc;
   if (items > 0x3fffffffL) return false;
   pl.nitems = (int)items;
@@ -458,42 +465,23 @@ static bool wgd_plan(WgdPlan& pl, int N, int D, int H, int W, int Cp, int ldp, i
   pl.ipw = (pl.nitems + nwg - 1) / nwg;
   pl.nwg = (pl.nitems + pl.ipw - 1) / pl.ipw;
   pl.xcd = (pl.nwg % 8 == 0 && pl.nwg * pl.ipw == pl.nitems) ? 1 : 0;
+  ch.kernel = LP_WGD;
+  ch.part = (long)pl.nwg * pl.ncp * pl.ncq * (c.k1f ? 28 : 27) * 1024 * 4;
   return true;
 }
-// bytes of partial slabs a call with these dimensions needs, or 0 when it is declined
-long bts_lp_wgd_workspace_(int N, int D, int H, int W, int Cp, int Cq) {
-  WgdPlan pl;
-  if (!wgd_plan(pl, N, D, H, W, Cp, Cp, Cq, Cq)) return 0;
-  return (long)pl.nwg * pl.ncp * pl.ncq * 27 * 1024 * 4;
-}
-// does the kernel take the shape with GroupNorm `in_G` (+ReLU) applied to its P planes (LpGnaFuse)?
-bool bts_lp_wgd_gna_ok_(int N, int D, int H, int W, int Cp, int Cq, int in_G) {
-  WgdPlan pl;
-  if (in_G <= 0 || in_G > 32 || D % in_G != 0 || Cp % in_G != 0 || Cp > 32 || !wgd_plan(pl, N, D, H, W, Cp, Cp, Cq, Cq)) return false;
-  const int cg = Cp / in_G;
-  return cg <= 8 && 8 % cg == 0;
-}
-// BTS_OK = ran (dw written by the shared finalize), 1 = declined
-// dy2 / dw1 / lddy2 (may be NULL / 0): the K1F form -- dw1 (Keras layout (1,1,1,Cin_ref,Cout)) (+)= the 1x1x1 weight gradient of a second conv
-// on the same input, from dy2 (N,D,H,W,Cq); its partial slabs sit behind the 27-tap ones in `ws` (bts_lp_wgd_workspace_ x 28 / 27)
-int bts_lp_wgd_launch_(int dtype, const void* x, const void* dy, float* dw, void* ws, long ws_bytes, int N, int D, int H, int W, int Cp, int ldp,
-                       int Cq, int ldq, int dup_start, int dup_shift, int accum, hipStream_t stream, const LpGnaFuse* ga, const void* dy2,
-                       float* dw1, int lddy2, long psplit) {
-  WgdPlan pl;
-  if (!wgd_plan(pl, N, D, H, W, Cp, ldp, Cq, ldq)) return 1;
-  if (psplit != 0 && (psplit < 0 || ga != nullptr || Cp % 32 != 0 || ldp < 32 || psplit % 8 != 0)) return 1;
-  if (ga != nullptr && (ldp != Cp || dup_shift != 0 || !bts_lp_wgd_gna_ok_(N, D, H, W, Cp, Cq, ga->G) || ga->cg != Cp / ga->G)) return 1;
-  const bool k1f = dy2 != nullptr;
-  if (k1f && (ga != nullptr || dw1 == nullptr || lddy2 < Cq || lddy2 % 8 != 0 || (((uintptr_t)dy2) & 15) ||
-              (long)D * H * W * (long)lddy2 * 2 >= 0x7fffffffL))
-    return 1;
-  if (ws_bytes < (long)pl.nwg * pl.ncp * pl.ncq * (k1f ? 28 : 27) * 1024 * 4) return 1;
+// dw (+)= the 27-tap gradient (the shared finalize); K1F: q.dw1 (Keras layout (1,1,1,Cin_ref,Cout)) (+)= the 1x1x1 weight gradient of a second
+// conv on the same input, from q.dy1 (N,D,H,W,Cq)
+int bts_lp_wgd_launch_(int dtype, const LpWgCall& c, const LpWgChoice& ch, const LpWgPtrs& q, hipStream_t stream) {
+  const WgdPlan& pl = ch.d;
+  const int Cp = c.Cin, Cq = c.Cout;
+  const LpGnaFuse* ga = q.ga;
+  const bool k1f = c.k1f != 0;
   LpWgdParams p;
-  p.p = (const unsigned short*)x; p.q = (const unsigned short*)dy; p.part = reinterpret_cast<float*>(ws);
-  p.N = N; p.D = D; p.H = H; p.W = W; p.Cp = Cp; p.ldp = ldp; p.Cq = Cq; p.ldq = ldq;
+  p.p = (const unsigned short*)q.x; p.q = (const unsigned short*)q.dy; p.part = reinterpret_cast<float*>(q.ws);
+  p.N = c.N; p.D = c.D; p.H = c.H; p.W = c.W; p.Cp = Cp; p.ldp = c.ldx; p.Cq = Cq; p.ldq = c.lddy;
   p.ntx = pl.ntx; p.nty = pl.nty; p.nzc = pl.nzc; p.ZC = pl.ZC; p.nitems = pl.nitems; p.ipw = pl.ipw; p.ncp = pl.ncp; p.ncq = pl.ncq; p.xcd_order = pl.xcd;
-  if (ga != nullptr) { p.ga = *ga; p.ga_zt = D / ga->G; } else { p.ga = LpGnaFuse{}; p.ga_zt = 1; }
-  p.q2 = (const unsigned short*)dy2; p.ldq2 = lddy2; p.psplit = psplit;
+  if (ga != nullptr) { p.ga = *ga; p.ga_zt = c.D / ga->G; } else { p.ga = LpGnaFuse{}; p.ga_zt = 1; }
+  p.q2 = (const unsigned short*)q.dy1; p.ldq2 = c.lddy1; p.psplit = c.x_split;
   p.part2 = p.part + (long)pl.nwg * pl.ncp * pl.ncq * 27 * 1024;
   (void)hipGetLastError();
 #define WGD_LAUNCH(TT) do { if (ga != nullptr) WGD_LAUNCH_(TT, true, false); else if (k1f) WGD_LAUNCH_(TT, false, true); else WGD_LAUNCH_(TT, false, false); } while (0)
@@ -509,13 +497,13 @@ int bts_lp_wgd_launch_(int dtype, const void* x, const void* dy, float* dw, void
     hipLaunchKernelGGL(kern, dim3(pl.nwg, pl.ncp, pl.ncq), dim3(512), WGD_LDS, stream, p);                                           \
   } while (0)
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(37, 2.0 * (k1f ? 28.0 : 27.0) * (double)Cp * Cq * (double)N * D * H * W, stream);
+  if (prof) bts_prof_begin(37, 2.0 * (k1f ? 28.0 : 27.0) * (double)Cp * Cq * (double)c.N * c.D * c.H * c.W, stream);
   if (dtype == LP_F16) WGD_LAUNCH(TF16); else WGD_LAUNCH(TBF16);
 #undef WGD_LAUNCH
 #undef WGD_LAUNCH_
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
-  const int r = bts_lp_wgrad_finalize_(p.part, dw, pl.nwg, pl.ncp, pl.ncq, 27, 27, 1, Cp, Cq, Cp + dup_shift, dup_start, dup_shift, accum, stream);
+  const int r = bts_lp_wgrad_finalize_(p.part, q.dw, pl.nwg, pl.ncp, pl.ncq, 27, 27, 1, Cp, Cq, Cp + c.dup_shift, c.dup_start, c.dup_shift, c.accum, stream);
   if (r != BTS_OK || !k1f) return r;
-  return bts_lp_wgrad_finalize_(p.part2, dw1, pl.nwg, pl.ncp, pl.ncq, 1, 1, 1, Cp, Cq, Cp + dup_shift, dup_start, dup_shift, accum, stream);
+  return bts_lp_wgrad_finalize_(p.part2, q.dw1, pl.nwg, pl.ncp, pl.ncq, 1, 1, 1, Cp, Cq, Cp + c.dup_shift, c.dup_start, c.dup_shift, c.accum, stream);
 }

@@ -12,7 +12,7 @@
 // the stride-2 walk through the fine tile (voxel 2o + t) costs nothing.  With 16-bit matrix instructions these layers are bound by
 // reading P once (8 fine voxels per coarse one, 27/16 matrix instructions per coarse voxel and 32x32 channel block): the kernel is
 // built to stream -- small double-buffered tiles (coarse 16x2x2), all 27 taps dealt to the 8 waves (3-4 accumulators each), persistent
-// workgroups, fp32 partials in the layout of lowp.hip's fixed-order finalize (shared with the stride-1 kernel).
+// workgroups, fp32 partials in the layout of lowp_wg.hip's fixed-order finalize (shared with the stride-1 kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -200,40 +200,34 @@ __global__ __launch_bounds__(512, 2) void lp_wgs_kernel(const LpWgsParams p) {
 }
 
 // =====================================================================================================================
-// plan + launch (the finalize is lowp.hip's)
+// plan + launch (the finalize is lowp_wg.hip's)
 // =====================================================================================================================
-int bts_lp_wgrad_finalize_(const float* part, float* dw, int nwg, int ncp, int ncqg, int nslot, int ntaps, int NQ, int Cp, int Cq, int Cin_ref,
-                           int dup_start, int dup_shift, int accum, hipStream_t stream);
-
-static void wgs_plan(int N, int Dc, int Hc, int Wc, int Cp, int Cq, int& nq, int& nwg, long& ntiles, int& ncp, int& ncqg, int& ntx, int& nty,
-                     int& ntz) {
-  nq = Cq >= 64 ? 2 : 1;
-  ncp = (Cp + 31) / 32;
-  ncqg = (Cq + 32 * nq - 1) / (32 * nq);
-  ntx = (Wc + WGS_TX - 1) / WGS_TX; nty = (Hc + WGS_TY - 1) / WGS_TY; ntz = (Dc + WGS_TZ - 1) / WGS_TZ;
-  ntiles = (long)N * ntz * nty * ntx;
-  long cap = 256 / ((long)ncp * ncqg);          // one 512-thread workgroup per CU over the whole launch
-  if (cap < 1) cap = 1;
-  nwg = (int)(ntiles < cap ? ntiles : cap);
+// who is P (fine grid) and who is Q (coarse grid) in a call with forward-input dims (D, H, W)
+struct WgsRoles { int Cp, ldp, Cq, ldq, Df, Hf, Wf, Dc, Hc, Wc; };
+static WgsRoles wgs_roles(const LpWgCall& c) {
+  if (c.kind == BTS_CONV_K3S2) return WgsRoles{c.Cin, c.ldx, c.Cout, c.lddy, c.D, c.H, c.W, c.D / 2, c.H / 2, c.W / 2};
+  return WgsRoles{c.Cout, c.lddy, c.Cin, c.ldx, 2 * c.D, 2 * c.H, 2 * c.W, c.D, c.H, c.W};
 }
-long bts_lp_wgs_workspace_(int N, int Dc, int Hc, int Wc, int Cp, int Cq) {
-  int nq, nwg, ncp, ncqg, ntx, nty, ntz;
-  long ntiles;
-  wgs_plan(N, Dc, Hc, Wc, Cp, Cq, nq, nwg, ntiles, ncp, ncqg, ntx, nty, ntz);
-  return (long)nwg * ncp * ncqg * 27 * 32 * 32 * nq * 4;
+bool lp_wgs_accept(const LpWgCall& c, LpWgChoice& ch) {
+  if (c.kind != BTS_CONV_K3S2 && c.kind != BTS_CONV_K3S2T) return false;
+  const WgsRoles r = wgs_roles(c);
+  if ((long)(WGS_FZ + 1) * r.Hf * r.Wf * (long)r.ldp * 2 >= 0x7fffffffL || (long)(WGS_TZ + 1) * r.Hc * r.Wc * (long)r.ldq * 2 >= 0x7fffffffL) return false;
+  LpWgPlan& g = ch.g;
+  lp_wg_tiles(g, c.N, r.Cp, r.Cq, (r.Wc + WGS_TX - 1) / WGS_TX, (r.Hc + WGS_TY - 1) / WGS_TY, (r.Dc + WGS_TZ - 1) / WGS_TZ);
+  ch.kernel = LP_WGS;
+  ch.part = (long)g.nwg * g.ncp * g.ncqg * 27 * 32 * 32 * g.nq * 4;
+  return true;
 }
 // dw[t][cp][cq] (+)= sum_o P[2o + t][cp] Q[o][cq].  P: (N, Df, Hf, Wf, Cp) stride ldp; Q: (N, Dc, Hc, Wc, Cq) stride ldq.
-int bts_lp_wgs_launch_(int dtype, const void* P, const void* Q, float* dw, void* ws, long ws_bytes, int N, int Df, int Hf, int Wf, int Dc, int Hc,
-                       int Wc, int Cp, int ldp, int Cq, int ldq, int accum, hipStream_t stream) {
-  if (Cp % 8 != 0 || Cq % 8 != 0 || ldp % 8 != 0 || ldq % 8 != 0) return BTS_ERR_SHAPE;
-  if ((((uintptr_t)P) & 15) || (((uintptr_t)Q) & 15) || (((uintptr_t)ws) & 15)) return BTS_ERR_ALIGN;
-  if ((long)(WGS_FZ + 1) * Hf * Wf * (long)ldp * 2 >= 0x7fffffffL || (long)(WGS_TZ + 1) * Hc * Wc * (long)ldq * 2 >= 0x7fffffffL) return BTS_ERR_SHAPE;
+int bts_lp_wgs_launch_(int dtype, const LpWgCall& c, const LpWgChoice& ch, const LpWgPtrs& q, hipStream_t stream) {
+  const WgsRoles r = wgs_roles(c);
+  const LpWgPlan& g = ch.g;
+  const int nq = g.nq, nwg = g.nwg;
+  const bool s2 = c.kind == BTS_CONV_K3S2;
   LpWgsParams p;
-  int nq, nwg;
-  wgs_plan(N, Dc, Hc, Wc, Cp, Cq, nq, nwg, p.ntiles, p.ncp, p.ncqg, p.ntx, p.nty, p.ntz);
-  if (ws_bytes < (long)nwg * p.ncp * p.ncqg * 27 * 32 * 32 * nq * 4) return BTS_ERR_WORKSPACE;
-  p.p = (const unsigned short*)P; p.q = (const unsigned short*)Q; p.part = reinterpret_cast<float*>(ws);
-  p.N = N; p.Df = Df; p.Hf = Hf; p.Wf = Wf; p.Dc = Dc; p.Hc = Hc; p.Wc = Wc; p.Cp = Cp; p.ldp = ldp; p.Cq = Cq; p.ldq = ldq;
+  p.p = (const unsigned short*)(s2 ? q.x : q.dy); p.q = (const unsigned short*)(s2 ? q.dy : q.x); p.part = reinterpret_cast<float*>(q.ws);
+  p.N = c.N; p.Df = r.Df; p.Hf = r.Hf; p.Wf = r.Wf; p.Dc = r.Dc; p.Hc = r.Hc; p.Wc = r.Wc; p.Cp = r.Cp; p.ldp = r.ldp; p.Cq = r.Cq; p.ldq = r.ldq;
+  p.ntx = g.ntx; p.nty = g.nty; p.ntz = g.ntz; p.ncp = g.ncp; p.ncqg = g.ncqg; p.ntiles = g.ntiles;
   const size_t shmem = 2 * (WGS_PBYTES + WGS_QBYTES) + 1024;
   (void)hipGetLastError();
 #define WGS_LAUNCH(TT, NQ_)                                                                                                  \
@@ -248,11 +242,11 @@ int bts_lp_wgs_launch_(int dtype, const void* P, const void* Q, float* dw, void*
     hipLaunchKernelGGL(kern, dim3(nwg, p.ncp * p.ncqg), dim3(512), shmem, stream, p);                                        \
   } while (0)
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(36, 2.0 * 27.0 * (double)Cp * Cq * (double)N * Dc * Hc * Wc, stream);
+  if (prof) bts_prof_begin(36, 2.0 * 27.0 * (double)r.Cp * r.Cq * (double)c.N * r.Dc * r.Hc * r.Wc, stream);
   if (dtype == LP_F16) { if (nq == 2) WGS_LAUNCH(TF16, 2); else WGS_LAUNCH(TF16, 1); }
   else { if (nq == 2) WGS_LAUNCH(TBF16, 2); else WGS_LAUNCH(TBF16, 1); }
 #undef WGS_LAUNCH
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
-  return bts_lp_wgrad_finalize_(p.part, dw, nwg, p.ncp, p.ncqg, 27, 27, nq, Cp, Cq, Cp, 0, 0, accum, stream);
+  return bts_lp_wgrad_finalize_(p.part, q.dw, nwg, p.ncp, p.ncqg, 27, 27, nq, r.Cp, r.Cq, r.Cp, 0, 0, c.accum, stream);
 }

@@ -161,8 +161,9 @@ def conv(kind, code, tdt, x, wp, bias, cout, out=None):
 
 
 def wgrad_supported(kind, cin, cout):
-    """shapes the 16-bit weight-gradient kernels take (channel counts in whole 16-byte chunks; the stride-1 3x3x3 / 1x1x1 kernel also
-    wants a power-of-two number of them per cout block)"""
+    """shapes the 16-bit weight-gradient kernels take, asked before anything runs (the trainer decides the fp32 route from it).  It mirrors
+    lp_wg_args of csrc/lowp_wg.hip: channel counts in whole 16-byte chunks (BTS_ERR_SHAPE otherwise) and, for the stride-1 3x3x3 / 1x1x1
+    kinds whose bias gradient comes from bts_lp_colsum, a Cout <= 256 whose chunks divide the 256-thread block"""
     if kind in (ops.K3S2, ops.K3S2T):
         return cin % 8 == 0 and cout % 8 == 0
     return kind in (ops.K3S1, ops.K1) and cin % 8 == 0 and cout % 8 == 0 and cout <= 256 and ((cout // 8) & (cout // 8 - 1)) == 0

@@ -311,7 +311,12 @@ int bts_lp_conv3d_bwd_weight_pair(int dtype, const void* x, long x_split, const 
 /* dw (fp32, Keras layout (kd,kh,kw,Cin_ref,Cout)) (+)= the weight gradient of a stride-1 3x3x3 / 1x1x1 conv from 16-bit x and dy
  * (voxel contraction on the 16-bit matrix pipe, fp32 partials, fixed-order finalize); db (may be NULL; dy dense then) (+)= sum dy.
  * dup_start / dup_shift as bts_conv_pack: Cin + dup_shift == Cin_ref, both copies of the folded slice receive the gradient.
- * BTS_ERR_UNSUPPORTED for the strided kinds and channel counts that are not multiples of 8: run bts_conv3d_bwd_weight on widened copies */
+ * The strided kinds too (no fold): x on the forward-input grid (D,H,W), dy on the half grid (K3S2, even sizes) or the doubled grid (K3S2T),
+ * dw in the layer's own Keras layout.  BTS_ERR_SHAPE for channel counts or strides that are not multiples of 8: run
+ * bts_conv3d_bwd_weight on widened copies.
+ * This call, bts_lp_conv3d_bwd_weight_pair and bts_lp_conv3d_gnin_bwd_weight choose their kernel and validate EVERYTHING before the first
+ * launch: a call that returns an argument status (also for a db that cannot be produced -- BTS_ERR_UNSUPPORTED where lddy != Cout,
+ * BTS_ERR_SHAPE where Cout > 256 or Cout / 8 does not divide 256) has not touched dw, whatever `accumulate` says. */
 long bts_lp_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout);
 int bts_lp_conv3d_bwd_weight(int kind, int dtype, const void* x, const void* dy, float* dw, float* db, void* workspace, long workspace_bytes,
                              int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int dup_start, int dup_shift, int accumulate,

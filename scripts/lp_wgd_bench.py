@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Stride-1 3x3x3 weight gradient with few output channels on 16-bit operands: the streaming kernel (lowp_wgd.hip) against lowp.hip's
+"""Stride-1 3x3x3 weight gradient with few output channels on 16-bit operands: the streaming kernel (lowp_wgd.hip) against lowp_wg.hip's
 general one (BTS_LP_WGD=0) on the CLI model's 128^3 layers at batch 8.  lp_wgd_bench.py [N] [dtype]"""
 import os
 import sys

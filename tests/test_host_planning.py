@@ -128,6 +128,36 @@ def test_split_data_gradient_query_matches_the_kernel_bounds(L):
     assert L._bts_lp_conv3d_bwd_data_sc_split_ok(1, 192, 192, 192, 64, 32) == 1
     assert L._bts_lp_conv3d_bwd_data_sc_split_ok(8, 128, 128, 128, 64, 32) == 1
 
+def test_weight_gradient_calls_refuse_an_impossible_bias_gradient_before_any_launch(L, monkeypatch):
+    """a 16-bit weight-gradient call that cannot produce its db (dy rows wider than Cout; a Cout whose 16-byte chunks do not tile the
+    256-thread column-sum block) answers from its plan, before dw is touched -- BTS_ERR_UNSUPPORTED / BTS_ERR_SHAPE as ever.  Fake,
+    never dereferenced device addresses and a workspace as large as the query asks: nothing else is wrong with these calls."""
+    monkeypatch.delenv('BTS_LP_WGD', raising=False)
+    P, BF16, N, D, H, W, ci = 0x100000, 2, 1, 32, 32, 32, 32
+    for co, lddy, want in ((32, 64, -3), (24, 24, -1)):
+        for kind in (0, 1, 2, 3):
+            nb = L._bts_lp_conv3d_bwd_weight_workspace(kind, N, D, H, W, ci, co)
+            assert nb > 0
+            r = L._bts_lp_conv3d_bwd_weight(kind, BF16, P, P, P, P, P, nb, N, D, H, W, ci, ci, co, lddy, 0, 0, 1, None)
+            assert r == want, (kind, co, lddy, r)
+        nb = L._bts_lp_conv3d_bwd_weight_pair_workspace(N, D, H, W, ci, co)
+        assert nb > 0
+        r = L._bts_lp_conv3d_bwd_weight_pair(BF16, P, 0, P, P, P, P, P, P, nb, N, D, H, W, ci, ci, co, lddy, co, 0, 0, 1, None)
+        assert r == want, ('pair', co, lddy, r)
+        nb = L._bts_lp_conv3d_bwd_weight_workspace(1, N, D, H, W, ci, co)
+        r = L._bts_lp_conv3d_gnin_bwd_weight(BF16, P, P, P, P, P, G, P, P, P, P, nb, N, D, H, W, ci, co, lddy, 1, None)
+        assert r == want, ('gnin', co, lddy, r)
+
+
+def test_paired_weight_gradient_query_at_the_split_level0_shapes(L, monkeypatch):
+    """the trainer's level-0 split (two dense 32-channel operands, no single-tensor fallback) relies on the paired launch taking
+    64 -> 32 at 128^3; the streaming kernel's 32-wide columns do not exist where W % 32 != 0"""
+    monkeypatch.delenv('BTS_LP_WGD', raising=False)
+    assert L._bts_lp_conv3d_bwd_weight_pair_workspace(8, 128, 128, 128, 64, 32) >= 0
+    assert L._bts_lp_conv3d_bwd_weight_pair_workspace(1, 128, 128, 128, 64, 32) >= 0
+    assert L._bts_lp_conv3d_bwd_weight_pair_workspace(1, 128, 128, 112, 64, 32) == -1
+
+
 def test_pack_descriptor_tables_are_written_inside_their_bounds(L):
     """bts_conv_pack_desc / bts_lp_pack_desc fill entry `index` of a host table of `*_desc_bytes()` entries: a guard band behind the
     table must stay untouched (the ASan run checks the same thing from the allocator's side)"""
