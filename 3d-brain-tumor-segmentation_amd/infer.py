@@ -10,8 +10,19 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
     by per-channel sigma as the training augmentation does (train.py:14-22), off by default;
   * the argmax is commented out (test.py:157-158) and `+1` / `>=3 -> 4` are applied to probabilities (:259-261);
     `labels()` applies them to the argmax, with 0 for masked-out voxels and voxels whose best class is below `threshold`.
-All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, the model forward).
+  * `Interpolator` (test.py:15-72) uses pixdim[0] (qfac) as a zoom factor and adds [1.0] element-wise (test.py:46); here the
+    spatial factors are (dx,dy,dz) = pixdim[1:4] and every channel is resampled on its own (scipy's 4-D call mixes the channels
+    by up to 9e-6 relative at C=4 through its approximate boundary initialisation on short axes, a library artefact);
+  * `Interpolator.reverse` (test.py:58-66,259-264) zooms the label VALUES with a cubic spline, which gives fractional labels, and
+    to round(n * 1/pixdim), which need not be the scan's extent; here the probabilities (configured order) and the brain mask
+    (order 0) are resampled to the scan's recorded native shape and the labels are taken there with bts_tta_finish.
+All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_spline_prefilter3d, bts_zoom3d, the model
+forward).
 """
+import glob
+import os
+
+import numpy as np
 import torch
 
 from . import ops
@@ -135,3 +146,117 @@ def segment_volume(model, x, mask, mean, std, spatial_res, spatial_tta=True, thr
     lab = tta.labels()
     y = y[:, :orig[0], :orig[1], :orig[2]] if df == 'channels_first' else y[:orig[0], :orig[1], :orig[2]]
     return y, lab[:orig[0], :orig[1], :orig[2]]
+
+
+def zoom_output_shape(shape, factors):
+    """spatial extent scipy.ndimage.zoom gives: int(round(n * factor)) per axis, Python's round (ties to even)"""
+    return tuple(int(round(int(n) * float(f))) for n, f in zip(shape, factors))
+
+
+class Interpolator(object):
+    """test.py:15-72 on the device: resample a scan to 1 mm^3 (cubic spline, reflect boundary), build the brain mask, and bring
+    the prediction back to the scan's own grid"""
+
+    def __init__(self, modalities, order=3, mode='reflect'):
+        if mode != 'reflect':
+            raise ValueError("Interpolator: mode %r is not supported; the only supported boundary mode is 'reflect'" % (mode,))
+        if order not in (0, 1, 3):
+            raise ValueError('Interpolator: order %r is not supported; supported spline orders are 0, 1 and 3' % (order,))
+        self.modalities = modalities
+        self.order = order
+        self.mode = mode
+        self.pixdim = None          # after __call__: mean of pixdim[0:4] over the modalities (test.py:41)
+        self.affine = None          # after __call__: mean 4x4 affine of the srows (test.py:42)
+        self.factors = None         # (dx,dy,dz) of the last resample
+        self.native_shape = None    # spatial extent of the last resampled scan
+        self.mask = None            # unpadded brain mask of the last resample, on the 1 mm^3 grid
+
+    @staticmethod
+    def _device_volume(image):
+        if isinstance(image, np.ndarray):
+            if not torch.cuda.is_available():
+                raise RuntimeError('Interpolator: resampling runs on the GPU (no CPU fallback exists for the product path)')
+            image = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).cuda()
+        if image.dim() != 4:
+            raise ValueError('Interpolator: image must be (D,H,W,C), got shape %s' % (tuple(image.shape),))
+        return image.to(torch.float32).contiguous()
+
+    def _zoom(self, x, out_shape, order, pad_to=None, want_mask=False):
+        coef = ops.spline_prefilter3d(x) if order == 3 else x
+        return ops.zoom3d(coef, out_shape, order=order, pad_to=pad_to, want_mask=want_mask)
+
+    def resample(self, image, pixdim, pad_res=None):
+        """image (D,H,W,C) numpy or device tensor, pixdim (dx,dy,dz) -> (image_1mm, mask (.., 1)) on the device; with pad_res
+        -> (image_padded, mask_padded, orig_shape) by the reference's padding rule (pad_to_spatial_res: a full extra block when
+        the extent is already a multiple).  All-ones pixdim skips the resample (test.py:45): mask and padding only."""
+        x = self._device_volume(image)
+        factors = tuple(float(v) for v in pixdim)
+        if len(factors) != 3:
+            raise ValueError('Interpolator: pixdim must be (dx,dy,dz), got %r' % (pixdim,))
+        self.factors = factors
+        self.native_shape = tuple(x.shape[:3])
+        unit = all(f == 1.0 for f in factors)
+        shape = self.native_shape if unit else zoom_output_shape(self.native_shape, factors)
+        pad_to = None if pad_res is None else tuple(s + pad_res - (s % pad_res) for s in shape)
+        y, m = self._zoom(x, shape, 0 if unit else self.order, pad_to=pad_to, want_mask=True)   # order 0 onto the same grid: a copy
+        self.mask = m if pad_to is None else m[:shape[0], :shape[1], :shape[2]]
+        if pad_res is None:
+            return y, m
+        return y, m, list(shape)
+
+    def __call__(self, path, pad_res=None):
+        """test.py:21-56: load *name*.nii* per modality, average pixdim / affine over the modalities, resample"""
+        from . import nifti
+        image, pixdim, affine = [], [], []
+        for name in self.modalities:
+            cards = sorted(glob.glob(os.path.join(path, '*' + name + '*' + '.nii' + '*')))
+            if not cards:
+                raise FileNotFoundError('Interpolator: no *%s*.nii* under %s' % (name, path))
+            data, header = nifti.load(cards[0])
+            image.append(np.asarray(data).astype(np.float32))
+            pixdim.append(header['pixdim'][:4])
+            affine.append(header['affine'])
+        self.pixdim = np.mean(pixdim, axis=0, dtype=np.float32)
+        self.affine = np.mean(affine, axis=0, dtype=np.float32)
+        return self.resample(np.stack(image, axis=-1), self.pixdim[1:4], pad_res=pad_res)
+
+    def reverse(self, prob, mask=None, path=None, threshold=0.5):
+        """prob (D1,H1,W1,K): cropped probability map on the 1 mm^3 grid, mask (D1,H1,W1,1) (default: the last resample's)
+        -> (probabilities (D,H,W,K), uint8 labels (D,H,W)) on the scan's native grid; with `path`, writes mask.nii there
+        (test.py:69-70) with the affine averaged in __call__ (identity if the scan came through resample())"""
+        if self.native_shape is None:
+            raise RuntimeError('Interpolator.reverse: no scan has been resampled yet')
+        mask = self.mask if mask is None else mask
+        p = prob.to(torch.float32).contiguous()
+        m = mask.to(torch.float32).contiguous()
+        if not all(f == 1.0 for f in self.factors):
+            p = self._zoom(p, self.native_shape, self.order)
+            m = self._zoom(m, self.native_shape, 0)
+        y, lab = ops.tta_finish(p.unsqueeze(0), m.unsqueeze(0), threshold)
+        y, lab = y[0], lab[0]
+        if path is not None:
+            from . import nifti
+            nifti.save(os.path.join(path, 'mask.nii'), lab.cpu().numpy(), np.eye(4) if self.affine is None else self.affine)
+        return y, lab
+
+
+def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
+                 order=3):
+    """test.py:235-264 for one scan: resample to 1 mm^3 with mask and padding in one pass, TTA inference, crop, resample back.
+    image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz) -> (probabilities, uint8 labels (D,H,W)) on that grid; the probabilities
+    are (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  With pixdim (1,1,1) this is
+    segment_volume with the reference's mask, bit for bit."""
+    interp = Interpolator(None, order=order)
+    xp, mp, orig = interp.resample(image, pixdim, pad_res=spatial_res)
+    df = getattr(model, 'data_format', 'channels_last')
+    tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
+                            tta_batch=tta_batch)
+    y = tta(xp, mp)
+    if all(f == 1.0 for f in interp.factors):
+        lab = tta.labels()
+        y = y[:, :orig[0], :orig[1], :orig[2]] if df == 'channels_first' else y[:orig[0], :orig[1], :orig[2]]
+        return y, lab[:orig[0], :orig[1], :orig[2]]
+    if df == 'channels_first':
+        y = y.permute(1, 2, 3, 0)
+    y, lab = interp.reverse(y[:orig[0], :orig[1], :orig[2]], threshold=threshold)
+    return (y.permute(3, 0, 1, 2) if df == 'channels_first' else y), lab

@@ -710,6 +710,48 @@ def tta_finish(prob, bmask, threshold=0.5, want_probabilities=True, want_labels=
     return y, labels
 
 
+# ---- resampling of a scan to the 1 mm^3 grid and back (test.py:15-72) ----
+def _check_volume(t, name):
+    _check(t, name)
+    if t.dim() != 4 or not t.is_contiguous():
+        raise ValueError('%s must be a dense (D,H,W,C) tensor, got shape %s strides %s' % (name, tuple(t.shape), t.stride()))
+
+
+def spline_prefilter3d(x, out=None):
+    """cubic B-spline coefficients of a dense (D,H,W,C) volume along D, H and W (the spline_filter half of
+    scipy.ndimage.zoom(order=3, mode='reflect')); C <= 8, spatial extents >= 4"""
+    _check_volume(x, 'spline_prefilter3d: x')
+    d, h, w, c = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError('spline_prefilter3d: out must be a dense float32 tensor of the shape of x')
+    lib().call('bts_spline_prefilter3d', _p(x), _p(out), d, h, w, c, _stream())
+    return out
+
+
+def zoom3d(coef, out_shape, order=3, pad_to=None, want_mask=False, mean=None, std=None):
+    """coef (D,H,W,C) evaluated on zoom()'s grid of spatial extent out_shape: order 3 takes spline_prefilter3d coefficients, orders 0
+    and 1 the samples themselves.  pad_to >= out_shape: extent of the result, zero outside out_shape (pad_to_spatial_res in the same
+    pass).  want_mask: also (max_c value > 0) as float32 (..., 1).  mean/std (C,): the result is normalised after the mask test.
+    -> volume, or (volume, mask) with want_mask"""
+    _check_volume(coef, 'zoom3d: coef')
+    if order not in (0, 1, 3):
+        raise ValueError('zoom3d: order must be 0, 1 or 3, got %r' % (order,))
+    do, ho, wo = (int(v) for v in out_shape)
+    dp, hp, wp = (do, ho, wo) if pad_to is None else (int(v) for v in pad_to)
+    if min(do, ho, wo) < 1 or dp < do or hp < ho or wp < wo:
+        raise ValueError('zoom3d: out_shape %s must be positive and within pad_to %s' % ((do, ho, wo), (dp, hp, wp)))
+    if (mean is None) != (std is None):
+        raise ValueError('zoom3d: mean and std go together')
+    d, h, w, c = coef.shape
+    out = torch.empty((dp, hp, wp, c), dtype=torch.float32, device=coef.device)
+    mask = torch.empty((dp, hp, wp, 1), dtype=torch.float32, device=coef.device) if want_mask else None
+    lib().call('bts_zoom3d', _p(coef), _p(out), _p(mask), _p(mean), _p(std), d, h, w, do, ho, wo, c, dp, hp, wp, int(order),
+               _stream())
+    return (out, mask) if want_mask else out
+
+
 # ---- training-time augmentation on the device (SURVEY 8 f-3) ----
 def channel_moments(x):
     """per-channel (mean, population variance) over all voxels of a dense (..., C) tensor, C <= 16 -> two (C,) tensors"""

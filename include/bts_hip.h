@@ -237,6 +237,20 @@ int bts_flip_affine(const float* src, float* dst, const float* mean, const float
 int bts_tta_finish(const float* prob, const float* bmask, float* y, uint8_t* labels, long nvox, int C, float threshold,
                    bts_stream_t stream);
 
+/* ===== resampling of a scan to the 1 mm^3 grid and back (test.py:15-72: Interpolator, scipy.ndimage.zoom(order=3, mode='reflect')) =====
+ * Dense fp32 (D,H,W,C) tensors, C innermost, 1 <= C <= 8; every channel is resampled on its own (zoom() per channel on 3-D arrays). */
+/* cubic B-spline coefficients of src along D, H and W with the exact half-sample-symmetric ('reflect') boundary (the spline_filter
+ * half of zoom(), test.py:46,62); src == dst allowed; spatial extents < 4 return BTS_ERR_SHAPE. */
+int bts_spline_prefilter3d(const float* src, float* dst, int D, int H, int W, int C, bts_stream_t stream);
+/* dst (Dpad,Hpad,Wpad,C) = coef (Din,Hin,Win,C) evaluated on the (Dout,Hout,Wout) grid of zoom(): output index o reads input
+ * coordinate o * (n-1)/(nout-1); order 0 | 1 | 3 (3: coef from bts_spline_prefilter3d; 0, 1: the samples themselves), reflect
+ * index mapping (test.py:46,62).  bmask (Dpad,Hpad,Wpad; may be NULL) = max_c value > 0 (test.py:53-54).  Voxels outside
+ * (Dout,Hout,Wout) are written as zero in both outputs (pad_to_spatial_res, test.py:164-178, without a pass of its own).
+ * mean/stdv (C floats, both or neither): dst = (value - mean[c]) / std[c] (test.py:107) applied after the mask test to every
+ * voxel, the padding included, i.e. dst is the normalised padded volume. */
+int bts_zoom3d(const float* coef, float* dst, float* bmask, const float* mean, const float* stdv, int Din, int Hin, int Win,
+               int Dout, int Hout, int Wout, int C, int Dpad, int Hpad, int Wpad, int order, bts_stream_t stream);
+
 /* ===== training-time augmentation on the device (train.py:14-49) ===== */
 /* per-channel mean / population variance of a (nvox, C) tensor with voxel stride ld (tf.nn.moments, train.py:18);
  * C <= 16; mean may be NULL; fp64 partials, fixed-order combine */
