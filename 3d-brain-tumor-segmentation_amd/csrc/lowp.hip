@@ -10,13 +10,11 @@
 // channels of the voxel -- NDHWC memory IS the operand layout), D: lane holds voxel lane&31 and couts 8*(r>>2) + 4*(lane>>5)
 // + (r&3): four consecutive couts per register quad = one 8-byte store.
 //
-// Two conv kernels:
+// The conv kernel of this file:
 //   lp_conv_s1_kernel      3x3x3 stride-1 'same' (90 % of the FLOPs): halo tile of 16 channels staged global -> registers ->
 //                          LDS (voxel stride 48 bytes: conflict-free 16-byte reads), wave = 32 x-columns x VB rows of one z
 //                          plane x CB cout blocks, weights straight from L2 (one fragment feeds VB matrix instructions)
-//   lp_conv_gather_kernel  1x1x1, stride-2 and transposed convs (gather form out[o*os+oo] = sum_t in[o*s+off_t] W[t], the
-//                          transposed conv as 8 output-parity classes): operands straight from global memory -- every input
-//                          voxel is needed by at most 8 outputs, an LDS tile would buy nothing
+// The 1x1x1, stride-2 and transposed convolutions (and the data gradients on those geometries) live in lowp_gather.hip.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -34,16 +32,6 @@ void bts_prof_end(hipStream_t stream);
 // lowp_s1d.hip: the DMA part of a K3S1 image (the stride-1 kernels' plans and launchers: lowp_common.h)
 long bts_lp_s1d_image_bytes_(int K, int N);
 int bts_lp_s1d_pack_(int dtype, const LpPackParams& p, void* dst, hipStream_t stream);
-// lowp_k1.hip: streaming 1x1x1 kernel (offered first; 1 = declined); gap partials per block of bts_lp_k1_gap_block_ positions
-int bts_lp_k1_gap_block_(long npos, long V, int Cin, int Cout);
-int bts_lp_s2t_launch_(int dtype, const void* x, const void* wp, const float* bias, void* y, int N, int D, int H, int W, int Cin, int ldx,
-                       int Cout, int ldy, int accum, hipStream_t stream);
-int bts_lp_k1_launch_(int dtype, const void* x, const void* wp, const float* bias, void* y, long npos, int Cin, int ldx, int Cout, int ldy,
-                      int accum, double* gap_part, int gap_block, hipStream_t stream);
-// lowp_up.hip: transposed form, all eight output classes in one pass (offered first; 1 = declined)
-int bts_lp_up_launch_(int dtype, const void* x, const void* wp_dma, const float* bias, void* y, int N, int D, int H, int W, int Cin, int ldx,
-                      int Cout, int ldy, int accum, hipStream_t stream, double* gnp = nullptr, int gn_G = 0);
-long bts_lp_up_gn_B_(int N, int D, int H, int W, int Cin, int Cout, int Gn);
 
 // =====================================================================================================================
 // weight packing: Keras layout fp32 -> [tap][k-step of 16 cin][cout block of 32][h][32 couts][8 cin] 16-bit
@@ -76,8 +64,6 @@ extern "C" long bts_lp_packed_bytes(int kind, int role, int Cin_slab, int Cout) 
   // order of the LDS-DMA kernels (lowp_s1d.hip, lowp_up.hip)
   return lp_has_dma_part(kind, role) ? first + bts_lp_s1d_image_bytes_(K, N) : first;
 }
-// byte offset of the DMA part inside a K3S1 image with K contraction channels and N output columns
-static long lp_s1d_part_offset(int K, int N) { return 27L * ((K + 15) / 16) * ((N + 31) / 32) * 1024; }
 static int lp_pack_params(LpPackParams& p, int kind, int role, const float* w, void* wp, int Cin_ref, int Cout, int Cin_slab, int dup_start,
                           int dup_shift) {
   if (kind < 0 || kind > 3 || role < 0 || role > 1) return BTS_ERR_UNSUPPORTED;
@@ -172,22 +158,6 @@ extern "C" int bts_lp_pack_batch(int dtype, const void* table_dev, int n, long t
   else hipLaunchKernelGGL(lp_pack_batch_kernel<TBF16>, dim3((unsigned)total_blocks), dim3(256), 0, stream, reinterpret_cast<const LpPackDesc*>(table_dev), n);
   BTS_LAUNCH_CHECK();
   return BTS_OK;
-}
-
-// one register quad (4 consecutive couts) of a result: bias added by the caller; optional read-modify-write accumulation
-template <typename T>
-__device__ __forceinline__ void lp_store_quad(unsigned short* dst, float o0, float o1, float o2, float o3, int nleft, int accum) {
-  if (nleft >= 4) {
-    if (accum) {
-      const u32x2 old = *reinterpret_cast<const u32x2*>(dst);
-      o0 += T::ld((unsigned short)(old[0] & 0xffffu)); o1 += T::ld((unsigned short)(old[0] >> 16));
-      o2 += T::ld((unsigned short)(old[1] & 0xffffu)); o3 += T::ld((unsigned short)(old[1] >> 16));
-    }
-    *reinterpret_cast<u32x2*>(dst) = u32x2{pack2<T>(o0, o1), pack2<T>(o2, o3)};
-  } else {
-    const float o[3] = {o0, o1, o2};
-    for (int j = 0; j < nleft; ++j) dst[j] = T::st(accum ? o[j] + T::ld(dst[j]) : o[j]);
-  }
 }
 
 // =====================================================================================================================
@@ -658,333 +628,6 @@ static int lp_s1_dispatch(const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptr
   return BTS_ERR_UNSUPPORTED;
 }
 
-// =====================================================================================================================
-// gather-form convolution (1x1x1, stride 2, transposed): operands straight from global memory
-// =====================================================================================================================
-struct LpTap { short dz, dy, dx, w; };   // input offset of the tap, index of its weight slab
-struct LpGatherParams {
-  const unsigned short* x;
-  const unsigned short* wp;
-  const float* bias;
-  unsigned short* y;
-  int N, Di, Hi, Wi, ldx;           // input grid
-  int Dg, Hg, Wg;                   // grid of this launch (output positions of one class)
-  int Do, Ho, Wo, ldy, Cout;        // output tensor
-  int s, os, ooz, ooy, oox;         // in = g*s + off_t ; out = g*os + oo
-  int KS, NB, ncg, ntaps, accum;
-  long npos;                        // N*Dg*Hg*Wg
-  double* gap_part;                 // fused global-average-pool partials [position block][Cout] (1x1x1 launches only), else NULL
-  LpTap taps[27];
-};
-
-template <typename T, int VB, int CB>
-__global__ __launch_bounds__(256, 2) void lp_conv_gather_kernel(const LpGatherParams p) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = tid >> 6;
-  const int h = lane >> 5, l32 = lane & 31;
-  const int cg = blockIdx.x % p.ncg;
-  const long blk = blockIdx.x / p.ncg;
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, 0, 0x7fffffff, 0x00020000);
-  const unsigned wlane = (unsigned)((h * 32 + l32) * 16);
-  // this lane's VB grid positions
-  int gz[VB], gy[VB], gx[VB], gn[VB];
-  bool live[VB];
-#pragma unroll
-  for (int v = 0; v < VB; ++v) {
-    long pos = ((blk * 4 + wave) * VB + v) * 32 + l32;
-    live[v] = pos < p.npos;
-    if (!live[v]) pos = 0;
-    gx[v] = (int)(pos % p.Wg); pos /= p.Wg;
-    gy[v] = (int)(pos % p.Hg); pos /= p.Hg;
-    gz[v] = (int)(pos % p.Dg);
-    gn[v] = (int)(pos / p.Dg);
-  }
-  f32x16 acc[VB][CB];
-#pragma unroll
-  for (int v = 0; v < VB; ++v)
-#pragma unroll
-    for (int c = 0; c < CB; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[v][c][r] = 0.f;
-  // Software pipeline over the flattened (tap, k-step) sequence: the operands of step i+1 are requested before the matrix
-  // instructions of step i run (both operands come straight from global memory: a step without its successor in flight
-  // would wait a full memory round trip for every 4-8 matrix instructions)
-  const unsigned short* src[VB];   // of the tap being REQUESTED
-  bool ok[VB];
-  int wtap = 0;
-  auto tap_setup = [&](int t) {
-    const LpTap tp = p.taps[t];
-    wtap = tp.w;
-#pragma unroll
-    for (int v = 0; v < VB; ++v) {
-      const int iz = gz[v] * p.s + tp.dz, iy = gy[v] * p.s + tp.dy, ix = gx[v] * p.s + tp.dx;
-      ok[v] = live[v] && (unsigned)iz < (unsigned)p.Di && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-      src[v] = p.x + ((((long)gn[v] * p.Di + iz) * p.Hi + iy) * p.Wi + ix) * (long)p.ldx + h * 8;
-    }
-  };
-  auto request = [&](int ks, u32x4 (&a)[CB], u32x4 (&b)[VB]) {
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-      const int cb = cg * CB + c;
-      a[c] = bload16(wr, wlane, (unsigned)((((wtap * p.KS + ks) * p.NB) + (cb < p.NB ? cb : 0)) * 1024));
-    }
-#pragma unroll
-    for (int v = 0; v < VB; ++v) {
-      b[v] = u32x4{0u, 0u, 0u, 0u};
-      if (ok[v]) b[v] = *reinterpret_cast<const u32x4*>(src[v] + ks * 16);
-    }
-  };
-  // ring of GD + 1 operand sets: step i computes on set i % (GD + 1) while the requests of steps i+1 .. i+GD are in flight
-  constexpr int GD = (VB + CB >= 6) ? 2 : 3;   // (4 x 2 tiles: a third set in flight would spill)
-  u32x4 ar[GD + 1][CB], br[GD + 1][VB];
-  const int total = p.ntaps * p.KS;
-  int rt = 0, rks = 0, issued = 0;
-  tap_setup(0);
-  auto issue = [&](u32x4 (&a)[CB], u32x4 (&b)[VB]) {   // request the operands of step `issued` (no-op past the end)
-    if (issued < total) {
-      request(rks, a, b);
-      ++issued;
-      if (++rks == p.KS) { rks = 0; if (++rt < p.ntaps) tap_setup(rt); }
-    }
-  };
-#pragma unroll
-  for (int j = 0; j < GD; ++j) issue(ar[j], br[j]);
-  for (int i0 = 0; i0 < total; i0 += GD + 1) {
-#pragma unroll
-    for (int j = 0; j <= GD; ++j) {
-      if (i0 + j < total) {
-        issue(ar[(j + GD) % (GD + 1)], br[(j + GD) % (GD + 1)]);
-#pragma unroll
-        for (int v = 0; v < VB; ++v)
-#pragma unroll
-          for (int c = 0; c < CB; ++c) acc[v][c] = T::mfma(ar[j][c], br[j][v], acc[v][c]);
-      }
-    }
-  }
-  float csum[CB][16];   // column sums of what this lane stores (dead code unless p.gap_part)
-#pragma unroll
-  for (int c = 0; c < CB; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) csum[c][r] = 0.f;
-#pragma unroll
-  for (int c = 0; c < CB; ++c) {
-    const int cb = cg * CB + c;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int co = cb * 32 + 8 * q + 4 * h;
-      float bq[4] = {0.f, 0.f, 0.f, 0.f};
-      if (p.bias && cb < p.NB) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (co + j < p.Cout) bq[j] = p.bias[co + j];
-      }
-#pragma unroll
-      for (int v = 0; v < VB; ++v) {
-        if (live[v] && cb < p.NB && co < p.Cout) {
-          const int oz = gz[v] * p.os + p.ooz, oy = gy[v] * p.os + p.ooy, ox = gx[v] * p.os + p.oox;
-          if (oz < p.Do && oy < p.Ho && ox < p.Wo) {
-            unsigned short* dst = p.y + ((((long)gn[v] * p.Do + oz) * p.Ho + oy) * p.Wo + ox) * (long)p.ldy + co;
-            const float o0 = acc[v][c][4 * q] + bq[0], o1 = acc[v][c][4 * q + 1] + bq[1], o2 = acc[v][c][4 * q + 2] + bq[2],
-                        o3 = acc[v][c][4 * q + 3] + bq[3];
-            lp_store_quad<T>(dst, o0, o1, o2, o3, p.Cout - co, p.accum);
-            csum[c][4 * q] += o0; csum[c][4 * q + 1] += o1; csum[c][4 * q + 2] += o2; csum[c][4 * q + 3] += o3;
-          }
-        }
-      }
-    }
-  }
-  // Fused global average pool of the output (resnet.py:121: the squeeze of the block's 1x1x1 shortcut output): column sums of
-  // this block's 128 * VB positions -- lanes (xor shuffles over the 32 positions of a wave), the 4 waves through LDS in fixed
-  // order, one fp64 partial per (position block, cout); bts_lp_conv1_gap's finalize adds the blocks of a sample
-  if (p.gap_part != nullptr) {   // (launch-uniform)
-    __shared__ float csh[4][CB * 32];
-#pragma unroll
-    for (int c = 0; c < CB; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float v = csum[c][r];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (l32 == 0) csh[wave][c * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = v;
-      }
-    __syncthreads();
-    if (tid < CB * 32) {
-      const int co = cg * CB * 32 + tid;
-      if (co < p.Cout) p.gap_part[blk * p.Cout + co] = ((double)csh[0][tid] + (double)csh[1][tid]) + ((double)csh[2][tid] + (double)csh[3][tid]);
-    }
-  }
-}
-
-// Stride-2 gather with whole-row loads.  In the kernel above a B operand is 16 bytes of each of 32 voxels that sit two rows apart:
-// an instruction touches 32 cache lines and uses 32 bytes of each, every line comes back for the other k-steps, and the L2 -> L1 fill
-// rate bounds the launch (0.09 of the matrix peak at 32 channels).  Here the k-steps of a tap go in groups of GK = 2 | 4 (64 | 128
-// bytes of a voxel's row): load instruction i has the GK lanes of a quad fetch the GK * 32 contiguous bytes of output voxel
-// (quad base + i), the quad transpose (lowp_common.h) hands every lane its own voxel's pieces, one per k-step.  Two register sets:
-// the next group's rows and weight fragments are in flight while the current group multiplies.  Needs Wg % GK == 0 (a quad never
-// leaves its output row).
-// VB = 4 (round 5): four position groups per wave share every weight fragment -- a wave's weight re-streaming from L2 (one fragment per
-// two matrix instructions at VB = 2, as much traffic as the activations) halves; GK = 2 only (register budget: 128 accumulators + two
-// operand sets).
-template <typename T, int CB, int GK, int VB = 2>
-__global__ __launch_bounds__(256, VB == 4 ? 1 : 2) void lp_conv_gatherq_kernel(const LpGatherParams p) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = tid >> 6;
-  const int h = lane >> 5, l32 = lane & 31, b = l32 & (GK - 1);
-  const int cg = blockIdx.x % p.ncg;
-  const long blk = blockIdx.x / p.ncg;
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, 0, 0x7fffffff, 0x00020000);
-  const unsigned wlane = (unsigned)((h * 32 + l32) * 16);
-  int gz[VB], gy[VB], gx[VB], gn[VB];
-  bool live[VB];
-  const unsigned short* base[VB];     // own voxel's quad base (n, s gz, s gy, s (gx - b)), this lane's piece of a chunk
-#pragma unroll
-  for (int v = 0; v < VB; ++v) {
-    long pos = ((blk * 4 + wave) * VB + v) * 32 + l32;
-    live[v] = pos < p.npos;           // (npos is a multiple of Wg, Wg of GK: the lanes of a quad are live together)
-    if (!live[v]) pos = 0;
-    gx[v] = (int)(pos % p.Wg); pos /= p.Wg;
-    gy[v] = (int)(pos % p.Hg); pos /= p.Hg;
-    gz[v] = (int)(pos % p.Dg);
-    gn[v] = (int)(pos / p.Dg);
-    base[v] = p.x + ((((long)gn[v] * p.Di + gz[v] * p.s) * p.Hi + gy[v] * p.s) * p.Wi + (long)(gx[v] - b) * p.s) * (long)p.ldx + (2 * b + h) * 8;
-  }
-  f32x16 acc[VB][CB];
-#pragma unroll
-  for (int v = 0; v < VB; ++v)
-#pragma unroll
-    for (int c = 0; c < CB; ++c)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[v][c][r] = 0.f;
-  const int NQ = p.KS / GK;                 // chunks per tap
-  const int total = p.ntaps * NQ;
-  int rt = 0, rq = 0, issued = 0;
-  u32x4 a0[GK][CB], a1[GK][CB], b0[VB][GK], b1[VB][GK];
-  auto issue = [&](u32x4 (&a)[GK][CB], u32x4 (&bb)[VB][GK]) {
-    if (issued >= total) return;
-    const LpTap tp = p.taps[rt];
-#pragma unroll
-    for (int j = 0; j < GK; ++j)
-#pragma unroll
-      for (int c = 0; c < CB; ++c) {
-        const int cb = cg * CB + c;
-        a[j][c] = bload16(wr, wlane, (unsigned)((((tp.w * p.KS + rq * GK + j) * p.NB) + (cb < p.NB ? cb : 0)) * 1024));
-      }
-    const long off = (((long)tp.dz * p.Hi + tp.dy) * p.Wi + tp.dx) * (long)p.ldx + rq * (GK * 16);
-#pragma unroll
-    for (int v = 0; v < VB; ++v) {
-      const int iz = gz[v] * p.s + tp.dz, iy = gy[v] * p.s + tp.dy;
-      const bool okzy = live[v] && (unsigned)iz < (unsigned)p.Di && (unsigned)iy < (unsigned)p.Hi;
-#pragma unroll
-      for (int i = 0; i < GK; ++i) {
-        const int ix = (gx[v] - b + i) * p.s + tp.dx;
-        bb[v][i] = u32x4{0u, 0u, 0u, 0u};
-        if (okzy && (unsigned)ix < (unsigned)p.Wi) bb[v][i] = *reinterpret_cast<const u32x4*>(base[v] + off + (long)i * p.s * p.ldx);
-      }
-    }
-    ++issued;
-    if (++rq == NQ) { rq = 0; ++rt; }
-  };
-  auto compute = [&](u32x4 (&a)[GK][CB], u32x4 (&bb)[VB][GK]) {
-#pragma unroll
-    for (int v = 0; v < VB; ++v) {
-      if constexpr (GK == 4) k1_quad_transpose(bb[v], b); else k1_pair_transpose(bb[v], b);
-    }
-#pragma unroll
-    for (int j = 0; j < GK; ++j)
-#pragma unroll
-      for (int v = 0; v < VB; ++v)
-#pragma unroll
-        for (int c = 0; c < CB; ++c) acc[v][c] = T::mfma(a[j][c], bb[v][j], acc[v][c]);
-  };
-  issue(a0, b0);
-  for (int g = 0; g < total; g += 2) {
-    issue(a1, b1);
-    compute(a0, b0);
-    if (g + 1 < total) {
-      issue(a0, b0);
-      compute(a1, b1);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < CB; ++c) {
-    const int cb = cg * CB + c;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int co = cb * 32 + 8 * q + 4 * h;
-      float bq[4] = {0.f, 0.f, 0.f, 0.f};
-      if (p.bias && cb < p.NB) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (co + j < p.Cout) bq[j] = p.bias[co + j];
-      }
-#pragma unroll
-      for (int v = 0; v < VB; ++v) {
-        if (live[v] && cb < p.NB && co < p.Cout) {
-          const int oz = gz[v] * p.os + p.ooz, oy = gy[v] * p.os + p.ooy, ox = gx[v] * p.os + p.oox;
-          if (oz < p.Do && oy < p.Ho && ox < p.Wo) {
-            unsigned short* dst = p.y + ((((long)gn[v] * p.Do + oz) * p.Ho + oy) * p.Wo + ox) * (long)p.ldy + co;
-            lp_store_quad<T>(dst, acc[v][c][4 * q] + bq[0], acc[v][c][4 * q + 1] + bq[1], acc[v][c][4 * q + 2] + bq[2], acc[v][c][4 * q + 3] + bq[3],
-                             p.Cout - co, p.accum);
-          }
-        }
-      }
-    }
-  }
-}
-
-// positions per workgroup of a gather launch (4 waves x VB x 32)
-static int lp_gather_vb(long npos, int NB) {
-  const int cb = NB >= 2 ? 2 : 1;
-  const long wg4 = ((npos + 511) / 512) * ((NB + cb - 1) / cb);
-  return wg4 >= 512 ? 4 : (wg4 >= 128 ? 2 : 1);
-}
-template <typename T>
-static int lp_gather_launch(LpGatherParams p, hipStream_t stream) {
-  p.npos = (long)p.N * p.Dg * p.Hg * p.Wg;
-  const int cb = p.NB >= 2 ? 2 : 1;
-  p.ncg = (p.NB + cb - 1) / cb;
-  int vb = lp_gather_vb(p.npos, p.NB);
-  // whole-row loads for the stride-2 forms on grids that fill the chip (BTS_LP_GATHERQ=0: the plain kernel, for A/B)
-  int gk = 0;
-  {
-    const char* e = getenv("BTS_LP_GATHERQ");
-    if (!(e && atoi(e) == 0) && p.s == 2 && p.gap_part == nullptr && vb >= 2 && p.KS % 2 == 0) {
-      if (p.KS % 4 == 0 && p.Wg % 4 == 0) gk = 4;
-      else if (p.Wg % 2 == 0) gk = 2;
-    }
-    // (below ~300 workgroups the plain kernel's smaller tiles win: 128 -> 128 at 8 x 32^3, 256 workgroups, 77 against 90 us)
-    { const char* m = getenv("BTS_LP_GATHERQ_MIN"); if (gk && ((p.npos + 255) / 256) * p.ncg < (m ? atol(m) : 288)) gk = 0; }
-    if (gk) {
-      // four position groups per wave: OFF by default -- measured in round 5 (profiles/r05_ab_e6_gatherq_vb4.txt): the 128 accumulators
-      // + two operand sets need 442 registers, i.e. one wave per SIMD, and the batch-8 step loses 1.7 ms (76.6 against 74.9), the
-      // inference forward nothing / 0.1 ms.  BTS_LP_GATHERQ_VB4=<n> (n > 1) takes grids of at least n double-size workgroups (tests, A/B)
-      const char* v4 = getenv("BTS_LP_GATHERQ_VB4");
-      const bool vb4 = v4 && atoi(v4) > 1 && cb == 2 && p.Wg % 2 == 0 && ((p.npos + 511) / 512) * p.ncg >= atol(v4);
-      vb = vb4 ? 4 : 2;
-      if (vb4) gk = 2;
-    }
-  }
-  const long blocks = ((p.npos + 128L * vb - 1) / (128L * vb)) * p.ncg;
-  if (blocks > 0x7fffffffL) return BTS_ERR_SHAPE;
-  const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(31, 2.0 * p.ntaps * 16.0 * p.KS * p.Cout * (double)p.npos, stream);
-  (void)hipGetLastError();
-  if (gk) {
-#define LP_GQ(CB_, GK_) hipLaunchKernelGGL((lp_conv_gatherq_kernel<T, CB_, GK_>), dim3((unsigned)blocks), dim3(256), 0, stream, p)
-    if (vb == 4) hipLaunchKernelGGL((lp_conv_gatherq_kernel<T, 2, 2, 4>), dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    else if (cb == 2) { if (gk == 4) LP_GQ(2, 4); else LP_GQ(2, 2); }
-    else { if (gk == 4) LP_GQ(1, 4); else LP_GQ(1, 2); }
-#undef LP_GQ
-    if (prof) bts_prof_end(stream);
-    BTS_LAUNCH_CHECK();
-    return BTS_OK;
-  }
-#define LP_G_CASE(VB_, CB_) if (vb == VB_ && cb == CB_) hipLaunchKernelGGL((lp_conv_gather_kernel<T, VB_, CB_>), dim3((unsigned)blocks), dim3(256), 0, stream, p);
-  LP_G_CASE(4, 1) LP_G_CASE(4, 2) LP_G_CASE(2, 1) LP_G_CASE(2, 2) LP_G_CASE(1, 1) LP_G_CASE(1, 2)
-#undef LP_G_CASE
-  if (prof) bts_prof_end(stream);
-  BTS_LAUNCH_CHECK();
-  return BTS_OK;
-}
-
 // The stride-1 kernel of a call: the z-marching kernel (lowp_s1z.hip) for few channels on a big volume, then the LDS-DMA tiled one
 // (lowp_s1d.hip), then the register-staged one.  Forms: GroupNorm-backward class sums (gnb), GroupNorm applied to the input (gna),
 // FS and a second input tensor (ldxb) only on the first, a split output only on the second, SC on the first two.  G and gnb are
@@ -1012,7 +655,6 @@ int lp_s1_choose(const LpS1Call& c, LpS1Choice& ch) {
   return r == BTS_OK ? 1 : r;
 }
 static bool lp_s1_same(const LpS1Choice& a, const LpS1Choice& b) { return a.kernel == b.kernel && a.ws == b.ws && a.B == b.B; }
-static bool lp_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // the query's view of a call: dense strides, aligned operands
 static LpS1Call lp_s1_call(int N, int D, int H, int W, int Cin, int Cout) {
   LpS1Call c{};
@@ -1026,84 +668,22 @@ static int lp_s1_run(int dtype, const LpS1Call& c, const LpS1Choice& ch, LpS1Ptr
   return ch.kernel == LP_S1Z ? bts_lp_s1z_launch_(dtype, c, ch, q, stream) : bts_lp_s1d_launch_(dtype, c, ch, q, stream);
 }
 
-// what every conv launch checks before it looks at the geometry
-static int lp_conv_check(int dtype, const void* x, const void* wp, const void* y, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy) {
-  if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BTS_ERR_SHAPE;
-  // (results are stored four couts = 8 bytes at a time; a head with fewer than four output channels stores them one by one)
-  const bool vec_out = Cout >= 4;
-  if (Cin % 16 != 0 || ldx % 8 != 0 || (vec_out && ldy % 4 != 0) || ldx < Cin || ldy < Cout) return BTS_ERR_ALIGN;
-  if (!lp_al16(x) || (((uintptr_t)y) & (vec_out ? 7 : 1)) || !lp_al16(wp)) return BTS_ERR_ALIGN;
-  return BTS_OK;
-}
 // geometry-driven core of both entry points below.  geo: 0 = 1x1x1, 1 = 3x3x3 stride 1, 2 = stride-2 gather (out = ceil(in/2),
 // in = 2o + k - pad), 3 = 8 output-parity classes of the transposed form (out = 2 in; even outputs take (i, k=0) and (i-1, k=2),
-// odd ones (i, k=1)).  (D,H,W) are the dims of `x`, the tensor the taps read; Cin its channels (the contraction).
+// odd ones (i, k=1)).  (D,H,W) are the dims of `x`, the tensor the taps read; Cin its channels (the contraction).  Every geometry but 1: lowp_gather.hip.
 static int lp_conv_run(int geo, int dtype, const void* x, const void* wp, const float* bias, void* y, void* workspace, long workspace_bytes,
-                       int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int accum, hipStream_t stream,
-                       double* gap_part = nullptr, double* gn_part = nullptr, int gn_G = 0) {
+                       int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int accum, hipStream_t stream) {
+  const LpGPtrs gq{x, wp, bias, y};
+  LpGChoice gch;
+  if (geo != 1) return bts_lp_g_conv_(dtype, LpGCall{geo, N, D, H, W, Cin, ldx, Cout, ldy, accum}, &gq, 0, gch, stream);
   const int chk = lp_conv_check(dtype, x, wp, y, N, D, H, W, Cin, ldx, Cout, ldy);
   if (chk != BTS_OK) return chk;
-  const int KS = Cin / 16, NB = (Cout + 31) / 32;
-  if (geo == 1) {
-    LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
-    c.ldx = ldx; c.ldy = ldy; c.accum = accum; c.aligned = lp_al16(x) && lp_al16(y) && lp_al16(wp);
-    LpS1Choice ch;
-    const int r = lp_s1_choose(c, ch);
-    if (r != BTS_OK) return r;
-    return lp_s1_run(dtype, c, ch, LpS1Ptrs{x, wp, bias, y, workspace, workspace_bytes}, stream);
-  }
-  LpGatherParams g;
-  g.x = (const unsigned short*)x; g.wp = (const unsigned short*)wp; g.bias = bias; g.y = (unsigned short*)y;
-  g.N = N; g.Di = D; g.Hi = H; g.Wi = W; g.ldx = ldx; g.ldy = ldy; g.Cout = Cout; g.KS = KS; g.NB = NB; g.accum = accum;
-  g.gap_part = (geo == 0) ? gap_part : nullptr;
-  auto run = [&](const LpGatherParams& q) { return dtype == LP_F16 ? lp_gather_launch<TF16>(q, stream) : lp_gather_launch<TBF16>(q, stream); };
-  if (geo == 0 && gap_part == nullptr) {     // (the fused-pool form is offered the streaming kernel by bts_lp_conv1_gap itself)
-    const int r = bts_lp_k1_launch_(dtype, x, wp, bias, y, (long)N * D * H * W, Cin, ldx, Cout, ldy, accum, nullptr, 0, stream);
-    if (r != 1) return r;
-  }
-  if (geo == 0) {
-    g.Dg = g.Do = D; g.Hg = g.Ho = H; g.Wg = g.Wo = W; g.s = 1; g.os = 1; g.ooz = g.ooy = g.oox = 0; g.ntaps = 1;
-    g.taps[0] = LpTap{0, 0, 0, 0};
-    return run(g);
-  }
-  if (geo == 2) {   // TF 'same', stride 2: out = ceil(in/2), pad_before = max((out-1)*2+3-in, 0) / 2
-    {   // 32 -> <= 32 channels on a big even grid: the LDS-tiled kernel (lowp_s2t.hip)
-      const int r = bts_lp_s2t_launch_(dtype, x, wp, bias, y, N, D, H, W, Cin, ldx, Cout, ldy, accum, stream);
-      if (r != 1) return r;
-    }
-    g.Do = (D + 1) / 2; g.Ho = (H + 1) / 2; g.Wo = (W + 1) / 2;
-    g.Dg = g.Do; g.Hg = g.Ho; g.Wg = g.Wo; g.s = 2; g.os = 1; g.ooz = g.ooy = g.oox = 0; g.ntaps = 27;
-    auto padb = [](int in, int out) { const int t = (out - 1) * 2 + 3 - in; return t > 0 ? t / 2 : 0; };
-    const int pz = padb(D, g.Do), py = padb(H, g.Ho), px = padb(W, g.Wo);
-    for (int t = 0; t < 27; ++t) g.taps[t] = LpTap{(short)(t / 9 - pz), (short)((t / 3) % 3 - py), (short)(t % 3 - px), (short)t};
-    return run(g);
-  }
-  if (geo == 3) {  // y[2i+k] += x[i] w[k], cropped to [0, 2n): 8 output-parity classes, every output written once
-    {
-      const int r = bts_lp_up_launch_(dtype, x, reinterpret_cast<const char*>(wp) + lp_s1d_part_offset(Cin, Cout), bias, y, N, D, H, W, Cin, ldx,
-                                      Cout, ldy, accum, stream, gn_part, gn_G);
-      if (r != 1) return r;
-    }
-    if (gn_part != nullptr) return 1;      // (only the merged kernel emits the statistics: nothing was launched)
-    g.Do = 2 * D; g.Ho = 2 * H; g.Wo = 2 * W; g.Dg = D; g.Hg = H; g.Wg = W; g.s = 1; g.os = 2;
-    for (int cls = 0; cls < 8; ++cls) {
-      const int pz = cls >> 2, py = (cls >> 1) & 1, px = cls & 1;
-      int ozs[2], kzs[2], oys[2], kys[2], oxs[2], kxs[2];
-      auto fill = [](int par, int* off, int* k) { if (par) { off[0] = 0; k[0] = 1; return 1; } off[0] = 0; k[0] = 0; off[1] = -1; k[1] = 2; return 2; };
-      const int noz = fill(pz, ozs, kzs), noy = fill(py, oys, kys), nox = fill(px, oxs, kxs);
-      int nt = 0;
-      for (int a = 0; a < noz; ++a)
-        for (int b2 = 0; b2 < noy; ++b2)
-          for (int c = 0; c < nox; ++c)
-            g.taps[nt++] = LpTap{(short)ozs[a], (short)oys[b2], (short)oxs[c], (short)((kzs[a] * 3 + kys[b2]) * 3 + kxs[c])};
-      g.ntaps = nt; g.ooz = pz; g.ooy = py; g.oox = px;
-      const int r = run(g);
-      if (r != BTS_OK) return r;
-    }
-    return BTS_OK;
-  }
-  return BTS_ERR_UNSUPPORTED;
+  LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
+  c.ldx = ldx; c.ldy = ldy; c.accum = accum; c.aligned = lp_al16(x) && lp_al16(y) && lp_al16(wp);
+  LpS1Choice ch;
+  const int r = lp_s1_choose(c, ch);
+  if (r != BTS_OK) return r;
+  return lp_s1_run(dtype, c, ch, LpS1Ptrs{x, wp, bias, y, workspace, workspace_bytes}, stream);
 }
 
 static long lp_s1_workspace(int N, int D, int H, int W, int Cin, int Cout) {
@@ -1172,7 +752,6 @@ extern "C" int bts_lp_conv3d_fwd_gn(int dtype, const void* x, const void* wp, co
 // its read of x go away.  wp = bts_lp_pack(K3S1, FWD), wp_pt = bts_lp_pack(K1, FWD) with the same Cin_slab / fold; y and res dense
 // (N,D,H,W,Cout).  The workspace query returns -1 and the call 1 (nothing launched) where the streaming kernel does not take the shape:
 // the caller runs bts_lp_conv1_gap + bts_lp_conv3d_fwd_gn.  BTS_LP_FS=0 in the environment: never (A/B aid).
-__global__ __launch_bounds__(256) void lp_colsum_finalize_kernel(const double* partial, float* out, int N, int C, int B, double scale);
 static long lp_fwd_gn_shortcut_workspace(int N, int D, int H, int W, int Cin, int ldx, int Cout, int G, LpS1Choice& ch) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0) return -1;
   LpS1Call c = lp_s1_call(N, D, H, W, Cin, Cout);
@@ -1213,10 +792,7 @@ extern "C" int bts_lp_conv3d_fwd_gn_shortcut(int dtype, const void* x, long x_sp
   if (r != BTS_OK) return r;
   const int r2 = bts_gn_finalize_partials_(q.gnp, mean, rstd, N * G, Bg, (double)(V * Cout / G), eps, stream);
   if (r2 != BTS_OK) return r2;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * Cout + 3) / 4), dim3(256), 0, stream, q.gap_part, gap, N, Cout, (int)Bf, 1.0 / (double)V);
-  BTS_LAUNCH_CHECK();
-  return BTS_OK;
+  return bts_lp_colsum_finalize_(q.gap_part, gap, N, Cout, (int)Bf, 1.0 / (double)V, stream);
 }
 // The same with GroupNorm + ReLU of the INPUT applied on the way in (in_relu must be 1): y = conv3x3x3(relu(GN_in(x))) + bias and the statistics of y --
 // conv2 of a ResnetBlock reading conv1's raw output (resnet.py:133-136: conv -> GroupNormalization -> relu -> conv) where no backward
@@ -1252,82 +828,6 @@ extern "C" int bts_lp_conv3d_gnin_fwd_gn(int dtype, const void* x, const float* 
   const int r = lp_s1_run(dtype, c, ch, q, stream);
   if (r != BTS_OK) return r;
   return bts_gn_finalize_partials_(q.gnp, mean, rstd, N * G, ch.B, (double)((long)D * H * W * Cout / G), eps, stream);
-}
-// y = Conv3DTranspose(k3, s2, 'same')(x) + bias (dense fine tensor, storage type) AND the slab-mode GroupNorm statistics of y -- ConvUpsample
-// (upsample.py:28-43: conv -> GroupNormalization) without the statistics pass over the fine tensor: (sum, sumsq) partials leave the
-// merged transposed-conv kernel's epilogue per fine plane.  (D,H,W) = the COARSE grid.  Shapes that kernel declines, or fine z-slabs
-// that are not whole planes, run the conv and bts_lp_gn_stats on the stored y.
-extern "C" long bts_lp_convT3d_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int G) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0) return -1;
-  const long B = bts_lp_up_gn_B_(N, D, H, W, Cin, Cout, G);
-  const long fused = B > 0 ? (long)N * G * B * 16 + 64 : 0;
-  const long stats = bts_lp_gn_workspace(N, 8L * D * H * W, Cout, G);
-  return (fused > stats ? fused : stats) + 64;
-}
-extern "C" int bts_lp_convT3d_fwd_gn(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd,
-                                     void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G,
-                                     float eps, hipStream_t stream) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || Cout % G != 0) return BTS_ERR_SHAPE;
-  if (workspace == nullptr || workspace_bytes < bts_lp_convT3d_fwd_gn_workspace(N, D, H, W, Cin, Cout, G) || (((uintptr_t)workspace) & 15))
-    return BTS_ERR_WORKSPACE;
-  const long Vf = 8L * D * H * W;
-  const long B = (Cin % 16 == 0) ? bts_lp_up_gn_B_(N, D, H, W, Cin, Cout, G) : 0;
-  if (B > 0) {
-    double* part = reinterpret_cast<double*>(workspace);
-    const int r = lp_conv_run(3, dtype, x, wp, bias, y, nullptr, 0, N, D, H, W, Cin, ldx, Cout, Cout, 0, stream, nullptr, part, G);
-    if (r == BTS_OK) return bts_gn_finalize_partials_(part, mean, rstd, N * G, B, (double)(Vf * Cout / G), eps, stream);
-    if (r != 1) return r;
-  }
-  const int r = lp_conv_run(3, dtype, x, wp, bias, y, nullptr, 0, N, D, H, W, Cin, ldx, Cout, Cout, 0, stream);
-  if (r != BTS_OK) return r;
-  return bts_lp_gn_stats(dtype, y, mean, rstd, workspace, workspace_bytes, N, Vf, Cout, G, BTS_GN_SLAB, eps, stream);
-}
-__global__ __launch_bounds__(256) void lp_colsum_finalize_kernel(const double* partial, float* out, int N, int C, int B, double scale);
-// res = conv1x1x1(x) + bias in the storage type AND gap[n][c] = mean over the voxels of (the unrounded) res -- the block's shortcut
-// and the squeeze of its gate (resnet.py:118-121) in one pass: the column sums leave the conv's epilogue as per-block partials, a
-// small finalize adds them.  Sample volumes that are not whole position blocks run the conv and bts_lp_colsum on the stored res.
-extern "C" long bts_lp_conv1_gap_workspace(int N, long V, int Cout) {
-  if (N <= 0 || V <= 0 || Cout <= 0) return -1;
-  const long a = ((long)N * V / 128 + 1) * Cout * 8 + 64;      // (VB >= 1: at most N*V/128 position blocks)
-  const long b = bts_lp_colsum_workspace(N, V, Cout);
-  return a > b ? a : b;
-}
-extern "C" int bts_lp_conv1_gap(int dtype, const void* x, const void* wp, const float* bias, void* res, float* gap, void* workspace,
-                                long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldres, hipStream_t stream) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0) return BTS_ERR_SHAPE;
-  const long V = (long)D * H * W;
-  if (workspace == nullptr || workspace_bytes < bts_lp_conv1_gap_workspace(N, V, Cout) || (((uintptr_t)workspace) & 15)) return BTS_ERR_WORKSPACE;
-  const int NB = (Cout + 31) / 32;
-  {   // streaming kernel: column sums per block of 256 positions
-    // (one sample: a partial row can never span two samples, so the last position block may be ragged -- 20x24x20 = 9600 positions,
-    // the deepest level of the full inference volume, is not a multiple of 256)
-    int kb = bts_lp_k1_gap_block_((long)N * V, V, Cin, Cout);
-    if (kb == 0 && N == 1 && bts_lp_k1_gap_block_(V, 256, Cin, Cout) > 0) kb = 256;
-    if (kb > 0 && (V % kb == 0 || N == 1) && ldres == Cout) {
-      double* part = reinterpret_cast<double*>(workspace);
-      const int r = bts_lp_k1_launch_(dtype, x, wp, bias, res, (long)N * V, Cin, ldx, Cout, ldres, 0, part, kb, stream);
-      if (r == BTS_OK) {
-        hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * Cout + 3) / 4), dim3(256), 0, stream, part, gap, N, Cout, (int)((V + kb - 1) / kb), 1.0 / (double)V);
-        BTS_LAUNCH_CHECK();
-        return BTS_OK;
-      }
-      if (r != 1) return r;
-    }
-  }
-  const long ppb = 128L * lp_gather_vb((long)N * V, NB);     // positions per block
-  if (V % ppb != 0 || ldres != Cout) {
-    const int r = lp_conv_run(0, dtype, x, wp, bias, res, nullptr, 0, N, D, H, W, Cin, ldx, Cout, ldres, 0, stream);
-    if (r != BTS_OK) return r;
-    if (ldres != Cout) return BTS_ERR_UNSUPPORTED;
-    return bts_lp_colsum(dtype, res, gap, workspace, workspace_bytes, N, V, Cout, (float)(1.0 / (double)V), stream);
-  }
-  double* part = reinterpret_cast<double*>(workspace);
-  const int r = lp_conv_run(0, dtype, x, wp, bias, res, nullptr, 0, N, D, H, W, Cin, ldx, Cout, ldres, 0, stream, part);
-  if (r != BTS_OK) return r;
-  hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * Cout + 3) / 4), dim3(256), 0, stream, part, gap, N, Cout, (int)(V / ppb),
-                     1.0 / (double)V);
-  BTS_LAUNCH_CHECK();
-  return BTS_OK;
 }
 // dx (+)= conv^T(dy) (replaces tf.GradientTape for these ops, train.py:142-151).  (D,H,W) are the forward INPUT dims, Cin / Cout
 // the forward channel counts; wp_bwd = bts_lp_pack(kind, BTS_ROLE_BWD_DATA, ...).  The data gradient of each kind is one of the
@@ -1774,6 +1274,12 @@ __global__ __launch_bounds__(256) void lp_colsum_finalize_kernel(const double* p
   s = wave_sum_f64(s);
   if (lane == 0) out[i] = (float)(s * scale);
 }
+int bts_lp_colsum_finalize_(const double* partial, float* out, int N, int C, int B, double scale, hipStream_t stream) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * C + 3) / 4), dim3(256), 0, stream, partial, out, N, C, B, scale);
+  BTS_LAUNCH_CHECK();
+  return BTS_OK;
+}
 static int lp_colsum_blocks(long V) {
   long b = V / 2048;
   if (b < 1) b = 1;
@@ -1796,9 +1302,7 @@ extern "C" int bts_lp_colsum(int dtype, const void* x, float* out, void* workspa
   if (dtype == LP_F16) hipLaunchKernelGGL(lp_colsum_kernel<TF16>, dim3(B, N), dim3(256), 0, stream, (const unsigned short*)x, partial, V, C, B);
   else hipLaunchKernelGGL(lp_colsum_kernel<TBF16>, dim3(B, N), dim3(256), 0, stream, (const unsigned short*)x, partial, V, C, B);
   BTS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lp_colsum_finalize_kernel, dim3((N * C + 3) / 4), dim3(256), 0, stream, partial, out, N, C, B, (double)scale);
-  BTS_LAUNCH_CHECK();
-  return BTS_OK;
+  return bts_lp_colsum_finalize_(partial, out, N, C, B, (double)scale, stream);
 }
 
 // ---- ResNet block epilogue (resnet.py:127-137): out = res * (sigmoid(res . w_sp) + ch[n]) + relu(GN2(c2))

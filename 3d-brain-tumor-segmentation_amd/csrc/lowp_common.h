@@ -1,8 +1,9 @@
-// Storage-type traits and small helpers shared by the 16-bit translation units (lowp.hip, lowp_s1d.hip).
+// Storage-type traits, small helpers and the host-side kernel plans shared by the 16-bit translation units (lowp*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "common.h"
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -49,6 +50,22 @@ template <typename T> __device__ __forceinline__ u32x4 pack8(const float (&o)[8]
 }
 __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
   return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
+}
+
+// one register quad (4 consecutive couts) of a result: bias added by the caller; optional read-modify-write accumulation
+template <typename T>
+__device__ __forceinline__ void lp_store_quad(unsigned short* dst, float o0, float o1, float o2, float o3, int nleft, int accum) {
+  if (nleft >= 4) {
+    if (accum) {
+      const u32x2 old = *reinterpret_cast<const u32x2*>(dst);
+      o0 += T::ld((unsigned short)(old[0] & 0xffffu)); o1 += T::ld((unsigned short)(old[0] >> 16));
+      o2 += T::ld((unsigned short)(old[1] & 0xffffu)); o3 += T::ld((unsigned short)(old[1] >> 16));
+    }
+    *reinterpret_cast<u32x2*>(dst) = u32x2{pack2<T>(o0, o1), pack2<T>(o2, o3)};
+  } else {
+    const float o[3] = {o0, o1, o2};
+    for (int j = 0; j < nleft; ++j) dst[j] = T::st(accum ? o[j] + T::ld(dst[j]) : o[j]);
+  }
 }
 
 // ---- weight packing: source addressing shared by every packed-image layout ----
@@ -252,6 +269,64 @@ int lp_s1_choose(const LpS1Call& c, LpS1Choice& ch);
 inline long lp_s1z_fs_B(const S1zPlan& pl) { return (long)pl.ntx * pl.nty * pl.nzc * 8; }      // FS column-sum rows per sample
 int bts_lp_s1z_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);     // q.wp = the DMA part
 int bts_lp_s1d_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);
+
+// ---- 1x1x1, stride-2 and transposed convolutions and the data gradients on those geometries: which kernel takes a call (lowp_k1.hip,
+// lowp_s2t.hip, lowp_up.hip, else lowp_gather.hip), decided ONCE per query or launch by lp_g_choose; queries and entry points answer from it ----
+struct LpGCall {          // geometry, shape, strides (elements) and requested form of one call -- no pointers
+  int geo;                // 0 = 1x1x1, 2 = stride-2 gather (out = ceil(in/2)), 3 = the 8 output-parity classes of the transposed form (out = 2 in)
+  int N, D, H, W, Cin, ldx, Cout, ldy, accum;      // (D, H, W: the tensor the taps read)
+  int want_gap;           // geo 0: column sums of the unrounded output as partial rows [sample][row][Cout] (the squeeze)
+  int G;                  // geo 3: GroupNorm partial sums of the fine output, slab mode, G groups (0: none)
+  int x16, wp16, y_al;    // x / the weight image on a 16-byte boundary; y on 16 | 8 (the streaming and the merged kernel store 16 bytes), 0: neither
+};
+struct K1Plan { int lf, cb, ncg, nit; long blocks; };      // lf: lp_k1f_kernel (whole 128-byte row pieces); nit: 256-position blocks per workgroup
+struct S2tPlan { int ntx, nty, ntz; long ntiles; };
+struct UpPlan { int mode, txl, ntx, nty, ntz, ncg; long nitems; };
+struct LpGatherPlan { int vb, cb, gk, ncg; long npos, blocks; };      // gk: 0 = lp_conv_gather_kernel<vb, cb>, 2 | 4 = lp_conv_gatherq_kernel<cb, gk[, vb]>
+enum { LP_G_K1 = 1, LP_G_S2T, LP_G_UP, LP_G_GATHER };
+struct LpGChoice {
+  int kernel;             // LP_G_K1 | LP_G_S2T | LP_G_UP | LP_G_GATHER (geo 3: eight launches of the one plan)
+  union { K1Plan k; S2tPlan t; UpPlan u; LpGatherPlan g; };      // the plan of `kernel`
+  long rows;              // partial rows the kernel writes: per sample for want_gap, per (n, group) for G; 0: it cannot, or none asked for
+};
+// the operands of a launch (NULL: absent); wp = the whole image, part = the partial rows: [N][rows][Cout] (want_gap) | [N*G][rows][2] (G)
+struct LpGPtrs { const void *x, *wp; const float* bias; void* y; double* part; };
+int bts_prof_on();
+void bts_prof_begin(int sym, double flops, hipStream_t stream);
+void bts_prof_end(hipStream_t stream);
+// the A/B switches of the family (BTS_LP_K1 | UP | S2T | GATHERQ = 0: the kernel is off and the gather kernels take its calls): read per call
+inline bool lp_switch_on(const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); }
+// true: the kernel takes the call (every switch, shape, stride, alignment and 31-bit condition of its launcher) -- its plan and rows are
+// filled in, and the launcher does not decline it.  Which geometry goes to which kernel is lp_g_choose's rule.
+bool lp_k1_accept(const LpGCall& c, LpGChoice& ch);
+bool lp_s2t_accept(const LpGCall& c, LpGChoice& ch);
+bool lp_up_accept(const LpGCall& c, LpGChoice& ch);
+bool lp_gather_accept(const LpGCall& c, LpGChoice& ch);
+// BTS_OK: ch = the call's kernel; rows = 0 where no kernel emits the partials asked for (ch = the choice of the plain call then: the
+// caller forms them from the stored result).  Otherwise the status of a call no kernel takes.
+int lp_g_choose(const LpGCall& c, LpGChoice& ch);
+int bts_lp_k1_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const LpGPtrs& q, hipStream_t stream);
+int bts_lp_s2t_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const LpGPtrs& q, hipStream_t stream);
+int bts_lp_up_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const LpGPtrs& q, hipStream_t stream);
+// One call of the family (c's alignment flags come from q): chosen, put through the common argument check and launched.  q->part holds
+// max_rows partial rows; partials that would not fit are not asked for.  q == NULL: the query's view, aligned operands, the choice only.
+int bts_lp_g_conv_(int dtype, LpGCall c, const LpGPtrs* q, long max_rows, LpGChoice& ch, hipStream_t stream);
+// lowp.hip: out[n][c] = scale * the sum of the B partial rows [n][b][c], fixed order
+int bts_lp_colsum_finalize_(const double* partial, float* out, int N, int C, int B, double scale, hipStream_t stream);
+
+// byte offset of the DMA part inside a K3S1 / K3S2T-forward / K3S2-data-gradient image with K contraction channels and N output columns
+inline long lp_s1d_part_offset(int K, int N) { return 27L * ((K + 15) / 16) * ((N + 31) / 32) * 1024; }
+inline bool lp_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// what every conv launch checks before it looks at the geometry
+inline int lp_conv_check(int dtype, const void* x, const void* wp, const void* y, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy) {
+  if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BTS_ERR_SHAPE;
+  // (results are stored four couts = 8 bytes at a time; a head with fewer than four output channels stores them one by one)
+  const bool vec_out = Cout >= 4;
+  if (Cin % 16 != 0 || ldx % 8 != 0 || (vec_out && ldy % 4 != 0) || ldx < Cin || ldy < Cout) return BTS_ERR_ALIGN;
+  if (!lp_al16(x) || (((uintptr_t)y) & (vec_out ? 7 : 1)) || !lp_al16(wp)) return BTS_ERR_ALIGN;
+  return BTS_OK;
+}
 
 // ---- 16-bit weight gradients: which of the three kernels takes a call (the streaming lp_wgd_kernel of lowp_wgd.hip, the general LDS-tiled
 // lp_wgrad_kernel of lowp_wg.hip, the strided lp_wgs_kernel of lowp_wgs.hip) and where its workspace areas lie, decided ONCE per query or

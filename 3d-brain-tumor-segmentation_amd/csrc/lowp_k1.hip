@@ -2,7 +2,7 @@
 // the decoder / VAE projections, and -- on the role-swapped image -- their data gradients (train.py:142-151 under TF autodiff).
 //
 // These layers read and write every voxel once and multiply it by a tiny matrix: at 128^3 they are bound by HBM, and what the general
-// gather kernel of lowp.hip lacked for that was memory-level parallelism (one 512-position tile per workgroup, its first loads a
+// gather kernel of lowp_gather.hip lacked for that was memory-level parallelism (one 512-position tile per workgroup, its first loads a
 // full round trip away from its first matrix instruction) and wide stores.  Here
 //   * the output grid is a flat list of positions (no spatial arithmetic at all: y[pos] = W^T x[pos] + b);
 //   * a wave owns 64 positions x all of the item's couts and keeps a ring of RD k-steps of operands in flight, three waves per SIMD
@@ -14,14 +14,9 @@
 //   * the fused global-average-pool partial sums of bts_lp_conv1_gap (column sums per 256-position block) leave from the same place.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "common.h"
 #include "bts_internal.h"
 #include "lowp_common.h"
-
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
 
 struct LpK1Params {
   const unsigned short* x;
@@ -325,46 +320,48 @@ __global__ __launch_bounds__(256, (CB == 2 && GAP) ? 2 : 3) void lp_k1f_kernel(c
   }
 }
 
-static bool k1_enabled() {   // BTS_LP_K1=0: 1x1x1 convs back on the general gather kernel (A/B; read per call)
-  const char* e = getenv("BTS_LP_K1");
-  return !(e && atoi(e) == 0);
+// Views: x rows of ldx elements, y rows of ldy, both 16-byte aligned with ld % 8 == 0.  With want_gap: dense y, and rows of kb positions that
+// never span two samples -- the largest of 2048 .. 256 that divides the sample (fewer, longer rows keep the finalize short), or 256 with a
+// ragged last row where there is one sample only (20x24x20 = 9600 positions, the deepest level of the full inference volume).
+bool lp_k1_accept(const LpGCall& c, LpGChoice& ch) {
+  const long V = (long)c.D * c.H * c.W, npos = c.N * V;
+  if (!lp_switch_on("BTS_LP_K1") || c.Cin % 16 != 0 || c.Cout % 8 != 0 || npos < 4096) return false;
+  if (c.ldx % 8 != 0 || c.ldy % 8 != 0 || !c.x16 || c.y_al != 16) return false;
+  int kb = 0;
+  if (c.want_gap) {
+    if (c.ldy != c.Cout) return false;
+    // (shorter rows = more workgroups were tried for the 160x192x160 volume, 2400 workgroups at 2048 positions per row: within the
+    // run-to-run noise at full resolution, 10-25 % slower at the 80x96x80 level where a workgroup's fixed costs stop amortising)
+    for (kb = 2048; kb >= LPK1_POS && V % kb != 0; kb >>= 1) {}
+    if (kb < LPK1_POS) { if (c.N != 1) return false; kb = LPK1_POS; }
+  }
+  K1Plan& k = ch.k;
+  const int NB = (c.Cout + 31) / 32;
+  k.lf = c.Cin % 64 == 0;      // whole 128-byte row pieces per load instruction
+  k.cb = NB >= 2 ? 2 : 1;
+  k.ncg = (NB + k.cb - 1) / k.cb;
+  k.nit = kb ? kb / LPK1_POS : 1;
+  k.blocks = ((npos + (long)LPK1_POS * k.nit - 1) / ((long)LPK1_POS * k.nit)) * k.ncg;
+  if (k.blocks > 0x7fffffffL) return false;
+  ch.rows = kb ? (V + kb - 1) / kb : 0;
+  return true;
 }
-// positions per gap partial row of the streaming kernel for samples of V positions (a row never spans two samples: the largest of 2048
-// .. 256 that divides V; fewer, longer rows keep the finalize short), or 0 when a call with these dimensions is declined
-int bts_lp_k1_gap_block_(long npos, long V, int Cin, int Cout) {
-  if (!k1_enabled() || Cin % 16 != 0 || Cout % 8 != 0 || npos < 4096) return 0;
-  // (shorter rows = more workgroups were tried for the 160x192x160 volume, 2400 workgroups at 2048 positions per row: within the
-  // run-to-run noise at full resolution, 10-25 % slower at the 80x96x80 level where a workgroup's fixed costs stop amortising)
-  for (int kb = 2048; kb >= LPK1_POS; kb >>= 1)
-    if (V % kb == 0) return kb;
-  return 0;
-}
-// BTS_OK = ran, 1 = declined.  Views: x rows of ldx elements, y rows of ldy, both 16-byte aligned with ld % 8 == 0.
-int bts_lp_k1_launch_(int dtype, const void* x, const void* wp, const float* bias, void* y, long npos, int Cin, int ldx, int Cout, int ldy,
-                      int accum, double* gap_part, int gap_block, hipStream_t stream) {
-  if (bts_lp_k1_gap_block_(npos, LPK1_POS, Cin, Cout) == 0) return 1;
-  // (npos % gap_block != 0: the caller vouches that the ragged last row belongs to the only sample)
-  if (gap_part != nullptr && (gap_block < LPK1_POS || gap_block % LPK1_POS != 0)) return 1;
-  if (ldx % 8 != 0 || ldy % 8 != 0 || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return 1;
+int bts_lp_k1_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const LpGPtrs& q, hipStream_t stream) {
+  const K1Plan& k = ch.k;
   LpK1Params p;
-  p.x = (const unsigned short*)x; p.wp = (const unsigned short*)wp; p.bias = bias; p.y = (unsigned short*)y;
-  p.npos = npos; p.ldx = ldx; p.ldy = ldy; p.Cout = Cout; p.KS = Cin / 16; p.NB = (Cout + 31) / 32; p.accum = accum; p.gap_part = gap_part; p.nit = gap_part != nullptr ? gap_block / LPK1_POS : 1;
-  const int cb = p.NB >= 2 ? 2 : 1;
-  const long blocks = (npos + (long)LPK1_POS * p.nit - 1) / ((long)LPK1_POS * p.nit);
-  if (blocks > 0x7fffffffL) return 1;
+  p.x = (const unsigned short*)q.x; p.wp = (const unsigned short*)q.wp; p.bias = q.bias; p.y = (unsigned short*)q.y;
+  p.npos = (long)c.N * c.D * c.H * c.W; p.ldx = c.ldx; p.ldy = c.ldy; p.Cout = c.Cout; p.KS = c.Cin / 16; p.NB = (c.Cout + 31) / 32; p.accum = c.accum;
+  p.gap_part = q.part; p.nit = k.nit; p.ncg = k.ncg;
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(34, 2.0 * Cin * (double)Cout * (double)npos, stream);
+  if (prof) bts_prof_begin(34, 2.0 * c.Cin * (double)c.Cout * (double)p.npos, stream);
   (void)hipGetLastError();
-  p.ncg = (p.NB + cb - 1) / cb;
-  if (blocks * p.ncg > 0x7fffffffL) return 1;
-  const dim3 grid((unsigned)(blocks * p.ncg));
-  const bool lf = Cin % 64 == 0;      // whole 128-byte row pieces per load instruction
-  const bool gp = gap_part != nullptr;
+  const dim3 grid((unsigned)k.blocks);
+  const bool gp = q.part != nullptr;
 #define K1_GO(KERN, T_) do {                                                                                                          \
-    if (cb == 2) { if (gp) hipLaunchKernelGGL((KERN<T_, 2, true>), grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL((KERN<T_, 2, false>), grid, dim3(256), 0, stream, p); } \
+    if (k.cb == 2) { if (gp) hipLaunchKernelGGL((KERN<T_, 2, true>), grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL((KERN<T_, 2, false>), grid, dim3(256), 0, stream, p); } \
     else { if (gp) hipLaunchKernelGGL((KERN<T_, 1, true>), grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL((KERN<T_, 1, false>), grid, dim3(256), 0, stream, p); }        \
   } while (0)
-  if (lf) { if (dtype == LP_F16) K1_GO(lp_k1f_kernel, TF16); else K1_GO(lp_k1f_kernel, TBF16); }
+  if (k.lf) { if (dtype == LP_F16) K1_GO(lp_k1f_kernel, TF16); else K1_GO(lp_k1f_kernel, TBF16); }
   else { if (dtype == LP_F16) K1_GO(lp_k1_kernel, TF16); else K1_GO(lp_k1_kernel, TBF16); }
 #undef K1_GO
   if (prof) bts_prof_end(stream);

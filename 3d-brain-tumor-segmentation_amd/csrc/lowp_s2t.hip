@@ -1,6 +1,6 @@
 // 3x3x3 stride-2 'same' convolution with 32 input and <= 32 output channels on 16-bit storage, LDS-tiled (round 3): the Conv3D of
 // downsample.py:30-48 at the top level -- 2ch x 128^3 x batch (or 160x192x160) -> half the grid, the single most expensive launch of the
-// gather kernels (lowp.hip: 1.03 ms of the batch-8 step, 0.34 ms of the inference forward, 1.2 TB/s of input).
+// gather kernels (lowp_gather.hip: 1.03 ms of the batch-8 step, 0.34 ms of the inference forward, 1.2 TB/s of input).
 //
 // Why the gather form is slow there: every output voxel reads 27 input rows, neighbouring outputs share 2/3 of them, and nothing holds
 // the shared rows but the 32 KB L1 -- each row comes from L2 27/8 times, in 32- or 64-byte pieces of 128-byte lines (the input is a
@@ -23,17 +23,12 @@
 // LDS utilisation.  Tried without effect: loads two tiles ahead (254 VGPRs, same time), an XCD-aware tile order (5 % slower).  What is
 // left is the serial chain per tile -- store, barrier, 27 dependent matrix instructions, barrier, reduce, barrier -- of one workgroup per
 // CU with nothing to overlap it with.
-// Declines everything else (the caller keeps the gather kernels): Cin != 32, Cout > 32 or not a multiple of 4, odd input extents.
+// Takes nothing else (lp_s2t_accept; the gather kernels keep the rest): Cin != 32, Cout > 32 or not a multiple of 4, odd input extents.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "common.h"
 #include "bts_internal.h"
 #include "lowp_common.h"
-
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
 
 struct LpS2tParams {
   const unsigned short* x;
@@ -190,36 +185,33 @@ __global__ __launch_bounds__(512, 1) void lp_s2t_kernel(const LpS2tParams p) {
   }
 }
 
-static bool s2t_enabled() {   // BTS_LP_S2T=0: the layer back on the gather kernels (A/B; read per call)
-  const char* e = getenv("BTS_LP_S2T");
-  return !(e && atoi(e) == 0);
+// Forward geometry only (TF 'same', stride 2, even input extents: no padding in front).
+bool lp_s2t_accept(const LpGCall& c, LpGChoice& ch) {
+  if (!lp_switch_on("BTS_LP_S2T") || c.Cin != 32 || c.Cout > 32 || c.Cout % 4 != 0 || (c.D & 1) || (c.H & 1) || (c.W & 1)) return false;
+  if (c.ldx % 8 != 0 || c.ldy % 4 != 0 || !c.x16 || c.y_al == 0 || !c.wp16) return false;
+  S2tPlan& t = ch.t;
+  t.ntx = (c.W / 2 + S2T_TX - 1) / S2T_TX; t.nty = (c.H / 2 + S2T_TY - 1) / S2T_TY; t.ntz = (c.D / 2 + S2T_TZ - 1) / S2T_TZ;
+  t.ntiles = (long)c.N * t.ntz * t.nty * t.ntx;
+  return t.ntiles >= 512;          // (small grids: the gather kernel's finer split fills the chip better)
 }
-// BTS_OK = ran, 1 = declined.  Forward geometry only (TF 'same', stride 2, even input extents: no padding in front).
-int bts_lp_s2t_launch_(int dtype, const void* x, const void* wp, const float* bias, void* y, int N, int D, int H, int W, int Cin, int ldx,
-                       int Cout, int ldy, int accum, hipStream_t stream) {
-  if (!s2t_enabled() || Cin != 32 || Cout > 32 || Cout % 4 != 0 || (D & 1) || (H & 1) || (W & 1)) return 1;
-  if (ldx % 8 != 0 || ldy % 4 != 0 || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 7) || (((uintptr_t)wp) & 15)) return 1;
+int bts_lp_s2t_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const LpGPtrs& q, hipStream_t stream) {
   LpS2tParams p;
-  p.x = (const unsigned short*)x; p.wp = (const unsigned short*)wp; p.bias = bias; p.y = (unsigned short*)y;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = ldx; p.Do = D / 2; p.Ho = H / 2; p.Wo = W / 2; p.ldy = ldy; p.Cout = Cout; p.accum = accum;
-  p.ntx = (p.Wo + S2T_TX - 1) / S2T_TX; p.nty = (p.Ho + S2T_TY - 1) / S2T_TY; p.ntz = (p.Do + S2T_TZ - 1) / S2T_TZ;
-  p.ntiles = (long)N * p.ntz * p.nty * p.ntx;
-  if (p.ntiles < 512) return 1;          // (small grids: the gather kernel's finer split fills the chip better)
+  p.x = (const unsigned short*)q.x; p.wp = (const unsigned short*)q.wp; p.bias = q.bias; p.y = (unsigned short*)q.y;
+  p.N = c.N; p.D = c.D; p.H = c.H; p.W = c.W; p.ldx = c.ldx; p.Do = c.D / 2; p.Ho = c.H / 2; p.Wo = c.W / 2; p.ldy = c.ldy; p.Cout = c.Cout;
+  p.accum = c.accum; p.ntx = ch.t.ntx; p.nty = ch.t.nty; p.ntz = ch.t.ntz; p.ntiles = ch.t.ntiles;
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(39, 2.0 * 27.0 * Cin * (double)Cout * (double)N * p.Do * p.Ho * p.Wo, stream);
-  const int grid = p.ntiles < 256 ? (int)p.ntiles : 256;
-  (void)hipGetLastError();
+  if (prof) bts_prof_begin(39, 2.0 * 27.0 * c.Cin * (double)c.Cout * (double)c.N * p.Do * p.Ho * p.Wo, stream);
   static bool attr_done[2] = {false, false};
-  if (dtype == LP_F16) {
-    auto kern = lp_s2t_kernel<TF16>;
-    if (!attr_done[0]) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, S2T_LDS) != hipSuccess) return 1; attr_done[0] = true; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), S2T_LDS, stream, p);
-  } else {
-    auto kern = lp_s2t_kernel<TBF16>;
-    if (!attr_done[1]) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, S2T_LDS) != hipSuccess) return 1; attr_done[1] = true; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), S2T_LDS, stream, p);
-  }
+  auto go = [&](auto kern, bool& done) -> int {
+    const hipError_t e = done ? hipSuccess : hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, S2T_LDS);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kern, dim3(p.ntiles < 256 ? (int)p.ntiles : 256), dim3(512), S2T_LDS, stream, p);
+    BTS_LAUNCH_CHECK();
+    return BTS_OK;
+  };
+  const int r = dtype == LP_F16 ? go(lp_s2t_kernel<TF16>, attr_done[0]) : go(lp_s2t_kernel<TBF16>, attr_done[1]);
   if (prof) bts_prof_end(stream);
-  BTS_LAUNCH_CHECK();
-  return BTS_OK;
+  return r;
 }

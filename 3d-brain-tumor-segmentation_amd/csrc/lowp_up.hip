@@ -19,15 +19,10 @@
 // Declines (the per-class gather runs): coarse W < 12, Cout % 8 != 0, odd offsets beyond 31 bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "bts_internal.h"
 #include "lowp_common.h"
-
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
@@ -317,26 +312,24 @@ __global__ __launch_bounds__(512, 2) void lp_up_kernel(const LpUpParams p) {
 // =====================================================================================================================
 // plan + launch
 // =====================================================================================================================
-static bool up_enabled() {   // BTS_LP_UP=0: the transposed form back on eight launches of the gather kernel (A/B; read per call)
-  const char* e = getenv("BTS_LP_UP");
-  return !(e && atoi(e) == 0);
-}
-struct UpPlan { int mode, txl, ntx, nty, ntz, ncg; long nitems; };
-static bool up_plan(int N, int D, int H, int W, int Cin, int Cout, UpPlan& pl) {      // (D,H,W) = the COARSE grid
-  if (!up_enabled() || Cin % 16 != 0 || Cout % 8 != 0 || W < 12) return false;
-  if ((long)N * D * H * W < 2048) return false;
-  const int NB = (Cout + 31) / 32;
+// (D,H,W) = the COARSE grid.  rows: GroupNorm-partial slots per (n, group) of the FINE tensor, where asked for and whole fine planes per group
+bool lp_up_accept(const LpGCall& c, LpGChoice& ch) {
+  if (!lp_switch_on("BTS_LP_UP") || c.Cin % 16 != 0 || c.Cout % 8 != 0 || c.W < 12) return false;
+  if ((long)c.N * c.D * c.H * c.W < 2048) return false;
+  if (c.ldx % 8 != 0 || c.ldy % 8 != 0 || !c.x16 || c.y_al != 16 || !c.wp16) return false;      // (the DMA part sits a multiple of 1 KB into the image)
+  if (((long)(c.D + 2) * c.H * c.W + 64) * (long)c.ldx * 2 >= 0x7fffffffL) return false;          // 31-bit offsets inside one volume
+  if ((8L * c.D * c.H * c.W + 64) * (long)c.ldy * 2 >= 0x7fffff00L) return false;
+  UpPlan& pl = ch.u;
+  const int NB = (c.Cout + 31) / 32;
   pl.mode = NB >= 2 ? 1 : 0;
-  pl.txl = W >= 24 ? 5 : 4;
+  pl.txl = c.W >= 24 ? 5 : 4;
   const int TX = 1 << pl.txl, ZP = 32 / TX, TZ = (pl.mode ? 1 : 2) * ZP;
-  pl.ntx = (W + TX - 1) / TX; pl.nty = (H + 3) / 4; pl.ntz = (D + TZ - 1) / TZ;
+  pl.ntx = (c.W + TX - 1) / TX; pl.nty = (c.H + 3) / 4; pl.ntz = (c.D + TZ - 1) / TZ;
   pl.ncg = pl.mode ? (NB + 1) / 2 : 1;
-  pl.nitems = (long)N * pl.ntz * pl.nty * pl.ntx * pl.ncg;
-  return pl.nitems <= 0x7fffffffL;
-}
-bool bts_lp_up_takes_(int N, int D, int H, int W, int Cin, int Cout) {
-  UpPlan pl;
-  return up_plan(N, D, H, W, Cin, Cout, pl);
+  pl.nitems = (long)c.N * pl.ntz * pl.nty * pl.ntx * pl.ncg;
+  if (pl.nitems > 0x7fffffffL) return false;
+  ch.rows = (c.G > 0 && (2 * c.D) % c.G == 0) ? (long)(2 * c.D / c.G) * pl.nty * pl.ntx * pl.ncg * (pl.mode ? 8 : 4) : 0;
+  return true;
 }
 
 template <typename T, int MODE, int TXL>
@@ -356,31 +349,19 @@ static int up_launch_t(const LpUpParams& p, hipStream_t stream) {
   return BTS_OK;
 }
 
-// GroupNorm-partial slots per (n, group) of the FINE tensor when the kernel takes the shape and can emit them (whole fine planes per
-// group); 0 otherwise
-long bts_lp_up_gn_B_(int N, int D, int H, int W, int Cin, int Cout, int Gn) {
-  UpPlan pl;
-  if (Gn <= 0 || (2 * D) % Gn != 0 || !up_plan(N, D, H, W, Cin, Cout, pl)) return 0;
-  return (long)(2 * D / Gn) * pl.nty * pl.ntx * pl.ncg * (pl.mode ? 8 : 4);
-}
-// BTS_OK = ran, 1 = declined.  x: coarse (N,D,H,W,Cin); y: fine (N,2D,2H,2W,Cout); wp_dma: the DMA part of the image.
-// gnp (may be NULL): fused GroupNorm partial sums of y, [N*gn_G][bts_lp_up_gn_B_][2]
-int bts_lp_up_launch_(int dtype, const void* x, const void* wp_dma, const float* bias, void* y, int N, int D, int H, int W, int Cin, int ldx,
-                      int Cout, int ldy, int accum, hipStream_t stream, double* gnp, int gn_G) {
-  UpPlan pl;
-  if (!up_plan(N, D, H, W, Cin, Cout, pl)) return 1;
-  if (gnp != nullptr && (gn_G <= 0 || (2 * D) % gn_G != 0)) return 1;
-  if (ldx % 8 != 0 || ldy % 8 != 0 || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 15) || (((uintptr_t)wp_dma) & 15)) return 1;
-  if (((long)(D + 2) * H * W + 64) * (long)ldx * 2 >= 0x7fffffffL) return 1;
-  if ((8L * D * H * W + 64) * (long)ldy * 2 >= 0x7fffff00L) return 1;
+// x: coarse (N,D,H,W,Cin); y: fine (N,2D,2H,2W,Cout).  q.part (may be NULL): fused GroupNorm partial sums of y, [N*G][ch.rows][2]
+int bts_lp_up_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const LpGPtrs& q, hipStream_t stream) {
+  const UpPlan& pl = ch.u;
+  const int gn_G = q.part != nullptr ? c.G : 0;
   LpUpParams p;
-  p.x = (const unsigned short*)x; p.wp = (const unsigned short*)wp_dma; p.bias = bias; p.y = (unsigned short*)y;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = ldx; p.ldy = ldy; p.Cout = Cout; p.KS = Cin / 16; p.NB = (Cout + 31) / 32;
-  p.ntx = pl.ntx; p.nty = pl.nty; p.ntz = pl.ntz; p.ncg = pl.ncg; p.nitems = pl.nitems; p.accum = accum;
-  p.gnp = gnp; p.gn_G = gn_G; p.gn_zt = gn_G > 0 ? 2 * D / gn_G : 1;
-  p.gn_B = gn_G > 0 ? (long)p.gn_zt * pl.nty * pl.ntx * pl.ncg * (pl.mode ? 8 : 4) : 0;
+  p.x = (const unsigned short*)q.x; p.bias = q.bias; p.y = (unsigned short*)q.y;
+  p.wp = (const unsigned short*)(reinterpret_cast<const char*>(q.wp) + lp_s1d_part_offset(c.Cin, c.Cout));
+  p.N = c.N; p.D = c.D; p.H = c.H; p.W = c.W; p.ldx = c.ldx; p.ldy = c.ldy; p.Cout = c.Cout; p.KS = c.Cin / 16; p.NB = (c.Cout + 31) / 32;
+  p.ntx = pl.ntx; p.nty = pl.nty; p.ntz = pl.ntz; p.ncg = pl.ncg; p.nitems = pl.nitems; p.accum = c.accum;
+  p.gnp = q.part; p.gn_G = gn_G; p.gn_zt = gn_G > 0 ? 2 * c.D / gn_G : 1;
+  p.gn_B = gn_G > 0 ? ch.rows : 0;
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(35, 2.0 * 27.0 * Cin * (double)Cout * (double)N * D * H * W, stream);
+  if (prof) bts_prof_begin(35, 2.0 * 27.0 * c.Cin * (double)c.Cout * (double)c.N * c.D * c.H * c.W, stream);
   int r;
 #define UP_CASE(M_, X_)                                                                                               \
   if (pl.mode == M_ && pl.txl == X_)                                                                                  \

@@ -443,7 +443,7 @@ int bts_lp_conv3d_gnin_bwd_weight(int dtype, const void* x, const float* in_gamm
 /* y = Conv3DTranspose(k3, s2, 'same')(x) + bias (dense fine tensor (N,2D,2H,2W,Cout), storage type) and the slab-mode GroupNorm
  * statistics of y in one pass: ConvUpsample (upsample.py:28-43: conv -> GroupNormalization) without a statistics pass over the fine
  * tensor.  (D,H,W): the COARSE grid; wp = bts_lp_pack(BTS_CONV_K3S2T, BTS_ROLE_FWD, ...).  Falls back to the conv + bts_lp_gn_stats
- * where the merged transposed-conv kernel declines the shape or a group is not whole fine planes. */
+ * where the merged transposed-conv kernel does not take the call or a group is not whole fine planes. */
 long bts_lp_convT3d_fwd_gn_workspace(int N, int D, int H, int W, int Cin, int Cout, int G);
 int bts_lp_convT3d_fwd_gn(int dtype, const void* x, const void* wp, const float* bias, void* y, float* mean, float* rstd, void* workspace,
                           long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int G, float eps,

@@ -128,6 +128,80 @@ def test_split_data_gradient_query_matches_the_kernel_bounds(L):
     assert L._bts_lp_conv3d_bwd_data_sc_split_ok(1, 192, 192, 192, 64, 32) == 1
     assert L._bts_lp_conv3d_bwd_data_sc_split_ok(8, 128, 128, 128, 64, 32) == 1
 
+@pytest.mark.parametrize('grid', GRIDS, ids=lambda g: '%dx%dx%dx%d' % g)
+def test_transposed_and_pooled_conv_queries_answer_from_one_plan(L, grid, monkeypatch):
+    """bts_lp_convT3d_fwd_gn_workspace (every K3S2T shape) answers from the plan the launch makes: the same answer twice, a positive
+    size, and at least as large for N samples as for one -- with the merged transposed kernel and the streaming 1x1x1 kernel on
+    (default) and off.  bts_lp_conv1_gap_workspace (every level) is held to the same three properties, but it is a closed-form upper
+    bound that sees neither Cin nor a switch (the launch asks for partial rows only where they fit it), so it is asked once."""
+    n, d, h, w = grid
+    up = [s for s in layer_shapes(n, d, h, w) if s[0] == 3]
+    assert len(up) >= 3
+    for switch in (None, 'BTS_LP_UP', 'BTS_LP_K1'):
+        for name in ('BTS_LP_UP', 'BTS_LP_K1', 'BTS_LP_S2T'):
+            monkeypatch.delenv(name, raising=False)
+        if switch:
+            monkeypatch.setenv(switch, '0')
+        for (kind, N, D, H, W, ci, co) in up:
+            a = L._bts_lp_convT3d_fwd_gn_workspace(N, D, H, W, ci, co, G)
+            assert a == L._bts_lp_convT3d_fwd_gn_workspace(N, D, H, W, ci, co, G) and a > 0, (switch, N, D, H, W, ci, co, a)
+            assert L._bts_lp_convT3d_fwd_gn_workspace(1, D, H, W, ci, co, G) <= a, (switch, N, D, H, W, ci, co, a)
+    for lvl in range(DEPTH):
+        V, f = (d >> lvl) * (h >> lvl) * (w >> lvl), F << lvl
+        a = L._bts_lp_conv1_gap_workspace(n, V, f)
+        assert a == L._bts_lp_conv1_gap_workspace(n, V, f) and a > 0, (n, V, f, a)
+        assert L._bts_lp_conv1_gap_workspace(1, V, f) <= a, (n, V, f, a)
+
+
+def test_transposed_conv_query_knows_the_merged_kernels_offset_bounds(L, monkeypatch):
+    """a fine tensor whose byte offsets leave 31 bits (coarse 1 x 160x192x160, 64 -> 32: 2.5 GB) is not the merged transposed kernel's: the
+    launch runs the gather kernels and bts_lp_gn_stats, so the query sizes the statistics pass and no partial slots (it used to size
+    4.9 MB of slots the launch never wrote)"""
+    monkeypatch.delenv('BTS_LP_UP', raising=False)
+    for ci in (64, 32):
+        assert L._bts_lp_convT3d_fwd_gn_workspace(1, 160, 192, 160, ci, 32, G) == L._bts_lp_gn_workspace(1, 8 * 160 * 192 * 160, 32, G) + 64
+    # (half the extent: the merged kernel takes it, and its slots are the larger need)
+    assert L._bts_lp_convT3d_fwd_gn_workspace(1, 80, 96, 80, 64, 32, G) > L._bts_lp_gn_workspace(1, 8 * 80 * 96 * 80, 32, G) + 64
+
+
+def test_gather_family_calls_refuse_bad_arguments_before_any_launch(L, monkeypatch):
+    """the 1x1x1, stride-2 and transposed entry points of the 16-bit engine return their argument statuses before any HIP call -- input
+    channels that are not whole 16-channel steps, an input stride that is not a multiple of 8, output rows narrower than Cout
+    (BTS_ERR_ALIGN), an unknown storage type (BTS_ERR_UNSUPPORTED), a short or misaligned workspace (BTS_ERR_WORKSPACE): the codes the
+    trial-order dispatch returned.  Fake, never dereferenced device addresses; on a grid no fast kernel takes (8^3) and on one they do
+    (32^3).  bts_lp_conv1_gap's storage type is asked at 8^3 only: at 32^3 the streaming kernel takes the fused call on its own
+    conditions, which have never included the type, and the call reaches its launch."""
+    for name in ('BTS_LP_UP', 'BTS_LP_K1', 'BTS_LP_S2T', 'BTS_LP_GATHERQ'):
+        monkeypatch.delenv(name, raising=False)
+    P, BF16, N, ci, co = 0x100000, 2, 1, 32, 32
+    ALIGN, UNSUPPORTED, WORKSPACE = -2, -3, -4
+    cases = (('Cin % 16', dict(ci=24), ALIGN), ('ldx % 8', dict(ldx=36), ALIGN), ('ldy < Cout', dict(ldy=16), ALIGN),
+             ('dtype', dict(dtype=7), UNSUPPORTED))
+    for S in (8, 32):
+        for what, kw, want in cases:
+            c_in = kw.get('ci', ci)
+            ldx, ldy, dtype = kw.get('ldx', c_in), kw.get('ldy', co), kw.get('dtype', BF16)
+            for kind in (0, 2, 3):
+                r = L._bts_lp_conv3d_fwd(kind, dtype, P, P, P, P, None, 0, N, S, S, S, c_in, ldx, co, ldy, None)
+                assert r == want, ('fwd', S, kind, what, r)
+                # (the data gradient contracts over the forward's Cout: dy is the operand with the channel and stride rules, dx the output)
+                r = L._bts_lp_conv3d_bwd_data(kind, dtype, P, P, P, None, 0, N, S, S, S, co, ldy, c_in, ldx, 0, None)
+                assert r == want, ('bwd_data', S, kind, what, r)
+            if what != 'ldy < Cout':      # (its y is dense by contract)
+                nb = L._bts_lp_convT3d_fwd_gn_workspace(N, S, S, S, c_in, co, G)
+                r = L._bts_lp_convT3d_fwd_gn(dtype, P, P, P, P, P, P, P, nb, N, S, S, S, c_in, ldx, co, G, 1e-5, None)
+                assert r == want, ('convT3d_fwd_gn', S, what, r)
+            if not (what == 'dtype' and S == 32):
+                nb = L._bts_lp_conv1_gap_workspace(N, S * S * S, co)
+                r = L._bts_lp_conv1_gap(dtype, P, P, P, P, P, P, nb, N, S, S, S, c_in, ldx, co, ldy, None)
+                assert r == want, ('conv1_gap', S, what, r)
+        for ws, short in ((P, 16), (P + 8, 0)):
+            nb = L._bts_lp_convT3d_fwd_gn_workspace(N, S, S, S, ci, co, G)
+            assert L._bts_lp_convT3d_fwd_gn(BF16, P, P, P, P, P, P, ws, short or nb, N, S, S, S, ci, ci, co, G, 1e-5, None) == WORKSPACE
+            nb = L._bts_lp_conv1_gap_workspace(N, S * S * S, co)
+            assert L._bts_lp_conv1_gap(BF16, P, P, P, P, P, ws, short or nb, N, S, S, S, ci, ci, co, co, None) == WORKSPACE
+
+
 def test_weight_gradient_calls_refuse_an_impossible_bias_gradient_before_any_launch(L, monkeypatch):
     """a 16-bit weight-gradient call that cannot produce its db (dy rows wider than Cout; a Cout whose 16-byte chunks do not tile the
     256-thread column-sum block) answers from its plan, before dw is touched -- BTS_ERR_UNSUPPORTED / BTS_ERR_SHAPE as ever.  Fake,

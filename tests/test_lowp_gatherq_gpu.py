@@ -1,4 +1,4 @@
-"""-m gpu: the whole-row stride-2 gather kernel of the 16-bit storage path (lp_conv_gatherq_kernel in csrc/lowp.hip: ConvDownsample's
+"""-m gpu: the whole-row stride-2 gather kernel of the 16-bit storage path (lp_conv_gatherq_kernel in csrc/lowp_gather.hip: ConvDownsample's
 Conv3D, downsample.py:28-35, below the top level, and -- on role-swapped images -- ConvUpsample's data gradient, upsample.py:28-33 under
 train.py:151) in its three register shapes: GK = 4 (four k-steps per load group), GK = 2, and VB = 4 (four position groups per wave
 sharing every weight fragment: round 5, measured slower and off by default, kept correct).  Small grids, the size thresholds lowered through BTS_LP_GATHERQ_MIN / BTS_LP_GATHERQ_VB4 so that
