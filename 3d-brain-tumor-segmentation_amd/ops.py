@@ -781,6 +781,79 @@ def augment_crop(x, y, var, crop, offsets, flip_mask, shift, scale, out_ch):
     return xo, yo
 
 
+# ---- dataset preprocessing on the device (preprocess.py:17-131) ----
+def _window(v, c, name):
+    """(st0, st1) of a view made by slicing a dense (S0,S1,S2,c) parent on its three spatial axes; no copy is ever made here"""
+    if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32:
+        raise ValueError('%s must be a float32 tensor on the GPU' % name)
+    if v.dim() != 4 or v.shape[3] != c or min(v.shape) < 1:
+        raise ValueError('%s must have shape (T0,T1,T2,%d), got %s' % (name, c, tuple(v.shape)))
+    if v.stride(3) != 1 or v.stride(2) != c:
+        raise ValueError('%s must be a spatial slice of a dense channels-last volume (strides (*,*,%d,1)), got strides %s'
+                         % (name, c, v.stride()))
+    if v.stride(1) < v.shape[2] * c or v.stride(0) < v.shape[1] * v.stride(1):
+        raise ValueError('%s: strides %s overlap for shape %s' % (name, v.stride(), tuple(v.shape)))
+    return v.stride(0), v.stride(1)
+
+
+def _f64(t, n, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.numel() != n or not t.is_contiguous():
+        raise ValueError('%s must be %d dense float64 values on the GPU' % (name, n))
+    return t
+
+
+def prepro_occupancy(x, occ):
+    """sets occ[a] = 1 (int32, S0+S1+S2 entries, axis 0 first) for every plane of every axis of the dense (S0,S1,S2,C) volume x that
+    holds an x != 0; never clears a flag, so one zeroed buffer collects a whole dataset"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('prepro_occupancy: x must be a dense (S0,S1,S2,C) volume')
+    _window(x, x.shape[3], 'prepro_occupancy: x')
+    if not x.is_contiguous():
+        raise ValueError('prepro_occupancy: x must be dense, got strides %s' % (x.stride(),))
+    s0, s1, s2, c = x.shape
+    if not isinstance(occ, torch.Tensor) or not occ.is_cuda or occ.dtype != torch.int32 or occ.numel() != s0 + s1 + s2 or not occ.is_contiguous():
+        raise ValueError('prepro_occupancy: occ must be %d dense int32 values on the GPU' % (s0 + s1 + s2))
+    lib().call('bts_prepro_occupancy', _p(x), _p(occ), s0, s1, s2, c, _stream())
+    return occ
+
+
+def prepro_sums(v, acc, mean=None):
+    """window v (T0,T1,T2,C) of a dense volume.  mean None: acc[0:C] += sum x, acc[C:2C] += #(x > 0); mean (C float64 on the GPU):
+    acc[0:C] += sum (x - mean)^2.  acc: float64 on the GPU (2C / C values); fp64 throughout, fixed summation order"""
+    if not isinstance(v, torch.Tensor) or v.dim() != 4:
+        raise ValueError('prepro_sums: v must be a (T0,T1,T2,C) window')
+    c = v.shape[3]
+    st0, st1 = _window(v, c, 'prepro_sums: v')
+    _f64(acc, c if mean is not None else 2 * c, 'prepro_sums: acc')
+    if mean is not None:
+        _f64(mean, c, 'prepro_sums: mean')
+    nb = lib().query('bts_prepro_workspace', c)
+    ws = workspace(nb, v.device)
+    lib().call('bts_prepro_sums', _p(v), st0, st1, v.shape[0], v.shape[1], v.shape[2], c, _p(mean), _p(acc), _p(ws), nb, _stream())
+    return acc
+
+
+def prepro_crop_norm(v, yv, mean, std):
+    """windows v (T0,T1,T2,C) and yv (T0,T1,T2,1) (or None) -> dense (float((double(x) - mean) / std), y with labels >= 4 -> 3);
+    mean, std: C float64 values on the GPU"""
+    if not isinstance(v, torch.Tensor) or v.dim() != 4:
+        raise ValueError('prepro_crop_norm: v must be a (T0,T1,T2,C) window')
+    c = v.shape[3]
+    st0, st1 = _window(v, c, 'prepro_crop_norm: x')
+    _f64(mean, c, 'prepro_crop_norm: mean')
+    _f64(std, c, 'prepro_crop_norm: std')
+    t0, t1, t2 = v.shape[:3]
+    xo = torch.empty((t0, t1, t2, c), dtype=torch.float32, device=v.device)
+    yo, yst0, yst1 = None, 0, 0
+    if yv is not None:
+        if not isinstance(yv, torch.Tensor) or yv.dim() != 4 or tuple(yv.shape) != (t0, t1, t2, 1):
+            raise ValueError('prepro_crop_norm: y must have shape %s' % ((t0, t1, t2, 1),))
+        yst0, yst1 = _window(yv, 1, 'prepro_crop_norm: y')
+        yo = torch.empty((t0, t1, t2, 1), dtype=torch.float32, device=v.device)
+    lib().call('bts_prepro_crop_norm', _p(v), _p(yv), st0, st1, yst0, yst1, t0, t1, t2, c, _p(mean), _p(std), _p(xo), _p(yo), _stream())
+    return xo, yo
+
+
 # ---- non-default samplers (SURVEY 8 f-4) ----
 def maxpool2_fwd(x):
     n, d, h, w, c = x.shape

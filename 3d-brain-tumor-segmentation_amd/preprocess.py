@@ -1,0 +1,261 @@
+"""Dataset preprocessing on the device: folders of NIfTI scans -> train-ready examples (reference preprocess.py:12-131).
+
+    python -m bts_amd.preprocess --in_locs a,b --modalities t1ce,flair --truth seg [--create_val] [--out_loc ./data]
+
+The names, the argument order and the results are the reference's: `create_dataset` finds the bounding box of all non-zero voxels
+of all cases and crops every case to it, `compute_norm` gives the per-channel mean and standard deviation of the training cases,
+`preprocess` (the reference's `main`) writes the normalised examples and `prepro.npy`.  What runs where: files are decoded on a
+thread pool of the host (bts_amd.nifti; zlib releases the GIL), each volume is uploaded once and stays resident, and the three
+passes over the voxels are kernels of csrc/prepro.hip (ops.prepro_occupancy, prepro_sums, prepro_crop_norm).
+
+Quirks of the reference that are kept, because the sizes in prepro.npy and everything downstream depend on them:
+  * the crop is [min:max] of the first / last occupied plane, so the last occupied plane of each axis is dropped and
+    size = max - min (preprocess.py:55-63);
+  * mean = sum(x) / #(x > 0) and std = sqrt(sum((x - mean)^2) / #(x > 0)): both sums run over every voxel of the crop, the count
+    over the strictly positive ones only (preprocess.py:75-83);
+  * "non-zero" is numpy's truth value: NaN counts, -0.0 does not (preprocess.py:39-47);
+  * with create_val the validation set is the first len // 11 cases in visiting order (the shuffled index list of
+    preprocess.py:105-106 is never used) and the statistics come from the training cases alone;
+  * labels >= 4 become 3 (preprocess.py:36); files are numbered from 1 per folder.
+
+Deviations:
+  * cases are visited in sorted order of their paths; the reference's order is whatever glob returns, i.e. the file system's;
+  * sum(x) is accumulated in float64.  The reference adds each volume up in float32 (np.sum of a float32 array) before it adds the
+    volumes in float64; on real scans the totals pass 2^24 and that float32 sum is inexact, so its mean differs from ours in the
+    low digits.  On integer-valued volumes whose per-volume totals stay below 2^24 the two are bit-equal;
+  * the label rule is applied by the kernel that writes the example, not to the resident volume (`remap_labels` is the eager form);
+  * examples are stored as `.npz` files with the arrays `x` and `y`, the form data.prepare_dataset reads, not as TFRecords.
+"""
+import argparse
+import glob
+import os
+import shutil
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import nifti, ops
+
+
+def get_npy_image(path, name):
+    """float32 array of the first file, in sorted order, that matches path/*<name>.nii* (preprocess.py:12-14)"""
+    found = sorted(glob.glob(os.path.join(path, '*' + name + '.nii' + '*')))
+    if not found:
+        raise ValueError('%s: no file matches *%s.nii*' % (path, name))
+    return np.asarray(nifti.load(found[0])[0]).astype(np.float32)
+
+
+def remap_labels(y):
+    """labels >= 4 -> 3 (preprocess.py:36), a new tensor or array; `normalize_example` applies the same rule when it writes"""
+    if isinstance(y, torch.Tensor):
+        return torch.where(y >= 4, torch.full_like(y, 3.0), y)
+    y = np.array(y, copy=True)
+    y[y >= 4] = 3
+    return y
+
+
+def _device(device):
+    return torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def _decode_case(path, names):
+    """every volume of one case as a C-contiguous float32 array with the axes reversed (NIfTI data is Fortran-ordered, so this is
+    the file's own byte order and costs no transposition on the host)"""
+    return [np.ascontiguousarray(get_npy_image(path, name).T) for name in names]
+
+
+def _upload_case(vols, dev):
+    """the decoded volumes of one case (axes reversed, see `_decode_case`) -> resident x (h,w,d,c) and y (h,w,d,1)"""
+    c = len(vols) - 1
+    x = torch.empty(vols[0].shape[::-1] + (c,), dtype=torch.float32, device=dev)
+    for ch in range(c):
+        x[..., ch].copy_(torch.from_numpy(vols[ch]).to(dev).permute(2, 1, 0))
+    y = torch.from_numpy(vols[c]).to(dev).permute(2, 1, 0).contiguous().unsqueeze(-1)
+    return x, y
+
+
+def create_dataset(locs, modalities, truth, device=None, workers=8):
+    """-> (x, y, size): lists of device views (h,w,d,c) / (h,w,d,1) of the resident raw volumes, restricted to the bounding box
+    common to all cases, and size = {'h','w','d','c'}   [preprocess.py:17-65]
+    Every entry of every folder of `locs` is a case; folders and cases are visited in sorted order (the reference visits them in
+    the file system's order).  Files are decoded by `workers` threads.  `y` holds the labels as stored; see `remap_labels`."""
+    dev = _device(device)
+    cases = [p for loc in locs for p in sorted(glob.glob(os.path.join(loc, '*')))]
+    if not cases:
+        raise ValueError('no case found under %s' % (list(locs),))
+    names = list(modalities) + [truth]
+    c = len(modalities)
+    xs, ys, shape, occ = [], [], None, None
+    workers = max(1, int(workers))
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        pending, nxt = [], 0
+        for k, path in enumerate(cases):
+            while nxt < len(cases) and len(pending) < 2 * workers:       # bounded look-ahead: decoded volumes wait on the host
+                pending.append(pool.submit(_decode_case, cases[nxt], names))
+                nxt += 1
+            vols = pending.pop(0).result()
+            for v in vols:
+                if v.ndim != 3:
+                    raise ValueError('%s: a volume of rank %d, expected 3' % (path, v.ndim))
+                if v.shape != vols[0].shape:
+                    raise ValueError('%s: the volumes of this case differ in shape: %s' % (path, [u.shape[::-1] for u in vols]))
+            if shape is None:
+                shape = vols[0].shape[::-1]
+                need = len(cases) * int(np.prod(shape)) * (c + 1) * 4
+                free = torch.cuda.mem_get_info(dev)[0]
+                if need > free:
+                    raise MemoryError('the dataset stays resident on the device: %d cases of %s x %d channels + labels need %.1f GB, '
+                                      '%.1f GB are free on %s' % (len(cases), shape, c, need / 1e9, free / 1e9, dev))
+                occ = torch.zeros((len(cases), sum(shape)), dtype=torch.int32, device=dev)
+            elif vols[0].shape[::-1] != shape:
+                raise ValueError('%s: shape %s differs from the %s of %s' % (path, vols[0].shape[::-1], shape, cases[0]))
+            x_, y_ = _upload_case(vols, dev)
+            ops.prepro_occupancy(x_, occ[k])
+            xs.append(x_)
+            ys.append(y_)
+    occ_h = occ.cpu().numpy()                                               # the one read-back of the search
+    for k, path in enumerate(cases):
+        if not occ_h[k].any():
+            raise ValueError('%s: the case has no non-zero voxel' % path)
+    total = occ_h.any(axis=0)
+    lo, hi, off = [], [], 0
+    for n in shape:
+        idx = np.nonzero(total[off:off + n])[0]
+        lo.append(int(idx[0]))
+        hi.append(int(idx[-1]))
+        off += n
+    if min(h - l for l, h in zip(lo, hi)) < 1:
+        raise ValueError('the bounding box [%s, %s) of %s has an axis of zero extent (the last occupied plane is dropped)'
+                         % (lo, hi, cases[0] if len(cases) == 1 else '%d cases' % len(cases)))
+    x = [v[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2], :] for v in xs]
+    y = [v[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2], :] for v in ys]
+    size = {'h': hi[0] - lo[0], 'w': hi[1] - lo[1], 'd': hi[2] - lo[2], 'c': c}
+    print('Maximal crop size: [{}, {}, {}, {}]'.format(size['h'], size['w'], size['d'], size['c']))
+    return x, y, size
+
+
+def compute_norm(x_train, in_ch):
+    """-> (mean, std), numpy float64 of shape (1,1,1,in_ch)   [preprocess.py:68-85]
+    Two passes of ops.prepro_sums over the device views; the divisions and the square root run in float64 on the host."""
+    if not x_train:
+        raise ValueError('compute_norm needs at least one training case')
+    dev = x_train[0].device
+    acc = torch.zeros(2 * in_ch, dtype=torch.float64, device=dev)
+    for x in x_train:
+        ops.prepro_sums(x, acc)
+    acc = acc.cpu().numpy()
+    n = acc[in_ch:].reshape(1, 1, 1, in_ch)
+    mean = acc[:in_ch].reshape(1, 1, 1, in_ch) / n
+    mean_d = torch.from_numpy(np.ascontiguousarray(mean.reshape(-1))).to(dev)
+    acc2 = torch.zeros(in_ch, dtype=torch.float64, device=dev)
+    for x in x_train:
+        ops.prepro_sums(x, acc2, mean=mean_d)
+    std = np.sqrt(acc2.cpu().numpy().reshape(1, 1, 1, in_ch) / n)
+    return mean, std
+
+
+def _stats_on(dev, v):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))).to(dev)
+
+
+def normalize_example(x, y, mean, std):
+    """device views x (h,w,d,c), y (h,w,d,1) -> dense device (float32((x - mean) / std) evaluated in float64, y with labels
+    >= 4 -> 3)   [preprocess.py:36,124]; mean / std: anything of c values (numpy, or float64 tensors already on the device)"""
+    m = mean if isinstance(mean, torch.Tensor) else _stats_on(x.device, mean)
+    s = std if isinstance(std, torch.Tensor) else _stats_on(x.device, std)
+    return ops.prepro_crop_norm(x, y, m, s)
+
+
+def make_dirs(out_loc):
+    """the folders of PreproArgParser.parse_args (args.py:72-81): out_loc is replaced if it exists -> (train_loc, val_loc)"""
+    if os.path.isdir(out_loc):
+        shutil.rmtree(out_loc)
+    train_loc, val_loc = os.path.join(out_loc, 'train'), os.path.join(out_loc, 'val')
+    os.mkdir(out_loc)
+    os.mkdir(train_loc)
+    os.mkdir(val_loc)
+    return train_loc, val_loc
+
+
+def _write(folder, x, y, mean_d, std_d):
+    for i, (xv, yv) in enumerate(zip(x, y), 1):
+        xn, yn = normalize_example(xv, yv, mean_d, std_d)
+        np.savez(os.path.join(folder, '{}.npz'.format(i)), x=xn.cpu().numpy(), y=yn.cpu().numpy())
+
+
+def _refuse_inputs_inside(out_loc, in_locs):
+    out = os.path.realpath(out_loc)
+    for loc in in_locs:
+        real = os.path.realpath(loc)
+        if real == out or real.startswith(out + os.sep):
+            raise ValueError('out_loc %s is replaced as a whole and contains the input folder %s' % (out_loc, loc))
+
+
+def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=None, workers=8):
+    """the reference's main (preprocess.py:99-131): out_loc/train/{i}.npz, out_loc/val/{i}.npz (arrays x (h,w,d,c) and y (h,w,d,1),
+    float32) and out_loc/prepro.npy -> {'size', 'mean', 'std', 'n_train', 'n_val'}
+    An existing out_loc is REMOVED with everything in it and created anew before any scan is read, as the reference's argument
+    parser does (args.py:73-74, `make_dirs`); an out_loc that is or contains one of `in_locs` raises ValueError and removes
+    nothing."""
+    _refuse_inputs_inside(out_loc, in_locs)
+    train_loc, val_loc = make_dirs(out_loc)
+    x_train, y_train, size = create_dataset(in_locs, modalities, truth, device=device, workers=workers)
+    x_val, y_val = [], []
+    if create_val:
+        split = len(x_train) // 11
+        x_val, y_val = x_train[:split], y_train[:split]
+        x_train, y_train = x_train[split:], y_train[split:]
+        print('{} validation examples.'.format(len(x_val)))
+    print('{} training examples.'.format(len(x_train)))
+    mean, std = compute_norm(x_train, len(modalities))
+    np.save(os.path.join(out_loc, 'prepro.npy'), {'size': size, 'norm': {'mean': mean, 'std': std}})
+    dev = x_train[0].device
+    mean_d, std_d = _stats_on(dev, mean), _stats_on(dev, std)
+    _write(train_loc, x_train, y_train, mean_d, std_d)
+    if create_val:
+        _write(val_loc, x_val, y_val, mean_d, std_d)
+    return {'size': size, 'mean': mean, 'std': std, 'n_train': len(x_train), 'n_val': len(x_val)}
+
+
+def load_prepro(path):
+    """prepro.npy -> ((h,w,d,c), mean (c,), std (c,)): what data.prepare_dataset(prepro_size=...) and
+    infer.TestTimeAugmentor(mean, std, ...) take (args.py:166-167, test.py:107)"""
+    p = np.load(path, allow_pickle=True).item()
+    size = tuple(int(p['size'][k]) for k in ('h', 'w', 'd', 'c'))
+    mean = np.asarray(p['norm']['mean'], dtype=np.float64).reshape(-1)
+    std = np.asarray(p['norm']['std'], dtype=np.float64).reshape(-1)
+    if mean.shape != (size[3],) or std.shape != (size[3],):
+        raise ValueError('%s: mean / std of %d / %d values for %d channels' % (path, mean.size, std.size, size[3]))
+    return size, mean, std
+
+
+def arg_parser():
+    """the flags of the reference's PreproArgParser (args.py:51-61)"""
+    p = argparse.ArgumentParser(prog='python -m bts_amd.preprocess', description=__doc__.split('\n')[0])
+    p.add_argument('--in_locs', type=str, required=True, help='Comma-separated list of paths to all data folders.')
+    p.add_argument('--modalities', type=str, required=True, help='Comma-separated list of all input modalities to use.')
+    p.add_argument('--truth', type=str, required=True, help='Truth label pattern to use.')
+    p.add_argument('--create_val', action='store_true', default=False, help='Whether to create validation set.')
+    p.add_argument('--out_loc', type=str, default='./data', help='Location to write preprocessed data.')
+    return p
+
+
+def parse_args(argv=None):
+    args = arg_parser().parse_args(argv)
+    args.in_locs = args.in_locs.split(',')
+    args.modalities = args.modalities.split(',')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    print('Preprocess args: {}'.format(args))
+    r = preprocess(args.in_locs, args.modalities, args.truth, args.out_loc, create_val=args.create_val)
+    print('mean {} std {}'.format(r['mean'].reshape(-1), r['std'].reshape(-1)))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

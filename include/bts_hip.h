@@ -264,6 +264,25 @@ int bts_augment_crop(const float* x, const float* y, const float* var, float* xo
                      int T0, int T1, int T2, int o0, int o1, int o2, int flip_mask, const float* shift, const float* scale,
                      int out_ch, bts_stream_t stream);
 
+/* ===== dataset preprocessing on the device (preprocess.py:17-131: create_dataset, compute_norm, main) =====
+ * Dense fp32 (S0,S1,S2,C) volumes, C innermost, 1 <= C <= 16.  A crop window (T0,T1,T2,C) of such a volume is addressed in place:
+ * `xwin` points at its origin, st0 / st1 are the element strides of the two outer axes, the voxel stride is C. */
+/* bounding-box search of preprocess.py:39-49 (np.any per plane): occ (S0+S1+S2 ints, axis 0 first) gets a 1 for every plane index
+ * of every axis that holds an x != 0 (NaN counts, -0.0 does not).  Flags are only ever set: zero occ once and run every case into
+ * it for the box of a whole dataset. */
+int bts_prepro_occupancy(const float* x, int* occ, int S0, int S1, int S2, int C, bts_stream_t stream);
+/* the accumulations of compute_norm (preprocess.py:75-77, 81-82) over one window, in fp64, fixed order, no float atomics.
+ * mean_or_null == NULL: acc[0:C] += sum x, acc[C:2C] += #(x > 0) (an exact double).
+ * mean_or_null = C device doubles: acc[0:C] += sum (double(x) - mean[c])^2.  acc: device doubles, accumulated in call order. */
+long bts_prepro_workspace(int C);
+int bts_prepro_sums(const float* xwin, long st0, long st1, int T0, int T1, int T2, int C, const double* mean_or_null, double* acc,
+                    void* workspace, long workspace_bytes, bts_stream_t stream);
+/* the stored example of preprocess.py:122-130: xo (T0,T1,T2,C) = float((double(x) - mean[c]) / std[c]) (IEEE fp64 subtract and
+ * divide, one rounding to fp32), yo (T0,T1,T2) = y >= 4 ? 3 : y (preprocess.py:36).  ywin: the same window of the (S0,S1,S2) label
+ * volume with element strides yst0 / yst1, voxel stride 1; ywin and yo may both be NULL.  mean, stdv: C device doubles. */
+int bts_prepro_crop_norm(const float* xwin, const float* ywin, long st0, long st1, long yst0, long yst1, int T0, int T1, int T2,
+                         int C, const double* mean, const double* stdv, float* xo, float* yo, bts_stream_t stream);
+
 /* library identification */
 const char* bts_version(void);
 
