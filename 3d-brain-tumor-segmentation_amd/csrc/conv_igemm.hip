@@ -31,7 +31,7 @@
 // and the fused entry points: shortcut pair (FUSE2), GroupNorm statistics in the epilogue, data-gradient pair (second input).
 #include <stdlib.h>
 #include "common.h"
-#include "bts_internal.h"
+#include "conv_plan.h"
 
 #define MAXSLOT 8
 
@@ -71,8 +71,7 @@ struct IgemmParams {
   // split-K: blockIdx.z handles k-groups [z*kg_per, ...); raw partials go to part[z][voxel][Npad] (no bias/act)
   int ksplit, kg_per;
   float* part;
-  long ws_bytes, ws_need;  // host-side planning only
-  int plan_only;
+  long reserved_[3];  // (unused: keeps the kernel-argument layout, and with it the compiled kernels, as they were)
   // fused GroupNorm statistics of the output (slab semantics: group = z-slab of D/G planes, whole tiles per group):
   // every workgroup writes (sum, sum of squares) of its tile to gnp[((n*G+g)*gn_B + b)*2], b = tile index inside the group
   double* gnp;
@@ -84,12 +83,6 @@ struct IgemmParams {
   int cls_tl[8][8];
   int cls_tw[8][8];
 };
-
-#define IG_FLAG_BIAS 1
-#define IG_FLAG_ACCUM 2
-#define IG_FLAG_SIGMOID 4
-#define IG_FLAG_VECIN 8
-#define IG_FLAG_VECOUT 16
 
 // One stage of the implicit GEMM: nkg k-groups (8 input channels each) x NT taps, fully unrolled over the taps.
 template <int NT, int MS, int NS, bool F2 = false, bool FIXG = false>
@@ -684,7 +677,7 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const PackDesc* __restr
   }
 }
 
-static inline int npad32(int n) { return (n + 31) / 32 * 32; }
+static inline int npad32(int n) { return conv_npad32(n); }
 
 extern "C" long bts_conv_packed_floats(int kind, int role, int Cin, int Cout) {
   const int ntaps = (kind == BTS_CONV_K1) ? 1 : 27;
@@ -811,11 +804,6 @@ void bts_img_mark_used_(const float* base, unsigned bit) {
   auto it = g_img.find(base);
   if (it == g_img.end() || it->second.kind != BTS_CONV_K3S1) return;
   if (!(it->second.used & bit)) { it->second.used |= bit; ++g_img_gen; }
-}
-int bts_img_note_use_(const float* base, unsigned bit, hipStream_t stream) {      // both, for launchers that have already accepted
-  const int r = bts_img_ensure_(base, bit, stream);
-  if (r == BTS_OK) bts_img_mark_used_(base, bit);
-  return r;
 }
 
 extern "C" int bts_conv_pack(int kind, int role, const float* w, float* wp, int Cin_ref, int Cout, int Cin_slab,
@@ -1045,64 +1033,65 @@ __global__ __launch_bounds__(256, 2) void upm_kernel(const UpmParams p) {
   }
 }
 
-// Shape-only part of the decision (shared by the workspace query): tile geometry and split-K factor.
-// returns 0 when the merged-class kernel does not fit the shape.
-static int plan_upm(UpmParams& p, int N, int Di, int Hi, int Wi, int Cin, int Cout, long* need) {
-  *need = 0;
-  if ((Cin & 7) || (Cout & 3) || Wi < 8 || Hi < 4 || Di < 2) return 0;
-  p.N = N; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout;
-  p.Npad = npad32(Cout); p.KG = Cin / 8;
+// The merged-class kernel takes the all-classes transposed form on 16-byte rows when its halo tile fits the slots and the grid fills the
+// chip, or the contraction is long enough to split (deterministic two-stage reduction) and the workspace holds the partials.
+static bool upm_accept(const ConvCall& c, ConvChoice& ch) {
+  UpmPlan& u = ch.u;
+  if ((c.ldx & 3) || (c.ldy & 3) || !c.x16 || !c.y16) return false;
+  if ((c.Cin & 7) || (c.Cout & 3) || c.Wi < 8 || c.Hi < 4 || c.Di < 2) return false;
+  const int Npad = npad32(c.Cout), KG = c.Cin / 8;
   int TX = 32;
-  while (TX > 8 && TX / 2 >= Wi) TX /= 2;
+  while (TX > 8 && TX / 2 >= c.Wi) TX /= 2;
   int TY = (TX == 32) ? 2 : 4;
   int TZ = 128 / (TX * TY);
-  p.lgTX = ilog2(TX); p.lgTY = ilog2(TY); p.TZ = TZ;
-  p.ntx = (Wi + TX - 1) / TX; p.nty = (Hi + TY - 1) / TY; p.ntz = (Di + TZ - 1) / TZ;
-  p.IX = TX + 1; p.IY = TY + 1; p.IZ = TZ + 1;
-  if (p.IZ * p.IY * p.IX * 2 > 256 * UPM_NSLOT) return 0;
-  const long wgs = (long)N * p.ntz * p.nty * p.ntx * (p.Npad / 32);
-  const long min_wgs = getenv("BTS_IGEMM_UPM_MIN") ? atol(getenv("BTS_IGEMM_UPM_MIN")) : 256;  // (tests force 1)
-  p.ksplit = 1; p.kg_per = p.KG;
+  u.lgTX = ilog2(TX); u.lgTY = ilog2(TY); u.TZ = TZ;
+  u.ntx = (c.Wi + TX - 1) / TX; u.nty = (c.Hi + TY - 1) / TY; u.ntz = (c.Di + TZ - 1) / TZ;
+  u.IX = TX + 1; u.IY = TY + 1; u.IZ = TZ + 1;
+  if (u.IZ * u.IY * u.IX * 2 > 256 * UPM_NSLOT) return false;
+  const long wgs = (long)c.N * u.ntz * u.nty * u.ntx * (Npad / 32);
+  const long min_wgs = conv_env_long("BTS_IGEMM_UPM_MIN", 256);  // (tests force 1)
+  u.ksplit = 1; u.kg_per = KG; u.need = 0;
   if (wgs < min_wgs) {
-    // too few workgroups to fill the chip: split the contraction (deterministic two-stage reduction) when it is long
-    if (p.KG < 8) return 0;
+    // too few workgroups to fill the chip: split the contraction when it is long
+    if (KG < 8) return false;
     int ks = (int)((512 + wgs - 1) / wgs);
-    if (ks > p.KG / 4) ks = p.KG / 4;
+    if (ks > KG / 4) ks = KG / 4;
     if (ks > 16) ks = 16;
-    if (ks < 2) return 0;
-    p.kg_per = (p.KG + ks - 1) / ks;
-    p.ksplit = (p.KG + p.kg_per - 1) / p.kg_per;
-    if (p.ksplit < 2 || wgs * p.ksplit < min_wgs / 2) return 0;
-    *need = (long)p.ksplit * N * 8 * Di * Hi * Wi * p.Npad * 4;
+    if (ks < 2) return false;
+    u.kg_per = (KG + ks - 1) / ks;
+    u.ksplit = (KG + u.kg_per - 1) / u.kg_per;
+    if (u.ksplit < 2 || wgs * u.ksplit < min_wgs / 2) return false;
+    u.need = (long)u.ksplit * c.N * 8 * c.Di * c.Hi * c.Wi * Npad * 4;
   }
-  return 1;
+  ch.sym = 20;
+  ch.ws = u.need;
+  return c.ws_bytes >= u.need;
 }
 
-// returns BTS_OK when the merged-class kernel took the launch, 1 when the shape is left to the per-class path
-static int launch_upm(const float* x, const float* wp, const float* bias, float* y, int N, int Di, int Hi, int Wi, int Cin,
-                      int ldx, int Cout, int ldy, int flags, void* ws, long ws_bytes, hipStream_t stream) {
-  if ((ldx & 3) || (ldy & 3) || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return 1;
+static int launch_upm(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
+  const UpmPlan& u = ch.u;
   UpmParams p;
-  long need = 0;
-  if (!plan_upm(p, N, Di, Hi, Wi, Cin, Cout, &need)) return 1;
-  if (need > 0 && (ws == nullptr || ws_bytes < need)) return 1;
-  p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.ldx = ldx; p.ldy = ldy; p.flags = flags;
-  p.part = reinterpret_cast<float*>(ws);
-  const long tiles = (long)N * p.ntz * p.nty * p.ntx;
+  p.N = c.N; p.Di = c.Di; p.Hi = c.Hi; p.Wi = c.Wi; p.Cin = c.Cin; p.Cout = c.Cout;
+  p.Npad = npad32(c.Cout); p.KG = c.Cin / 8;
+  p.lgTX = u.lgTX; p.lgTY = u.lgTY; p.TZ = u.TZ; p.ntx = u.ntx; p.nty = u.nty; p.ntz = u.ntz; p.IX = u.IX; p.IY = u.IY; p.IZ = u.IZ;
+  p.ksplit = u.ksplit; p.kg_per = u.kg_per;
+  p.x = q.x; p.wp = q.wp; p.bias = q.bias; p.y = q.y; p.ldx = c.ldx; p.ldy = c.ldy; p.flags = c.flags;
+  p.part = reinterpret_cast<float*>(q.ws);
+  const long tiles = (long)c.N * p.ntz * p.nty * p.ntx;
   const int ny = p.Npad / 32;
   const int tileVox = p.IZ * p.IY * p.IX;
   const size_t shmem = (size_t)2 * tileVox * 12 * sizeof(float);
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(20, 2.0 * 27.0 * Cin * Cout * (double)N * Di * Hi * Wi, stream);
+  if (prof) bts_prof_begin(20, 2.0 * 27.0 * c.Cin * c.Cout * (double)c.N * c.Di * c.Hi * c.Wi, stream);
   (void)hipGetLastError(); hipLaunchKernelGGL(upm_kernel, dim3((unsigned)tiles, ny, p.ksplit), dim3(256), shmem, stream, p);
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
   if (p.ksplit > 1) {
-    const long nvox = (long)N * 8 * Di * Hi * Wi;
-    long blocks = (nvox * Cout + 255) / 256;
+    const long nvox = (long)c.N * 8 * c.Di * c.Hi * c.Wi;
+    long blocks = (nvox * c.Cout + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    (void)hipGetLastError(); hipLaunchKernelGGL(igemm_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, p.part, bias, y, nvox, Cout, p.Npad, ldy,
-                       p.ksplit, flags);
+    (void)hipGetLastError(); hipLaunchKernelGGL(igemm_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, p.part, q.bias, q.y, nvox, c.Cout, p.Npad,
+                       c.ldy, p.ksplit, p.flags);
     BTS_LAUNCH_CHECK();
   }
   return BTS_OK;
@@ -1224,22 +1213,25 @@ __global__ __launch_bounds__(256, 4) void k1s_kernel(const K1sParams p) {
   }
 }
 
-// returns BTS_OK when taken, 1 when the shape is left to the staged igemm path
-static int launch_k1s(const float* x, const float* wp, const float* bias, float* y, long nvox, int Cin, int ldx, int Cout, int ldy,
-                      int flags, hipStream_t stream) {
-  if ((Cin & 7) || (ldx & 3) || (((uintptr_t)x) & 15)) return 1;  // whole k-groups, 16-byte row quads
-  const long min_vox = getenv("BTS_IGEMM_K1S_MIN") ? atol(getenv("BTS_IGEMM_K1S_MIN")) : 256 * 256;  // (tests force 1)
-  if (nvox < min_vox) return 1;  // small grids (deep levels): too few workgroups, keep the split-K capable path
+// The streaming kernel takes 1x1x1 calls on whole k-groups and 16-byte row quads; small grids (deep levels: too few workgroups) stay
+// with the split-K capable staged kernel.
+static bool k1s_accept(const ConvCall& c, ConvChoice& ch) {
+  if ((c.Cin & 7) || (c.ldx & 3) || !c.x16) return false;
+  const long nvox = (long)c.N * c.Di * c.Hi * c.Wi;
+  if (nvox < conv_env_long("BTS_IGEMM_K1S_MIN", 256 * 256)) return false;  // (tests force 1)
+  ch.sym = 21;
+  return (nvox + 255) / 256 <= 0x7fffffffL;
+}
+static int launch_k1s(const ConvCall& c, const ConvChoice&, const ConvPtrs& q, hipStream_t stream) {
   K1sParams p;
-  p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.nvox = nvox;
-  p.Cin = Cin; p.ldx = ldx; p.Cout = Cout; p.ldy = ldy; p.Npad = npad32(Cout); p.KG = Cin / 8;
-  p.flags = flags & (IG_FLAG_BIAS | IG_FLAG_ACCUM | IG_FLAG_SIGMOID);
-  if ((ldy % 4 == 0) && (((uintptr_t)y) % 16 == 0)) p.flags |= IG_FLAG_VECOUT;
-  const long gx = (nvox + 255) / 256;
-  if (gx > 0x7fffffffL) return 1;
+  p.x = q.x; p.wp = q.wp; p.bias = q.bias; p.y = q.y; p.nvox = (long)c.N * c.Di * c.Hi * c.Wi;
+  p.Cin = c.Cin; p.ldx = c.ldx; p.Cout = c.Cout; p.ldy = c.ldy; p.Npad = npad32(c.Cout); p.KG = c.Cin / 8;
+  p.flags = c.flags;
+  if ((c.ldy % 4 == 0) && c.y16) p.flags |= IG_FLAG_VECOUT;
+  const long gx = (p.nvox + 255) / 256;
   const bool prof = bts_prof_on();
   const int ns = (p.Npad >= 64) ? 2 : 1;
-  if (prof) bts_prof_begin(21, 2.0 * Cin * (double)Cout * (double)nvox, stream);
+  if (prof) bts_prof_begin(21, 2.0 * c.Cin * (double)c.Cout * (double)p.nvox, stream);
   (void)hipGetLastError();
   if (ns == 2) hipLaunchKernelGGL(k1s_kernel<2>, dim3((unsigned)gx, (p.Npad + 63) / 64), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(k1s_kernel<1>, dim3((unsigned)gx, 1), dim3(256), 0, stream, p);
@@ -1358,23 +1350,25 @@ __global__ __launch_bounds__(256, 4) void dsc_kernel(const DscParams p) {
   }
 }
 
-// returns BTS_OK when taken, 1 when the shape is left to the MFMA path
-static int launch_dsc(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin, int ldx,
-                      int Cout, int ldy, int flags, hipStream_t stream) {
-  if (Cout > 4 || (Cin & 7) || (ldx & 3) || (((uintptr_t)x) & 15)) return 1;
-  const long tiles = (long)N * ((D + 1) / 2) * ((H + 3) / 4) * ((W + 31) / 32);
-  const long min_tiles = getenv("BTS_IGEMM_DSC_MIN") ? atol(getenv("BTS_IGEMM_DSC_MIN")) : 1024;  // (tests force 1)
-  if (tiles < min_tiles || tiles > 0x7fffffffL) return 1;
+// The direct kernel takes 3x3x3 calls into <= 4 channels on whole k-groups and 16-byte rows when the grid is worth it.
+static bool dsc_accept(const ConvCall& c, ConvChoice& ch) {
+  if (c.Cout > 4 || (c.Cin & 7) || (c.ldx & 3) || !c.x16) return false;
+  const long tiles = (long)c.N * ((c.Di + 1) / 2) * ((c.Hi + 3) / 4) * ((c.Wi + 31) / 32);
+  ch.sym = 22;
+  return tiles >= conv_env_long("BTS_IGEMM_DSC_MIN", 1024) && tiles <= 0x7fffffffL;  // (tests force 1)
+}
+static int launch_dsc(const ConvCall& c, const ConvChoice&, const ConvPtrs& q, hipStream_t stream) {
   DscParams p;
-  p.x = x; p.wp = wp; p.bias = bias; p.y = y;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.Cout = Cout; p.ldy = ldy;
-  p.Npad = npad32(Cout); p.KG = Cin / 8;
-  p.ntx = (W + 31) / 32; p.nty = (H + 3) / 4; p.ntz = (D + 1) / 2;
-  p.flags = flags & (IG_FLAG_BIAS | IG_FLAG_ACCUM | IG_FLAG_SIGMOID);
+  p.x = q.x; p.wp = q.wp; p.bias = q.bias; p.y = q.y;
+  p.N = c.N; p.D = c.Di; p.H = c.Hi; p.W = c.Wi; p.Cin = c.Cin; p.ldx = c.ldx; p.Cout = c.Cout; p.ldy = c.ldy;
+  p.Npad = npad32(c.Cout); p.KG = c.Cin / 8;
+  p.ntx = (c.Wi + 31) / 32; p.nty = (c.Hi + 3) / 4; p.ntz = (c.Di + 1) / 2;
+  p.flags = c.flags;
+  const long tiles = (long)c.N * p.ntz * p.nty * p.ntx;
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(22, 2.0 * 27.0 * Cin * (double)Cout * (double)N * D * H * W, stream);
+  if (prof) bts_prof_begin(22, 2.0 * 27.0 * c.Cin * (double)c.Cout * (double)c.N * c.Di * c.Hi * c.Wi, stream);
   (void)hipGetLastError();
-  if (Cout <= 2) hipLaunchKernelGGL(dsc_kernel<2>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
+  if (c.Cout <= 2) hipLaunchKernelGGL(dsc_kernel<2>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(dsc_kernel<4>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
@@ -1513,112 +1507,44 @@ __global__ __launch_bounds__(256, 2) void c2_kernel(const C2Params p) {
   }
 }
 
-// returns BTS_OK when taken, 1 when the shape is left to the tiled kernel
-static int launch_c2(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin, int ldx,
-                     int Cout, int ldy, int flags, const float* wp2, const float* bias2, float* y2, int ldy2, double* gnp, int gnG,
-                     long* gn_B, hipStream_t stream) {
-  if (Cin != 2 || Cout > 32 || Cout % 4 != 0 || ldy % 4 != 0 || (((uintptr_t)y) & 15)) return 1;
-  if (flags & (IG_FLAG_ACCUM | IG_FLAG_SIGMOID)) return 1;
-  if (y2 != nullptr && (ldy2 % 4 != 0 || (((uintptr_t)y2) & 15))) return 1;
+// The two-channel kernel takes plain 3x3x3 calls (bias at most) into <= 32 channels on 16-byte output rows, with or without the fused
+// shortcut output, when the grid is worth it; it writes the GroupNorm partials where the slab groups hold whole 4-plane tiles.
+static bool c2_accept(const ConvCall& c, ConvChoice& ch) {
+  if (c.Cin != 2 || c.Cout > 32 || c.Cout % 4 != 0 || c.ldy % 4 != 0 || !c.y16) return false;
+  if (c.flags & (IG_FLAG_ACCUM | IG_FLAG_SIGMOID)) return false;
+  if (c.second == CONV_Y2 && (c.ld2 % 4 != 0 || !c.p2_16)) return false;
+  const int nty = (c.Hi + 3) / 4, ntx = (c.Wi + 31) / 32;
+  const long tiles = (long)c.N * ((c.Di + 3) / 4) * nty * ntx;
+  if (tiles < conv_env_long("BTS_IGEMM_C2_MIN", 512) || tiles > 0x7fffffffL) return false;  // (tests force 1)
+  ch.sym = 25;
+  ch.gn_B = (long)conv_gn_zt(c, 4) * nty * ntx;
+  return true;
+}
+static int launch_c2(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
+  const bool f2 = c.second == CONV_Y2;
   C2Params p;
-  p.x = x; p.wp = wp; p.bias = (flags & IG_FLAG_BIAS) ? bias : nullptr; p.y = y;
-  p.wp2 = wp2; p.bias2 = bias2; p.y2 = y2;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = ldx; p.Cout = Cout; p.ldy = ldy; p.ldy2 = ldy2; p.Npad = npad32(Cout);
-  p.ntz = (D + 3) / 4; p.nty = (H + 3) / 4; p.ntx = (W + 31) / 32;
-  const long tiles = (long)N * p.ntz * p.nty * p.ntx;
-  const long min_tiles = getenv("BTS_IGEMM_C2_MIN") ? atol(getenv("BTS_IGEMM_C2_MIN")) : 512;  // (tests force 1)
-  if (tiles < min_tiles || tiles > 0x7fffffffL) return 1;
-  p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1;
-  if (gnp != nullptr && gnG > 0 && D % gnG == 0 && (D / gnG) % 4 == 0 && getenv("BTS_IGEMM_NOGNFUSE") == nullptr) {
-    p.gnp = gnp; p.gn_G = gnG; p.gn_zt = (D / gnG) / 4;
-  }
+  p.x = q.x; p.wp = q.wp; p.bias = (c.flags & IG_FLAG_BIAS) ? q.bias : nullptr; p.y = q.y;
+  p.wp2 = f2 ? q.wp2 : nullptr; p.bias2 = f2 ? q.bias2 : nullptr; p.y2 = f2 ? q.y2 : nullptr;
+  p.N = c.N; p.D = c.Di; p.H = c.Hi; p.W = c.Wi; p.ldx = c.ldx; p.Cout = c.Cout; p.ldy = c.ldy; p.ldy2 = f2 ? c.ld2 : 0; p.Npad = npad32(c.Cout);
+  p.ntz = (c.Di + 3) / 4; p.nty = (c.Hi + 3) / 4; p.ntx = (c.Wi + 31) / 32;
+  const long tiles = (long)c.N * p.ntz * p.nty * p.ntx;
+  p.gnp = ch.gn_B ? q.gnp : nullptr; p.gn_G = ch.gn_B ? c.G : 0; p.gn_zt = ch.gn_B ? (c.Di / c.G) / 4 : 1;
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(25, 2.0 * (27.0 + (y2 ? 1.0 : 0.0)) * Cin * (double)Cout * (double)N * D * H * W, stream);
+  if (prof) bts_prof_begin(25, 2.0 * (27.0 + (f2 ? 1.0 : 0.0)) * c.Cin * (double)c.Cout * (double)c.N * c.Di * c.Hi * c.Wi, stream);
   (void)hipGetLastError();
-  if (y2 != nullptr) hipLaunchKernelGGL(c2_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
+  if (f2) hipLaunchKernelGGL(c2_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(c2_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
-  if (gn_B && p.gnp != nullptr) *gn_B = (long)p.gn_zt * p.nty * p.ntx;
   return BTS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // Launch logic
 // ---------------------------------------------------------------------------------------------
-enum Geo { GEO_K1 = 0, GEO_S1 = 1, GEO_DOWN = 2, GEO_UP = 3 };
-
-template <int MS, int NS, int WM, int WN, int KGS, bool FUSE2 = false, bool FIXG = false, bool T27 = false>
-static int launch_cfg(IgemmParams& p, hipStream_t stream) {
-  constexpr int S = KGS * 8 + 4;
-  const int tileVox = p.IZ * p.IY * p.IX;
-  if (tileVox * KGS * 2 > 256 * MAXSLOT) return BTS_ERR_SHAPE;
-  // a single stage (all channels fit one staging pass, e.g. the 1x1x1 convs with Cin <= 32) needs no second buffer:
-  // half the LDS -> twice the resident workgroups to hide the (then un-overlapped) staging latency
-  const int nstages_all = (p.KG + KGS - 1) / KGS;
-  const size_t shmem = (size_t)((nstages_all > 1 && !IG_TRI(MS, NS, KGS, FUSE2, FIXG)) ? 2 : 1) * tileVox * S * sizeof(float);
-  auto kern = igemm_kernel<MS, NS, WM, WN, KGS, FUSE2, FIXG, T27>;
-  static bool attr_done = false;
-  if (!attr_done && !p.plan_only) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
-  const int NT = 32 * NS * WN;
-  dim3 grid(p.N * p.ntz * p.nty * p.ntx, (p.Npad + NT - 1) / NT, p.ncls > 1 ? p.ncls : 1);
-  // split-K when the tile grid cannot fill the chip and the contraction is long (tiny spatial grids, wide channels)
-  p.ksplit = 1;
-  p.kg_per = p.KG;
-  p.ws_need = 0;
-  const long wgs = (long)grid.x * grid.y;
-  // two workgroups fit a CU: below 512 tiles the chip is not full and a single wave per SIMD cannot keep the matrix
-  // pipe busy, so the contraction is split (measured: 16^3 256->256 0.157 -> 0.137 ms, 16^3 768->256 0.46 -> 0.38 ms);
-  // the 1x1x1 staging variant has too little work per k-group for that and keeps the old, lower threshold
-  const long sk_below = (KGS == 1) ? 512 : 192, sk_target = (KGS == 1) ? 512 : 384;
-  if (!FUSE2 && p.ncls <= 1 && wgs < sk_below && p.KG >= 4 * KGS) {
-    int ks = (int)((sk_target + wgs - 1) / wgs);
-    const int maxks = p.KG / (2 * KGS);
-    if (ks > maxks) ks = maxks;
-    if (ks > 64) ks = 64;
-    if (ks > 1) {
-      int per = (p.KG + ks - 1) / ks;
-      per = (per + KGS - 1) / KGS * KGS;
-      ks = (p.KG + per - 1) / per;
-      const long need = (long)ks * p.N * p.Do * p.Ho * p.Wo * p.Npad * 4;
-      if (ks > 1 && (p.plan_only || (p.part != nullptr && p.ws_bytes >= need))) {
-        p.ksplit = ks;
-        p.kg_per = per;
-        p.ws_need = need;
-        grid.z = ks;
-      }
-    }
-  }
-  if (p.ksplit > 1) p.gnp = nullptr;  // split-K tiles are finished by the reduce kernel: no fused statistics
-  p.gn_gridy = (int)grid.y;
-  if (p.plan_only) return BTS_OK;
-  const bool prof = bts_prof_on();
-  if (prof) {
-    constexpr int cfgid = (MS == 2 && NS == 1) ? 0 : (MS == 2 && NS == 2) ? 1 : (MS == 1 && NS == 2) ? 2 : (WN == 2) ? 3 : 4;
-    const double taps = (p.ncls > 1) ? 27.0 : (double)p.ntaps;
-    bts_prof_begin(cfgid + (KGS == 4 ? 8 : 0), 2.0 * taps * p.Cin * p.Cout * (double)p.N * p.Do * p.Ho * p.Wo, stream);
-  }
-  (void)hipGetLastError(); hipLaunchKernelGGL(kern, grid, dim3(256), shmem, stream, p);
-  if (prof) bts_prof_end(stream);
-  BTS_LAUNCH_CHECK();
-  if (p.ksplit > 1) {
-    const long nvox = (long)p.N * p.Do * p.Ho * p.Wo;
-    long blocks = (nvox * p.Cout + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    (void)hipGetLastError(); hipLaunchKernelGGL(igemm_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, p.part, p.bias, p.y, nvox, p.Cout,
-                       p.Npad, p.ldy, p.ksplit, p.flags);
-    BTS_LAUNCH_CHECK();
-  }
-  return BTS_OK;
-}
-
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-// cfg ids: 0:(2,1,4,1) M256 N32 | 1:(2,2,4,1) M256 N64 | 2:(1,2,2,2) M64 N128 | 3:(1,1,2,2) M64 N64 | 4:(1,1,4,1) M128 N32
+// cfg ids: IgemmPlan (conv_plan.h)
 static int choose_cfg(int geo, int N, int Do, int Ho, int Wo, int Npad, int* Mout) {
   const long vox = (long)Do * Ho * Wo;
   int M, cfg;
@@ -1641,132 +1567,21 @@ static int choose_cfg(int geo, int N, int Do, int Ho, int Wo, int Npad, int* Mou
   return cfg;
 }
 
-// geometry + config selection for one gather-conv launch
-static int launch_igemm(int geo, const float* x, const float* wp, const float* bias, float* y, int N, int Di, int Hi,
-                        int Wi, int Cin, int ldx, int Do, int Ho, int Wo, int Cout, int ldy, int ODa, int OHa, int OWa,
-                        int pz, int py, int px, int flags, hipStream_t stream, void* ws = nullptr, long ws_bytes = 0,
-                        long* need_out = nullptr, const float* wp2 = nullptr, const float* bias2 = nullptr,
-                        float* y2 = nullptr, int ldy2 = 0, double* gnp = nullptr, int gnG = 0, long* gn_B = nullptr,
-                        const float* x2 = nullptr, int ldx2 = 0) {
-  if (gn_B) *gn_B = 0;  // stays 0 unless the tiled kernel took the launch and emitted the GroupNorm partials
-  if (geo == GEO_S1 && wp2 == nullptr && need_out == nullptr && Cout <= 4) {
-    { const int e = bts_img_ensure_(wp, 1u, stream); if (e != BTS_OK) return e; }      // (a declined launch costs at most one early pack)
-    const int r = launch_dsc(x, wp, bias, y, N, Di, Hi, Wi, Cin, ldx, Cout, ldy, flags, stream);
-    if (r != 1) { bts_img_mark_used_(wp, 1u); return r; }
-  }
-  if (geo == GEO_S1 && need_out == nullptr && Cin == 2 && x2 == nullptr && (wp2 == nullptr) == (y2 == nullptr)) {
-    { const int e = bts_img_ensure_(wp, 1u, stream); if (e != BTS_OK) return e; }
-    const int r = launch_c2(x, wp, bias, y, N, Di, Hi, Wi, Cin, ldx, Cout, ldy, flags, wp2, bias2, y2, ldy2, gnp, gnG, gn_B, stream);
-    if (r != 1) { bts_img_mark_used_(wp, 1u); return r; }
-  }
-  if (geo == GEO_S1 && need_out == nullptr && !(flags & IG_FLAG_SIGMOID)) {
-    // Winograd form (conv_wino.hip) on the second part of the K3S1 image; the fused shortcut output / second input of the
-    // pair entry points then run as their own 1x1x1 launches
-    const long pairs = (long)((Cin + 7) / 8) * 2 * npad32(Cout) * 4;
-    const float* up = wp + 27L * pairs;
-    int r = bts_w3_launch_(x, up + 48L * pairs, (flags & IG_FLAG_BIAS) ? bias : nullptr, y, N, Di, Hi, Wi, Cin, ldx, Cout, ldy,
-                           (flags & IG_FLAG_ACCUM) ? 1 : 0, gnp, gnG, gn_B, ws, ws_bytes, stream);
-    if (r == 1)
-      r = bts_wino_launch_(x, up, (flags & IG_FLAG_BIAS) ? bias : nullptr, y, N, Di, Hi, Wi, Cin, ldx, Cout, ldy,
-                           (flags & IG_FLAG_ACCUM) ? 1 : 0, gnp, gnG, gn_B, ws, ws_bytes, stream);
-    if (r == BTS_OK) {
-      if (y2 != nullptr)
-        return launch_igemm(GEO_K1, x, wp2, bias2, y2, N, Di, Hi, Wi, Cin, ldx, Di, Hi, Wi, Cout, ldy2, Di, Hi, Wi, 0, 0, 0,
-                            bias2 ? IG_FLAG_BIAS : 0, stream);
-      if (x2 != nullptr)
-        return launch_igemm(GEO_K1, x2, wp2, nullptr, y, N, Di, Hi, Wi, Cin, ldx2, Di, Hi, Wi, Cout, ldy, Di, Hi, Wi, 0, 0, 0,
-                            IG_FLAG_ACCUM, stream);
-      return BTS_OK;
-    }
-    if (r != 1) return r;
-  }
-  if (geo == GEO_K1 && wp2 == nullptr && need_out == nullptr) {
-    const int r = launch_k1s(x, wp, bias, y, (long)N * Di * Hi * Wi, Cin, ldx, Cout, ldy, flags, stream);
-    if (r != 1) return r;
-  }
-  if (geo == GEO_UP && pz < 0 && wp2 == nullptr && !(flags & ~(IG_FLAG_BIAS | IG_FLAG_ACCUM | IG_FLAG_SIGMOID | IG_FLAG_VECIN | IG_FLAG_VECOUT))) {
-    // merged parity classes (no workspace needed); shapes it declines fall through to the per-class launch
-    if (need_out != nullptr) {
-      // planning call: whether the merged kernel takes the launch also depends on pointer alignment we do not have here,
-      // so report its split-K requirement as an upper bound (the per-class path needs none)
-      UpmParams pp;
-      long need = 0;
-      if (plan_upm(pp, N, Di, Hi, Wi, Cin, Cout, &need) && need > 0) { *need_out = need; return BTS_OK; }
-    } else {
-      const int r = launch_upm(x, wp, bias, y, N, Di, Hi, Wi, Cin, ldx, Cout, ldy, flags, ws, ws_bytes, stream);
-      if (r != 1) return r;
-    }
-  }
-  if (geo == GEO_S1 && need_out == nullptr) {      // the implicit-GEMM form reads the first part
-    const int e = bts_img_note_use_(wp, 1u, stream);
-    if (e != BTS_OK) return e;
-  }
-  IgemmParams p;
-  p.wp2 = wp2; p.bias2 = bias2; p.y2 = y2; p.ldy2 = ldy2;
-  p.x2 = x2; p.ldx2 = ldx2;   // second input (x2 + wp2 without y2): see IgemmParams
-  p.part = reinterpret_cast<float*>(ws);
-  p.ws_bytes = ws_bytes;
-  p.plan_only = need_out != nullptr;
-  p.ws_need = 0;
-  p.x = x; p.wp = wp; p.bias = bias; p.y = y;
-  p.N = N; p.Di = Di; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.ldx = ldx;
-  p.Do = Do; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.ldy = ldy;
-  p.Npad = npad32(Cout); p.KG = (Cin + 7) / 8;
-  p.ODa = ODa; p.OHa = OHa; p.OWa = OWa;
-  p.os = 1; p.ooz = p.ooy = p.oox = 0;
-  p.s = 1;
-  p.flags = flags;
-  if ((ldx % 4 == 0) && (Cin % 4 == 0) && (((uintptr_t)x) % 16 == 0)) p.flags |= IG_FLAG_VECIN;
-  if ((ldy % 4 == 0) && (Cout % 4 == 0) && (((uintptr_t)y) % 16 == 0)) p.flags |= IG_FLAG_VECOUT;
-
-  // tap table: offsets relative to o*s
-  int offz[27], offy[27], offx[27], tw[27], nt = 0;
-  int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  if (geo == GEO_K1) {
-    offz[0] = offy[0] = offx[0] = 0; tw[0] = 0; nt = 1;
-  } else if (geo == GEO_S1) {
-    for (int t = 0; t < 27; ++t) { offz[t] = t / 9 - 1; offy[t] = (t / 3) % 3 - 1; offx[t] = t % 3 - 1; tw[t] = t; }
-    nt = 27;
-    lo[0] = lo[1] = lo[2] = -1; hi[0] = hi[1] = hi[2] = 1;
-  } else if (geo == GEO_DOWN) {
-    for (int t = 0; t < 27; ++t) { offz[t] = t / 9; offy[t] = (t / 3) % 3; offx[t] = t % 3; tw[t] = t; }
-    nt = 27;
-    hi[0] = hi[1] = hi[2] = 2;
-    p.s = 2;
-  } else if (pz < 0) {  // GEO_UP, all 8 parity classes in one launch: common halo (offset -1 on every axis)
-    lo[0] = lo[1] = lo[2] = -1;
-    p.os = 2;
-    nt = 8;  // placeholder; per-class tables are filled below once the tile geometry is known
-  } else {  // GEO_UP, single parity class (pz,py,px)
-    const int par[3] = {pz, py, px};
-    int kz[2], ky[2], kx[2], dz[2], dy[2], dx[2], nz, ny, nx;
-    auto axis = [](int pp, int* k, int* d) {
-      if (pp == 0) { k[0] = 0; d[0] = 0; k[1] = 2; d[1] = -1; return 2; }
-      k[0] = 1; d[0] = 0; return 1;
-    };
-    nz = axis(par[0], kz, dz); ny = axis(par[1], ky, dy); nx = axis(par[2], kx, dx);
-    for (int a = 0; a < nz; ++a)
-      for (int bb = 0; bb < ny; ++bb)
-        for (int c = 0; c < nx; ++c) {
-          offz[nt] = dz[a]; offy[nt] = dy[bb]; offx[nt] = dx[c];
-          tw[nt] = (kz[a] * 3 + ky[bb]) * 3 + kx[c];
-          ++nt;
-        }
-    lo[0] = par[0] == 0 ? -1 : 0; lo[1] = par[1] == 0 ? -1 : 0; lo[2] = par[2] == 0 ? -1 : 0;
-    p.os = 2; p.ooz = pz; p.ooy = py; p.oox = px;
-  }
-  p.ntaps = nt;
-  p.ncls = 1;
-  p.loz = lo[0]; p.loy = lo[1]; p.lox = lo[2];
-
-  // ---- config selection ----
-  const int k1 = (geo == GEO_K1);
+// The tiled kernel takes every call of the family, so this one returns a status: BTS_OK with the plan (config, tile geometry, split-K,
+// GroupNorm slots), BTS_ERR_UNSUPPORTED for the fused shortcut output on cfg 1 (the 64-accumulator tiling has no registers for the
+// second set), BTS_ERR_SHAPE for a halo tile beyond the staging slots.
+static int igemm_accept(const ConvCall& c, ConvChoice& ch) {
+  IgemmPlan& g = ch.g;
+  const bool k1 = c.geo == GEO_K1, up = c.geo == GEO_UP, fuse2 = c.second == CONV_Y2;
+  const int Do = up ? c.Di : c.Do, Ho = up ? c.Hi : c.Ho, Wo = up ? c.Wi : c.Wo;      // the iteration grid (UP: one parity class)
+  const int Npad = npad32(c.Cout), KG = (c.Cin + 7) / 8, KGS = k1 ? 4 : 1;
   int M;  // voxels per workgroup tile
-  int cfg = choose_cfg(geo, (geo == GEO_UP && pz < 0) ? 8 * N : N, Do, Ho, Wo, p.Npad, &M);
+  g.cfg = choose_cfg(c.geo, up ? 8 * c.N : c.N, Do, Ho, Wo, Npad, &M);
+  if (fuse2 && g.cfg == 1) return BTS_ERR_UNSUPPORTED;
   // tile dims (powers of two in x,y)
   int TX = 32;
   while (TX > 4 && TX / 2 >= Wo) TX /= 2;  // smallest pow2 >= Wo, capped at 32
-  if (geo == GEO_DOWN && TX > 8) TX = 8;
+  if (c.geo == GEO_DOWN && TX > 8) TX = 8;
   if (TX > M) TX = M;
   int TY = 4;
   while (TY > 1 && TY / 2 >= Ho) TY /= 2;
@@ -1774,27 +1589,121 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
   int TZ = M / (TX * TY);
   // prefer shrinking z extent into y when the volume is shallow in z
   while (TZ > 1 && TZ / 2 >= Do && TY * 2 <= 64) { TZ /= 2; TY *= 2; }
-  p.lgTX = ilog2(TX); p.lgTY = ilog2(TY); p.TZ = TZ;
-  p.ntx = (Wo + TX - 1) / TX; p.nty = (Ho + TY - 1) / TY; p.ntz = (Do + TZ - 1) / TZ;
-  p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1; p.gn_gridy = 1;
-  if (gnp != nullptr && gnG > 0 && geo != GEO_UP && Do % gnG == 0 && (Do / gnG) % TZ == 0 && getenv("BTS_IGEMM_NOGNFUSE") == nullptr) {
-    p.gnp = gnp; p.gn_G = gnG; p.gn_zt = (Do / gnG) / TZ;   // whole tiles per z-slab group
+  g.lgTX = ilog2(TX); g.lgTY = ilog2(TY); g.TZ = TZ;
+  g.ntx = (Wo + TX - 1) / TX; g.nty = (Ho + TY - 1) / TY; g.ntz = (Do + TZ - 1) / TZ;
+  const int s = c.geo == GEO_DOWN ? 2 : 1, span = k1 ? 1 : up ? 2 : 3;      // input stride; taps per axis
+  g.IX = (TX - 1) * s + span; g.IY = (TY - 1) * s + span; g.IZ = (TZ - 1) * s + span;
+  if (g.IZ * g.IY * g.IX * KGS * 2 > 256 * MAXSLOT) return BTS_ERR_SHAPE;
+  static const int NT[5] = {32, 64, 128, 64, 32};      // couts per workgroup of the config
+  g.gridy = (Npad + NT[g.cfg] - 1) / NT[g.cfg];
+  // split-K when the tile grid cannot fill the chip and the contraction is long (tiny spatial grids, wide channels)
+  g.ksplit = 1;
+  g.kg_per = KG;
+  g.need = 0;
+  const long wgs = (long)((unsigned)c.N * g.ntz * g.nty * g.ntx) * g.gridy;
+  // two workgroups fit a CU: below 512 tiles the chip is not full and a single wave per SIMD cannot keep the matrix
+  // pipe busy, so the contraction is split (measured: 16^3 256->256 0.157 -> 0.137 ms, 16^3 768->256 0.46 -> 0.38 ms);
+  // the 1x1x1 staging variant has too little work per k-group for that and keeps the old, lower threshold
+  const long sk_below = k1 ? 192 : 512, sk_target = k1 ? 384 : 512;
+  if (!fuse2 && !up && wgs < sk_below && KG >= 4 * KGS) {
+    int ks = (int)((sk_target + wgs - 1) / wgs);
+    const int maxks = KG / (2 * KGS);
+    if (ks > maxks) ks = maxks;
+    if (ks > 64) ks = 64;
+    if (ks > 1) {
+      int per = (KG + ks - 1) / ks;
+      per = (per + KGS - 1) / KGS * KGS;
+      ks = (KG + per - 1) / per;
+      const long need = (long)ks * c.N * Do * Ho * Wo * Npad * 4;
+      if (ks > 1 && c.ws_bytes >= need) {
+        g.ksplit = ks;
+        g.kg_per = per;
+        g.need = need;
+      }
+    }
   }
-  p.IX = (TX - 1) * p.s + (hi[2] - lo[2] + 1);
-  p.IY = (TY - 1) * p.s + (hi[1] - lo[1] + 1);
-  p.IZ = (TZ - 1) * p.s + (hi[0] - lo[0] + 1);
-  const int KGS = k1 ? 4 : 1;
-  const int S = KGS * 8 + 4;
-  for (int t = 0; t < nt; ++t) {
-    p.tap_lds[t] = (((offz[t] - lo[0]) * p.IY + (offy[t] - lo[1])) * p.IX + (offx[t] - lo[2])) * S;
-    p.tap_w[t] = tw[t];
+  // split-K tiles are finished by the reduce kernel: no fused statistics; nor from the parity classes
+  g.gn_zt = (g.ksplit > 1 || up) ? 0 : conv_gn_zt(c, TZ);
+  ch.sym = g.cfg + (k1 ? 8 : 0);
+  ch.ws = g.need;
+  ch.gn_B = (long)g.gn_zt * g.nty * g.ntx * g.gridy;
+  return BTS_OK;
+}
+
+template <int MS, int NS, int WM, int WN, int KGS, bool FUSE2 = false, bool FIXG = false, bool T27 = false>
+static int launch_cfg(const IgemmParams& p, const ConvChoice& ch, hipStream_t stream) {
+  constexpr int S = KGS * 8 + 4;
+  const int tileVox = p.IZ * p.IY * p.IX;
+  // a single stage (all channels fit one staging pass, e.g. the 1x1x1 convs with Cin <= 32) needs no second buffer:
+  // half the LDS -> twice the resident workgroups to hide the (then un-overlapped) staging latency
+  const int nstages_all = (p.KG + KGS - 1) / KGS;
+  const size_t shmem = (size_t)((nstages_all > 1 && !IG_TRI(MS, NS, KGS, FUSE2, FIXG)) ? 2 : 1) * tileVox * S * sizeof(float);
+  auto kern = igemm_kernel<MS, NS, WM, WN, KGS, FUSE2, FIXG, T27>;
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    attr_done = true;
   }
-  for (int t = nt; t < 27; ++t) { p.tap_lds[t] = 0; p.tap_w[t] = 0; }
+  const dim3 grid(p.N * p.ntz * p.nty * p.ntx, ch.g.gridy, p.ncls > 1 ? p.ncls : p.ksplit);
+  const bool prof = bts_prof_on();
+  if (prof) {
+    const double taps = (p.ncls > 1) ? 27.0 : (double)p.ntaps;
+    bts_prof_begin(ch.sym, 2.0 * taps * p.Cin * p.Cout * (double)p.N * p.Do * p.Ho * p.Wo, stream);
+  }
+  (void)hipGetLastError(); hipLaunchKernelGGL(kern, grid, dim3(256), shmem, stream, p);
+  if (prof) bts_prof_end(stream);
+  BTS_LAUNCH_CHECK();
+  if (p.ksplit > 1) {
+    const long nvox = (long)p.N * p.Do * p.Ho * p.Wo;
+    long blocks = (nvox * p.Cout + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    (void)hipGetLastError(); hipLaunchKernelGGL(igemm_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, p.part, p.bias, p.y, nvox, p.Cout,
+                       p.Npad, p.ldy, p.ksplit, p.flags);
+    BTS_LAUNCH_CHECK();
+  }
+  return BTS_OK;
+}
+
+// The launch igemm_accept planned: the tap tables of the geometry (UP: one per parity class) on the plan's tiles, and the instantiation
+// of its config.
+static int launch_igemm(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
+  const IgemmPlan& g = ch.g;
+  const bool k1 = c.geo == GEO_K1, up = c.geo == GEO_UP;
+  IgemmParams p;
+  p.wp2 = c.second ? q.wp2 : nullptr;
+  p.bias2 = c.second == CONV_Y2 ? q.bias2 : nullptr; p.y2 = c.second == CONV_Y2 ? q.y2 : nullptr; p.ldy2 = c.second == CONV_Y2 ? c.ld2 : 0;
+  p.x2 = c.second == CONV_X2 ? q.x2 : nullptr; p.ldx2 = c.second == CONV_X2 ? c.ld2 : 0;   // second input (x2 + wp2 without y2): see IgemmParams
+  p.part = reinterpret_cast<float*>(q.ws);
+  p.x = q.x; p.wp = q.wp; p.bias = q.bias; p.y = q.y;
+  p.N = c.N; p.Di = c.Di; p.Hi = c.Hi; p.Wi = c.Wi; p.Cin = c.Cin; p.ldx = c.ldx;
+  p.Do = up ? c.Di : c.Do; p.Ho = up ? c.Hi : c.Ho; p.Wo = up ? c.Wi : c.Wo; p.Cout = c.Cout; p.ldy = c.ldy;
+  p.Npad = npad32(c.Cout); p.KG = (c.Cin + 7) / 8;
+  p.ODa = c.Do; p.OHa = c.Ho; p.OWa = c.Wo;
+  p.os = up ? 2 : 1; p.ooz = p.ooy = p.oox = 0;
+  p.s = c.geo == GEO_DOWN ? 2 : 1;
+  p.flags = c.flags;
+  if ((c.ldx % 4 == 0) && (c.Cin % 4 == 0) && c.x16) p.flags |= IG_FLAG_VECIN;
+  if ((c.ldy % 4 == 0) && (c.Cout % 4 == 0) && c.y16) p.flags |= IG_FLAG_VECOUT;
+  p.lgTX = g.lgTX; p.lgTY = g.lgTY; p.TZ = g.TZ; p.ntx = g.ntx; p.nty = g.nty; p.ntz = g.ntz; p.IX = g.IX; p.IY = g.IY; p.IZ = g.IZ;
+  p.ksplit = g.ksplit; p.kg_per = g.kg_per;
+  p.gnp = g.gn_zt ? q.gnp : nullptr; p.gn_G = g.gn_zt ? c.G : 0; p.gn_zt = g.gn_zt ? g.gn_zt : 1; p.gn_gridy = g.gridy;
+
+  // tap table: offsets relative to o*s, LDS offsets relative to the tile's low corner
+  const int lo = (c.geo == GEO_S1 || up) ? -1 : 0;      // (UP: the common halo of the 8 classes, offset -1 on every axis)
+  const int S = (k1 ? 4 : 1) * 8 + 4;
+  p.ntaps = k1 ? 1 : up ? 8 : 27;      // (UP: placeholder; the per-class tables are below)
+  p.ncls = 1;
+  p.loz = p.loy = p.lox = lo;
+  for (int t = 0; t < 27; ++t) {
+    p.tap_lds[t] = (k1 || up || t >= p.ntaps) ? 0 : ((t / 9 * p.IY + (t / 3) % 3) * p.IX + t % 3) * S;      // (S1: t - 1 - lo = DOWN: t - lo)
+    p.tap_w[t] = (k1 || up) ? 0 : t;
+  }
   p.tap_sz = p.IY * p.IX * S; p.tap_sy = p.IX * S; p.tap_sx = S;
-  if (geo == GEO_UP && pz < 0) {
+  if (up) {
     p.ncls = 8;
-    for (int c = 0; c < 8; ++c) {
-      const int par[3] = {(c >> 2) & 1, (c >> 1) & 1, c & 1};
+    for (int cl = 0; cl < 8; ++cl) {
+      const int par[3] = {(cl >> 2) & 1, (cl >> 1) & 1, cl & 1};
       int k[3][2], d[3][2], n[3];
       for (int a = 0; a < 3; ++a) {
         if (par[a] == 0) { k[a][0] = 0; d[a][0] = 0; k[a][1] = 2; d[a][1] = -1; n[a] = 2; }
@@ -1804,99 +1713,162 @@ static int launch_igemm(int geo, const float* x, const float* wp, const float* b
       for (int a = 0; a < n[0]; ++a)
         for (int bb = 0; bb < n[1]; ++bb)
           for (int cc = 0; cc < n[2]; ++cc) {
-            p.cls_tl[c][ct] = (((d[0][a] + 1) * p.IY + (d[1][bb] + 1)) * p.IX + (d[2][cc] + 1)) * S;
-            p.cls_tw[c][ct] = (k[0][a] * 3 + k[1][bb]) * 3 + k[2][cc];
+            p.cls_tl[cl][ct] = (((d[0][a] + 1) * p.IY + (d[1][bb] + 1)) * p.IX + (d[2][cc] + 1)) * S;
+            p.cls_tw[cl][ct] = (k[0][a] * 3 + k[1][bb]) * 3 + k[2][cc];
             ++ct;
           }
-      p.cls_nt[c] = ct;
-      for (; ct < 8; ++ct) { p.cls_tl[c][ct] = 0; p.cls_tw[c][ct] = 0; }
+      p.cls_nt[cl] = ct;
+      for (; ct < 8; ++ct) { p.cls_tl[cl][ct] = 0; p.cls_tw[cl][ct] = 0; }
     }
   }
 
-  int rc;
-  const bool fixg = (geo == GEO_S1) && p.IX == 34 && p.IY == 6;
-  if (fixg && !k1 && (cfg == 0 || cfg == 1)) {
-    if (p.y2 != nullptr) {
-      if (cfg == 0) rc = launch_cfg<2, 1, 4, 1, 1, true, true>(p, stream);
-      else rc = BTS_ERR_UNSUPPORTED;
-    } else {
-      if (cfg == 0) rc = launch_cfg<2, 1, 4, 1, 1, false, true>(p, stream);
-      else rc = launch_cfg<2, 2, 4, 1, 1, false, true>(p, stream);
-    }
-  } else if (k1) {
-    switch (cfg) {
-      case 0: rc = launch_cfg<2, 1, 4, 1, 4>(p, stream); break;
-      case 1: rc = launch_cfg<2, 2, 4, 1, 4>(p, stream); break;
-      case 2: rc = launch_cfg<1, 2, 2, 2, 4>(p, stream); break;
-      case 3: rc = launch_cfg<1, 1, 2, 2, 4>(p, stream); break;
-      default: rc = launch_cfg<1, 1, 4, 1, 4>(p, stream); break;
-    }
-  } else if (p.y2 != nullptr) {  // fused shortcut conv: every tiling but the 64-accumulator one has the registers
-    switch (cfg) {
-      case 0: rc = launch_cfg<2, 1, 4, 1, 1, true>(p, stream); break;
-      case 2: rc = launch_cfg<1, 2, 2, 2, 1, true>(p, stream); break;
-      case 3: rc = launch_cfg<1, 1, 2, 2, 1, true>(p, stream); break;
-      case 4: rc = launch_cfg<1, 1, 4, 1, 1, true>(p, stream); break;
-      default: rc = BTS_ERR_UNSUPPORTED; break;
-    }
-  } else if (p.ntaps == 27 && p.ncls <= 1) {
-    switch (cfg) {
-      case 0: rc = launch_cfg<2, 1, 4, 1, 1, false, false, true>(p, stream); break;
-      case 1: rc = launch_cfg<2, 2, 4, 1, 1, false, false, true>(p, stream); break;
-      case 2: rc = launch_cfg<1, 2, 2, 2, 1, false, false, true>(p, stream); break;
-      case 3: rc = launch_cfg<1, 1, 2, 2, 1, false, false, true>(p, stream); break;
-      default: rc = launch_cfg<1, 1, 4, 1, 1, false, false, true>(p, stream); break;
-    }
-  } else {
-    switch (cfg) {
-      case 0: rc = launch_cfg<2, 1, 4, 1, 1>(p, stream); break;
-      case 1: rc = launch_cfg<2, 2, 4, 1, 1>(p, stream); break;
-      case 2: rc = launch_cfg<1, 2, 2, 2, 1>(p, stream); break;
-      case 3: rc = launch_cfg<1, 1, 2, 2, 1>(p, stream); break;
-      default: rc = launch_cfg<1, 1, 4, 1, 1>(p, stream); break;
+  const bool fixg = (c.geo == GEO_S1) && p.IX == 34 && p.IY == 6;
+  if (fixg && (g.cfg == 0 || g.cfg == 1)) {
+    if (p.y2 != nullptr) return launch_cfg<2, 1, 4, 1, 1, true, true>(p, ch, stream);      // (cfg 0: igemm_accept refused cfg 1)
+    if (g.cfg == 0) return launch_cfg<2, 1, 4, 1, 1, false, true>(p, ch, stream);
+    return launch_cfg<2, 2, 4, 1, 1, false, true>(p, ch, stream);
+  }
+  if (k1) {
+    switch (g.cfg) {
+      case 0: return launch_cfg<2, 1, 4, 1, 4>(p, ch, stream);
+      case 1: return launch_cfg<2, 2, 4, 1, 4>(p, ch, stream);
+      case 2: return launch_cfg<1, 2, 2, 2, 4>(p, ch, stream);
+      case 3: return launch_cfg<1, 1, 2, 2, 4>(p, ch, stream);
+      default: return launch_cfg<1, 1, 4, 1, 4>(p, ch, stream);
     }
   }
-  if (need_out) {
-    *need_out = p.ws_need;
-    if (geo == GEO_S1) {  // the Winograd form may split the contraction where the implicit GEMM does not (and vice versa)
-      const long wn = bts_wino_workspace_(N, Di, Hi, Wi, Cin, Cout);
-      if (wn > *need_out) *need_out = wn;
-      const long w3 = bts_w3_workspace_(N, Di, Hi, Wi, Cin, Cout);
-      if (w3 > *need_out) *need_out = w3;
+  if (p.y2 != nullptr) {  // fused shortcut conv: every tiling but the 64-accumulator one has the registers
+    switch (g.cfg) {
+      case 0: return launch_cfg<2, 1, 4, 1, 1, true>(p, ch, stream);
+      case 2: return launch_cfg<1, 2, 2, 2, 1, true>(p, ch, stream);
+      case 3: return launch_cfg<1, 1, 2, 2, 1, true>(p, ch, stream);
+      default: return launch_cfg<1, 1, 4, 1, 1, true>(p, ch, stream);
     }
   }
-  if (gn_B && rc == BTS_OK && p.gnp != nullptr) *gn_B = (long)p.gn_zt * p.nty * p.ntx * p.gn_gridy;
-  return rc;
-}
-
-static int geo_of_kind_fwd(int kind) {
-  switch (kind) {
-    case BTS_CONV_K1: return GEO_K1;
-    case BTS_CONV_K3S1: return GEO_S1;
-    case BTS_CONV_K3S2: return GEO_DOWN;
-    default: return GEO_UP;
+  if (!up) {      // 27 taps, one class
+    switch (g.cfg) {
+      case 0: return launch_cfg<2, 1, 4, 1, 1, false, false, true>(p, ch, stream);
+      case 1: return launch_cfg<2, 2, 4, 1, 1, false, false, true>(p, ch, stream);
+      case 2: return launch_cfg<1, 2, 2, 2, 1, false, false, true>(p, ch, stream);
+      case 3: return launch_cfg<1, 1, 2, 2, 1, false, false, true>(p, ch, stream);
+      default: return launch_cfg<1, 1, 4, 1, 1, false, false, true>(p, ch, stream);
+    }
+  }
+  switch (g.cfg) {
+    case 0: return launch_cfg<2, 1, 4, 1, 1>(p, ch, stream);
+    case 1: return launch_cfg<2, 2, 4, 1, 1>(p, ch, stream);
+    case 2: return launch_cfg<1, 2, 2, 2, 1>(p, ch, stream);
+    case 3: return launch_cfg<1, 1, 2, 2, 1>(p, ch, stream);
+    default: return launch_cfg<1, 1, 4, 1, 1>(p, ch, stream);
   }
 }
 
-static int conv_fwd_impl(int kind, const float* x, const float* wp_fwd, const float* bias, float* y, void* ws, long ws_bytes,
-                         long* need_out, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int flags,
-                         hipStream_t stream) {
+// The kernel of a call, in the order the forms were always offered: 3x3x3 stride 1 -- the direct kernel (no second weight set), the
+// two-channel kernel (Cin == 2, no second input), the Winograd forms (never with the sigmoid; the second form then runs as a 1x1x1 launch
+// of its own: ch.second); 1x1x1 -- the streaming kernel; transposed -- the merged-class kernel (both without a second form); then the tiled
+// kernel, whose status is that of a call no kernel takes.
+static int conv_choose(const ConvCall& c, ConvChoice& ch) {
+  ch = ConvChoice{};
+  const bool s1 = c.geo == GEO_S1;
+  if (s1 && !c.second && dsc_accept(c, ch)) { ch.kernel = CONV_DSC; return BTS_OK; }
+  if (s1 && c.Cin == 2 && c.second != CONV_X2 && c2_accept(c, ch)) { ch.kernel = CONV_C2; return BTS_OK; }
+  if (s1 && !(c.flags & IG_FLAG_SIGMOID)) {
+    ch.second = c.second;
+    if (w3_accept(c, ch)) { ch.kernel = CONV_W3; return BTS_OK; }
+    if (wino_accept(c, ch)) { ch.kernel = CONV_WINO; return BTS_OK; }
+    ch.second = 0;
+  }
+  if (c.geo == GEO_K1 && !c.second && k1s_accept(c, ch)) { ch.kernel = CONV_K1S; return BTS_OK; }
+  if (c.geo == GEO_UP && !c.second && upm_accept(c, ch)) { ch.kernel = CONV_UPM; return BTS_OK; }
+  ch.kernel = CONV_IGEMM;
+  return igemm_accept(c, ch);
+}
+
+// Ensures the image part the chosen kernel reads (3x3x3 stride 1: 1 implicit GEMM and the small-channel kernels | 2 | 4 the Winograd
+// forms), launches, and records the part as in use once the launch was accepted.
+static int conv_launch(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
+  const unsigned bit = c.geo != GEO_S1 ? 0u : ch.kernel == CONV_W3 ? 4u : ch.kernel == CONV_WINO ? 2u : 1u;
+  if (bit) { const int e = bts_img_ensure_(q.wp, bit, stream); if (e != BTS_OK) return e; }
+  int r;
+  switch (ch.kernel) {
+    case CONV_DSC: r = launch_dsc(c, ch, q, stream); break;
+    case CONV_C2: r = launch_c2(c, ch, q, stream); break;
+    case CONV_W3: r = bts_w3_launch_(c, ch, q, stream); break;
+    case CONV_WINO: r = bts_wino_launch_(c, ch, q, stream); break;
+    case CONV_K1S: r = launch_k1s(c, ch, q, stream); break;
+    case CONV_UPM: r = launch_upm(c, ch, q, stream); break;
+    default: r = launch_igemm(c, ch, q, stream); break;
+  }
+  if (r == BTS_OK && bit) bts_img_mark_used_(q.wp, bit);
+  return r;
+}
+// One call of the engine (c's alignment flags come from q; c.ws_bytes = the bytes behind q.ws): chosen -- with the 1x1x1 call a Winograd
+// form leaves over -- before anything is packed or launched, then run.  gn_B: the GroupNorm slots written (0: none).
+static int conv_run(ConvCall c, const ConvPtrs& q, hipStream_t stream, long* gn_B = nullptr) {
+  auto al16 = [](const void* a) { return (((uintptr_t)a) & 15) == 0; };
+  c.x16 = al16(q.x); c.y16 = al16(q.y); c.p2_16 = al16(c.second == CONV_Y2 ? (const void*)q.y2 : (const void*)q.x2); c.ws16 = al16(q.ws);
+  if (q.ws == nullptr || c.ws_bytes < 0) c.ws_bytes = 0;
+  if (gn_B) *gn_B = 0;
+  ConvChoice ch, ch2;
+  int r = conv_choose(c, ch);
+  if (r != BTS_OK) return r;
+  ConvCall c2 = c;
+  ConvPtrs q2 = {};
+  if (ch.second) {
+    c2.geo = GEO_K1; c2.second = c2.G = 0; c2.ws_bytes = 0;
+    if (ch.second == CONV_Y2) {      // y2 = bias2 + conv1x1x1(x)
+      c2.ldy = c.ld2; c2.y16 = c.p2_16; c2.flags = q.bias2 ? IG_FLAG_BIAS : 0;
+      q2.x = q.x; q2.wp = q.wp2; q2.bias = q.bias2; q2.y = q.y2;
+    } else {                         // y += conv1x1x1(x2)
+      c2.ldx = c.ld2; c2.x16 = c.p2_16; c2.flags = IG_FLAG_ACCUM;
+      q2.x = q.x2; q2.wp = q.wp2; q2.y = q.y;
+    }
+    r = conv_choose(c2, ch2);
+    if (r != BTS_OK) return r;
+  }
+  r = conv_launch(c, ch, q, stream);
+  if (r == BTS_OK && ch.second) r = conv_launch(c2, ch2, q2, stream);
+  if (r == BTS_OK && gn_B) *gn_B = ch.gn_B;
+  return r;
+}
+
+// The call of a forward (dir 0) or data-gradient (dir 1) entry point; kind, (N, D, H, W, Cin, Cout) and the flags as the ABI names them,
+// ldx / ldy: rows of the forward input / output (dir 1: of dx, the tensor written / of dy, the tensor read).  The data gradient of the
+// stride-2 conv is the gather form over the fine grid's parity classes, that of the transposed conv the stride-2 'same' conv of dy.
+static int conv_call_of(int dir, int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int flags, ConvCall& c) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || ldx < Cin || ldy < Cout) return BTS_ERR_SHAPE;
-  int f = 0;
-  if (bias) f |= IG_FLAG_BIAS;
-  if (flags & BTS_CONV_FLAG_SIGMOID) f |= IG_FLAG_SIGMOID;
-  if (flags & BTS_CONV_FLAG_ACCUM) f |= IG_FLAG_ACCUM;
-  const int geo = geo_of_kind_fwd(kind);
-  if (geo == GEO_K1 || geo == GEO_S1)
-    return launch_igemm(geo, x, wp_fwd, bias, y, N, D, H, W, Cin, ldx, D, H, W, Cout, ldy, D, H, W, 0, 0, 0, f, stream, ws,
-                        ws_bytes, need_out);
-  if (geo == GEO_DOWN) {
-    if ((D | H | W) & 1) return BTS_ERR_SHAPE;  // TF 'same' pads (0,1) only for even sizes
-    return launch_igemm(geo, x, wp_fwd, bias, y, N, D, H, W, Cin, ldx, D / 2, H / 2, W / 2, Cout, ldy, D / 2, H / 2,
-                        W / 2, 0, 0, 0, f, stream, ws, ws_bytes, need_out);
+  if (kind == BTS_CONV_K3S2 && ((D | H | W) & 1)) return BTS_ERR_SHAPE;  // TF 'same' pads (0,1) only for even sizes
+  const bool same = kind == BTS_CONV_K1 || kind == BTS_CONV_K3S1, half = kind == BTS_CONV_K3S2;
+  const int Df = same ? D : half ? D / 2 : 2 * D, Hf = same ? H : half ? H / 2 : 2 * H, Wf = same ? W : half ? W / 2 : 2 * W;
+  c = ConvCall{};
+  c.geo = kind == BTS_CONV_K1 ? GEO_K1 : kind == BTS_CONV_K3S1 ? GEO_S1 : half == (dir == 0) ? GEO_DOWN : GEO_UP;
+  c.N = N;
+  if (dir == 0) { c.Di = D; c.Hi = H; c.Wi = W; c.Do = Df; c.Ho = Hf; c.Wo = Wf; c.Cin = Cin; c.ldx = ldx; c.Cout = Cout; c.ldy = ldy; }
+  else { c.Di = Df; c.Hi = Hf; c.Wi = Wf; c.Do = D; c.Ho = H; c.Wo = W; c.Cin = Cout; c.ldx = ldy; c.Cout = Cin; c.ldy = ldx; }
+  if ((flags & BTS_CONV_FLAG_SIGMOID) && dir == 0) c.flags |= IG_FLAG_SIGMOID;
+  if (flags & BTS_CONV_FLAG_ACCUM) c.flags |= IG_FLAG_ACCUM;
+  return BTS_OK;
+}
+// the query's view of a call: aligned operands and a workspace as large as needed
+static void conv_query_view(ConvCall& c) { c.x16 = c.y16 = c.p2_16 = c.ws16 = 1; c.ws_bytes = LONG_MAX; }
+// Workspace for a call on dense operands: the maximum over the kernels that split the contraction and could take the call under some
+// switch setting or operand alignment (the Winograd forms may split where the implicit GEMM does not, and vice versa).  For the
+// transposed form, whether the merged kernel takes the launch also depends on pointer alignment a query does not have, so its split-K
+// requirement is reported as an upper bound (the tiled kernel's parity classes need none).  -1: no kernel takes the call.
+static long conv_ws_query(int dir, int kind, int N, int D, int H, int W, int Cin, int Cout) {
+  ConvCall c;
+  ConvChoice ch;
+  if (conv_call_of(dir, kind, N, D, H, W, Cin, Cin, Cout, Cout, 0, c) != BTS_OK) return -1;
+  conv_query_view(c);
+  if (c.geo == GEO_UP && upm_accept(c, ch) && ch.ws > 0) return ch.ws;
+  if (igemm_accept(c, ch) != BTS_OK) return -1;
+  long need = ch.ws;
+  if (c.geo == GEO_S1) {
+    const long wn = wino_ws_need(c), w3 = w3_ws_need(c);
+    need = need > wn ? need : wn;
+    need = need > w3 ? need : w3;
   }
-  return launch_igemm(GEO_UP, x, wp_fwd, bias, y, N, D, H, W, Cin, ldx, D, H, W, Cout, ldy, 2 * D, 2 * H, 2 * W, -1, -1, -1,
-                      f, stream, ws, ws_bytes, need_out);
+  return need;
 }
 
 // Forward. x:(N,D,H,W,Cin) ld=ldx ; y:(N,Do,Ho,Wo,Cout) ld=ldy with (Do,Ho,Wo) = (D,H,W) | (D/2,..) | (2D,..).
@@ -1904,33 +1876,17 @@ static int conv_fwd_impl(int kind, const float* x, const float* wp_fwd, const fl
 extern "C" int bts_conv3d_fwd(int kind, const float* x, const float* wp_fwd, const float* bias, float* y, void* workspace,
                               long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy,
                               int flags, hipStream_t stream) {
-  return conv_fwd_impl(kind, x, wp_fwd, bias, y, workspace, workspace_bytes, nullptr, N, D, H, W, Cin, ldx, Cout, ldy, flags,
-                       stream);
+  ConvCall c;
+  const int r = conv_call_of(0, kind, N, D, H, W, Cin, ldx, Cout, ldy, flags, c);
+  if (r != BTS_OK) return r;
+  if (bias) c.flags |= IG_FLAG_BIAS;
+  c.ws_bytes = workspace_bytes;
+  ConvPtrs q = {};
+  q.x = x; q.wp = wp_fwd; q.bias = bias; q.y = y; q.ws = workspace;
+  return conv_run(c, q, stream);
 }
 extern "C" long bts_conv3d_fwd_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout) {
-  long need = 0;
-  if (conv_fwd_impl(kind, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &need, N, D, H, W, Cin, Cin, Cout, Cout, 0,
-                    nullptr) != BTS_OK)
-    return -1;
-  return need;
-}
-
-static int conv_bwd_impl(int kind, const float* dy, const float* wp_bwd, float* dx, void* ws, long ws_bytes, long* need_out,
-                         int N, int D, int H, int W, int Cin, int lddx, int Cout, int lddy, int flags, hipStream_t stream) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || lddx < Cin || lddy < Cout) return BTS_ERR_SHAPE;
-  int f = 0;
-  if (flags & BTS_CONV_FLAG_ACCUM) f |= IG_FLAG_ACCUM;
-  if (kind == BTS_CONV_K1 || kind == BTS_CONV_K3S1)
-    return launch_igemm(kind == BTS_CONV_K1 ? GEO_K1 : GEO_S1, dy, wp_bwd, nullptr, dx, N, D, H, W, Cout, lddy, D, H, W,
-                        Cin, lddx, D, H, W, 0, 0, 0, f, stream, ws, ws_bytes, need_out);
-  if (kind == BTS_CONV_K3S2) {  // gather form over the fine grid's parity classes
-    if ((D | H | W) & 1) return BTS_ERR_SHAPE;
-    return launch_igemm(GEO_UP, dy, wp_bwd, nullptr, dx, N, D / 2, H / 2, W / 2, Cout, lddy, D / 2, H / 2, W / 2, Cin, lddx,
-                        D, H, W, -1, -1, -1, f, stream, ws, ws_bytes, need_out);
-  }
-  // transposed conv: d/dx is the stride-2 'same' conv of dy (fine grid 2D x 2H x 2W) -> coarse grid
-  return launch_igemm(GEO_DOWN, dy, wp_bwd, nullptr, dx, N, 2 * D, 2 * H, 2 * W, Cout, lddy, D, H, W, Cin, lddx, D, H, W,
-                      0, 0, 0, f, stream, ws, ws_bytes, need_out);
+  return conv_ws_query(0, kind, N, D, H, W, Cin, Cout);
 }
 
 // Data gradient. dy has the forward output's shape, dx the forward input's shape (N,D,H,W,Cin).
@@ -1938,31 +1894,41 @@ static int conv_bwd_impl(int kind, const float* dy, const float* wp_bwd, float* 
 extern "C" int bts_conv3d_bwd_data(int kind, const float* dy, const float* wp_bwd, float* dx, void* workspace,
                                    long workspace_bytes, int N, int D, int H, int W, int Cin, int lddx, int Cout, int lddy,
                                    int flags, hipStream_t stream) {
-  return conv_bwd_impl(kind, dy, wp_bwd, dx, workspace, workspace_bytes, nullptr, N, D, H, W, Cin, lddx, Cout, lddy, flags,
-                       stream);
+  ConvCall c;
+  const int r = conv_call_of(1, kind, N, D, H, W, Cin, lddx, Cout, lddy, flags, c);
+  if (r != BTS_OK) return r;
+  c.ws_bytes = workspace_bytes;
+  ConvPtrs q = {};
+  q.x = dy; q.wp = wp_bwd; q.y = dx; q.ws = workspace;
+  return conv_run(c, q, stream);
 }
 extern "C" long bts_conv3d_bwd_data_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout) {
-  long need = 0;
-  if (conv_bwd_impl(kind, nullptr, nullptr, nullptr, nullptr, 0, &need, N, D, H, W, Cin, Cin, Cout, Cout, 0, nullptr) != BTS_OK)
-    return -1;
-  return need;
+  return conv_ws_query(1, kind, N, D, H, W, Cin, Cout);
 }
 
 // Fused pair of the ResNet block (resnet.py:118 and :133-134): y = conv3x3x3(x) + bias, y2 = conv1x1x1(x) + bias2 from ONE
 // pass over x. wp_fwd: K3S1 forward packing, wp2: K1 forward packing of the shortcut kernel (same Cin/Cout).
-// Returns BTS_ERR_UNSUPPORTED when the selected tiling has no register room for the second accumulator set
-// (bts_conv3d_fwd_can_fuse tells beforehand): the caller then issues the two convolutions separately.
+// Returns BTS_ERR_UNSUPPORTED when the tiled kernel is the one to take the call and its tiling has no register room for the second
+// accumulator set; bts_conv3d_fwd_can_fuse tells beforehand, from the tiled kernel's plan alone (whatever the switches and the
+// operands leave to the other kernels): the caller then issues the two convolutions separately.
 extern "C" int bts_conv3d_fwd_can_fuse(int N, int D, int H, int W, int Cin, int Cout) {
-  int M;
-  return choose_cfg(GEO_S1, N, D, H, W, npad32(Cout), &M) != 1;
+  ConvCall c;
+  ConvChoice ch;
+  if (conv_call_of(0, BTS_CONV_K3S1, N, D, H, W, Cin, Cin, Cout, Cout, 0, c) != BTS_OK) return 0;
+  conv_query_view(c);
+  c.second = CONV_Y2; c.ld2 = Cout;
+  return igemm_accept(c, ch) == BTS_OK;
 }
 extern "C" int bts_conv3d_fwd_fused2(const float* x, const float* wp_fwd, const float* bias, float* y, const float* wp2,
                                      const float* bias2, float* y2, int N, int D, int H, int W, int Cin, int ldx, int Cout,
                                      int ldy, int ldy2, hipStream_t stream) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || ldx < Cin || ldy < Cout || ldy2 < Cout) return BTS_ERR_SHAPE;
-  if (!wp2 || !y2) return BTS_ERR_SHAPE;
-  return launch_igemm(GEO_S1, x, wp_fwd, bias, y, N, D, H, W, Cin, ldx, D, H, W, Cout, ldy, D, H, W, 0, 0, 0,
-                      bias ? IG_FLAG_BIAS : 0, stream, nullptr, 0, nullptr, wp2, bias2, y2, ldy2);
+  ConvCall c;
+  if (conv_call_of(0, BTS_CONV_K3S1, N, D, H, W, Cin, ldx, Cout, ldy, 0, c) != BTS_OK || ldy2 < Cout || !wp2 || !y2) return BTS_ERR_SHAPE;
+  if (bias) c.flags |= IG_FLAG_BIAS;
+  c.second = CONV_Y2; c.ld2 = ldy2;
+  ConvPtrs q = {};
+  q.x = x; q.wp = wp_fwd; q.bias = bias; q.y = y; q.wp2 = wp2; q.bias2 = bias2; q.y2 = y2;
+  return conv_run(c, q, stream);
 }
 
 // ---- convolution + GroupNorm statistics of its output (resnet.py:80-93, downsample.py:41-43: conv -> GroupNormalization) ----
@@ -1986,40 +1952,29 @@ extern "C" long bts_conv3d_fwd_gn_workspace(int kind, int N, int D, int H, int W
   return fused > gw ? fused : gw;
 }
 // y = conv(x) + bias (y dense: ldy == Cout) and (mean, rstd) = slab-mode GroupNorm statistics of y.  The statistics come out
-// of the conv epilogue when the tiled kernel takes the launch without split-K and the z-slab groups hold whole tiles;
+// of the conv epilogue where the chosen kernel writes the partials (ConvChoice::gn_B: no split-K, slab groups of whole tiles);
 // otherwise bts_gn_stats runs on y afterwards (same result up to the summation order, both deterministic).
+// wp2 != NULL: the fused shortcut pair; the workspace then serves the Winograd forms' split-K on small grids (the fused tiled pair never splits).
 static int conv_fwd_gn_impl(int kind, const float* x, const float* wp, const float* bias, float* y, const float* wp2,
                             const float* bias2, float* y2, int ldy2, void* ws, long ws_bytes, int N, int D, int H, int W, int Cin,
                             int ldx, int Cout, int G, float eps, float* mean, float* rstd, hipStream_t stream) {
   if (G <= 0 || Cout % G != 0) return BTS_ERR_SHAPE;
   if (ws == nullptr || ws_bytes < bts_conv3d_fwd_gn_workspace(kind, N, D, H, W, Cin, Cout, G)) return BTS_ERR_WORKSPACE;
-  int Do = D, Ho = H, Wo = W;
-  if (kind == BTS_CONV_K3S2) { Do = D / 2; Ho = H / 2; Wo = W / 2; }
-  if (kind == BTS_CONV_K3S2T) { Do = 2 * D; Ho = 2 * H; Wo = 2 * W; }
-  const long cw = (bts_conv3d_fwd_workspace(kind, N, D, H, W, Cin, Cout) + 63) & ~63L;
-  double* gnp = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + cw);
-  long gnB = 0;
-  int r;
-  if (wp2 != nullptr) {
-    // the workspace serves the Winograd form's split-K on small grids (the fused implicit-GEMM pair never splits)
-    r = launch_igemm(GEO_S1, x, wp, bias, y, N, D, H, W, Cin, ldx, D, H, W, Cout, Cout, D, H, W, 0, 0, 0, bias ? IG_FLAG_BIAS : 0,
-                     stream, ws, cw, nullptr, wp2, bias2, y2, ldy2, gnp, G, &gnB);
-  } else {
-    const int geo = geo_of_kind_fwd(kind);
-    const int f = bias ? IG_FLAG_BIAS : 0;
-    if (geo == GEO_K1 || geo == GEO_S1)
-      r = launch_igemm(geo, x, wp, bias, y, N, D, H, W, Cin, ldx, D, H, W, Cout, Cout, D, H, W, 0, 0, 0, f, stream, ws, cw, nullptr,
-                       nullptr, nullptr, nullptr, 0, gnp, G, &gnB);
-    else if (geo == GEO_DOWN) {
-      if ((D | H | W) & 1) return BTS_ERR_SHAPE;
-      r = launch_igemm(geo, x, wp, bias, y, N, D, H, W, Cin, ldx, Do, Ho, Wo, Cout, Cout, Do, Ho, Wo, 0, 0, 0, f, stream, ws, cw,
-                       nullptr, nullptr, nullptr, nullptr, 0, gnp, G, &gnB);
-    } else
-      r = launch_igemm(GEO_UP, x, wp, bias, y, N, D, H, W, Cin, ldx, D, H, W, Cout, Cout, Do, Ho, Wo, -1, -1, -1, f, stream, ws, cw);
-  }
+  ConvCall c;
+  int r = conv_call_of(0, kind, N, D, H, W, Cin, ldx, Cout, Cout, 0, c);
   if (r != BTS_OK) return r;
-  const long V = (long)Do * Ho * Wo;
-  if (gnB > 0) return bts_gn_finalize_partials_(gnp, mean, rstd, N * G, gnB, (double)V * Cout / G, eps, stream);
+  if (bias) c.flags |= IG_FLAG_BIAS;
+  if (wp2 != nullptr) { c.second = CONV_Y2; c.ld2 = ldy2; }
+  const long cw = (bts_conv3d_fwd_workspace(kind, N, D, H, W, Cin, Cout) + 63) & ~63L;
+  c.G = G; c.ws_bytes = cw;
+  ConvPtrs q = {};
+  q.x = x; q.wp = wp; q.bias = bias; q.y = y; q.wp2 = wp2; q.bias2 = bias2; q.y2 = y2; q.ws = ws;
+  q.gnp = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + cw);
+  long gnB = 0;
+  r = conv_run(c, q, stream, &gnB);
+  if (r != BTS_OK) return r;
+  const long V = (long)c.Do * c.Ho * c.Wo;
+  if (gnB > 0) return bts_gn_finalize_partials_(q.gnp, mean, rstd, N * G, gnB, (double)V * Cout / G, eps, stream);
   return bts_gn_stats(y, mean, rstd, ws, ws_bytes, N, V, Cout, G, BTS_GN_SLAB, eps, stream);
 }
 extern "C" int bts_conv3d_fwd_gn(int kind, const float* x, const float* wp_fwd, const float* bias, float* y, void* workspace,
@@ -2041,8 +1996,8 @@ extern "C" int bts_conv3d_fwd_fused2_gn(const float* x, const float* wp_fwd, con
 }
 
 // dx (+)= data gradient of a 3x3x3 stride-1 conv (dy, wp_bwd) + data gradient of a 1x1x1 conv of the SAME input (dy2, wp2_bwd):
-// the two gradient paths of a ResNet block's input (resnet.py:118,134) in one pass over dx.  Falls back to two launches when
-// the tiled kernel would split the contraction or dy2 cannot be read with 16-byte loads.
+// the two gradient paths of a ResNet block's input (resnet.py:118,134) in one pass over dx.  Two calls instead where a kernel of the
+// 3x3x3 gradient may split the contraction (its workspace answer is not 0) or dy2 cannot be read with 16-byte loads.
 extern "C" long bts_conv3d_bwd_data_pair_workspace(int N, int D, int H, int W, int Cin, int Cout) {
   const long a = bts_conv3d_bwd_data_workspace(BTS_CONV_K3S1, N, D, H, W, Cin, Cout);
   const long b = bts_conv3d_bwd_data_workspace(BTS_CONV_K1, N, D, H, W, Cin, Cout);
@@ -2052,38 +2007,56 @@ extern "C" long bts_conv3d_bwd_data_pair_workspace(int N, int D, int H, int W, i
 extern "C" int bts_conv3d_bwd_data_pair(const float* dy, const float* wp_bwd, const float* dy2, const float* wp2_bwd, float* dx,
                                         void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int lddx,
                                         int Cout, int lddy, int lddy2, int flags, hipStream_t stream) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || lddx < Cin || lddy < Cout || lddy2 < Cout) return BTS_ERR_SHAPE;
-  long need = 0;
-  int r = conv_bwd_impl(BTS_CONV_K3S1, nullptr, nullptr, nullptr, nullptr, 0, &need, N, D, H, W, Cin, Cin, Cout, Cout, 0, nullptr);
-  if (r != BTS_OK) return r;
+  ConvCall c;
+  if (conv_call_of(1, BTS_CONV_K3S1, N, D, H, W, Cin, lddx, Cout, lddy, flags, c) != BTS_OK || lddy2 < Cout) return BTS_ERR_SHAPE;
+  const long need = conv_ws_query(1, BTS_CONV_K3S1, N, D, H, W, Cin, Cout);
+  if (need < 0) return BTS_ERR_SHAPE;
+  c.ws_bytes = workspace_bytes;
+  ConvPtrs q = {};
+  q.x = dy; q.wp = wp_bwd; q.y = dx; q.ws = workspace;
   const bool fuse = need == 0 && (Cout % 8 == 0) && (lddy2 % 4 == 0) && ((((uintptr_t)dy2) & 15) == 0) && Cin > 4 &&
                     getenv("BTS_IGEMM_NOPAIR") == nullptr;
   if (fuse) {
-    int f = 0;
-    if (flags & BTS_CONV_FLAG_ACCUM) f |= IG_FLAG_ACCUM;
-    return launch_igemm(GEO_S1, dy, wp_bwd, nullptr, dx, N, D, H, W, Cout, lddy, D, H, W, Cin, lddx, D, H, W, 0, 0, 0, f, stream,
-                        workspace, workspace_bytes, nullptr, wp2_bwd, nullptr, nullptr, 0, nullptr, 0, nullptr, dy2, lddy2);
+    c.second = CONV_X2; c.ld2 = lddy2;
+    q.x2 = dy2; q.wp2 = wp2_bwd;
+    return conv_run(c, q, stream);
   }
-  r = conv_bwd_impl(BTS_CONV_K3S1, dy, wp_bwd, dx, workspace, workspace_bytes, nullptr, N, D, H, W, Cin, lddx, Cout, lddy, flags, stream);
+  const int r = conv_run(c, q, stream);
   if (r != BTS_OK) return r;
-  return conv_bwd_impl(BTS_CONV_K1, dy2, wp2_bwd, dx, workspace, workspace_bytes, nullptr, N, D, H, W, Cin, lddx, Cout, lddy2,
-                       flags | BTS_CONV_FLAG_ACCUM, stream);
+  return bts_conv3d_bwd_data(BTS_CONV_K1, dy2, wp2_bwd, dx, workspace, workspace_bytes, N, D, H, W, Cin, lddx, Cout, lddy2,
+                             flags | BTS_CONV_FLAG_ACCUM, stream);
 }
 
-// Which igemm_kernel<...> instantiation a call resolves to: returns cfg + 8*(KGS==4); cfg ids as in choose_cfg.
+// Which igemm_kernel<...> instantiation the tiled kernel would run a call on: cfg + 8*(KGS==4); cfg ids: IgemmPlan (conv_plan.h).
 // Lets the host attribute measured launch times to kernel symbols (bench.py roofline).
+static int conv_config_query(int dir, int kind, int N, int D, int H, int W, int Cin, int Cout) {
+  ConvCall c;
+  ConvChoice ch;
+  int r = conv_call_of(dir, kind, N, D, H, W, Cin, Cin, Cout, Cout, 0, c);
+  if (r != BTS_OK) return r;
+  conv_query_view(c);
+  r = igemm_accept(c, ch);
+  return r != BTS_OK ? r : ch.sym;
+}
 extern "C" int bts_conv3d_fwd_config(int kind, int N, int D, int H, int W, int Cin, int Cout) {
-  int M;
-  const int geo = geo_of_kind_fwd(kind);
-  int Do = D, Ho = H, Wo = W;
-  if (geo == GEO_DOWN) { Do = D / 2; Ho = H / 2; Wo = W / 2; }
-  return choose_cfg(geo, geo == GEO_UP ? 8 * N : N, Do, Ho, Wo, npad32(Cout), &M) + (geo == GEO_K1 ? 8 : 0);
+  return conv_config_query(0, kind, N, D, H, W, Cin, Cout);
 }
 extern "C" int bts_conv3d_bwd_data_config(int kind, int N, int D, int H, int W, int Cin, int Cout) {
-  int M;
-  int geo = GEO_S1, Do = D, Ho = H, Wo = W;
-  if (kind == BTS_CONV_K1) geo = GEO_K1;
-  else if (kind == BTS_CONV_K3S2) { geo = GEO_UP; Do = D / 2; Ho = H / 2; Wo = W / 2; }
-  else if (kind == BTS_CONV_K3S2T) geo = GEO_DOWN;
-  return choose_cfg(geo, geo == GEO_UP ? 8 * N : N, Do, Ho, Wo, npad32(Cin), &M) + (geo == GEO_K1 ? 8 : 0);
+  return conv_config_query(1, kind, N, D, H, W, Cin, Cout);
+}
+// The profile symbol of the kernel that takes a call first (host only): 20 upm | 21 k1s | 22 dsc | 25 c2 | 23 wino | 27 w3 | the tiled
+// kernel's bts_conv3d_*_config id; a negative value is the status of a call no kernel takes.  Arguments: bts_hip.h.
+extern "C" int bts_conv3d_kernel(int dir, int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int flags, int second,
+                                 int ld2, int G, int aligned, long workspace_bytes) {
+  ConvCall c;
+  ConvChoice ch;
+  int r = conv_call_of(dir != 0, kind, N, D, H, W, Cin, ldx, Cout, ldy, flags, c);
+  if (r != BTS_OK) return r;
+  if (second < 0 || second > CONV_X2 || G < 0) return BTS_ERR_SHAPE;
+  if (second && (c.geo != GEO_S1 || ld2 < c.Cout * (second == CONV_Y2) + c.Cin * (second == CONV_X2))) return BTS_ERR_SHAPE;
+  c.second = second; c.ld2 = second ? ld2 : 0; c.G = G;
+  c.x16 = aligned & 1; c.y16 = (aligned >> 1) & 1; c.p2_16 = (aligned >> 2) & 1; c.ws16 = (aligned >> 3) & 1;
+  c.ws_bytes = workspace_bytes < 0 ? LONG_MAX : workspace_bytes;
+  r = conv_choose(c, ch);
+  return r != BTS_OK ? r : ch.sym;
 }

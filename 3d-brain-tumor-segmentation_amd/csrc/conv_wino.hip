@@ -23,7 +23,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
-#include "bts_internal.h"
+#include "conv_plan.h"
 
 int bts_prof_on();
 void bts_prof_begin(int sym, double flops, hipStream_t stream);
@@ -432,11 +432,7 @@ static int wino_enabled() {  // BTS_WINO=0: every 3x3x3 conv on the implicit GEM
   return e ? atoi(e) : 1;
 }
 
-struct WinoPlan {
-  int xw, ntz, nty, ntx, nb, ksplit, kg_per;
-  long wgs, need;
-};
-// tile geometry and k-split of one call; false = not a Winograd shape
+// tile geometry and k-split of one shape; false = not a Winograd shape
 static bool wino_plan(WinoPlan& q, int N, int D, int H, int W, int Cin, int Cout) {
   if (Cin % 8 != 0 || Cout % 4 != 0 || Cout < 16) return false;
   if (W < 12 || H < 4 || D < 4) return false;  // a narrower grid leaves most matrix columns of a wave empty
@@ -450,31 +446,17 @@ static bool wino_plan(WinoPlan& q, int N, int D, int H, int W, int Cin, int Cout
   q.wgs = (long)N * q.ntz * q.nty * q.ntx * q.nb;
   if (q.wgs > 0x7fffffffL / q.nb) return false;
   // one workgroup per CU at a time: a grid below ~one wave of workgroups is split along the input channels
-  const int KG = Cin / 8;
-  q.ksplit = 1;
-  q.kg_per = KG;
-  q.need = 0;
-  if (q.wgs < 192 && KG >= 8) {
-    int ks = (int)((256 + q.wgs - 1) / q.wgs);
-    if (ks > KG / 4) ks = KG / 4;   // at least 4 stages per workgroup
-    if (ks > 16) ks = 16;
-    if (ks > 1) {
-      const int per = (KG + ks - 1) / ks;
-      ks = (KG + per - 1) / per;
-      if (ks > 1) {
-        q.ksplit = ks;
-        q.kg_per = per;
-        q.need = (long)ks * N * D * H * W * (q.nb * 32) * 4;
-      }
-    }
-  }
+  wino_split(q, N, D, H, W, Cin, 192, 256);
   return true;
 }
-// workspace the Winograd form wants for a call (0 = none / not taken): lets the planner size the buffer for both forms
-long bts_wino_workspace_(int N, int D, int H, int W, int Cin, int Cout) {
+long wino_ws_need(const ConvCall& c) {
   WinoPlan q;
-  if (!wino_enabled() || !wino_plan(q, N, D, H, W, Cin, Cout)) return 0;
-  return q.need;
+  return wino_enabled() && wino_plan(q, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout) ? q.need : 0;
+}
+bool wino_accept(const ConvCall& c, ConvChoice& ch) {
+  if (!wino_enabled() || !wino_call_ok(c) || !wino_plan(ch.w, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout)) return false;
+  ch.sym = 23;
+  return wino_plan_ok(c, ch);
 }
 
 template <int XW>
@@ -487,8 +469,6 @@ static int wino_launch_cfg(const WinoParams& p, const WinoPlan& q, double flops,
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  // (p.up = image base + 27 x the padded (cin, cout) pairs: conv_igemm.hip's image layout; p.KG = Cin / 8, q.nb = cout blocks of 32)
-  { const int e = bts_img_note_use_(p.up - 27L * ((long)p.KG * 2 * (q.nb * 32) * 4), 2u, stream); if (e != BTS_OK) return e; }
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(23, flops, stream);
   (void)hipGetLastError();
@@ -499,47 +479,28 @@ static int wino_launch_cfg(const WinoParams& p, const WinoPlan& q, double flops,
   return BTS_OK;
 }
 
-// Returns BTS_OK when the launch was taken, 1 when declined (the caller runs the implicit GEMM), another code on error.
-// up: the Winograd part of the K3S1 packed image.  gn_B: as launch_igemm's.  ws: split-K workspace (may be NULL).
-int bts_wino_launch_(const float* x, const float* up, const float* bias, float* y, int N, int D, int H, int W, int Cin, int ldx,
-                     int Cout, int ldy, int accum, double* gnp, int gnG, long* gn_B, void* ws, long ws_bytes, hipStream_t stream) {
-  if (!wino_enabled()) return 1;
-  if (ldx % 4 != 0 || ldy % 4 != 0) return 1;
-  if ((((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return 1;
-  if (((long)(D + 2) * H * W + 64) * (long)ldx * 4 >= 0x7fffffffL) return 1;  // 31-bit byte offsets inside one volume
-  WinoPlan q;
-  if (!wino_plan(q, N, D, H, W, Cin, Cout)) return 1;
-  {  // the output side forms 31-bit byte offsets too: voxel index * (ldy, or the padded split-K row) * 4, 0x80000000 = masked lane
-    const long orow = (long)ldy > (long)q.nb * 32 ? (long)ldy : (long)q.nb * 32;
-    if (((long)D * H * W + 64) * orow * 4 >= 0x7fffffffL) return 1;
-  }
-  if (q.ksplit > 1 && (ws == nullptr || ws_bytes < q.need || (((uintptr_t)ws) & 15))) { q.ksplit = 1; q.kg_per = Cin / 8; }
-  int min_wgs = 192;
-  { const char* e = getenv("BTS_WINO_MIN_WGS"); if (e) min_wgs = atoi(e); }
-  if (q.wgs * q.ksplit < min_wgs) return 1;
+// The launch wino_accept planned.  q.wp: the K3S1 packed image; its Winograd part starts 27 x the padded (cin, cout) pairs in
+// (conv_igemm.hip's image layout).  q.ws: the split-K workspace of ch.ws bytes.
+int bts_wino_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
+  const WinoPlan& pl = ch.w;
+  const int N = c.N, D = c.Di, H = c.Hi, W = c.Wi, Cin = c.Cin, Cout = c.Cout;
+  const float* bias = (c.flags & IG_FLAG_BIAS) ? q.bias : nullptr;
+  const int accum = (c.flags & IG_FLAG_ACCUM) ? 1 : 0;
   WinoParams p;
-  p.x = x; p.up = up; p.bias = bias; p.y = y;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = ldx; p.Cout = Cout; p.ldy = ldy; p.KG = Cin / 8;
-  p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx;
+  p.x = q.x; p.up = q.wp + 27L * ((long)(Cin / 8) * 2 * (pl.nb * 32) * 4); p.bias = bias; p.y = q.y;
+  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = c.ldx; p.Cout = Cout; p.ldy = c.ldy; p.KG = Cin / 8;
+  p.ntz = pl.ntz; p.nty = pl.nty; p.ntx = pl.ntx;
   p.accum = accum;
-  p.ksplit = q.ksplit; p.kg_per = q.kg_per; p.Npad = q.nb * 32; p.part = reinterpret_cast<float*>(ws);
-  p.nb = q.nb; p.ntiles = N * q.ntz * q.nty * q.ntx; p.tiles_per_xcd = (p.ntiles + 7) / 8;
+  p.ksplit = pl.ksplit; p.kg_per = pl.kg_per; p.Npad = pl.nb * 32; p.part = reinterpret_cast<float*>(q.ws);
+  p.nb = pl.nb; p.ntiles = N * pl.ntz * pl.nty * pl.ntx; p.tiles_per_xcd = (p.ntiles + 7) / 8;
   // items per workgroup: as many as leave every CU (32 per XCD, one workgroup each at a time) at least two workgroups
   {
-    const long per_cu = ((long)p.tiles_per_xcd * q.nb) / 32;
-    p.T = q.ksplit > 1 ? 1 : (per_cu >= 8 ? 4 : per_cu >= 4 ? 2 : 1);
+    const long per_cu = ((long)p.tiles_per_xcd * pl.nb) / 32;
+    p.T = pl.ksplit > 1 ? 1 : (per_cu >= 8 ? 4 : per_cu >= 4 ? 2 : 1);
   }
-  p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1;
-  if (q.ksplit == 1 && gnp != nullptr && gnG > 0 && D % gnG == 0 && (D / gnG) % 4 == 0 && getenv("BTS_IGEMM_NOGNFUSE") == nullptr) {
-    p.gnp = gnp; p.gn_G = gnG; p.gn_zt = (D / gnG) / 4;
-  }
+  p.gnp = pl.gn_zt ? q.gnp : nullptr; p.gn_G = pl.gn_zt ? c.G : 0; p.gn_zt = pl.gn_zt ? pl.gn_zt : 1;
   const double flops = 2.0 * 27 * Cin * Cout * (double)N * D * H * W;
-  const int r = (q.xw == 32) ? wino_launch_cfg<32>(p, q, flops, stream) : wino_launch_cfg<16>(p, q, flops, stream);
-  if (r != BTS_OK) return r;
-  if (q.ksplit > 1) {
-    const int rr = bts_igemm_reduce_(p.part, bias, y, (long)N * D * H * W, Cout, p.Npad, ldy, q.ksplit, bias != nullptr, accum, stream);
-    if (rr != BTS_OK) return rr;
-  }
-  if (gn_B && p.gnp != nullptr) *gn_B = (long)p.gn_zt * q.nty * q.ntx * q.nb;
-  return BTS_OK;
+  const int r = (pl.xw == 32) ? wino_launch_cfg<32>(p, pl, flops, stream) : wino_launch_cfg<16>(p, pl, flops, stream);
+  if (r != BTS_OK || pl.ksplit == 1) return r;
+  return bts_igemm_reduce_(p.part, bias, q.y, (long)N * D * H * W, Cout, p.Npad, c.ldy, pl.ksplit, bias != nullptr, accum, stream);
 }

@@ -29,7 +29,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
-#include "bts_internal.h"
+#include "conv_plan.h"
 #include "wino_util.h"
 
 int bts_prof_on();
@@ -403,10 +403,6 @@ static int w3_enabled() {  // BTS_WINO=0: no Winograd form at all; BTS_W3=0: thi
   return e ? atoi(e) : 1;
 }
 
-struct W3Plan {
-  int ntz, nty, ntx, nb, ksplit, kg_per;
-  long wgs, need;
-};
 static bool w3_plan(W3Plan& q, int N, int D, int H, int W, int Cin, int Cout) {
   if (Cin % 8 != 0 || Cout % 4 != 0 || Cout < 16) return false;
   if (W < 12 || H < 4 || D < 4) return false;
@@ -416,70 +412,43 @@ static bool w3_plan(W3Plan& q, int N, int D, int H, int W, int Cin, int Cout) {
   q.nb = (Cout + 31) / 32;
   q.wgs = (long)N * q.ntz * q.nty * q.ntx * q.nb;
   if (q.wgs > 0x7fffffffL / 16) return false;
-  const int KG = Cin / 8;
-  q.ksplit = 1;
-  q.kg_per = KG;
-  q.need = 0;
-  if (q.wgs < 384 && KG >= 8) {
-    int ks = (int)((512 + q.wgs - 1) / q.wgs);
-    if (ks > KG / 4) ks = KG / 4;
-    if (ks > 16) ks = 16;
-    if (ks > 1) {
-      const int per = (KG + ks - 1) / ks;
-      ks = (KG + per - 1) / per;
-      if (ks > 1) {
-        q.ksplit = ks;
-        q.kg_per = per;
-        q.need = (long)ks * N * D * H * W * (q.nb * 32) * 4;
-      }
-    }
-  }
+  wino_split(q, N, D, H, W, Cin, 384, 512);
   return true;
 }
-long bts_w3_workspace_(int N, int D, int H, int W, int Cin, int Cout) {
+long w3_ws_need(const ConvCall& c) {
   W3Plan q;
-  if (!w3_enabled() || !w3_plan(q, N, D, H, W, Cin, Cout)) return 0;
-  return q.need;
+  return w3_enabled() && w3_plan(q, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout) ? q.need : 0;
+}
+bool w3_accept(const ConvCall& c, ConvChoice& ch) {
+  if (!w3_enabled() || !wino_call_ok(c) || !w3_plan(ch.w, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout)) return false;
+  ch.sym = 27;
+  return wino_plan_ok(c, ch);
 }
 
-// Returns BTS_OK when the launch was taken, 1 when declined (the caller offers conv_wino.hip, then the implicit GEMM).
-// up3: the third part of the K3S1 packed image.
-int bts_w3_launch_(const float* x, const float* up3, const float* bias, float* y, int N, int D, int H, int W, int Cin, int ldx,
-                   int Cout, int ldy, int accum, double* gnp, int gnG, long* gn_B, void* ws, long ws_bytes, hipStream_t stream) {
-  if (!w3_enabled()) return 1;
-  if (ldx % 4 != 0 || ldy % 4 != 0) return 1;
-  if ((((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return 1;
-  if (((long)(D + 2) * H * W + 64) * (long)ldx * 4 >= 0x7fffffffL) return 1;
-  W3Plan q;
-  if (!w3_plan(q, N, D, H, W, Cin, Cout)) return 1;
-  {  // the output side forms 31-bit byte offsets too: voxel index * (ldy, or the padded split-K row) * 4, 0x80000000 = masked lane
-    const long orow = (long)ldy > (long)q.nb * 32 ? (long)ldy : (long)q.nb * 32;
-    if (((long)D * H * W + 64) * orow * 4 >= 0x7fffffffL) return 1;
-  }
-  if (q.ksplit > 1 && (ws == nullptr || ws_bytes < q.need || (((uintptr_t)ws) & 15))) { q.ksplit = 1; q.kg_per = Cin / 8; }
-  int min_wgs = 192;
-  { const char* e = getenv("BTS_WINO_MIN_WGS"); if (e) min_wgs = atoi(e); }
-  if (q.wgs * q.ksplit < min_wgs) return 1;
+// The launch w3_accept planned.  q.wp: the K3S1 packed image; its third part starts (27 + 48) x the padded (cin, cout) pairs in
+// (conv_igemm.hip's image layout).  q.ws: the split-K workspace of ch.ws bytes.
+int bts_w3_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
+  const W3Plan& pl = ch.w;
+  const int N = c.N, D = c.Di, H = c.Hi, W = c.Wi, Cin = c.Cin, Cout = c.Cout;
+  const float* bias = (c.flags & IG_FLAG_BIAS) ? q.bias : nullptr;
+  const int accum = (c.flags & IG_FLAG_ACCUM) ? 1 : 0;
   W3Params p;
-  p.x = x; p.up = up3; p.bias = bias; p.y = y;
-  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = ldx; p.Cout = Cout; p.ldy = ldy; p.KG = Cin / 8;
-  p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx;
+  p.x = q.x; p.up = q.wp + 75L * ((long)(Cin / 8) * 2 * (pl.nb * 32) * 4); p.bias = bias; p.y = q.y;
+  p.N = N; p.D = D; p.H = H; p.W = W; p.ldx = c.ldx; p.Cout = Cout; p.ldy = c.ldy; p.KG = Cin / 8;
+  p.ntz = pl.ntz; p.nty = pl.nty; p.ntx = pl.ntx;
   p.accum = accum;
-  p.ksplit = q.ksplit; p.kg_per = q.kg_per; p.Npad = q.nb * 32; p.part = reinterpret_cast<float*>(ws);
-  p.nb = q.nb; p.ntiles = N * q.ntz * q.nty * q.ntx; p.tiles_per_xcd = (p.ntiles + 7) / 8;
-  p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1;
-  if (q.ksplit == 1 && gnp != nullptr && gnG > 0 && D % gnG == 0 && (D / gnG) % 4 == 0 && getenv("BTS_IGEMM_NOGNFUSE") == nullptr) {
-    p.gnp = gnp; p.gn_G = gnG; p.gn_zt = (D / gnG) / 4;
-  }
+  p.ksplit = pl.ksplit; p.kg_per = pl.kg_per; p.Npad = pl.nb * 32; p.part = reinterpret_cast<float*>(q.ws);
+  p.nb = pl.nb; p.ntiles = N * pl.ntz * pl.nty * pl.ntx; p.tiles_per_xcd = (p.ntiles + 7) / 8;
+  p.gnp = pl.gn_zt ? q.gnp : nullptr; p.gn_G = pl.gn_zt ? c.G : 0; p.gn_zt = pl.gn_zt ? pl.gn_zt : 1;
   static bool attr_done = false;
   const size_t shmem = (2 * W3BUF + W3EX + 64 + 16) * sizeof(float);
   // items per workgroup (chaining needs two stages per item): each XCD runs 32 workgroups at a time (one per CU), so a launch
   // takes ceil(workgroups per XCD / 32) rounds of T items; the T <= 8 with the fewest item-times wins, ties go to the larger T
   // (fewer un-overlapped first fetches)
   {
-    const long items = (long)p.tiles_per_xcd * q.nb;
+    const long items = (long)p.tiles_per_xcd * pl.nb;
     p.T = 1;
-    if (q.ksplit == 1 && p.KG >= 2) {
+    if (pl.ksplit == 1 && p.KG >= 2) {
       long best = -1;
       for (int t = 1; t <= 8; ++t) {
         const long rounds = ((items + t - 1) / t + 31) / 32;
@@ -490,25 +459,19 @@ int bts_w3_launch_(const float* x, const float* up3, const float* bias, float* y
       if (e && atoi(e) > 0) p.T = atoi(e);
     }
   }
-  const long wgs_per_xcd = ((long)p.tiles_per_xcd * q.nb + p.T - 1) / p.T;
+  const long wgs_per_xcd = ((long)p.tiles_per_xcd * pl.nb + p.T - 1) / p.T;
   if (!attr_done) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(w3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  // (up3 = image base + (27 + 48) x the padded (cin, cout) pairs: conv_igemm.hip's image layout)
-  { const int e = bts_img_note_use_(up3 - 75L * ((long)((Cin + 7) / 8) * 2 * (((Cout + 31) / 32) * 32) * 4), 4u, stream); if (e != BTS_OK) return e; }
   const double flops = 2.0 * 27 * Cin * Cout * (double)N * D * H * W;
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(27, flops, stream);
   (void)hipGetLastError();
-  hipLaunchKernelGGL(w3_kernel, dim3((unsigned)(8L * wgs_per_xcd), 1, q.ksplit), dim3(256), shmem, stream, p);
+  hipLaunchKernelGGL(w3_kernel, dim3((unsigned)(8L * wgs_per_xcd), 1, pl.ksplit), dim3(256), shmem, stream, p);
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
-  if (q.ksplit > 1) {
-    const int rr = bts_igemm_reduce_(p.part, bias, y, (long)N * D * H * W, Cout, p.Npad, ldy, q.ksplit, bias != nullptr, accum, stream);
-    if (rr != BTS_OK) return rr;
-  }
-  if (gn_B && p.gnp != nullptr) *gn_B = (long)p.gn_zt * q.nty * q.ntx * q.nb;
-  return BTS_OK;
+  if (pl.ksplit == 1) return BTS_OK;
+  return bts_igemm_reduce_(p.part, bias, q.y, (long)N * D * H * W, Cout, p.Npad, c.ldy, pl.ksplit, bias != nullptr, accum, stream);
 }

@@ -92,6 +92,16 @@ int bts_conv3d_bwd_data(int kind, const float* dy, const float* wp_bwd, float* d
  * used by bench.py to attribute measured launch times to kernel symbols */
 int bts_conv3d_fwd_config(int kind, int N, int D, int H, int W, int Cin, int Cout);
 int bts_conv3d_bwd_data_config(int kind, int N, int D, int H, int W, int Cin, int Cout);
+/* Host only: the profile symbol (bts_profile_get) of the kernel that takes a call first -- 20 merged transposed | 21 streaming 1x1x1 |
+ * 22 direct <= 4 couts | 25 two-channel input | 23 Winograd F(2x2,3x3) x direct | 27 Winograd F(2x2x2,3x3x3) | the tiled kernel's
+ * bts_conv3d_*_config id -- or the negative status of a call no kernel takes.  dir 0: bts_conv3d_fwd's kind, sizes, ldx, ldy and flags;
+ * dir 1: bts_conv3d_bwd_data's (ldx = lddx, ldy = lddy).  second: 0 | 1 the fused shortcut output of bts_conv3d_fwd_fused2 (ld2 = ldy2) |
+ * 2 the second input of bts_conv3d_bwd_data_pair (ld2 = lddy2), both BTS_CONV_K3S1 only.  G > 0: GroupNorm partials asked for
+ * (bts_conv3d_fwd_gn).  aligned: bit 0 the tensor read, 1 the tensor written, 2 y2 | dy2, 3 the workspace lies on a 16-byte boundary.
+ * workspace_bytes: what the call may use, 0 none, < 0 as much as it asks for.  The BTS_WINO, BTS_W3, BTS_WINO_MIN_WGS, BTS_IGEMM_*
+ * environment switches are read per call, as the launches read them. */
+int bts_conv3d_kernel(int dir, int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int flags, int second,
+                      int ld2, int G, int aligned, long workspace_bytes);
 long bts_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout);
 /* dw in the reference layout (Cin_ref = Cin + dup_shift); db (may be NULL; not produced for K3S2T: use bts_colsum). */
 int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, float* dw, float* db, void* workspace,

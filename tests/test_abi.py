@@ -67,6 +67,10 @@ def test_argument_validation_without_gpu(cdll):
     assert L._bts_adam_tf_step(None, None, None, None, 0, 1e-4, 0.9, 0.999, 1e-7, 1.0, None) == -1
     # kernel-symbol query used by bench.py
     assert L._bts_conv3d_fwd_config(1, 1, 128, 128, 128, 32, 32) == 0
+    # ... and the kernel that takes the call first (dense, aligned, any workspace): here the Winograd F(2x2x2,3x3x3) form, symbol 27
+    assert 'bts_conv3d_kernel' in declared_symbols()
+    assert L._bts_conv3d_kernel(0, 1, 1, 128, 128, 128, 32, 32, 32, 32, 0, 0, 0, 0, 15, -1) == 27
+    assert L._bts_conv3d_kernel(0, 1, 0, 128, 128, 128, 32, 32, 32, 32, 0, 0, 0, 0, 15, -1) == -1
     # split-K planning is host-only: the VAE's 1024->16 stride-2 conv on 16^3 needs a workspace, the 128^3 convs do not
     assert L._bts_conv3d_fwd_workspace(2, 1, 16, 16, 16, 1024, 16) > 0
     assert L._bts_conv3d_fwd_workspace(1, 1, 128, 128, 128, 32, 32) == 0

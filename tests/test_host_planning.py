@@ -252,3 +252,120 @@ def test_pack_descriptor_tables_are_written_inside_their_bounds(L):
                 assert r > 0, (kind, role, ci, co, r)      # = blocks of this entry
             first += r
         assert buf.raw[nb * len(shapes):] == b'\xa5' * guard
+
+
+# ---- the fp32 conv engine's dispatch: bts_conv3d_kernel answers from the choice the launches run on ----
+SYM = dict(upm=20, k1s=21, dsc=22, wino=23, c2=25, w3=27)
+TILED = tuple(range(5)) + tuple(range(8, 13))      # igemm_kernel config ids, + 8: the 1x1x1 staging variant
+CONV_SWITCHES = ('BTS_WINO', 'BTS_W3', 'BTS_WINO_MIN_WGS', 'BTS_IGEMM_DSC_MIN', 'BTS_IGEMM_C2_MIN', 'BTS_IGEMM_K1S_MIN', 'BTS_IGEMM_UPM_MIN',
+                 'BTS_IGEMM_NOGNFUSE', 'BTS_IGEMM_NOPAIR')
+FWD, BWD, Y2, X2, SIGMOID = 0, 1, 1, 2, 1
+
+
+def conv_kernel(L, direction, kind, N, D, H, W, ci, co, flags=0, second=0, groups=0, aligned=15, ws=-1, ldx=None, ldy=None, ld2=None):
+    """bts_conv3d_kernel on dense rows unless told otherwise; aligned: bit 0 read, 1 written, 2 second operand, 3 workspace; ws < 0: all it asks"""
+    if ld2 is None:
+        ld2 = 0 if not second else (co if (second == Y2) == (direction == FWD) else ci)
+    return L._bts_conv3d_kernel(direction, kind, N, D, H, W, ci, ldx or ci, co, ldy or co, flags, second, ld2, groups, aligned, ws)
+
+
+@pytest.fixture
+def default_switches(monkeypatch):
+    for name in CONV_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    return monkeypatch
+
+
+@pytest.mark.parametrize('grid', GRIDS, ids=lambda g: '%dx%dx%dx%d' % g)
+def test_conv_kernel_query_is_deterministic_and_agrees_with_the_config_queries(L, grid, default_switches):
+    """every layer shape, forward and data gradient: the same kernel twice, a known symbol, and where it is the tiled kernel the
+    config the bts_conv3d_*_config queries (bench.py's attribution) name"""
+    for (kind, N, D, H, W, ci, co) in layer_shapes(*grid):
+        for direction, cfg in ((FWD, L._bts_conv3d_fwd_config), (BWD, L._bts_conv3d_bwd_data_config)):
+            k = conv_kernel(L, direction, kind, N, D, H, W, ci, co)
+            assert k == conv_kernel(L, direction, kind, N, D, H, W, ci, co), (direction, kind, N, D, H, W, ci, co)
+            assert k in TILED or k in SYM.values(), (direction, kind, N, D, H, W, ci, co, k)
+            if k in TILED:
+                assert k == cfg(kind, N, D, H, W, ci, co), (direction, kind, N, D, H, W, ci, co, k)
+            assert (k >= 8 and k in TILED) <= (kind == 0)
+            if kind == 1:      # the forms of the 3x3x3 stride-1 call name a kernel too (or the tiled kernel's refusal of the fused pair)
+                for second in ((Y2,) if direction == FWD else (X2,)):
+                    k2 = conv_kernel(L, direction, kind, N, D, H, W, ci, co, second=second)
+                    assert k2 == conv_kernel(L, direction, kind, N, D, H, W, ci, co, second=second)
+                    assert k2 in TILED or k2 in SYM.values() or k2 == -3, (direction, N, D, H, W, ci, co, second, k2)
+                kg = conv_kernel(L, direction, kind, N, D, H, W, ci, co, groups=G)
+                assert kg == k, (direction, N, D, H, W, ci, co, k, kg)      # asking for GroupNorm partials never changes the kernel
+
+
+@pytest.mark.parametrize('grid', GRIDS, ids=lambda g: '%dx%dx%dx%d' % g)
+def test_can_fuse_is_the_tiled_kernels_answer_to_the_fused_pair(L, grid, default_switches):
+    """bts_conv3d_fwd_can_fuse is 0 exactly where the tiled kernel, were the fused-shortcut call left to it, would run cfg 1 and refuse
+    (BTS_ERR_UNSUPPORTED).  It answers for every switch setting, so the equivalence is read with the Winograd forms off; with them on,
+    a refused call still always has can_fuse == 0 (the forms take the pair as two launches wherever they accept the 3x3x3 part)."""
+    seen = set()
+    for (kind, N, D, H, W, ci, co) in layer_shapes(*grid):
+        if kind != 1:
+            continue
+        fuse = L._bts_conv3d_fwd_can_fuse(N, D, H, W, ci, co)
+        k_on = conv_kernel(L, FWD, 1, N, D, H, W, ci, co, second=Y2)
+        default_switches.setenv('BTS_WINO', '0')
+        k_off = conv_kernel(L, FWD, 1, N, D, H, W, ci, co, second=Y2)
+        default_switches.delenv('BTS_WINO')
+        assert fuse == L._bts_conv3d_fwd_can_fuse(N, D, H, W, ci, co)
+        assert (fuse == 0) == (k_off == -3), (N, D, H, W, ci, co, fuse, k_off)
+        assert k_off == -3 or k_off == SYM['c2'] or (k_off in TILED and k_off != 1), (N, D, H, W, ci, co, k_off)
+        assert k_on != -3 or fuse == 0, (N, D, H, W, ci, co, fuse, k_on)
+        seen.add(fuse)
+    assert seen == {0, 1}      # (every grid has layers of both sorts)
+
+
+def test_conv_dispatch_facts_of_the_plan_table(L, default_switches):
+    """DESIGN "Dispatch plan", at 1 x 128^3"""
+    S = (1, 128, 128, 128)
+    assert conv_kernel(L, FWD, 1, *S, 32, 2) == SYM['dsc']
+    assert conv_kernel(L, FWD, 1, *S, 2, 32) == SYM['c2']
+    assert conv_kernel(L, FWD, 1, *S, 2, 32, second=Y2) == SYM['c2']      # ... with the fused shortcut output in the same launch
+    assert conv_kernel(L, FWD, 1, *S, 32, 32) == SYM['w3']
+    assert conv_kernel(L, BWD, 1, *S, 32, 32) == SYM['w3']
+    assert conv_kernel(L, FWD, 1, *S, 32, 32, flags=SIGMOID) in TILED      # never a Winograd form with the sigmoid
+    assert conv_kernel(L, FWD, 0, *S, 32, 32) == SYM['k1s']
+    assert conv_kernel(L, FWD, 0, 1, 16, 16, 16, 32, 32) in range(8, 13)
+    default_switches.setenv('BTS_W3', '0')
+    assert conv_kernel(L, FWD, 1, *S, 32, 32) == SYM['wino']
+    assert conv_kernel(L, FWD, 1, *S, 32, 32, flags=SIGMOID) in TILED
+    default_switches.setenv('BTS_WINO', '0')
+    assert conv_kernel(L, FWD, 1, *S, 32, 32) == L._bts_conv3d_fwd_config(1, *S, 32, 32) == 0
+    default_switches.delenv('BTS_W3')      # BTS_WINO=0 alone switches both forms off
+    assert conv_kernel(L, FWD, 1, *S, 32, 32) == 0
+    assert conv_kernel(L, FWD, 1, *S, 32, 2) == SYM['dsc'] and conv_kernel(L, FWD, 1, *S, 2, 32) == SYM['c2']
+
+
+def test_conv_kernel_query_sees_what_the_operands_allow(L, default_switches):
+    """a query never names a kernel whose launcher would refuse the call: a misaligned or oddly strided x sends a Winograd, streaming or
+    direct shape to the tiled kernel, and a split-K shape without a usable workspace gets the kernel that runs unsplit"""
+    S = (1, 128, 128, 128)
+    X_OFF, NO_WS = 14, 0
+    for direction in (FWD, BWD):
+        assert conv_kernel(L, direction, 1, *S, 32, 32, aligned=X_OFF) == 0
+        assert conv_kernel(L, direction, 1, *S, 32, 32, ldx=34) == 0
+        assert conv_kernel(L, direction, 0, *S, 32, 32, aligned=X_OFF) == 8
+    assert conv_kernel(L, FWD, 1, *S, 32, 32, aligned=13) == 0                  # y off its 16-byte boundary
+    assert conv_kernel(L, FWD, 1, *S, 32, 2, aligned=X_OFF) in TILED            # dsc reads 16-byte rows
+    assert conv_kernel(L, FWD, 1, *S, 2, 32, aligned=13) in TILED               # c2 stores them
+    assert conv_kernel(L, FWD, 1, *S, 2, 32, second=Y2, aligned=11) in TILED    # ... to y2 as well
+    # 256 -> 256 at 16^3: 128 Winograd workgroups -- the F(2x2x2,3x3x3) form takes the call only with its 4-way split-K workspace
+    T = (1, 16, 16, 16, 256, 256)
+    need = L._bts_conv3d_fwd_workspace(1, *T)
+    assert need > 0
+    assert conv_kernel(L, FWD, 1, *T) == conv_kernel(L, FWD, 1, *T, ws=need) == SYM['w3']
+    for kw in (dict(ws=NO_WS), dict(ws=need - 4), dict(ws=need, aligned=7)):      # none, short, misaligned
+        assert conv_kernel(L, FWD, 1, *T, **kw) in TILED, kw
+    assert conv_kernel(L, FWD, 1, *T, ws=NO_WS) == L._bts_conv3d_fwd_config(1, *T)
+    # the merged transposed kernel needs its split-K workspace on a small grid too: without it the tiled kernel runs the 8 classes
+    U = (1, 8, 8, 8, 256, 128)
+    assert L._bts_conv3d_fwd_workspace(3, *U) > 0
+    assert conv_kernel(L, FWD, 3, *U) == SYM['upm'] and conv_kernel(L, FWD, 3, *U, ws=NO_WS) in TILED
+    assert conv_kernel(L, FWD, 3, *U, aligned=X_OFF) in TILED
+    # statuses come back as they do from the launch: odd extents under stride 2, rows narrower than the channels
+    assert conv_kernel(L, FWD, 2, 1, 7, 8, 8, 32, 32) == -1 and conv_kernel(L, FWD, 1, *S, 32, 32, ldx=16) == -1
+    assert conv_kernel(L, FWD, 2, 1, 8, 8, 8, 32, 32, second=Y2) == -1          # the second forms exist for 3x3x3 stride 1 only

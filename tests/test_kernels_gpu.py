@@ -639,3 +639,96 @@ def test_conv_two_channel_input(monkeypatch, n, dims, cout):
     flat = r3.reshape(n, g, -1)
     check_close(mean, flat.mean(dim=2).reshape(-1), 'c2 GN mean', rtol=2e-5, atol=2e-5)
     check_close(rstd, (1.0 / torch.sqrt(flat.var(dim=2, unbiased=False) + 1e-5)).reshape(-1), 'c2 GN rstd', rtol=2e-5, atol=2e-5)
+
+
+ROUTE_SWITCHES = ('BTS_WINO', 'BTS_W3', 'BTS_WINO_MIN_WGS', 'BTS_IGEMM_DSC_MIN', 'BTS_IGEMM_C2_MIN', 'BTS_IGEMM_K1S_MIN', 'BTS_IGEMM_UPM_MIN',
+                  'BTS_IGEMM_NOGNFUSE', 'BTS_IGEMM_NOPAIR')
+# route: kind, (D, H, W), Cin, Cout, switches, the kernel the route is named after ('igemm': a tiled config)
+ROUTES = {
+    'w3': (1, (8, 8, 32), 32, 32, dict(BTS_WINO_MIN_WGS='1'), 'w3_kernel'),
+    'wino': (1, (8, 8, 32), 32, 32, dict(BTS_WINO_MIN_WGS='1', BTS_W3='0'), 'wino_kernel'),
+    'igemm': (1, (8, 8, 32), 32, 32, dict(BTS_WINO='0'), 'igemm_kernel'),
+    'dsc': (1, (8, 8, 32), 8, 2, dict(BTS_IGEMM_DSC_MIN='1'), 'dsc_kernel'),
+    'c2': (1, (8, 8, 32), 2, 32, dict(BTS_IGEMM_C2_MIN='1'), 'c2_kernel'),
+    'upm': (3, (4, 4, 8), 8, 8, dict(BTS_IGEMM_UPM_MIN='1'), 'upm_kernel'),
+    'k1s': (0, (8, 8, 32), 8, 8, dict(BTS_IGEMM_K1S_MIN='1'), 'k1s_kernel'),
+}
+
+
+def _route_env(monkeypatch, env):
+    for k in ROUTE_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _profiled(fn):
+    from bts_amd import ops
+    ops.profile_enable(True)
+    out = fn()
+    torch.cuda.synchronize()
+    ops.profile_enable(False)
+    return out, [s for s, _, _ in ops.profile_records()]
+
+
+def _named(direction, kind, n, dims, cin, cout, second=0):
+    """the kernel bts_conv3d_kernel names for a call on dense, aligned tensors with the workspace its query sizes"""
+    from bts_amd import ops
+    from bts_amd._lib import lib
+    ld2 = cout if second else 0      # (y2 and dy2 both have the forward output's channels)
+    sym = lib()._bts_conv3d_kernel(direction, kind, n, dims[0], dims[1], dims[2], cin, cin, cout, cout, 0, second, ld2, 0, 15, -1)
+    assert sym >= 0, sym
+    return ops.kernel_symbol(sym)
+
+
+@pytest.mark.parametrize('route', sorted(ROUTES))
+def test_conv_runs_the_kernel_the_dispatch_query_names(monkeypatch, route):
+    """one forward call per route of the fp32 dispatch, at the smallest shape its kernel takes with the thresholds forced down: the
+    launch recorded by the profiler is the one bts_conv3d_kernel names, and the result meets the oracle"""
+    from bts_amd import ops
+    kind, dims, cin, cout, env, want = ROUTES[route]
+    _route_env(monkeypatch, env)
+    n, (d, h, w) = 1, dims
+    x, wt, b = rnd((n, d, h, w, cin), 91), rnd(wshape(kind, cin, cout), 92, 0.2), rnd((cout,), 93)
+    named = _named(0, kind, n, dims, cin, cout)
+    assert named.startswith(want), (route, named)
+    wp = ops.conv_pack(kind, ops.ROLE_FWD, wt.to(dev()), cin, cout)
+    y, names = _profiled(lambda: ops.conv_fwd(kind, x.to(dev()), wp, b.to(dev()), cout))
+    assert names == [named], (route, names, named)
+    check_contraction(y, ref_conv(kind, x.double(), wt.double(), b.double()), ref_conv(kind, x.double().abs(), wt.double().abs(), b.double().abs()),
+                      'route ' + route)
+
+
+@pytest.mark.parametrize('form,w3', [('shortcut', '1'), ('shortcut', '0'), ('pair', '1'), ('pair', '0')])
+def test_conv_second_form_behind_a_winograd_kernel_is_a_1x1x1_launch(monkeypatch, form, w3):
+    """the fused shortcut output and the data-gradient pair with a Winograd form taking the 3x3x3 part: two launches, the Winograd
+    kernel bts_conv3d_kernel names for the call and then the kernel it names for the 1x1x1 part, both results against the oracle"""
+    from bts_amd import ops
+    _route_env(monkeypatch, dict(BTS_WINO_MIN_WGS='1', BTS_W3=w3))
+    n, dims, cin, cout = 1, (8, 8, 32), 32, 32
+    d, h, w = dims
+    w3x3, w1x1 = rnd((3, 3, 3, cin, cout), 95, 0.2), rnd((1, 1, 1, cin, cout), 96, 0.3)
+    direction, second = (0, 1) if form == 'shortcut' else (1, 2)
+    first, then = _named(direction, 1, n, dims, cin, cout, second), _named(direction, 0, n, dims, cin, cout)
+    assert first == ('w3_kernel' if w3 == '1' else 'wino_kernel') and then.startswith('igemm_kernel')
+    if form == 'shortcut':
+        x, b3, b1 = rnd((n, d, h, w, cin), 94), rnd((cout,), 97), rnd((cout,), 98)
+        wp3 = ops.conv_pack(ops.K3S1, ops.ROLE_FWD, w3x3.to(dev()), cin, cout)
+        wp1 = ops.conv_pack(ops.K1, ops.ROLE_FWD, w1x1.to(dev()), cin, cout)
+        (c1, res), names = _profiled(lambda: ops.conv_fwd_fused2(x.to(dev()), wp3, b3.to(dev()), wp1, b1.to(dev()), cout))
+        assert names == [first, then], names
+        xd, xa = x.double(), x.double().abs()
+        check_contraction(c1, R.conv3d(xd, w3x3.double(), b3.double()), R.conv3d(xa, w3x3.double().abs(), b3.double().abs()), 'shortcut pair conv3')
+        check_contraction(res, R.conv3d(xd, w1x1.double(), b1.double()), R.conv3d(xa, w1x1.double().abs(), b1.double().abs()), 'shortcut pair conv1')
+    else:
+        x = rnd((n, d, h, w, cin), 94).double().requires_grad_(True)
+        dy, dy2 = rnd((n, d, h, w, cout), 97), rnd((n, d, h, w, cout), 98)
+        ((R.conv3d(x, w3x3.double(), None) * dy.double()).sum() + (R.conv3d(x, w1x1.double(), None) * dy2.double()).sum()).backward()
+        xa = x.detach().abs().requires_grad_(True)
+        ((R.conv3d(xa, w3x3.double().abs(), None) * dy.double().abs()).sum() + (R.conv3d(xa, w1x1.double().abs(), None) * dy2.double().abs()).sum()).backward()
+        wpb3 = ops.conv_pack(1, ops.ROLE_BWD, w3x3.to(dev()), cin, cout)
+        wpb1 = ops.conv_pack(0, ops.ROLE_BWD, w1x1.to(dev()), cin, cout)
+        dx = torch.empty((n, d, h, w, cin), device=dev())
+        _, names = _profiled(lambda: ops.conv_bwd_data_pair(dy.to(dev()), wpb3, dy2.to(dev()), wpb1, dx, False))
+        assert names == [first, then], names
+        check_contraction(dx, x.grad, xa.grad, 'data-gradient pair')
