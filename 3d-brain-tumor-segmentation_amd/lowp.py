@@ -160,10 +160,13 @@ def conv(kind, code, tdt, x, wp, bias, cout, out=None):
     return out
 
 
-def wgrad_supported(kind, cin, cout):
+def wgrad_supported(kind, cin, cout, extents=None):
     """shapes the 16-bit weight-gradient kernels take, asked before anything runs (the trainer decides the fp32 route from it).  It mirrors
     lp_wg_args of csrc/lowp_wg.hip: channel counts in whole 16-byte chunks (BTS_ERR_SHAPE otherwise) and, for the stride-1 3x3x3 / 1x1x1
-    kinds whose bias gradient comes from bts_lp_colsum, a Cout <= 256 whose chunks divide the 256-thread block"""
+    kinds whose bias gradient comes from bts_lp_colsum, a Cout <= 256 whose chunks divide the 256-thread block.  extents: (d, h, w) of
+    the forward input, which the stride-2 kind needs -- its transposing-read kernel takes even extents only"""
+    if kind == ops.K3S2 and any(v & 1 for v in extents):
+        return False
     if kind in (ops.K3S2, ops.K3S2T):
         return cin % 8 == 0 and cout % 8 == 0
     return kind in (ops.K3S1, ops.K1) and cin % 8 == 0 and cout % 8 == 0 and cout <= 256 and ((cout // 8) & (cout // 8 - 1)) == 0
@@ -175,9 +178,7 @@ def conv_bwd_weight(kind, code, x, dy, dw, db, dup_start=0, dup_shift=0, accumul
     the kernels' reach (the caller then runs the fp32 kernel on widened copies)"""
     n, d, h, w, cin = x.shape
     cout = dy.shape[-1]
-    if not wgrad_supported(kind, cin, cout) or (db is not None and not dy.is_contiguous()):
-        return False
-    if kind == ops.K3S2 and ((d | h | w) & 1):
+    if not wgrad_supported(kind, cin, cout, (d, h, w)) or (db is not None and not dy.is_contiguous()):
         return False
     nb = lib().query('bts_lp_conv3d_bwd_weight_workspace', kind, n, d, h, w, cin, cout)
     ws = ops.workspace(nb, x.device)
@@ -222,6 +223,16 @@ def cast_pad16(code, tdt, src):
     rows = src.numel() // c
     out = torch.empty(tuple(src.shape[:-1]) + (16,), dtype=tdt, device=src.device)
     lib().call('bts_lp_cast_pad16', code, _p(src), src.stride(-2), _p(out), rows, c, _stream())
+    return out
+
+
+def cast_padded(code, tdt, x):
+    """fp32 (N,D,H,W,C) -> storage type, zero-padded to whole 16-channel matrix steps (the 2-channel volumes, model.py:18: one pass)"""
+    c = x.shape[-1]
+    if c <= 4 and x.is_contiguous():
+        return cast_pad16(code, tdt, x)
+    out = torch.zeros(tuple(x.shape[:4]) + ((c + 15) // 16 * 16,), dtype=tdt, device=x.device)
+    cast(code, tdt, x, out=out[..., :c])
     return out
 
 
@@ -352,14 +363,19 @@ def gn_apply(code, x, gamma, beta, mean, rstd, groups, mode, relu, out=None):
     return out
 
 
+def gn_bwd_tiled(v, c, groups):
+    """does the 16-bit GroupNorm-backward tiling (bts_lp_gn_bwd and the fused passes built on it) fit v voxels of c channels in `groups`
+    slab-mode groups?  Whole 2048-element chunks per group, a power-of-two c <= 256 whose groups (<= 32 channels) divide the 256-thread block"""
+    return not ((v * c) % groups or (v * c // groups) % 2048 or c // groups > 32 or 256 % (c // groups) or c > 256 or c & (c - 1))
+
+
 def gn_bwd(code, tdt, x, dy, gamma, beta, mean, rstd, dgamma, dbeta, groups, relu, want_f32=True, dbias=None):
     """slab-mode GroupNorm backward on 16-bit tensors -> (dx in the storage type, dx in fp32 or None); None if the shape is outside the
     kernel's tiling (the caller then runs the fp32 kernel on widened copies).  dbias: fp32 view that receives (+=) the column sums of
     dx -- the bias gradient of the conv that produced x -- from the same pass"""
     n, c = x.shape[0], x.shape[4]
     v = x.shape[1] * x.shape[2] * x.shape[3]
-    L = v * c // groups
-    if (v * c) % groups or L % 2048 or c // groups > 32 or 256 % (c // groups) or c > 256 or c & (c - 1):
+    if not gn_bwd_tiled(v, c, groups):
         return None
     nb = lib().query('bts_lp_gn_bwd_workspace', n, v, c, groups)
     ws = ops.workspace(nb, x.device)
@@ -394,9 +410,7 @@ def conv_bwd_data_gn_bwd(code, tdt, dy, wp_bwd, c, gamma, beta, mean, rstd, dgam
     takes the layer, GroupNorm's class sums come out of its epilogue (no reduce pass over da and c).  None when the GroupNorm kernels'
     tiling does not fit (gn_bwd's conditions): the caller runs the two steps itself"""
     n, d, h, w, cg = c.shape
-    v = d * h * w
-    L = v * cg // groups
-    if (v * cg) % groups or L % 2048 or cg // groups > 32 or 256 % (cg // groups) or cg > 256 or cg & (cg - 1) or not c.is_contiguous():
+    if not gn_bwd_tiled(d * h * w, cg, groups) or not c.is_contiguous():
         return None
     cdy = dy.shape[-1]
     nb = lib().query('bts_lp_conv3d_bwd_data_gn_bwd_workspace', n, d, h, w, cg, cdy, groups)
@@ -499,9 +513,7 @@ def block_bwd(code, tdt, dout, res, c2, sp, gap, h, ch, w1, w2, wsp, gamma, beta
     outside the fused kernels' tiling (the caller then runs se_bwd and gn_bwd).  Parameter / bias gradients accumulate."""
     n, f = res.shape[0], res.shape[4]
     v = res.shape[1] * res.shape[2] * res.shape[3]
-    L = v * f // groups
-    cg = f // groups
-    if (v * f) % groups or L % 2048 or cg > 32 or 256 % cg or f > 256 or f & (f - 1) or not (res.is_contiguous() and c2.is_contiguous()):
+    if not gn_bwd_tiled(v, f, groups) or not (res.is_contiguous() and c2.is_contiguous()):
         return None
     r = w1.shape[1]
     nb = lib().query('bts_lp_block_bwd_workspace', n, v, f, r, groups)
@@ -751,16 +763,8 @@ class LowPrecisionForward(object):
         if self.fuse_first and x.shape[-1] == 2 and enc0.cin_ref == 2:
             # the raw 2-channel volume straight into the first block's two convolutions (csrc/lowp_c2.hip): no padded 16-channel copy
             first = first_block(self.code, self.tdt, x, enc0.conv1_k.t, enc0.conv1_b.t, enc0.ptwise_k.t, enc0.ptwise_b.t, enc0.filters, enc0.norm1)
-        # the input volume in the storage type, zero-padded to one 16-channel matrix step (in_ch = 2: model.py:18)
-        if first is not None:
-            pass
-        elif x.shape[-1] <= 4:
-            x = cast_pad16(self.code, self.tdt, x)
-        else:
-            cpad = (x.shape[-1] + 15) // 16 * 16
-            xin = torch.zeros(tuple(x.shape[:4]) + (cpad,), dtype=self.tdt, device=x.device)
-            cast(self.code, self.tdt, x, out=xin[..., :x.shape[-1]])
-            x = xin
+        if first is None:
+            x = cast_padded(self.code, self.tdt, x)
         enc, dec = m.encoder, m.decoder
         n = x.shape[0]
         residuals = []

@@ -29,11 +29,14 @@ from .lowp import DTYPES, block_epilogue, cast, colsum, conv, conv1_gap, conv_bw
 from .tape import Tensor, bump_weights_epoch, weights_epoch
 
 
+def _couts(kind, w):
+    return w.shape[-2 if kind == ops.K3S2T else -1]           # (Conv3DTranspose kernels are (kd, kh, kw, Cout, Cin))
+
+
 def _wgrad16(kind, code, x, dy, dw, *a, **kw):
     """lowp.conv_bwd_weight where the caller has already checked the shape: a declined launch would leave `dw` unwritten (scratch
     tensors are uninitialised memory), so it is an error here, never a silent skip"""
-    cout = dw.shape[-2] if kind == ops.K3S2T else dw.shape[-1]           # (Conv3DTranspose kernels are (kd, kh, kw, Cout, Cin))
-    if dy.shape[-1] != cout or not lowp.conv_bwd_weight(kind, code, x, dy, dw, *a, **kw):
+    if dy.shape[-1] != _couts(kind, dw) or not lowp.conv_bwd_weight(kind, code, x, dy, dw, *a, **kw):
         raise RuntimeError('16-bit weight gradient declined: kind %d, x %s, dy %s, dw %s' % (kind, tuple(x.shape), tuple(dy.shape), tuple(dw.shape)))
 
 
@@ -165,23 +168,20 @@ class LowPrecisionTrainer(object):
         return buf
 
     def _gn_bwd(self, norm, c, dy, mean, rstd, want_f32=True, dbias=None):
-        """GroupNorm (+ReLU) backward -> (dc in the storage type with channels padded to a matrix step, dc in fp32 or None);
+        """GroupNorm (+ReLU) backward -> (dc in the storage type with channels padded to a matrix step, dc in fp32 or None, db_done);
         parameter gradients accumulate.  16-bit kernel where its tiling fits, else the fp32 kernel on widened copies.  dbias: the
-        producing conv's bias-gradient slot; self._db_done says whether the pass filled it (else the weight gradient must)"""
+        producing conv's bias-gradient slot; db_done says whether the pass filled it (else the weight gradient must)"""
         r = None
-        self._db_done = False
         if norm._mode == ops.GN_SLAB:
             pad = c.shape[-1] % 16 != 0
             r = lowp.gn_bwd(self.code, self.tdt, c, dy, norm.gamma.t, norm.beta.t, mean, rstd, self._gslot(norm.gamma), self._gslot(norm.beta),
                             norm.groups, True, want_f32=want_f32 or pad, dbias=dbias)
-            self._db_done = r is not None and dbias is not None
-        if r is not None and r[0].shape[-1] % 16 == 0:
-            return r
-        if r is not None:
-            return self._b16_k(r[1]), r[1]
-        dc = ops.gn_bwd(self._f32(c), self._f32(dy), norm.gamma.t, norm.beta.t, mean, rstd, self._gslot(norm.gamma), self._gslot(norm.beta),
-                        norm.groups, norm._mode, True, accumulate_params=True)
-        return self._b16_k(dc), dc
+        if r is None:
+            dc = ops.gn_bwd(self._f32(c), self._f32(dy), norm.gamma.t, norm.beta.t, mean, rstd, self._gslot(norm.gamma), self._gslot(norm.beta),
+                            norm.groups, norm._mode, True, accumulate_params=True)
+            return self._b16_k(dc), dc, False
+        dc16, dc = r
+        return (dc16 if dc16.shape[-1] % 16 == 0 else self._b16_k(dc)), dc, dbias is not None
 
     @staticmethod
     def _wg(tensors, fn):
@@ -196,6 +196,82 @@ class LowPrecisionTrainer(object):
         for t in tensors:
             t.record_stream(side)
 
+    def _wgrad_lowp(self, kind, x, kernel, cin_live=None, cout16=None):
+        """does this conv's weight gradient run on the 16-bit kernels (else: the fp32 kernels on widened operands)?  The one place that
+        says so: _wgrad decides with it, and a caller asks it beforehand where the answer shapes what it prepares (an fp32 twin of dy,
+        who forms the bias gradient).  x: the 16-bit input, a split concat included; cin_live: its real channels where the rest is zero
+        padding; cout16: the channels of the 16-bit dy where that is zero-padded past the kernel's.  Padded operands go to the 16-bit route
+        only for the stride-1 3x3x3 kind (the 128^3 layers: the first block, the VAE's output conv), through a scratch gradient"""
+        d, h, w, cin = lowp.xdims(x)[1:5]
+        cout16 = _couts(kind, kernel.t) if cout16 is None else cout16
+        if (cin_live is not None or cout16 != _couts(kind, kernel.t)) and kind != ops.K3S1:
+            return False
+        return cout16 % 16 == 0 and lowp.wgrad_supported(kind, cin, cout16, (d, h, w))
+
+    @staticmethod
+    def _add_live(slot, scratch):
+        """slot (taps.., cin, cout) += the live part of `scratch`, the same gradient taken over zero-padded input channels (per tap the
+        first cin rows: one dense run of cin * cout) or output channels (the first cout columns of every row)"""
+        cin, cout = slot.shape[-2:]
+        if scratch.shape[-1] == cout:
+            taps = slot.numel() // (cin * cout)
+            ops.add_strided(slot.view(taps, cin * cout), scratch.view(taps, -1)[:, :cin * cout], True)
+        else:
+            ops.add_strided(slot.view(-1, cout), scratch.view(-1, scratch.shape[-1])[:, :cout], True)
+
+    def _wgrad(self, kind, x, dy16, dy32, kernel, bias, need_db, fold=(0, 0), cin_live=None, shortcut=None, gn_in=None):
+        """A conv's weight gradient and, if need_db (no earlier pass formed it), its bias gradient, accumulated into the parameters' slots of
+        the flat gradient buffer on the weight-gradient stream: every weight gradient of the step.  x: the conv's 16-bit input (fold: see
+        _block_fwd); dy16 / dy32: the output gradient in the storage type and its fp32 twin, either may be missing (no dy16: fp32 route).
+        shortcut = (dres16, dres32, ptwise_k, ptwise_b, need_db): a ResnetBlock's 1x1x1 shortcut conv, which reads the same x -- both
+        gradients from one pass over x where the paired streaming kernel takes the layer.  gn_in = (norm, mean, rstd): x is the RAW input
+        of that GroupNorm (+ReLU), which the kernel applies on the way in.
+        16-bit route: a gradient over zero-padded channels goes to a scratch tensor whose live part is added to the slot; under padded couts
+        the bias gradient is the column sums of dy32.  fp32 route: x (its live channels) and a missing dy32 are widened on the main stream;
+        the transposed kind's kernel forms no bias gradient: column sums again"""
+        code, (dup_start, dup_shift) = self.code, fold
+        convs = []      # (kind, dy16, dy32, weight slot, bias slot or None, couts) of the conv and of the shortcut riding along
+        for k, g16, g32, kn, b, need in [(kind, dy16, dy32, kernel, bias, need_db)] + ([(ops.K1,) + tuple(shortcut)] if shortcut else []):
+            convs.append((k, g16, g32, self._gslot(kn), self._gslot(b) if need else None, _couts(k, kn.t)))
+        if dy16 is None or not self._wgrad_lowp(kind, x, kernel, cin_live, dy16.shape[-1]):
+            if gn_in is not None:
+                raise RuntimeError('fp32 weight gradient of a conv whose normalised input was never written: x %s' % (tuple(x.shape),))
+            x32 = self._f32(x if cin_live is None else x[..., :cin_live])
+            wide = [(k, g32 if g32 is not None else self._f32(g16[..., :cout]), dw, db) for k, g16, g32, dw, db, cout in convs]
+
+            def launch32():
+                for k, g32, dw, db in wide:
+                    ops.conv_bwd_weight(k, x32, g32, dw, None if k == ops.K3S2T else db, dup_start, dup_shift, accumulate=True)
+                    if k == ops.K3S2T and db is not None:
+                        ops.colsum(g32, sum_over_n=True, out=db, accumulate=True)
+            return self._wg((x32,) + tuple(c[1] for c in wide), launch32)
+        cin = lowp.xdims(x)[4]
+        tails = [(g32, db) for _, g16, g32, _, db, cout in convs if db is not None and g16.shape[-1] != cout]
+
+        def launch16():
+            jobs = []       # (kind, dy, gradient tensor, bias slot or None, the real slot where the gradient tensor is a scratch one)
+            for k, g16, _, dw, db, cout in convs:
+                if cin_live is None and g16.shape[-1] == cout:
+                    jobs.append((k, g16, dw, db, None))
+                else:
+                    scratch = torch.empty(tuple(dw.shape[:3]) + (cin, g16.shape[-1]), dtype=torch.float32, device=dw.device)
+                    jobs.append((k, g16, scratch, db if g16.shape[-1] == cout else None, dw))
+            _, g0, dw0, db0, slot0 = jobs[0]
+            if gn_in is not None:
+                lowp.conv_bwd_weight_normed_input(code, x, gn_in[0], gn_in[1], gn_in[2], g0, dw0, db0, accumulate=slot0 is None)
+            elif not (len(jobs) == 2 and jobs[1][3] is None and
+                      lowp.conv_bwd_weight_pair(code, x, g0, jobs[1][1], dw0, jobs[1][2], db0, dup_start, dup_shift, slot0 is None)):
+                if lowp.is_split(x):
+                    raise RuntimeError('split concat input: the paired weight-gradient launch declined a shape its query accepted')
+                for k, g, dw, db, slot in jobs:
+                    _wgrad16(k, code, x, g, dw, db, dup_start, dup_shift, slot is None)
+            for _, _, dw, _, slot in jobs:
+                if slot is not None:
+                    self._add_live(slot, dw)
+            for g32, db in tails:
+                ops.colsum(g32, sum_over_n=True, out=db, accumulate=True)
+        self._wg((x,) + tuple(c[1] for c in convs) + tuple(t[0] for t in tails), launch16)
+
     def _written(self, params):
         """one backward stage finished writing these parameters' gradients (the weight-gradient launches may still sit on the side
         stream: GradSync orders a bucket behind that stream's events, not behind the stream).  Data parallel: a bucket of the flat
@@ -206,18 +282,26 @@ class LowPrecisionTrainer(object):
         clock.nodes_replayed += 1
         clock.sync.params_written(params)
 
-    def _level0_split_ok(self, n, d, h, w, nb, f, spare, dec):
-        """level 0 as two dense 32-channel operands: only where EVERY reader of the pair takes the list (there is no single-tensor fallback)"""
-        if nb != 1 or f != 32 or spare != 32 or not dec.levels:
-            return False
+    def _level0_splits(self, n, d, h, w):
+        """-> (split_fwd, split_grad), asked once per step before the forward starts (queries only).  Level 0 of the CLI model is the
+        64-wide slab [o_0 (32) | up-sampled (32)] (decoder.py:75) whose readers mostly want ONE half: 64-byte halves of 128-byte lines.
+        split_grad: the slab's GRADIENT is a (2, N, D, H, W, 32) buffer, dense for the encoder block's backward (dout = [0, 32)) and the
+        up-sampler's GroupNorm backward (dy = [32, 64)), where the decoder top block's fused data-gradient launch can write two tensors.
+        split_fwd: so is the slab itself (virtual concat as a list of segments), only where EVERY reader of the pair takes the
+        list (there is no single-tensor fallback): conv1 + shortcut of the decoder's top block as two z-marching passes, one per operand
+        (bts_lp_conv3d_fwd_gn_shortcut), their paired weight gradient (bts_lp_conv3d_bwd_weight_pair), and the data gradient leaving
+        split.  split_fwd implies split_grad; a channels_first model (no slab-mode GroupNorm) or BTS_LP_FS=0 takes split_grad alone"""
+        enc, dec = self.model.encoder, self.model.decoder
+        if len(enc.levels[0][0]) != 1 or enc.base_filters != 32 or len(enc.levels) < 2 or not dec.levels:
+            return False, False
         up, blk = dec.levels[-1]
+        if up.filters != 32 or not lowp.conv_bwd_data_sc_split_ok(n, d, h, w, 64, blk.filters):
+            return False, False
         from ._lib import lib
-        if up.filters != 32 or blk.norm1._mode != ops.GN_SLAB or not lowp.wgrad_supported(ops.K3S1, 64, blk.filters):
-            return False
-        L = lib()
-        return (lowp.conv_bwd_data_sc_split_ok(n, d, h, w, 64, blk.filters)
-                and L.probe('bts_lp_conv3d_fwd_gn_shortcut_workspace', n, d, h, w, 64, 32, blk.filters, blk.norm1.groups) >= 0
-                and L.probe('bts_lp_conv3d_bwd_weight_pair_workspace', n, d, h, w, 64, blk.filters) >= 0)
+        split_fwd = (blk.norm1._mode == ops.GN_SLAB and lowp.wgrad_supported(ops.K3S1, 64, blk.filters)
+                     and lib().probe('bts_lp_conv3d_fwd_gn_shortcut_workspace', n, d, h, w, 64, 32, blk.filters, blk.norm1.groups) >= 0
+                     and lib().probe('bts_lp_conv3d_bwd_weight_pair_workspace', n, d, h, w, 64, blk.filters) >= 0)
+        return split_fwd, True
 
     @staticmethod
     def _backward_stages(n_vae, n_dec, blocks_per_level):
@@ -260,7 +344,7 @@ class LowPrecisionTrainer(object):
         # relu(GN1(c1)) has two readers, conv2's forward and conv2's weight gradient: where both kernels can normalise their input planes
         # themselves (the streaming kernels of the 128^3 level), the tensor is never written (a = None: the backward knows)
         a = None
-        if self.fuse_gn1_apply and lowp.wgrad_supported(ops.K3S1, f, f) and lowp.gnin_train_ok(c1, f, blk.norm1, blk.norm2):
+        if self.fuse_gn1_apply and self._wgrad_lowp(ops.K3S1, c1, blk.conv2_k) and lowp.gnin_train_ok(c1, f, blk.norm1, blk.norm2):
             c2, m2, r2 = lowp.conv_gn_normed_input(code, tdt, c1, blk.norm1, m1, r1, True, wp_c2, blk.conv2_b.t, f, blk.norm2)
         else:
             a = gn_apply(code, c1, blk.norm1.gamma.t, blk.norm1.beta.t, m1, r1, g, blk.norm1._mode, True)
@@ -286,14 +370,14 @@ class LowPrecisionTrainer(object):
         dup_start, dup_shift = s['fold']
         key = id(blk)
         x = s['x']
-        cin_slab = s['cin_slab']
-        # conv2's weight gradient on the 16-bit kernel?  (f is a multiple of 16 here: LowPrecisionForward refuses other models at construction)
-        lp2 = lowp.wgrad_supported(ops.K3S1, f, f)
-        # conv1 / shortcut weight gradients on the 16-bit kernel; the first block reads the 2-channel volume zero-padded to one matrix
-        # step: its gradients are taken over all 16 stored channels into a scratch tensor and the live rows added to the real slots
+        # conv2's weight gradient, and conv1's / the shortcut's, on the 16-bit kernels?  (f is a multiple of 16 here: LowPrecisionForward
+        # refuses other models at construction.)  The first block reads the 2-channel volume zero-padded to one matrix step
         xc = lowp.xdims(x)[4]
-        pad_in = cin_slab < xc
-        lp1 = lowp.wgrad_supported(ops.K3S1, xc, f)
+        cin_live = s['cin_slab'] if s['cin_slab'] < xc else None
+        lp2 = self._wgrad_lowp(ops.K3S1, s['c1'], blk.conv2_k)
+        lp1 = self._wgrad_lowp(ops.K3S1, x, blk.conv1_k, cin_live)
+        # Who forms each conv's bias gradient: the pass that writes the conv's dy where it can (it sums the columns on the way), else the
+        # weight-gradient launch.  db2_done / db1_done: conv2's / conv1's is formed; the shortcut's is exactly where lp1 (the gate passes)
         # conv branch: GN2 (+ReLU) -> conv2 -> GN1 (+ReLU) -> conv1
         # gate backward and GroupNorm-2 backward both read dout: one pair of passes where the fused kernels' tiling fits
         # (bts_lp_block_bwd: 89.4 -> 87.5 ms per batch-8 step)
@@ -304,24 +388,12 @@ class LowPrecisionTrainer(object):
                                    self._gslot(blk.se_w2), self._gslot(blk.spatial_k).reshape(-1), self._gslot(n2.gamma), self._gslot(n2.beta),
                                    dbias_pt=self._gslot(blk.ptwise_b), dbias_c2=self._gslot(blk.conv2_b))
         if fused is not None:
-            dres_fused, dc2_16 = fused
-            dc2 = None
-            self._db_done = True
+            (dres_16, dc2_16), dc2, db2_done = fused, None, True
         else:
-            dc2_16, dc2 = self._gn_bwd(n2, s['c2'], dout, s['m2'], s['r2'], want_f32=not lp2, dbias=self._gslot(blk.conv2_b) if lp2 else None)
-        if lp2 and s['a'] is None:      # the forward never wrote relu(GN1(c1)): the weight-gradient kernel forms it from c1 on the way in
-            db2 = None if self._db_done else self._gslot(blk.conv2_b)
-            c1_, m1_, r1_ = s['c1'], s['m1'], s['r1']
-            self._wg((c1_, dc2_16), lambda: lowp.conv_bwd_weight_normed_input(code, c1_, n1, m1_, r1_, dc2_16, self._gslot(blk.conv2_k), db2,
-                                                                              accumulate=True))
-        elif lp2:
-            a16 = s['a']
-            db2 = None if self._db_done else self._gslot(blk.conv2_b)
-            self._wg((a16, dc2_16), lambda: _wgrad16(ops.K3S1, code, a16, dc2_16, self._gslot(blk.conv2_k), db2, accumulate=True))
-        else:
-            a32 = self._f32(s['a'])
-            self._wg((a32, dc2), lambda: ops.conv_bwd_weight(ops.K3S1, a32, dc2, self._gslot(blk.conv2_k), self._gslot(blk.conv2_b),
-                                                             accumulate=True))
+            dc2_16, dc2, db2_done = self._gn_bwd(n2, s['c2'], dout, s['m2'], s['r2'], want_f32=not lp2, dbias=self._gslot(blk.conv2_b) if lp2 else None)
+        # (no a: the forward never wrote relu(GN1(c1)), the weight-gradient kernel forms it from c1 on the way in)
+        a, gn_in = (s['c1'], (n1, s['m1'], s['r1'])) if s['a'] is None else (s['a'], None)
+        self._wgrad(ops.K3S1, a, dc2_16, dc2, blk.conv2_k, blk.conv2_b, not db2_done, gn_in=gn_in)
         wp_c2b = self._pk((key, 'c2b'), ops.K3S1, blk.conv2_k, f, f, role=ops.ROLE_BWD)
         both = None
         if n1._mode == ops.GN_SLAB and dc2_16.shape[-1] == f:
@@ -331,64 +403,31 @@ class LowPrecisionTrainer(object):
                                              self._gslot(n1.beta), n1.groups, True, want_f32=not lp1,
                                              dbias=self._gslot(blk.conv1_b) if lp1 else None)
         if both is not None:
-            da, dc1_16, dc1, _ = both
-            self._db_done = lp1
+            (da, dc1_16, dc1, _), db1_done = both, lp1
             del dc2, dc2_16
         else:
             da = torch.empty_like(s['c1'])
             conv_bwd_data(ops.K3S1, code, dc2_16, wp_c2b, da, False)
             del dc2, dc2_16
-            dc1_16, dc1 = self._gn_bwd(n1, s['c1'], da, s['m1'], s['r1'], want_f32=not lp1, dbias=self._gslot(blk.conv1_b) if lp1 else None)
-        db1 = None if (lp1 and self._db_done) else self._gslot(blk.conv1_b)
+            dc1_16, dc1, db1_done = self._gn_bwd(n1, s['c1'], da, s['m1'], s['r1'], want_f32=not lp1, dbias=self._gslot(blk.conv1_b) if lp1 else None)
         del da
         # gate branch (16-bit kernels; fp32 copies only where a weight gradient still runs on the fp32 kernels)
-        if fused is not None:
-            dres_16 = dres_fused
-        else:
+        if fused is None:
             dres_16 = lowp.se_bwd(code, self.tdt, dout, s['res'], s['sp'], s['gap'], s['hbuf'], s['ch'], blk.se_w1.t, blk.se_w2.t,
                                   blk.spatial_k.t.reshape(-1), self._gslot(blk.se_w1), self._gslot(blk.se_w2),
                                   self._gslot(blk.spatial_k).reshape(-1), dbias=self._gslot(blk.ptwise_b) if lp1 else None)
         dres = None if lp1 else self._f32(dres_16)
         # weight gradients of the two convolutions that read the block input
-        if lp1 and pad_in:
-            def wgrads():
-                tk = torch.empty((3, 3, 3, x.shape[-1], f), dtype=torch.float32, device=x.device)
-                tp = torch.empty((1, 1, 1, x.shape[-1], f), dtype=torch.float32, device=x.device)
-                # (both from one pass over x where the streaming kernel takes the layer: see the branch below)
-                if not lowp.conv_bwd_weight_pair(code, x, dc1_16, dres_16, tk, tp, db1, 0, 0, False):
-                    _wgrad16(ops.K3S1, code, x, dc1_16, tk, db1, 0, 0, False)
-                    _wgrad16(ops.K1, code, x, dres_16, tp, None, 0, 0, False)
-                # live rows of the padded gradients into the real slots (library kernel: rows = taps, columns = the cin_slab x f prefix)
-                ops.add_strided(self._gslot(blk.conv1_k).view(27, cin_slab * f), tk.view(27, -1)[:, :cin_slab * f], True)
-                ops.add_strided(self._gslot(blk.ptwise_k).view(1, cin_slab * f), tp.view(1, -1)[:, :cin_slab * f], True)
-            self._wg((x, dc1_16, dres_16), wgrads)
-        elif lp1:
-            def wgrads():
-                # conv1's and the shortcut's weight gradients from ONE pass over the block input (round 6: the 1x1x1 gradient is one more
-                # accumulator of the streaming 3x3x3 kernel; bts_lp_conv3d_bwd_weight_pair) where that kernel takes the layer
-                if lowp.conv_bwd_weight_pair(code, x, dc1_16, dres_16, self._gslot(blk.conv1_k), self._gslot(blk.ptwise_k), db1, dup_start, dup_shift, True):
-                    return
-                if lowp.is_split(x):
-                    raise RuntimeError('split concat input: the paired weight-gradient launch declined a shape its query accepted')
-                _wgrad16(ops.K3S1, code, x, dc1_16, self._gslot(blk.conv1_k), db1, dup_start, dup_shift, True)
-                _wgrad16(ops.K1, code, x, dres_16, self._gslot(blk.ptwise_k), None, dup_start, dup_shift, True)   # (bias: se_bwd)
-            self._wg((x, dc1_16, dres_16), wgrads)
-        else:   # fp32 kernels on the widened input view
-            x32 = self._f32(x[..., :cin_slab])
-
-            def wgrads():
-                ops.conv_bwd_weight(ops.K3S1, x32, dc1, self._gslot(blk.conv1_k), self._gslot(blk.conv1_b), dup_start, dup_shift, accumulate=True)
-                ops.conv_bwd_weight(ops.K1, x32, dres, self._gslot(blk.ptwise_k), self._gslot(blk.ptwise_b), dup_start, dup_shift, accumulate=True)
-            self._wg((x32, dc1, dres), wgrads)
+        self._wgrad(ops.K3S1, x, dc1_16, dc1, blk.conv1_k, blk.conv1_b, not db1_done, s['fold'], cin_live,
+                    shortcut=(dres_16, dres, blk.ptwise_k, blk.ptwise_b, not lp1))
         if dx is not None:
-            cin = xc
-            assert dx.shape[-1] == cin or (dx.dim() == 6 and dx.shape[0] * 32 == cin)
-            wpb1 = self._pk((key, 'c1b'), ops.K3S1, blk.conv1_k, blk.cin_ref, f, cin, dup_start, dup_shift, role=ops.ROLE_BWD)
-            wpbp = self._pk((key, 'ptb'), ops.K1, blk.ptwise_k, blk.cin_ref, f, cin, dup_start, dup_shift, role=ops.ROLE_BWD)
+            assert dx.shape[-1] == xc or (dx.dim() == 6 and dx.shape[0] * 32 == xc)
+            wpb1 = self._pk((key, 'c1b'), ops.K3S1, blk.conv1_k, blk.cin_ref, f, xc, dup_start, dup_shift, role=ops.ROLE_BWD)
+            wpbp = self._pk((key, 'ptb'), ops.K1, blk.ptwise_k, blk.cin_ref, f, xc, dup_start, dup_shift, role=ops.ROLE_BWD)
             # conv1's and the shortcut's data gradients in ONE launch (round 6): the shortcut is an extra K-segment at the centre tap of
             # conv1's data-gradient kernel -- no second launch that read-modify-writes the Cin-wide dx (bts_lp_conv3d_bwd_data_sc; shapes the
             # fused kernels decline run as the two launches inside the same call)
-            if dx.dim() == 6:           # the concat's gradient as dense 32-channel tensors (see step(): gsplit)
+            if dx.dim() == 6:           # the concat's gradient as dense 32-channel tensors (see _level0_splits)
                 assert first and dc1_16.shape == dres_16.shape
                 if not lowp.conv_bwd_data_sc(code, dc1_16, wpb1, dres_16, wpbp, dx, False):
                     raise RuntimeError('split data gradient: the fused launch declined a shape its query accepted')
@@ -429,27 +468,10 @@ class LowPrecisionTrainer(object):
             self._linear_bwd(s, dy, dx, accumulate, cin_live)
             return self._written(lay.trainable_variables)
         nrm = lay.norm
-        x = s['x'] if cin_live is None else s['x'][..., :cin_live]
-        cout = s['c'].shape[-1]
-        lp16 = cin_live is None and cout % 16 == 0 and lowp.wgrad_supported(kind, x.shape[-1], cout) and \
-            not (kind == ops.K3S2 and any(v & 1 for v in x.shape[1:4]))
-        dc16, dc = self._gn_bwd(nrm, s['c'], dy, s['m'], s['r'], want_f32=not lp16, dbias=self._gslot(lay.conv_b) if lp16 else None)
-        if lp16 and dc16.is_contiguous():
-            # 16-bit operands straight into the transposing-read weight-gradient kernel (no widened copies)
-            dbs = None if self._db_done else self._gslot(lay.conv_b)
-            self._wg((x, dc16), lambda: _wgrad16(kind, self.code, x, dc16, self._gslot(lay.conv_k), dbs, accumulate=True))
-        else:
-            x32 = self._f32(x)
-            if dc is None:
-                dc = self._f32(dc16)
-
-            def wgrads():
-                if kind == ops.K3S2T:
-                    ops.conv_bwd_weight(kind, x32, dc, self._gslot(lay.conv_k), None, accumulate=True)
-                    ops.colsum(dc, sum_over_n=True, out=self._gslot(lay.conv_b), accumulate=True)
-                else:
-                    ops.conv_bwd_weight(kind, x32, dc, self._gslot(lay.conv_k), self._gslot(lay.conv_b), accumulate=True)
-            self._wg((x32, dc), wgrads)
+        lp16 = self._wgrad_lowp(kind, s['x'], lay.conv_k, cin_live)
+        dc16, dc, db_done = self._gn_bwd(nrm, s['c'], dy, s['m'], s['r'], want_f32=not lp16, dbias=self._gslot(lay.conv_b) if lp16 else None)
+        # (16-bit route: the operands straight into the transposing-read weight-gradient kernel, no widened copies)
+        self._wgrad(kind, s['x'], dc16, dc, lay.conv_k, lay.conv_b, not db_done, cin_live=cin_live)
         if dx is not None:
             wpb = self._pk((id(lay), 'b'), kind, lay.conv_k, lay.cin, lay.filters, role=ops.ROLE_BWD)
             conv_bwd_data(kind, self.code, dc16, wpb, dx, accumulate)
@@ -461,17 +483,10 @@ class LowPrecisionTrainer(object):
         lay = s['lay']
         f = lay.filters
         fp = (f + 15) // 16 * 16                              # (the contraction of the data gradient steps over 16 channels)
-        x = s['x'] if cin_live is None else s['x'][..., :cin_live]
         n, d2, h2, w2 = dy.shape[:4]
         buf = (torch.zeros if fp != f else torch.empty)((n, d2 // 2, h2 // 2, w2 // 2, fp), dtype=self.tdt, device=dy.device)
         dc16 = lowp.upsample2_bwd(self.code, dy, dx=buf[..., :f])
-        if cin_live is None and fp == f and lowp.wgrad_supported(ops.K1, x.shape[-1], f):
-            self._wg((x, dc16), lambda: _wgrad16(ops.K1, self.code, x, dc16, self._gslot(lay.ptwise_k), self._gslot(lay.ptwise_b),
-                                                             accumulate=True))
-        else:
-            x32, dc = self._f32(x), self._f32(dc16)
-            self._wg((x32, dc), lambda: ops.conv_bwd_weight(ops.K1, x32, dc, self._gslot(lay.ptwise_k), self._gslot(lay.ptwise_b),
-                                                            accumulate=True))
+        self._wgrad(ops.K1, s['x'], dc16, None, lay.ptwise_k, lay.ptwise_b, True, cin_live=cin_live)
         if dx is not None:
             wpb = self._pk((id(lay), 'b'), ops.K1, lay.ptwise_k, lay.cin, f, role=ops.ROLE_BWD)
             conv_bwd_data(ops.K1, self.code, buf, wpb, dx, accumulate)
@@ -482,60 +497,64 @@ class LowPrecisionTrainer(object):
     def step(self, optimizer, dice_fn, x, y):
         """train.py:140-152 with 16-bit storage -> (loss, macro_dice, micro_dice) as 1-element Tensors"""
         m = self.model
-        code, tdt = self.code, self.tdt
-        enc, dec, vae = m.encoder, m.decoder, m.vae
-        if not torch.is_tensor(x):
-            x = torch.as_tensor(x)
-        if not torch.is_tensor(y):
-            y = torch.as_tensor(y)
+        x, y = torch.as_tensor(x), torch.as_tensor(y)
         dev = torch.device('cuda', torch.cuda.current_device())
         fence = ops.step_fence('train')          # at most two steps in flight (see ops.step_fence)
         self._clock = None
         x, y = x.to(dev).float(), y.to(dev).float()
-        cf = m.data_format == 'channels_first'
-        if cf:          # raw NCDHW volumes -> the engine's NDHWC memory (tape.as_tensor does the same for the fp32 step)
+        if m.data_format == 'channels_first':    # raw NCDHW volumes -> the engine's NDHWC memory (tape.as_tensor does the same for the fp32 step)
             x, y = x.permute(0, 2, 3, 4, 1), y.permute(0, 2, 3, 4, 1)
         x, y = x.contiguous(), y.contiguous()
-        n = x.shape[0]
         ops.fill(m.flat_grads, 0.0)
-        # ------------------------------------------------ forward ------------------------------------------------
-        xin = x
-        cur = None
-        if enc.dropout_rate > 0:                                                      # encoder.py:39,71
+        split_fwd, split_grad = self._level0_splits(*x.shape[:4])
+        fw = self._forward(self._stage_input(x), split_fwd)
+        # loss, metric (fp32: util.py:13-24,35-57, train.py:145-148)
+        sums = ops.loss_sums(fw['y_pred'], y, x, fw['y_vae'], fw['proj'])
+        parallel.all_reduce_sum(sums)
+        lt, _ = ops.loss_value(sums, fw['y_pred'].shape[-1], True)
+        l2v = ops.l2_reg_fwd(m.flat_params, m._l2_ranges) if m._l2_ranges else None
+        loss_t = ops.scalar_lincomb(lt, l2v, 1.0, 1.0) if l2v is not None else lt
+        macro, micro = dice_fn(Tensor(y, requires_grad=False), Tensor(fw['y_pred'], requires_grad=False))     # (engine layout already)
+        self.last_labels = dice_fn.last_labels
+        # `one` seeds the backward: d loss / d loss, times the loss scale (float16: see the class docstring)
+        one = torch.full((1,), self.loss_scale, dtype=torch.float32, device=dev)
+        sync = self._backward(fw, x, y, sums, one, l2v is not None, split_grad)
+        self._update(optimizer, sync, one, l2v is not None)
+        ops.step_fence_done(fence)
+        return Tensor(loss_t, requires_grad=False), macro, micro
+
+    def _stage_input(self, x):
+        """the fp32 volume (engine layout) -> the encoder's 16-bit input, zero-padded to a 16-channel matrix step; input dropout
+        (encoder.py:39,71) on the way"""
+        enc = self.model.encoder
+        if enc.dropout_rate > 0:
             if enc._mask is not None:
                 msk = torch.as_tensor(enc._mask)
-                if cf and msk.dim() == 5:                                             # (an injected mask is in the public layout)
+                if self.model.data_format == 'channels_first' and msk.dim() == 5:     # (an injected mask is in the public layout)
                     msk = msk.permute(0, 2, 3, 4, 1)
-                msk = (msk != 0).to(torch.uint8).to(dev).contiguous()
+                msk = (msk != 0).to(torch.uint8).to(x.device).contiguous()
                 enc._mask = None
-                xin = ops.dropout_apply(x, msk, enc.dropout_rate)
+                x = ops.dropout_apply(x, msk, enc.dropout_rate)
             else:
                 enc._seed += 1
                 if x.shape[-1] <= 4:      # the draw, the scaling and the cast into the 16-channel matrix step in one pass (same generator, same seed)
-                    cur = lowp.dropout_cast_pad16(code, tdt, x, enc.dropout_rate, enc._seed)
-                else:
-                    xin = ops.dropout_apply(x, ops.dropout_mask(x.shape, enc.dropout_rate, enc._seed, dev), enc.dropout_rate)
-        if cur is not None:
-            pass
-        elif x.shape[-1] <= 4 and xin.is_contiguous():      # in_ch = 2 (model.py:18): one pass writes the whole 16-channel matrix step
-            cur = lowp.cast_pad16(code, tdt, xin)
-        else:
-            cpad = (x.shape[-1] + 15) // 16 * 16
-            cur = torch.zeros(tuple(x.shape[:4]) + (cpad,), dtype=tdt, device=dev)
-            cast(code, tdt, xin, out=cur[..., :x.shape[-1]])
-        del xin
+                    return lowp.dropout_cast_pad16(self.code, self.tdt, x, enc.dropout_rate, enc._seed)
+                x = ops.dropout_apply(x, ops.dropout_mask(x.shape, enc.dropout_rate, enc._seed, x.device), enc.dropout_rate)
+        return lowp.cast_padded(self.code, self.tdt, x)
+
+    def _forward(self, cur, split_fwd):
+        """encoder, decoder and VAE branch on the staged input -> the record of what the loss and the backward read"""
+        m = self.model
+        code, tdt = self.code, self.tdt
+        enc, dec, vae = m.encoder, m.decoder, m.vae
+        n, dev = cur.shape[0], cur.device
         levels = []                     # per encoder level: (slab, used, [block saves], down save or None)
         for i, (convs, down) in enumerate(enc.levels):
             d, h, w = cur.shape[1:4]
             f = enc.base_filters * 2 ** i
             nb = len(convs)
             spare = f if i < enc.depth - 1 else 0
-            # Level 0 of the CLI model: [o_0 (32) | up-sampled (32)] (decoder.py:75) as TWO dense tensors instead of a 64-wide slab (SURVEY K13:
-            # virtual concat as a list of segments) where every reader of the pair takes the list -- conv1 + shortcut of the decoder's top
-            # block ride on two z-marching passes, one per operand (bts_lp_conv3d_fwd_gn_shortcut, x_split), their weight gradients read
-            # one 32-channel block of P per workgroup anyway (bts_lp_conv3d_bwd_weight_pair, x_split), the data gradient leaves split as well
-            # (gsplit below).  The readers of ONE operand (the down-sampler, the skip level's kernels) then fetch whole 128-byte lines.
-            split0 = i == 0 and self._level0_split_ok(n, d, h, w, nb, f, spare, dec)
+            split0 = i == 0 and split_fwd       # level 0 as two dense 32-channel operands: see _level0_splits
             if split0:
                 slab = torch.empty((2, n, d, h, w, 32), dtype=tdt, device=dev)
             else:
@@ -561,26 +580,24 @@ class LowPrecisionTrainer(object):
             li = len(levels) - 2 - k
             slab, cres = levels[li][0], levels[li][1]
             f = up.filters
-            if lowp.is_split(slab):       # (level 0 as two dense operands: see above)
+            if lowp.is_split(slab):       # (level 0 as two dense operands)
                 _, us = self._sampler_fwd(up, ops.K3S2T, yk, out=slab[1])
                 yk, bs = self._block_fwd(blk, slab, None)
             else:
                 _, us = self._sampler_fwd(up, ops.K3S2T, yk, out=slab[..., cres:cres + f])
                 yk, bs = self._block_fwd(blk, slab[..., :cres + f], None)
             dsaves.append((us, bs, li, cres, f))
-        y_last = yk
-        y_pred = head(code, y_last, dec.out_k.t.reshape(dec.out_k.t.shape[-2], dec.out_k.t.shape[-1]), dec.out_b.t, True)
+        y_pred = head(code, yk, dec.out_k.t.reshape(dec.out_k.t.shape[-2], dec.out_k.t.shape[-1]), dec.out_b.t, True)
         # VAE branch (vae.py:114-143)
         hdn, vds = self._sampler_fwd(vae.downsample, ops.K3S2, top)
         flat = self._f32(hdn).reshape(n, -1)
         proj = ops.dense_fwd(flat, vae.proj_k.t, vae.proj_b.t, False)
-        L = vae.latent_size
         if vae._eps is not None:
             eps = torch.as_tensor(vae._eps, dtype=torch.float32).to(dev).contiguous()
             vae._eps = None
         else:
             vae._seed += 1
-            eps = ops.normal((n, L), vae._seed, dev)
+            eps = ops.normal((n, vae.latent_size), vae._seed, dev)
         z = ops.vae_sample_fwd(proj, eps)
         u = ops.dense_fwd(z, vae.unproj_k.t, vae.unproj_b.t, True)
         u5 = u.reshape((n,) + tuple(vae._unflat))
@@ -591,32 +608,32 @@ class LowPrecisionTrainer(object):
             yv, us = self._sampler_fwd(up, ops.K3S2T, yv)
             yv, bs = self._block_fwd(blk, yv, None)
             vsaves.append((us, bs))
-        yv_last = yv
-        if vae.out_ch < 8 and yv_last.shape[-1] % 16 == 0:
+        if vae.out_ch < 8 and yv.shape[-1] % 16 == 0:
             # out_ch = in_ch = 2 (vae.py:92-99): fewer than the 8 couts a 16-byte store carries, which left this 128^3 layer to the
             # register-staged kernel (0.97 ms of the batch-8 step).  Kernel and bias zero-padded to 8 output channels -> the streaming
             # kernels take it (the pad columns multiply zeros; only the live ones are read back)
-            cvv = yv_last.shape[-1]
+            cvv = yv.shape[-1]
             wpad = self._padded((id(vae), 'out_k8'), vae.out_k, 8)
             bpad = self._padded((id(vae), 'out_b8'), vae.out_b, 8)
-            y8 = conv(ops.K3S1, code, tdt, yv_last, self._pk((id(vae), 'out8'), ops.K3S1, wpad, cvv, 8), bpad.t, 8)
+            y8 = conv(ops.K3S1, code, tdt, yv, self._pk((id(vae), 'out8'), ops.K3S1, wpad, cvv, 8), bpad.t, 8)
             y_vae = self._f32(y8[..., :vae.out_ch])
             del y8
         else:
-            wp_vo = self._pk((id(vae), 'out'), ops.K3S1, vae.out_k, yv_last.shape[-1], vae.out_ch)
-            y_vae = self._f32(conv(ops.K3S1, code, tdt, yv_last, wp_vo, vae.out_b.t, vae.out_ch))
-        # ------------------------------------------------ loss, metric (fp32: util.py:13-24,35-57, train.py:145-148) -------------
-        c = y_pred.shape[-1]
-        sums = ops.loss_sums(y_pred, y, x, y_vae, proj)
-        parallel.all_reduce_sum(sums)
-        lt, _ = ops.loss_value(sums, c, True)
-        l2v = ops.l2_reg_fwd(m.flat_params, m._l2_ranges) if m._l2_ranges else None
-        loss_t = ops.scalar_lincomb(lt, l2v, 1.0, 1.0) if l2v is not None else lt
-        macro, micro = dice_fn(Tensor(y, requires_grad=False), Tensor(y_pred, requires_grad=False))     # (engine layout already)
-        self.last_labels = dice_fn.last_labels
-        # ------------------------------------------------ backward ------------------------------------------------
-        # `one` seeds the backward: d loss / d loss, times the loss scale (float16: see the class docstring)
-        one = torch.full((1,), self.loss_scale, dtype=torch.float32, device=dev)
+            wp_vo = self._pk((id(vae), 'out'), ops.K3S1, vae.out_k, yv.shape[-1], vae.out_ch)
+            y_vae = self._f32(conv(ops.K3S1, code, tdt, yv, wp_vo, vae.out_b.t, vae.out_ch))
+        return dict(levels=levels, dsaves=dsaves, vsaves=vsaves, vds=vds, vus=vus, y_last=yk, y_pred=y_pred, yv_last=yv, y_vae=y_vae,
+                    hdn=hdn, flat=flat, proj=proj, eps=eps, z=z, u=u, u16=u16)
+
+    def _backward(self, fw, x, y, sums, one, l2, split_grad):
+        """the explicit backward of _forward's graph into the model's flat gradient buffer; -> the gradient exchange that ran inside it
+        (parallel.GradSync) or None"""
+        m = self.model
+        code, tdt = self.code, self.tdt
+        enc, dec, vae = m.encoder, m.decoder, m.vae
+        levels, dsaves, vsaves = fw['levels'], fw['dsaves'], fw['vsaves']
+        y_pred, y_vae, proj, y_last, yv_last = fw['y_pred'], fw['y_vae'], fw['proj'], fw['y_last'], fw['yv_last']
+        n, dev = x.shape[0], x.device
+        top_used = levels[-1][1]
         dyp = torch.empty_like(y_pred)
         dyv = torch.empty_like(y_vae)
         dproj = torch.empty_like(proj)
@@ -626,20 +643,8 @@ class LowPrecisionTrainer(object):
         # top: the decoder block's conv1 data gradient (its view [0, cres + f) is the whole slab); the top level: the VAE's
         # down-sampling conv's data gradient (its view [0, top_used) is the whole slab, which has no spare channels)
         assert levels[-1][0].shape[-1] == top_used
-        # Level 0 of the CLI model: the slab is [o_0 (32) | up-sampled (32)] and its gradient has two readers that each want ONE half -- the
-        # encoder block's backward (dout = [0, 32)) and the up-sampler's GroupNorm backward (dy = [32, 64)) -- twice each (reduce + apply
-        # pass): as channel slices of a 64-wide slab they fetch 64-byte halves of 128-byte lines.  Where the fused data-gradient launch can
-        # write its 64 columns as two dense tensors, the gradient "slab" is a (2, N, D, H, W, 32) buffer instead (round 6)
-        gsplit = None
-        if len(levels) > 1 and dsaves:
-            slab0, used0 = levels[0][0], levels[0][1]
-            f0 = dsaves[-1][4]
-            blk0 = dsaves[-1][1]['blk']
-            n0, d0, h0, w0, width0 = lowp.xdims(slab0)[:5]
-            if used0 == 32 and f0 == 32 and width0 == 64 and len(levels[0][2]) == 1 and \
-                    lowp.conv_bwd_data_sc_split_ok(n, d0, h0, w0, 64, blk0.filters):
-                gsplit = torch.empty((2, n, d0, h0, w0, 32), dtype=tdt, device=dev)
-            assert gsplit is not None or not lowp.is_split(slab0)      # (_level0_split_ok asked the same question)
+        # level 0's gradient as two dense 32-channel tensors: see _level0_splits
+        gsplit = torch.empty((2,) + tuple(lowp.xdims(levels[0][0])[:4]) + (32,), dtype=tdt, device=dev) if split_grad else None
         gslabs = [None if (i == 0 and gsplit is not None) else torch.empty_like(lv[0]) for i, lv in enumerate(levels)]
 
         def gview(i, c0, c1):
@@ -656,71 +661,57 @@ class LowPrecisionTrainer(object):
         sync = parallel.grad_sync(m)
         if sync is not None:
             self._clock = _Progress(sync, self._backward_stages(len(vsaves), len(dsaves), [len(lv[2]) for lv in levels]))
-            sync.begin(self._clock, l2_grad=one if l2v is not None else None, prefilled=True)
+            sync.begin(self._clock, l2_grad=one if l2 else None, prefilled=True)
         # VAE branch backward.  Its output conv has out_ch = in_ch = 2 channels (vae.py:92-99): dy is stored zero-padded to one matrix step
         # (16 channels, like the input volume) so that the weight gradient (padded columns dropped afterwards) and the data gradient
         # (role-swapped image of the zero-padded kernel) run on the 16-bit kernels instead of the fp32 ones over widened copies
         cv, co = yv_last.shape[-1], vae.out_ch
-        if cv % 16 == 0 and co <= 16 and lowp.wgrad_supported(ops.K3S1, cv, 16):
-            if co <= 4 and dyv.is_contiguous():
-                dyv16 = lowp.cast_pad16(code, tdt, dyv)
-            else:
-                dyv16 = torch.zeros(tuple(dyv.shape[:4]) + (16,), dtype=tdt, device=dev)
-                cast(code, tdt, dyv, out=dyv16[..., :co])
-
-            def wg_out():
-                tk = torch.empty((3, 3, 3, cv, 16), dtype=torch.float32, device=dev)
-                _wgrad16(ops.K3S1, code, yv_last, dyv16, tk, None, 0, 0, False)
-                ops.add_strided(self._gslot(vae.out_k).view(-1, co), tk.view(-1, 16)[:, :co], True)      # the co live columns of the padded gradient
-                ops.colsum(dyv, sum_over_n=True, out=self._gslot(vae.out_b), accumulate=True)
-            self._wg((yv_last, dyv16, dyv), wg_out)
+        lp = cv % 16 == 0 and co <= 16 and self._wgrad_lowp(ops.K3S1, yv_last, vae.out_k, cout16=16)
+        dyv16 = lowp.cast_padded(code, tdt, dyv) if lp else None
+        self._wgrad(ops.K3S1, yv_last, dyv16, dyv, vae.out_k, vae.out_b, True)
+        if dyv16 is not None:
             wpb = self._pk((id(vae), 'out16b'), ops.K3S1, self._padded((id(vae), 'out_k16'), vae.out_k, 16), cv, 16, role=ops.ROLE_BWD)
             dv = torch.empty(yv_last.shape, dtype=tdt, device=dev)
             conv_bwd_data(ops.K3S1, code, dyv16, wpb, dv, False)
             del dyv16
         else:
-            ylv32 = self._f32(yv_last)
-            self._wg((ylv32, dyv), lambda: ops.conv_bwd_weight(ops.K3S1, ylv32, dyv, self._gslot(vae.out_k), self._gslot(vae.out_b),
-                                                               accumulate=True))
-            dv32 = torch.empty_like(ylv32)
+            dv32 = torch.empty(yv_last.shape, dtype=torch.float32, device=dev)
             wpb = vae.packed('out_b', ops.K3S1, ops.ROLE_BWD, vae.out_k, yv_last.shape[-1], vae.out_ch)
             ops.conv_bwd_data(ops.K3S1, dyv, wpb, dv32, False)
             dv = self._b16(dv32)
-            del dv32, ylv32
+            del dv32
         self._written([vae.out_k, vae.out_b])
         for us, bs in reversed(vsaves):
             dblk_in = torch.empty(bs['x'].shape, dtype=tdt, device=dev)
             self._block_bwd(bs, dv, dblk_in, first=True)
             dv = torch.empty(us['x'].shape, dtype=tdt, device=dev)
             self._sampler_bwd(us, dblk_in, dv, False)
-        du16 = torch.zeros_like(u16)
-        self._sampler_bwd(vus, dv, du16, False, cin_live=1)
+        u, z = fw['u'], fw['z']
+        du16 = torch.zeros_like(fw['u16'])
+        self._sampler_bwd(fw['vus'], dv, du16, False, cin_live=1)
         du5 = self._f32(du16[..., :1]).reshape(u.shape)
         gz = ops.relu_bwd(u, du5)
         dz = torch.empty_like(z)
         ops.dense_bwd(z, vae.unproj_k.t, gz, dz, self._gslot(vae.unproj_k), self._gslot(vae.unproj_b), accumulate_dx=False,
                       accumulate_params=True)
-        ops.vae_sample_bwd(proj, eps, dz, dproj)
-        dflat = torch.empty_like(flat)
-        ops.dense_bwd(flat, vae.proj_k.t, dproj, dflat, self._gslot(vae.proj_k), self._gslot(vae.proj_b), accumulate_dx=False,
+        ops.vae_sample_bwd(proj, fw['eps'], dz, dproj)
+        dflat = torch.empty_like(fw['flat'])
+        ops.dense_bwd(fw['flat'], vae.proj_k.t, dproj, dflat, self._gslot(vae.proj_k), self._gslot(vae.proj_b), accumulate_dx=False,
                       accumulate_params=True)
         self._written([vae.unproj_k, vae.unproj_b, vae.proj_k, vae.proj_b])
-        dhdn = self._b16(dflat.reshape(hdn.shape))
-        self._sampler_bwd(vds, dhdn, gslabs[-1][..., :top_used], False)           # first writer of the top level's slab gradient
+        dhdn = self._b16(dflat.reshape(fw['hdn'].shape))
+        self._sampler_bwd(fw['vds'], dhdn, gslabs[-1][..., :top_used], False)           # first writer of the top level's slab gradient
         # decoder head (decoder.py:55-63): sigmoid, 1x1x1 conv to out_ch -- dx, dW and db from one pass over the 16-bit activations
-        dpre = dyp
         wk2 = dec.out_k.t.reshape(dec.out_k.t.shape[-2], dec.out_k.t.shape[-1])
-        dcur = lowp.head_bwd(code, tdt, y_last, dpre, wk2, self._gslot(dec.out_k).reshape(wk2.shape), self._gslot(dec.out_b), True)
-        if dcur is None:       # head outside the fused kernel's shapes: fp32 kernels on widened copies
-            ylast32 = self._f32(y_last)
-            self._wg((ylast32, dpre), lambda: ops.conv_bwd_weight(ops.K1, ylast32, dpre, self._gslot(dec.out_k), self._gslot(dec.out_b),
-                                                                 accumulate=True))
-            dlast32 = torch.empty_like(ylast32)
+        dcur = lowp.head_bwd(code, tdt, y_last, dyp, wk2, self._gslot(dec.out_k).reshape(wk2.shape), self._gslot(dec.out_b), True)
+        if dcur is None:       # head outside the fused kernel's shapes: fp32 kernels on a widened copy
+            self._wgrad(ops.K1, y_last, None, dyp, dec.out_k, dec.out_b, True)
+            dlast32 = torch.empty(y_last.shape, dtype=torch.float32, device=dev)
             wpb = dec.packed('out_b', ops.K1, ops.ROLE_BWD, dec.out_k, y_last.shape[-1], dec.out_ch)
-            ops.conv_bwd_data(ops.K1, dpre, wpb, dlast32, False)
+            ops.conv_bwd_data(ops.K1, dyp, wpb, dlast32, False)
             dcur = self._b16(dlast32)
-            del dlast32, ylast32
-        del dpre
+            del dlast32
+        del dyp
         self._written([dec.out_k, dec.out_b])
         for idx in range(len(dsaves) - 1, -1, -1):
             us, bs, li, cres, f = dsaves[idx]
@@ -746,22 +737,27 @@ class LowPrecisionTrainer(object):
                     self._sampler_bwd(pds, dprev, gview(i - 1, 0, pused), True)
                 else:
                     self._block_bwd(saves[0], dout, None)
-        # regulariser (train.py:146), exchange, optimiser (train.py:151-152)
-        ops.join_side_stream()
+        ops.join_side_stream()      # (here: the temporaries of the last weight-gradient launches are still alive)
+        return sync
+
+    def _update(self, optimizer, sync, one, l2):
+        """regulariser (train.py:146), exchange, overflow flag, optimiser (train.py:151-152)"""
+        m = self.model
         if sync is not None:
             self._clock = None
             sync.finish()              # parameters no stage reported (none in this graph) and pad-only buckets; waits for the handles
             scale = 1.0
         else:
-            if l2v is not None:
+            if l2:
                 k = parallel.l2_grad_scale()
                 ops.l2_reg_bwd(m.flat_params, m.flat_grads, [(o, ln, cf * k) for o, ln, cf in m._l2_ranges], one)
             scale = parallel.all_reduce_gradients(m)
         grads = [p._gview for p in m.trainable_variables]
+        flag = None
         if self.dynamic_scale:
             # after the exchange every rank holds the same summed gradient, so every rank's flag -- and later decision -- is the same
             if self._flags is None:
-                self._flags = [(torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32).pin_memory()) for _ in range(2)]
+                self._flags = [(torch.zeros(1, dtype=torch.int32, device=one.device), torch.zeros(1, dtype=torch.int32).pin_memory()) for _ in range(2)]
                 self._flag_turn = 0
             flag, mirror = self._flags[self._flag_turn]
             self._flag_turn ^= 1
@@ -773,12 +769,8 @@ class LowPrecisionTrainer(object):
             ev.record()
             self._pending = (ev, mirror, optimizer, used)
             # un-scaling rides on Adam's gradient read (1 / scale: a power of two, exact); the update is dropped on the device on overflow
-            optimizer.apply_gradients(zip(grads, m.trainable_variables), model=m, grad_scale=scale / used, skip_flag=flag)
-            ops.step_fence_done(fence)
-            return Tensor(loss_t, requires_grad=False), macro, micro
-        optimizer.apply_gradients(zip(grads, m.trainable_variables), model=m, grad_scale=scale)
-        ops.step_fence_done(fence)
-        return Tensor(loss_t, requires_grad=False), macro, micro
+            scale /= used
+        optimizer.apply_gradients(zip(grads, m.trainable_variables), model=m, grad_scale=scale, skip_flag=flag)
 
     def settle(self):
         """read the overflow flag of the last dynamic-scale step (if it has not been read yet) and apply its consequences: skipped
