@@ -16,8 +16,13 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
   * `Interpolator.reverse` (test.py:58-66,259-264) zooms the label VALUES with a cubic spline, which gives fractional labels, and
     to round(n * 1/pixdim), which need not be the scan's extent; here the probabilities (configured order) and the brain mask
     (order 0) are resampled to the scan's recorded native shape and the labels are taken there with bts_tta_finish.
-All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_spline_prefilter3d, bts_zoom3d, the model
-forward).
+  * the skull-stripping hand-over (test.py:238-258) is `segment_case`: the skull model's masked mean probability, inverted, multiplies
+    the scan, which is cropped and padded again to the tumour model's resolution in the same pass (bts_skull_strip);
+  * the score (test.py:226-232,266-270) hands a 1-channel raw label volume and a spline-zoomed label volume to DiceCoefficient, which
+    expects one-hot truth and probabilities; `label_scores` gives the per-class Dice the call evidently intends, between the truth and
+    the predicted label map on the scan's own grid, from a confusion matrix counted on the device (bts_label_confusion).
+All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_spline_prefilter3d, bts_zoom3d,
+bts_skull_strip, bts_label_confusion, the model forward).
 """
 import glob
 import os
@@ -260,3 +265,116 @@ def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True,
         y = y.permute(1, 2, 3, 0)
     y, lab = interp.reverse(y[:orig[0], :orig[1], :orig[2]], threshold=threshold)
     return (y.permute(3, 0, 1, 2) if df == 'channels_first' else y), lab
+
+
+class StageSpec(object):
+    """one model of the two-stage pipeline with everything its TestTimeAugmentor takes (test.py:185-221).  The augmentor is built
+    once and kept: the 16-bit engine packs its weight images on the first forward"""
+
+    def __init__(self, model, mean, std, spatial_res, spatial_tta=True, channel_tta=0, threshold=0.5, compute_dtype='float32',
+                 tta_batch=None):
+        self.model, self.mean, self.std = model, mean, std
+        self.spatial_res = int(spatial_res)
+        self.spatial_tta, self.channel_tta, self.threshold = bool(spatial_tta), int(channel_tta), float(threshold)
+        self.compute_dtype, self.tta_batch = compute_dtype, tta_batch
+        self._tta = None
+
+    @property
+    def data_format(self):
+        return getattr(self.model, 'data_format', 'channels_last')
+
+    def augmentor(self):
+        """the stage's TestTimeAugmentor, with the channel-TTA generator back at its seed: every case draws what a fresh augmentor
+        would (segment_scan builds one per call)"""
+        if self._tta is not None:
+            self._tta._gen.manual_seed(0)
+        if self._tta is None:
+            self._tta = TestTimeAugmentor(self.mean, self.std, self.model, self.data_format, spatial_tta=self.spatial_tta,
+                                          channel_tta=self.channel_tta, threshold=self.threshold, compute_dtype=self.compute_dtype,
+                                          tta_batch=self.tta_batch)
+        return self._tta
+
+
+def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False):
+    """test.py:235-264 for one scan, with the optional skull-stripping stage (test.py:238-248): resample to 1 mm^3 padded to the first
+    model's resolution, [skull model with TTA, x * (1 - p) cropped and padded again to the tumour model's resolution,] tumour model
+    with TTA, crop, resample back.  tumor, skull: StageSpec; image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz)
+    -> (probabilities, uint8 labels (D,H,W)) on that grid, as segment_scan gives them; without `skull` this IS segment_scan.
+    return_stages: also a dict of the device tensors each stage handed to the next -- 'x1mm', 'mask' (padded to the first model's
+    resolution), 'skull_prob' (masked mean probability, same extent), 'x_stripped', 'mask_repadded' (padded to the tumour model's
+    resolution), 'prob_1mm' (the tumour model's cropped probabilities on the 1 mm^3 grid, channels last); None where a stage did not run."""
+    if skull is not None:
+        out_ch = getattr(getattr(skull.model, 'decoder', None), 'out_ch', None)
+        if out_ch != 1:
+            raise ValueError('segment_case: the skull-stripping model must have out_ch == 1 (its probability multiplies every channel '
+                             'of the scan, test.py:245), got out_ch = %r' % (out_ch,))
+    interp = Interpolator(None, order=order)
+    first = tumor if skull is None else skull
+    xp, mp, orig = interp.resample(image, pixdim, pad_res=first.spatial_res)
+    stages = {'x1mm': xp, 'mask': mp, 'skull_prob': None, 'x_stripped': None, 'mask_repadded': None, 'prob_1mm': None}
+    if skull is not None:
+        p = skull.augmentor()(xp, mp)
+        if skull.data_format == 'channels_first':
+            p = p.permute(1, 2, 3, 0)
+        p = p.contiguous()
+        res = tumor.spatial_res
+        xp, mp = ops.skull_strip(xp, p, mp, orig, tuple(s + res - (s % res) for s in orig))
+        stages.update(skull_prob=p, x_stripped=xp, mask_repadded=mp)
+    df = tumor.data_format
+    tta = tumor.augmentor()
+    y = tta(xp, mp)
+    if df == 'channels_first':
+        y = y.permute(1, 2, 3, 0)
+    y = y[:orig[0], :orig[1], :orig[2]]
+    stages['prob_1mm'] = y
+    if all(f == 1.0 for f in interp.factors):
+        lab = tta.labels()[:orig[0], :orig[1], :orig[2]]
+    else:
+        y, lab = interp.reverse(y, threshold=tumor.threshold)
+    if df == 'channels_first':
+        y = y.permute(3, 0, 1, 2)
+    return (y, lab, stages) if return_stages else (y, lab)
+
+
+def scores_from_confusion(confusion):
+    """K x K counts [truth class, predicted class] -> the scores of `label_scores`, float64 arithmetic on the host"""
+    m = np.asarray(confusion)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 2:
+        raise ValueError('confusion must be K x K with K >= 2, got shape %s' % (m.shape,))
+    m = m.astype(np.int64)
+    k = m.shape[0]
+
+    def dice(sel):                   # 2 I / (P + T) of the union of the classes `sel`; nan when truth and prediction are both empty
+        inter, t, p = int(m[np.ix_(sel, sel)].sum()), int(m[sel, :].sum()), int(m[:, sel].sum())
+        return 2.0 * inter / (p + t) if p + t else float('nan')
+
+    inter = np.diag(m)[1:].astype(np.float64)
+    true, pred = m.sum(axis=1)[1:].astype(np.float64), m.sum(axis=0)[1:].astype(np.float64)
+    out = {'confusion': m,
+           'macro': float(np.mean((2.0 * inter + 1.0) / (pred + true + 1.0))),                       # util.py:54
+           'micro': float(inter.sum() / (pred.sum() + true.sum())) if pred.sum() + true.sum() else float('nan'),   # util.py:55
+           'dice': [dice([c]) for c in range(1, k)]}
+    if k == 4:                       # BraTS regions over labels {1,2,4} = classes {1,2,3}
+        out.update(wt=dice([1, 2, 3]), tc=dice([1, 3]), et=dice([3]))
+    return out
+
+
+def label_scores(truth, pred, n_classes=4):
+    """per-class Dice between two uint8 label maps of equal shape (device tensors or numpy) -> {'confusion' (K,K) int64 numpy,
+    'macro', 'micro', 'dice' [class 1..K-1], and for n_classes == 4 'wt', 'tc', 'et'}.  Labels >= K-1 count as class K-1 (BraTS 4 -> 3,
+    preprocess.py:36).  macro = mean_c (2 I_c + 1) / (P_c + T_c + 1) and micro = sum I / (sum P + sum T) over classes 1..K-1 are
+    util.py:54-55 on the one-hot of the two maps with the background dropped (train.py:39-41), the missing factor 2 of micro included;
+    dice[c] = 2 I / (P + T), nan when both are empty; wt / tc / et: the same over labels {1,2,4} / {1,4} / {4}."""
+    if tuple(truth.shape) != tuple(pred.shape):
+        raise ValueError('label_scores: truth has shape %s, the prediction %s' % (tuple(truth.shape), tuple(pred.shape)))
+    maps = []
+    for t in (truth, pred):
+        if isinstance(t, np.ndarray):
+            if t.dtype != np.uint8:
+                raise ValueError('label_scores: label maps must be uint8, got %s' % t.dtype)
+            if not torch.cuda.is_available():
+                raise RuntimeError('label_scores: the confusion matrix is counted on the GPU (no CPU fallback exists for the product path)')
+            t = torch.from_numpy(np.ascontiguousarray(t)).cuda()
+        maps.append(t.contiguous())
+    counts = ops.label_confusion(maps[0], maps[1], n_classes)
+    return scores_from_confusion(counts.cpu().numpy())

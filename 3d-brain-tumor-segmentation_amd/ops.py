@@ -752,6 +752,51 @@ def zoom3d(coef, out_shape, order=3, pad_to=None, want_mask=False, mean=None, st
     return (out, mask) if want_mask else out
 
 
+# ---- the two-stage hand-over and the per-case score (test.py:181-270) ----
+def skull_strip(x, p, m, orig, pad_to, out=None):
+    """x (Da,Ha,Wa,C), p and m (Da,Ha,Wa,1) dense float32; orig = the unpadded extent (D,H,W); pad_to = (Db,Hb,Wb) >= orig
+    -> (xo (Db,Hb,Wb,C) = x * (1 - p) inside orig, 0 outside; mo (Db,Hb,Wb,1) = m inside, 0 outside)   [test.py:244-254]
+    out: (xo, mo) dense float32 tensors of those shapes to write into"""
+    _check_volume(x, 'skull_strip: x')
+    da, ha, wa, c = x.shape
+    for t, name in ((p, 'p'), (m, 'm')):
+        _check_volume(t, 'skull_strip: ' + name)
+        if tuple(t.shape) != (da, ha, wa, 1):
+            raise ValueError('skull_strip: %s must have shape %s, got %s' % (name, (da, ha, wa, 1), tuple(t.shape)))
+    d, h, w = (int(v) for v in orig)
+    db, hb, wb = (int(v) for v in pad_to)
+    if out is None:
+        xo = torch.empty((db, hb, wb, c), dtype=torch.float32, device=x.device)
+        mo = torch.empty((db, hb, wb, 1), dtype=torch.float32, device=x.device)
+    else:
+        xo, mo = out
+        _check_volume(xo, 'skull_strip: xo')
+        _check_volume(mo, 'skull_strip: mo')
+        if tuple(xo.shape) != (db, hb, wb, c) or tuple(mo.shape) != (db, hb, wb, 1):
+            raise ValueError('skull_strip: out must have shapes %s and %s, got %s and %s'
+                             % ((db, hb, wb, c), (db, hb, wb, 1), tuple(xo.shape), tuple(mo.shape)))
+    lib().call('bts_skull_strip', _p(x), _p(p), _p(m), _p(xo), _p(mo), da, ha, wa, d, h, w, db, hb, wb, c, _stream())
+    return xo, mo
+
+
+def label_confusion(truth, pred, n_classes=4, counts=None):
+    """truth, pred: dense uint8 label maps of equal size on the GPU -> counts (K,K) int64 on the GPU with
+    counts[min(t,K-1), min(p,K-1)] += 1 per voxel.  counts: a zeroed (or partly filled) buffer to add into; a new one otherwise"""
+    k = int(n_classes)
+    for t, name in ((truth, 'truth'), (pred, 'pred')):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError('label_confusion: %s must be a dense uint8 tensor on the GPU' % name)
+    if truth.numel() != pred.numel():
+        raise ValueError('label_confusion: %d truth and %d predicted voxels' % (truth.numel(), pred.numel()))
+    if counts is None:
+        counts = torch.zeros((max(k, 0), max(k, 0)), dtype=torch.int64, device=truth.device)
+    elif not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype != torch.int64 or counts.numel() != k * k \
+            or not counts.is_contiguous():
+        raise ValueError('label_confusion: counts must be %d dense int64 values on the GPU' % (k * k))
+    lib().call('bts_label_confusion', _p(truth), _p(pred), truth.numel(), k, _p(counts), _stream())
+    return counts
+
+
 # ---- training-time augmentation on the device (SURVEY 8 f-3) ----
 def channel_moments(x):
     """per-channel (mean, population variance) over all voxels of a dense (..., C) tensor, C <= 16 -> two (C,) tensors"""

@@ -1,0 +1,240 @@
+"""Segment folders of scans end to end: the reference's test.py main() (test.py:181-270) on the device.
+
+    python -m bts_amd.test --in_locs a,b --modalities t1ce,flair --tumor_model DIR --tumor_prepro DIR/prepro.npy
+                           [--skull_model DIR --skull_prepro FILE] [--truth seg] [--out_loc DIR] [--dtype float16]
+
+This module is named after the reference's script and is NOT a pytest module: pytest's `test_*.py` pattern does not match `test.py`
+and `testpaths` points at tests/, so it is never collected.
+
+Every sub-folder of every folder of --in_locs is a case.  Per case: the modalities (and, with --truth, the label) are decoded by host
+threads while the device works on the previous case; `infer.segment_case` resamples to 1 mm^3, runs the optional skull-stripping
+model and the tumour model with test-time augmentation and brings the labels back to the scan's grid; `mask.nii` is written with
+the affine averaged over the modalities into the case folder (test.py:69-70), or into DIR/<case>/ with --out_loc; a labelled case
+prints the reference's line (test.py:269) from `infer.label_scores`.  With --out_loc a `scores.csv` holds one row per labelled case
+and a last row computed from the summed confusion matrix.
+
+The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
+accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc.
+
+Deviations:
+  * cases are visited in sorted order of their paths (the reference: the file system's order);
+  * each model is built at the crop size recorded in its train_args.pkl, as test.py:186-188 does, so that the checkpoint's
+    VAE variables (tied to that extent, vae.py:101-111) load; a train_args.pkl without one builds at the first case's padded shape;
+  * a case with a missing modality is reported by name and skipped (the reference's glob(...)[0] ends the run with an IndexError);
+  * the score is `infer.label_scores` (see bts_amd.infer on why the reference's call is not functional).
+"""
+import argparse
+import glob
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import nifti
+from .infer import Interpolator, StageSpec, label_scores, scores_from_confusion, segment_case, zoom_output_shape
+from .preprocess import load_prepro
+from .train import load_checkpoint, load_train_args
+
+N_CLASSES = 4        # background + the three BraTS labels 1, 2, 4 (4 counts as class 3, preprocess.py:36)
+
+
+def arg_parser():
+    """the flags of the reference's TestArgParser (args.py:199-235) and ours"""
+    p = argparse.ArgumentParser(prog='python -m bts_amd.test', description=__doc__.split('\n')[0])
+    p.add_argument('--in_locs', type=str, required=True, help='Comma-separated paths of test data.')
+    p.add_argument('--modalities', type=str, required=True, help='Comma-separated modalities to be used as input')
+    p.add_argument('--truth', type=str, default='', help='Truth label pattern to use (optional).')
+    p.add_argument('--tumor_prepro', type=str, required=True, help='Path to Numpy preprocessing dump for tumor segmentation.')
+    p.add_argument('--skull_prepro', type=str, default='', help='Path to Numpy preprocessing dump for skull segmentation.')
+    p.add_argument('--tumor_model', type=str, required=True, help='Path to checkpoint folder for tumor segmentation.')
+    p.add_argument('--skull_model', type=str, default='', help='Path to checkpoint folder for skull-stripping segmentation.')
+    p.add_argument('--order', type=int, default=3, help='Order of interpolation function to be used in voxel resizing.')
+    p.add_argument('--mode', type=str, default='reflect', help='Method of handling image edges in interpolation.')
+    p.add_argument('--spatial_tta', action='store_true', default=True, help='Whether to apply spatial augmentation on all spatial axes.')
+    p.add_argument('--channel_tta', type=int, default=0, help='Additional intensity shifting samples to take.')
+    p.add_argument('--threshold', type=float, default=0.5, help='Threshold at which to create mask from probabilities.')
+    p.add_argument('--gpu', action='store_true', default=False, help='Accepted for the reference\'s command line; the GPU is always used.')
+    p.add_argument('--dtype', type=str, default='float32', choices=('float32', 'float16', 'bfloat16'),
+                   help='Storage type of activations and weight images in both stages.')
+    p.add_argument('--tta_batch', type=int, default=None, help='Augmented copies per forward (default: 1 in float32, 4 in 16 bits).')
+    p.add_argument('--workers', type=int, default=8, help='Host threads that decode the next cases; 0 decodes in line.')
+    p.add_argument('--out_loc', type=str, default='', help='Write DIR/<case>/mask.nii and DIR/scores.csv instead of into the case folders.')
+    return p
+
+
+def parse_args(argv=None):
+    args = arg_parser().parse_args(argv)
+    args.modalities = args.modalities.split(',')
+    args.in_locs = args.in_locs.split(',')
+    if not 0 < args.threshold < 1:                                                   # args.py:243-244
+        raise AssertionError('Threshold must be a probability between (0, 1).')
+    if args.skull_model and not args.skull_prepro:                                   # args.py:245-246
+        raise AssertionError('Need skull preprocessing stats if model is provided.')
+    args.skull_strip = bool(args.skull_model)
+    return args
+
+
+def find_cases(in_locs, out_loc=''):
+    """every sub-folder of every folder, folders and entries in sorted order -> [(name, path)]; plain files (a scores.csv of an earlier
+    run) and the output folder itself are no cases"""
+    out = os.path.realpath(out_loc) if out_loc else None
+    return [(os.path.basename(p.rstrip(os.sep)), p) for loc in in_locs for p in sorted(glob.glob(os.path.join(loc, '*')))
+            if os.path.isdir(p) and os.path.realpath(p) != out]
+
+
+def _first(path, name):
+    found = sorted(glob.glob(os.path.join(path, '*' + name + '*' + '.nii' + '*')))
+    return found[0] if found else None
+
+
+def decode_case(path, modalities, truth):
+    """host side of one case (test.py:21-42,226-232) -> {'vols': float32 volumes with the axes reversed (the file's own byte order, see
+    preprocess._decode_case), 'pixdim', 'affine': means over the modalities, 'truth': uint8 volume (axes reversed) or None}, or
+    {'missing': name} when a modality has no file"""
+    vols, pixdim, affine = [], [], []
+    for name in modalities:
+        card = _first(path, name)
+        if card is None:
+            return {'missing': name}
+        data, header = nifti.load(card)
+        vols.append(np.ascontiguousarray(np.asarray(data).astype(np.float32).T))
+        pixdim.append(header['pixdim'][:4])
+        affine.append(header['affine'])
+    y = None
+    card = _first(path, truth) if truth else None
+    if card is not None:
+        y = np.ascontiguousarray(np.asarray(nifti.load(card)[0]).astype(np.uint8).T)
+    return {'vols': vols, 'pixdim': np.mean(pixdim, axis=0, dtype=np.float32), 'affine': np.mean(affine, axis=0, dtype=np.float32),
+            'truth': y}
+
+
+def upload_case(case, dev):
+    """-> (x (D,H,W,C) float32, truth (D,H,W) uint8 or None) on `dev`; the transposition to the scan's axis order runs there"""
+    vols = case['vols']
+    x = torch.empty(vols[0].shape[::-1] + (len(vols),), dtype=torch.float32, device=dev)
+    for ch, v in enumerate(vols):
+        if v.shape != vols[0].shape:
+            raise ValueError('the modalities differ in shape: %s' % ([u.shape[::-1] for u in vols],))
+        x[..., ch].copy_(torch.from_numpy(v).to(dev).permute(2, 1, 0))
+    y = case['truth']
+    if y is not None:
+        y = torch.from_numpy(y).to(dev).permute(2, 1, 0).contiguous()
+    return x, y
+
+
+def load_stage(folder, prepro, args, shape_1mm):
+    """checkpoint folder + prepro.npy -> StageSpec: the model rebuilt from train_args.pkl's model_args (args.py:250-260), built, filled
+    with load_checkpoint; spatial_res = 2 ** depth; mean / std from the prepro dump.  shape_1mm: the first case's extent on the
+    1 mm^3 grid, the build shape (padded to the resolution) where train_args.pkl records no crop size"""
+    from .model import Model
+    targs = load_train_args(folder)
+    kw = dict(targs['model_args'])
+    kw.setdefault('in_ch', len(args.modalities))
+    model = Model(**kw)
+    res = 2 ** int(model.encoder.depth)
+    crop = targs.get('crop_size')
+    build = tuple(int(s) for s in crop) if crop else tuple(s + res - (s % res) for s in shape_1mm)
+    model.build((1,) + build + (kw['in_ch'],))
+    load_checkpoint(folder, model)
+    _, mean, std = load_prepro(prepro)
+    if mean.size != kw['in_ch']:
+        raise ValueError('%s holds statistics of %d channels, the model of %s takes %d' % (prepro, mean.size, folder, kw['in_ch']))
+    return StageSpec(model, mean, std, res, spatial_tta=args.spatial_tta, channel_tta=args.channel_tta, threshold=args.threshold,
+                     compute_dtype=args.dtype, tta_batch=args.tta_batch)
+
+
+def require_gpu():
+    """-> the current device; no CPU path: without a GPU the command ends with the Interpolator's message"""
+    Interpolator._device_volume(np.zeros((1, 1, 1, 1), dtype=np.float32))
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _fmt(v):
+    return '%.6f' % v
+
+
+def score_row(name, s):
+    return [name, _fmt(s['macro']), _fmt(s['micro'])] + [_fmt(v) for v in s['dice']] + [_fmt(s[k]) for k in ('wt', 'tc', 'et')]
+
+
+def _decoded(cases, args):
+    """the decoded cases in order; with workers > 0 a bounded number of them is decoded ahead by host threads"""
+    if args.workers <= 0:
+        for _, path in cases:
+            yield decode_case(path, args.modalities, args.truth)
+        return
+    with ThreadPoolExecutor(max_workers=args.workers) as pool:
+        pending, nxt = [], 0
+        for _ in cases:
+            while nxt < len(cases) and len(pending) < args.workers + 1:
+                pending.append(pool.submit(decode_case, cases[nxt][1], args.modalities, args.truth))
+                nxt += 1
+            yield pending.pop(0).result()
+
+
+def run(args):
+    """-> {'cases', 'scored', 'skipped': [(name, modality)], 'scores': [(name, label_scores dict)], 'total': scores of the summed
+    confusion matrix or None}"""
+    dev = require_gpu()
+    Interpolator(args.modalities, order=args.order, mode=args.mode)      # refuses an unsupported --order / --mode before any work
+    cases = find_cases(args.in_locs, args.out_loc)
+    if not cases:
+        raise ValueError('no case found under %s' % (args.in_locs,))
+    if args.out_loc:
+        os.makedirs(args.out_loc, exist_ok=True)
+    tumor = skull = None
+    scores, skipped, done = [], [], 0
+    total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
+    t0 = time.time()
+    for (name, path), case in zip(cases, _decoded(cases, args)):
+        if 'missing' in case:
+            print('{}: no *{}*.nii* file, case skipped'.format(name, case['missing']), flush=True)
+            skipped.append((name, case['missing']))
+            continue
+        x, y = upload_case(case, dev)
+        pixdim = tuple(float(v) for v in case['pixdim'][1:4])
+        if tumor is None:
+            unit = all(f == 1.0 for f in pixdim)
+            shape_1mm = tuple(x.shape[:3]) if unit else zoom_output_shape(tuple(x.shape[:3]), pixdim)
+            tumor = load_stage(args.tumor_model, args.tumor_prepro, args, shape_1mm)
+            if args.skull_strip:
+                skull = load_stage(args.skull_model, args.skull_prepro, args, shape_1mm)
+        _, lab = segment_case(tumor, x, pixdim, skull=skull, order=args.order)
+        s = None
+        if y is not None:
+            s = label_scores(y, lab, N_CLASSES)
+            total += s['confusion']
+        where = os.path.join(args.out_loc, name) if args.out_loc else path
+        os.makedirs(where, exist_ok=True)
+        nifti.save(os.path.join(where, 'mask.nii'), lab.cpu().numpy(), case['affine'])
+        done += 1
+        if s is not None:
+            scores.append((name, s))
+            print('{}. Macro: {ma: 1.4f}. Micro: {mi: 1.4f}'.format(name, ma=s['macro'], mi=s['micro']), flush=True)    # test.py:269
+    overall = scores_from_confusion(total) if scores else None
+    if args.out_loc:
+        head = ['case', 'macro', 'micro'] + ['dice_%d' % c for c in range(1, N_CLASSES)] + ['wt', 'tc', 'et']
+        rows = [head] + [score_row(n, s) for n, s in scores]
+        if overall is not None:
+            rows.append(score_row('total', overall))
+        with open(os.path.join(args.out_loc, 'scores.csv'), 'w') as f:
+            f.write(''.join(','.join(r) + '\n' for r in rows))
+    dt = time.time() - t0
+    print('{} cases segmented ({} scored) in {:.1f} s, {:.2f} cases/s; {} skipped for a missing modality{}'.format(
+        done, len(scores), dt, done / dt if dt > 0 else 0.0, len(skipped),
+        ': ' + ', '.join('%s (%s)' % sk for sk in skipped) if skipped else ''), flush=True)
+    return {'cases': done, 'scored': len(scores), 'skipped': skipped, 'scores': scores, 'total': overall}
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    print('Test args: {}'.format(args))
+    run(args)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -261,6 +261,21 @@ int bts_spline_prefilter3d(const float* src, float* dst, int D, int H, int W, in
 int bts_zoom3d(const float* coef, float* dst, float* bmask, const float* mean, const float* stdv, int Din, int Hin, int Win,
                int Dout, int Hout, int Wout, int C, int Dpad, int Hpad, int Wpad, int order, bts_stream_t stream);
 
+/* ===== segmenting a folder of scans end to end (test.py:181-270: main) =====
+ * The skull-stripping hand-over between the two models (test.py:244-254: invert, multiply, slice, pad again) in one pass.
+ * x (Da,Ha,Wa,C) fp32: the scan padded to the skull model's resolution; p (Da,Ha,Wa,1): that stage's masked mean probability; m
+ * (Da,Ha,Wa,1): the brain mask.  (D,H,W): the unpadded extent; (Db,Hb,Wb): the tumour model's padded extent, each axis >= (D,H,W).
+ * xo (Db,Hb,Wb,C) = x * (1.0f - p) inside (D,H,W), 0 outside; mo (Db,Hb,Wb,1) = m inside, 0 outside (the mask is carried unchanged,
+ * test.py:251-254).  One fp32 subtract and one fp32 multiply per value: bit-equal to numpy float32 x * (1 - p).  BTS_ERR_SHAPE for
+ * C < 1, a non-positive extent, or an unpadded extent larger than either padded one. */
+int bts_skull_strip(const float* x, const float* p, const float* m, float* xo, float* mo, int Da, int Ha, int Wa, int D, int H, int W,
+                    int Db, int Hb, int Wb, int C, bts_stream_t stream);
+/* The device side of the per-case score (test.py:226-232,266-270; the Dice sums of util.py:50-55 follow from the counts on the host):
+ * counts[min(t,K-1) * K + min(p,K-1)] += 1 for every voxel of two dense uint8 label maps (truth, prediction), K in 2..8; counts: K*K
+ * int64 on the device, accumulated across calls (zero it once per score).  K = 4 folds BraTS label 4 onto class 3 (preprocess.py:36).
+ * Integer atomics only: exact and bit-reproducible.  BTS_ERR_SHAPE for K outside 2..8 or nvox < 0; nvox == 0 launches nothing. */
+int bts_label_confusion(const uint8_t* truth, const uint8_t* pred, long nvox, int K, long* counts, bts_stream_t stream);
+
 /* ===== training-time augmentation on the device (train.py:14-49) ===== */
 /* per-channel mean / population variance of a (nvox, C) tensor with voxel stride ld (tf.nn.moments, train.py:18);
  * C <= 16; mean may be NULL; fp64 partials, fixed-order combine */
