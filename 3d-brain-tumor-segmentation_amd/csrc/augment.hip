@@ -9,18 +9,23 @@
 #define AUG_MAXC 16
 #define AUG_BLOCKS 512
 
-// per-block fp64 partial sums of x and x^2 for every channel; combined in a fixed order by the finalize kernel
+// per-block fp64 partial sums of d and d^2, d = x - pivot[c] with pivot = the first voxel's value, for every channel; combined in a
+// fixed order by the finalize kernel.  Shifted because E[x^2] - mean^2 on raw intensities (mean 1000, deviation 1) cancels six digits
+// of the fp64 sums, and a constant volume came out with a variance of +-1e-8 instead of 0; on d a constant volume sums exact zeros.
 __global__ __launch_bounds__(256) void moments_partial_kernel(const float* __restrict__ x, double* part, long nvox, int C,
                                                               int ld) {
   __shared__ double sh[4];
   double s[AUG_MAXC], q[AUG_MAXC];
 #pragma unroll
   for (int c = 0; c < AUG_MAXC; ++c) { s[c] = 0.0; q[c] = 0.0; }
+  double pv[AUG_MAXC];
+#pragma unroll
+  for (int c = 0; c < AUG_MAXC; ++c) pv[c] = (c < C) ? (double)x[c] : 0.0;
   for (long v = blockIdx.x * (long)blockDim.x + threadIdx.x; v < nvox; v += (long)gridDim.x * blockDim.x) {
     const float* row = x + v * ld;
 #pragma unroll
     for (int c = 0; c < AUG_MAXC; ++c)
-      if (c < C) { const double t = (double)row[c]; s[c] += t; q[c] += t * t; }
+      if (c < C) { const double t = (double)row[c] - pv[c]; s[c] += t; q[c] += t * t; }
   }
 #pragma unroll
   for (int c = 0; c < AUG_MAXC; ++c) {
@@ -31,15 +36,16 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const float* __res
     }
   }
 }
-__global__ void moments_finalize_kernel(const double* part, float* mean, float* var, int nblocks, int C, long nvox) {
+__global__ void moments_finalize_kernel(const float* __restrict__ x, const double* part, float* mean, float* var, int nblocks, int C,
+                                        long nvox) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   double s = 0.0, q = 0.0;
   for (int b = 0; b < nblocks; ++b) { s += part[((long)b * C + c) * 2 + 0]; q += part[((long)b * C + c) * 2 + 1]; }
-  const double m = s / (double)nvox;
-  double vv = q / (double)nvox - m * m;  // population variance (tf.nn.moments)
+  const double m = s / (double)nvox;      // mean of x - pivot
+  double vv = q / (double)nvox - m * m;  // population variance (tf.nn.moments); a shift leaves it unchanged
   if (vv < 0.0) vv = 0.0;
-  if (mean) mean[c] = (float)m;
+  if (mean) mean[c] = (float)((double)x[c] + m);
   var[c] = (float)vv;
 }
 
@@ -54,7 +60,7 @@ extern "C" int bts_channel_moments(const float* x, float* mean, float* var, void
   double* part = reinterpret_cast<double*>(workspace);
   (void)hipGetLastError(); hipLaunchKernelGGL(moments_partial_kernel, dim3((int)blocks), dim3(256), 0, stream, x, part, nvox, C, ld);
   BTS_LAUNCH_CHECK();
-  (void)hipGetLastError(); hipLaunchKernelGGL(moments_finalize_kernel, dim3(1), dim3(64), 0, stream, part, mean, var, (int)blocks, C, nvox);
+  (void)hipGetLastError(); hipLaunchKernelGGL(moments_finalize_kernel, dim3(1), dim3(64), 0, stream, x, part, mean, var, (int)blocks, C, nvox);
   BTS_LAUNCH_CHECK();
   return BTS_OK;
 }

@@ -153,6 +153,8 @@ int bts_dropout_mask(uint8_t* mask, long n, float rate, uint64_t seed, bts_strea
 int bts_dropout_apply(const float* x, const uint8_t* mask, float* y, long n, float rate, bts_stream_t stream);
 int bts_normal(float* out, long n, uint64_t seed, bts_stream_t stream);
 int bts_vae_sample_fwd(const float* proj, const float* eps, float* z, int N, int L, bts_stream_t stream);
+/* dproj (N, 2L) += the gradient of z: dproj[:, :L] += dz, dproj[:, L:] += dz * 0.5 * exp(0.5 * logvar) * eps.  ACCUMULATES: dproj already
+ * holds the loss's own gradient with respect to proj (bts_loss_bwd) when the tape reaches the sampling step. */
 int bts_vae_sample_bwd(const float* proj, const float* eps, const float* dz, float* dproj, int N, int L, bts_stream_t stream);
 int bts_fill(float* p, long n, float v, bts_stream_t stream);
 int bts_axpy(float* y, const float* x, long n, float a, bts_stream_t stream);
@@ -176,6 +178,8 @@ int bts_loss_sums(const float* y_pred, const float* y, const float* x, const flo
                   void* workspace, long workspace_bytes, int N, long V, int C, int ldp, int ldy, int Cx, int ldx, int ldv,
                   int Lz, bts_stream_t stream);
 int bts_loss_value(const double* sums, float* loss, float* parts, int C, int has_vae, bts_stream_t stream);
+/* dlogit (N,V,C) and dyvae (N,V,Cx) are written DENSE (voxel strides C and Cx) whatever ldp / ldy / ldx / ldv say about the inputs; dproj
+ * (N, 2 Lz) is overwritten.  gscale: one device float or NULL (= 1).  through_sigmoid: multiply by p (1 - p) of the given y_pred. */
 int bts_loss_bwd(const float* y_pred, const float* y, const float* x, const float* y_vae, const float* proj,
                  const double* sums, const float* gscale, float* dlogit, float* dyvae, float* dproj, int N, long V, int C,
                  int ldp, int ldy, int Cx, int ldx, int ldv, int Lz, int through_sigmoid, bts_stream_t stream);
@@ -278,7 +282,8 @@ int bts_label_confusion(const uint8_t* truth, const uint8_t* pred, long nvox, in
 
 /* ===== training-time augmentation on the device (train.py:14-49) ===== */
 /* per-channel mean / population variance of a (nvox, C) tensor with voxel stride ld (tf.nn.moments, train.py:18);
- * C <= 16; mean may be NULL; fp64 partials, fixed-order combine */
+ * C <= 16; mean may be NULL; fp64 partials of x minus the first voxel's value (no cancellation against the mean: a constant volume
+ * has variance exactly 0), fixed-order combine */
 long bts_channel_moments_workspace(int C);
 int bts_channel_moments(const float* x, float* mean, float* var, void* workspace, long workspace_bytes, long nvox, int C,
                         int ld, bts_stream_t stream);
