@@ -6,12 +6,13 @@ axes with p = 0.5, one-hot labels minus the background channel -- note the refer
 too (the same map function serves both, train.py:74-89).  Differences:
   * storage: TFRecord protos (train.py:51-58, preprocess.py:88-96) need TensorFlow; examples are read from `.npz` files
     holding the same two arrays (`x`: (h,w,d,c) float32, `y`: (h,w,d,1) float32);
-  * the transformation runs on the GPU (bts_channel_moments + bts_augment_crop: one pass over the crop), the host only
-    draws the 2c + 6 random numbers -- at ~70 ms per step a tf.data-style host pipeline would otherwise be the bottleneck;
+  * the transformation runs on the GPU (bts_channel_moments + bts_augment_crop / bts_augment_batch: one pass over the crop),
+    the host only draws the 2c + 6 random numbers -- at ~70 ms per step a tf.data-style host pipeline would otherwise be the bottleneck;
   * the draws come from a seeded torch generator in a documented order (shift[c], scale[c], 3 crop offsets, 3 flips), so
     an epoch is reproducible; TF's stream cannot be.
 """
 import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -79,15 +80,30 @@ class _Dataset(object):
     """re-iterable epoch of (x, y) device batches.  Data parallel: every rank draws the SAME permutation from
     the shared shuffle generator and keeps positions rank, rank+world, ... of it, truncated to len // world examples so
     that all ranks run the same number of steps (the per-step exchanges would deadlock otherwise); the augmentation draws
-    come from a second, per-rank generator."""
+    come from a second, per-rank generator.
 
-    def __init__(self, files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, device, rank=0, world=1):
+    resident_bytes / workers (both 0: the per-example path as it always was).  Otherwise a batch is one bts_augment_batch launch
+    over the examples' device tensors, and
+      * an example whose x + y bytes still fit under `resident_bytes` stays on the device once read, with its per-channel variance (a
+        property of the file: the same fixed-order fp64 result every time); the others are streamed -- read, uploaded, moments, used,
+        dropped.  An epoch whose examples are all resident reads no file and uploads no volume: only the draws and the pointer /
+        offset tables leave the host.  A rank keeps what it visits;
+      * with workers > 0 host threads read the epoch's next non-resident examples ahead, consumed in visiting order.
+    All draws stay on the iterating thread in visiting order, so for a given seed the batches are bit-identical whatever the two
+    arguments are; residency is not state (state_dict is the two generators)."""
+
+    channels_first = False
+
+    def __init__(self, files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, device, rank=0, world=1,
+                 resident_bytes=0, workers=0):
         self.files, self.batch_size, self.prepro_size = files, int(batch_size), tuple(prepro_size)
         self.crop_size, self.out_ch, self.shuffle = tuple(crop_size), int(out_ch), shuffle
         self.rank, self.world = int(rank), max(1, int(world))
         self.order_gen = torch.Generator().manual_seed(seed)
         self.gen = torch.Generator().manual_seed(seed + 7919 * (self.rank + 1))
         self.device = device
+        self.resident_bytes, self.workers = max(0, int(resident_bytes)), max(0, int(workers))
+        self._resident, self._resident_used = {}, 0           # file index -> (x, y, var) on the device; bytes of their x + y
 
     def _per_rank(self):
         return len(self.files) // self.world if self.world > 1 else len(self.files)
@@ -104,18 +120,33 @@ class _Dataset(object):
         self.order_gen.set_state(st['order_gen'].to(torch.uint8).cpu())
         self.gen.set_state(st['gen'].to(torch.uint8).cpu())
 
-    def __iter__(self):
+    def _order(self):
         order = list(range(len(self.files)))
         if self.shuffle:                                                   # train.py:60-61 (buffer = whole file list)
             order = torch.randperm(len(order), generator=self.order_gen).tolist()
         if self.world > 1:
             order = order[self.rank::self.world][:self._per_rank()]
+        return order
+
+    def _read(self, i):
+        """host side of one example -> (x (h,w,d,c), y (h,w,d,1)) float32 arrays"""
+        h, w, d, c = self.prepro_size
+        z = np.load(self.files[i])
+        return (np.ascontiguousarray(z['x'], dtype=np.float32).reshape(h, w, d, c),
+                np.ascontiguousarray(z['y'], dtype=np.float32).reshape(h, w, d, 1))
+
+    def __iter__(self):
+        if self.resident_bytes == 0 and self.workers == 0:
+            return self._iter_per_example()
+        return self._iter_batched()
+
+    def _iter_per_example(self):
+        order = self._order()
         h, w, d, c = self.prepro_size
         xs, ys = [], []
         for i in order:
-            z = np.load(self.files[i])
-            x = torch.from_numpy(np.ascontiguousarray(z['x'], dtype=np.float32).reshape(h, w, d, c)).to(self.device)
-            y = torch.from_numpy(np.ascontiguousarray(z['y'], dtype=np.float32).reshape(h, w, d, 1)).to(self.device)
+            xh, yh = self._read(i)
+            x, y = torch.from_numpy(xh).to(self.device), torch.from_numpy(yh).to(self.device)
             xa, ya = augment_example(x, y, self.crop_size, self.out_ch, draw(self.gen, c, (h, w, d), self.crop_size))
             xs.append(xa)
             ys.append(ya)
@@ -128,18 +159,66 @@ class _Dataset(object):
     def _emit(self, xs, ys):
         return torch.stack(xs), torch.stack(ys)
 
+    def _host_examples(self, todo):
+        """the examples of `todo` in order; with workers > 0 a bounded number of them is read ahead by host threads"""
+        if self.workers <= 0:
+            for i in todo:
+                yield self._read(i)
+            return
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            pending, nxt = [], 0
+            for _ in todo:
+                while nxt < len(todo) and len(pending) < self.workers + 1:
+                    pending.append(pool.submit(self._read, todo[nxt]))
+                    nxt += 1
+                yield pending.pop(0).result()
+
+    def _iter_batched(self):
+        order = self._order()
+        h, w, d, c = self.prepro_size
+        # an index occurs once per epoch and the resident set only grows: what this epoch has to read is known now
+        host = self._host_examples([i for i in order if i not in self._resident])
+        batch, draws = [], []
+        for i in order:
+            ex = self._resident.get(i)
+            if ex is None:
+                xh, yh = next(host)
+                # (uploads run on the current stream, like everything that reads them: a yielded batch is ordered behind them)
+                x, y = torch.from_numpy(xh).to(self.device), torch.from_numpy(yh).to(self.device)
+                ex = (x, y, ops.channel_moments(x)[1])
+                nbytes = (x.numel() + y.numel()) * 4
+                if self._resident_used + nbytes <= self.resident_bytes:
+                    self._resident[i] = ex
+                    self._resident_used += nbytes
+            batch.append(ex)
+            draws.append(draw(self.gen, c, (h, w, d), self.crop_size))
+            if len(batch) == self.batch_size:
+                yield self._augment(batch, draws)
+                batch, draws = [], []
+        if batch:
+            yield self._augment(batch, draws)
+
+    def _augment(self, batch, draws):
+        return ops.augment_batch([b[0] for b in batch], [b[1] for b in batch], [b[2] for b in batch], self.crop_size,
+                                 [dr.offsets for dr in draws], [dr.flip_mask for dr in draws], [dr.shift for dr in draws],
+                                 [dr.scale for dr in draws], self.out_ch, self.channels_first)
+
 
 class _ChannelsFirstDataset(_Dataset):
     """public NCDHW batches (train.py:45-47 transposes each example); the engine's layers re-lay them out on entry"""
+
+    channels_first = True
 
     def _emit(self, xs, ys):
         return torch.stack(xs).permute(0, 4, 1, 2, 3).contiguous(), torch.stack(ys).permute(0, 4, 1, 2, 3).contiguous()
 
 
 def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=True, data_format='channels_last', seed=0,
-                    device=None, rank=None, world=None):
+                    device=None, rank=None, world=None, resident_bytes=0, workers=0):
     """-> (re-iterable dataset of (x, y) device batches, number of examples)   [train.py:12-64]
-    rank / world default to the process group's (one shard of the examples per rank, see _Dataset)."""
+    rank / world default to the process group's (one shard of the examples per rank, see _Dataset).
+    resident_bytes: budget of example bytes kept on the device after their first read; workers: host threads reading ahead
+    (see _Dataset; the batches do not depend on either)."""
     if data_format not in ('channels_last', 'channels_first'):
         raise ValueError('unknown data_format %r' % (data_format,))
     from . import parallel
@@ -148,4 +227,4 @@ def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=Tru
     files = sorted(os.path.join(loc, f) for f in os.listdir(loc) if f.endswith('.npz'))
     dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
     cls = _Dataset if data_format == 'channels_last' else _ChannelsFirstDataset
-    return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world), len(files)
+    return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world, resident_bytes, workers), len(files)

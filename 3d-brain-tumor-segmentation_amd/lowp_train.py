@@ -523,6 +523,33 @@ class LowPrecisionTrainer(object):
         ops.step_fence_done(fence)
         return Tensor(loss_t, requires_grad=False), macro, micro
 
+    def evaluate(self, dice_fn, x, y):
+        """validation iteration (train.py:166-172) with 16-bit storage -> (loss, macro_dice, micro_dice) as 1-element Tensors.  The
+        forward and the loss are step()'s, without input dropout (training=False); no backward, no update, the flat gradient buffer is
+        not touched.  The random counters move as in the fp32 train.eval_step -- the reparameterisation draw advances once (the
+        reference samples eps in validation too), the dropout counter not at all -- so the training trajectory does not depend on
+        which engine validated"""
+        m = self.model
+        x, y = torch.as_tensor(x), torch.as_tensor(y)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        fence = ops.step_fence('eval')
+        self._clock = None
+        x, y = x.to(dev).float(), y.to(dev).float()
+        if m.data_format == 'channels_first':
+            x, y = x.permute(0, 2, 3, 4, 1), y.permute(0, 2, 3, 4, 1)
+        x, y = x.contiguous(), y.contiguous()
+        split_fwd, _ = self._level0_splits(*x.shape[:4])
+        fw = self._forward(lowp.cast_padded(self.code, self.tdt, x), split_fwd)
+        sums = ops.loss_sums(fw['y_pred'], y, x, fw['y_vae'], fw['proj'])
+        parallel.all_reduce_sum(sums)
+        lt, _ = ops.loss_value(sums, fw['y_pred'].shape[-1], True)
+        l2v = ops.l2_reg_fwd(m.flat_params, m._l2_ranges) if m._l2_ranges else None
+        loss_t = ops.scalar_lincomb(lt, l2v, 1.0, 1.0) if l2v is not None else lt
+        macro, micro = dice_fn(Tensor(y, requires_grad=False), Tensor(fw['y_pred'], requires_grad=False))
+        self.last_labels = dice_fn.last_labels
+        ops.step_fence_done(fence)
+        return Tensor(loss_t, requires_grad=False), macro, micro
+
     def _stage_input(self, x):
         """the fp32 volume (engine layout) -> the encoder's 16-bit input, zero-padded to a 16-channel matrix step; input dropout
         (encoder.py:39,71) on the way"""

@@ -826,6 +826,50 @@ def augment_crop(x, y, var, crop, offsets, flip_mask, shift, scale, out_ch):
     return xo, yo
 
 
+def augment_batch_max():
+    """examples one launch of bts_augment_batch carries (ops.augment_batch takes any number: the call splits)"""
+    return int(lib().query('bts_augment_batch_max'))
+
+
+def augment_batch(xs, ys, variances, crop, offsets, flip_masks, shifts, scales, out_ch, channels_first=False, out=None):
+    """augment_crop for N examples in one launch, written straight into the batch tensors.  xs: N dense (S0,S1,S2,C) tensors of one
+    shape, ys: their labels, variances: N (C,) device tensors; offsets: N triples, flip_masks: N ints, shifts / scales: N lists of
+    C floats -> (x (N,T0,T1,T2,C), y (N,T0,T1,T2,out_ch)), or with channels_first (N,C,T0,T1,T2), (N,out_ch,T0,T1,T2).
+    out: (x, y) dense tensors of those shapes to write into (views of larger buffers are fine)"""
+    n = len(xs)
+    if n == 0 or not (len(ys) == len(variances) == len(offsets) == len(flip_masks) == len(shifts) == len(scales) == n):
+        raise ValueError('augment_batch: %d examples need as many labels, variances and draws' % n)
+    s0, s1, s2, c = xs[0].shape
+    for x, y, v in zip(xs, ys, variances):
+        _check(x, 'x'), _check(y, 'y'), _check(v, 'var')
+        if tuple(x.shape) != (s0, s1, s2, c) or y.numel() != s0 * s1 * s2 or v.numel() != c:
+            raise ValueError('augment_batch: every example must be a (%d,%d,%d,%d) volume with its labels and %d variances' % (s0, s1, s2, c, c))
+        if not (x.is_contiguous() and y.is_contiguous() and v.is_contiguous()):
+            raise ValueError('augment_batch: dense tensors only')
+    t0, t1, t2 = (int(t) for t in crop)
+    dev = xs[0].device
+    xshape = (n, c, t0, t1, t2) if channels_first else (n, t0, t1, t2, c)
+    yshape = (n, out_ch, t0, t1, t2) if channels_first else (n, t0, t1, t2, out_ch)
+    if out is None:
+        xo = torch.empty(xshape, dtype=torch.float32, device=dev)
+        yo = torch.empty(yshape, dtype=torch.float32, device=dev)
+    else:
+        xo, yo = out
+        _check(xo, 'out x'), _check(yo, 'out y')
+        if tuple(xo.shape) != xshape or tuple(yo.shape) != yshape or not (xo.is_contiguous() and yo.is_contiguous()):
+            raise ValueError('augment_batch: out must be dense %s and %s tensors' % (xshape, yshape))
+    ptrs = ctypes.c_void_p * n
+    off = (ctypes.c_int * (3 * n))(*[int(o) for tri in offsets for o in tri])
+    fl = (ctypes.c_int * n)(*[int(f) for f in flip_masks])
+    sh = (ctypes.c_float * (n * c))(*[float(v) for row in shifts for v in row])
+    sc = (ctypes.c_float * (n * c))(*[float(v) for row in scales for v in row])
+    as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)      # noqa: E731
+    lib().call('bts_augment_batch', as_p(ptrs(*[x.data_ptr() for x in xs])), as_p(ptrs(*[y.data_ptr() for y in ys])),
+               as_p(ptrs(*[v.data_ptr() for v in variances])), _p(xo), _p(yo), n, s0, s1, s2, c, t0, t1, t2, as_p(off), as_p(fl), as_p(sh),
+               as_p(sc), int(out_ch), 1 if channels_first else 0, _stream())
+    return xo, yo
+
+
 # ---- dataset preprocessing on the device (preprocess.py:17-131) ----
 def _window(v, c, name):
     """(st0, st1) of a view made by slicing a dense (S0,S1,S2,c) parent on its three spatial axes; no copy is ever made here"""

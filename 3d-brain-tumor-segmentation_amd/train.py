@@ -12,10 +12,30 @@ Differences, each deliberate:
     bit-exactly (tests/test_train_gpu.py);
   * metric accumulation stays on the device (one scalar add per step) and is read once per epoch -- the reference
     synchronises every step through `.update_state`.
+
+The command (the reference's train.py:219-223 with args.py:86-196):
+
+    python -m bts_amd.train --train_loc DIR/train --val_loc DIR/val --prepro_loc DIR/prepro.npy --save_folder OUT
+                            [--dtype bfloat16] [--batch_size 8] [--load_folder OUT] ...
+
+The flags and defaults are the reference's TrainArgParser (args.py:91-143), its two size checks included (args.py:170-174).  --gpu is
+accepted and implied: there is no CPU path.  Added: --dtype (training AND validation type), --workers, --resident_gb, --seed.
+Examples are the `.npz` files `python -m bts_amd.preprocess` writes; with a process group in the environment (torchrun) every rank
+runs the command, takes its shard and rank 0 writes the files.
+
+Deviations:
+  * `--downsampling avg` is refused at parse time by name (the reference accepts it and then calls None: no such layer exists);
+  * an empty --val_loc is refused (the reference ends in os.listdir(''));
+  * an empty --save_folder writes no files (the reference ends in os.mkdir(''));
+  * --load_folder reads `crop_size` as the key of the pickled dict it is (args.py:184 asks the dict for an attribute) and resumes
+    at the container's `next_epoch` with the optimiser state (see above);
+  * `train_args.pkl` is the plain dict of the arguments (`model_args` with `in_ch`, `crop_size`, ...), written by rank 0 alone.
 """
+import argparse
 import json
 import os
 import pickle
+import sys
 
 import numpy as np
 import torch
@@ -253,28 +273,36 @@ def eval_step(model, loss_fn, dice_fn, x, y):
 
 
 def fit(model, optimizer, loss_fn, dice_fn, train_data, val_data, n_epochs, patience=10, save_folder=None,
-        train_step_fn=None, eval_step_fn=None, log=print, compute_dtype=None):
+        train_step_fn=None, eval_step_fn=None, log=print, compute_dtype=None, eval_dtype=None):
     """The reference's `train(args)` from the logging set-up on (train.py:116-216).
 
     compute_dtype: None / 'float32' = the fp32 engine (util.train_step); 'bfloat16' / 'float16' = the 16-bit-storage engine
     (lowp_train.LowPrecisionTrainer.step: fp32 master weights, fp32 statistics, fp16 with dynamic loss scaling) for the training
-    iterations (its loss is util.DiceVAELoss, like train.py:143-147; loss_fn is then used by validation only) -- validation
-    stays on the fp32 engine.
+    iterations (its loss is util.DiceVAELoss, like train.py:143-147; loss_fn is then used by fp32 validation only).
+    eval_dtype: None / 'float32' = validation on the fp32 engine (eval_step), whatever the training type; 'bfloat16' / 'float16' =
+    validation through the same 16-bit engine (LowPrecisionTrainer.evaluate: no switch of engines, weight images and allocator
+    footprint once per epoch).  Both advance the random counters alike, so the training trajectory is the same either way.
 
     train_data / val_data: re-iterable collections of (x, y) batches (NDHWC tensors on the device).
     Resumes at `model.epoch` (train.py:133).  Returns the list of per-epoch rows (dicts).  On data-parallel runs every
     rank must call fit() (with the same n_epochs / patience; equally long shards) and iterates its own shard; rank 0 alone writes
     files, and rank 0's validation Dice drives the save / stop decision of all ranks."""
-    if train_step_fn is None and compute_dtype not in (None, 'float32'):
+    def trainer16(dtype):
         from .lowp_train import LowPrecisionTrainer
         trainer = getattr(model, '_trainer16', None)
-        if trainer is None or trainer.dtype_name != compute_dtype:
-            trainer = model._trainer16 = LowPrecisionTrainer(model, compute_dtype)
+        if trainer is None or trainer.dtype_name != dtype:
+            trainer = model._trainer16 = LowPrecisionTrainer(model, dtype)
+        return trainer
+    if train_step_fn is None and compute_dtype not in (None, 'float32'):
+        trainer = trainer16(compute_dtype)
         saved = (getattr(model, '_resume', None) or {}).get('loss_scale')
         if saved and saved.get('dtype') == compute_dtype:
             trainer.loss_scale, trainer._clean_steps = float(saved['scale']), int(saved['clean_steps'])
             trainer.skipped_steps = int(saved.get('skipped_steps', 0))
         train_step_fn = lambda x, y: trainer.step(optimizer, dice_fn, x, y)     # noqa: E731
+    if eval_step_fn is None and eval_dtype not in (None, 'float32'):
+        evaluator = trainer16(eval_dtype)
+        eval_step_fn = lambda x, y: evaluator.evaluate(dice_fn, x, y)           # noqa: E731
     tstep = train_step_fn or (lambda x, y: train_step(model, optimizer, loss_fn, dice_fn, x, y))
     estep = eval_step_fn or (lambda x, y: eval_step(model, loss_fn, dice_fn, x, y))
     writer = save_folder is not None and parallel.rank() == 0
@@ -339,3 +367,132 @@ def fit(model, optimizer, loss_fn, dice_fn, train_data, val_data, n_epochs, pati
         for k in names:
             m[k].reset_states()
     return history
+
+
+# ---- the command ----------------------------------------------------------------------------------------------------
+def arg_parser():
+    """the flags of the reference's TrainArgParser (args.py:91-143) and ours"""
+    p = argparse.ArgumentParser(prog='python -m bts_amd.train', description=__doc__.split('\n')[0])
+    p.add_argument('--train_loc', type=str, required=True, help='Folder of .npz training examples.')
+    p.add_argument('--prepro_loc', type=str, required=True, help='The prepro.npy written by the preprocessing command.')
+    p.add_argument('--val_loc', type=str, default='', help='Folder of .npz validation examples.')
+    p.add_argument('--save_folder', type=str, default='', help='Folder for train.log, the checkpoint and train_args.pkl; empty: nothing is written.')
+    p.add_argument('--load_folder', type=str, default='', help='Folder of an earlier run to resume; its train_args.pkl decides model and crop.')
+    p.add_argument('--lr', type=float, default=1e-4, help='Learning rate at epoch 0 of the polynomial schedule.')
+    p.add_argument('--batch_size', type=int, default=1, help='Examples per step (per rank).')
+    p.add_argument('--patience', type=int, default=-1, help='Stop after this many epochs without a better validation Dice; -1: never.')
+    p.add_argument('--n_epochs', type=int, default=300, help='Last epoch + 1.')
+    p.add_argument('--gpu', action='store_true', default=False, help='Accepted for the reference\'s command line; the GPU is always used.')
+    p.add_argument('--crop_size', type=str, default='128,128,128', help='Training crop as h,w,d.')
+    p.add_argument('--data_format', type=str, dest='model_args.data_format', default='channels_first',
+                   choices=['channels_last', 'channels_first'], help='Memory order of the batches the model takes.')
+    p.add_argument('--base_filters', type=int, dest='model_args.base_filters', default=32,
+                   help='Filters of the first level; doubled per level.')
+    p.add_argument('--depth', type=int, dest='model_args.depth', default=4, help='Levels of the encoder.')
+    p.add_argument('--l2_scale', type=float, dest='model_args.l2_scale', default=1e-5,
+                   help='Weight of the L2 term on every conv kernel.')
+    p.add_argument('--dropout', type=float, dest='model_args.dropout', default=0.2, help='Dropout rate on the input volume.')
+    p.add_argument('--groups', type=int, dest='model_args.groups', default=8, help='Groups of every GroupNorm.')
+    p.add_argument('--reduction', type=int, dest='model_args.reduction', default=8,
+                   help='Channel reduction of the squeeze-excitation gates.')
+    p.add_argument('--downsampling', type=str, dest='model_args.downsampling', default='conv', choices=['conv', 'max', 'avg'],
+                   help='Down-sampler (avg: listed by the reference, built by neither).')
+    p.add_argument('--upsampling', type=str, dest='model_args.upsampling', default='conv', choices=['conv', 'linear'],
+                   help='Up-sampler.')
+    p.add_argument('--out_ch', type=int, dest='model_args.out_ch', default=3, help='Output classes (labels without the background).')
+    p.add_argument('--dtype', type=str, default='float32', choices=('float32', 'bfloat16', 'float16'),
+                   help='Storage type of activations and weight images in training and validation.')
+    p.add_argument('--workers', type=int, default=8, help='Host threads that read the next examples; 0 reads in line.')
+    p.add_argument('--resident_gb', type=float, default=None,
+                   help='Budget (GB) of examples kept on the device after their first read (default: a quarter of its memory; 0: none).')
+    p.add_argument('--seed', type=int, default=0, help='Seed of the shuffle and augmentation generators.')
+    return p
+
+
+def parse_args(argv=None):
+    """args.py:145-196: model_args.* folded into a dict, crop split, sizes from the prepro dump, the two size checks, --load_folder;
+    writes train_args.pkl (rank 0, when there is a save folder)"""
+    from .preprocess import load_prepro
+    args = arg_parser().parse_args(argv)
+    args.model_args = {}
+    for key in [k for k in vars(args) if k.startswith('model_args.')]:                                    # args.py:24-38
+        args.model_args[key.split('.', 1)[1]] = getattr(args, key)
+        delattr(args, key)
+    args.data_format = args.model_args['data_format']
+    if args.model_args['downsampling'] == 'avg':
+        raise ValueError("--downsampling avg: the reference lists 'avg' and builds no such layer (its model calls None); use conv or max")
+    if not args.val_loc:
+        raise ValueError('--val_loc is empty: every epoch validates (train.py:165), a validation folder is needed')
+    args.crop_size = [int(s) for s in args.crop_size.split(',')]
+    size, _, _ = load_prepro(args.prepro_loc)
+    args.prepro_size = [int(s) for s in size]
+    if (args.model_args['base_filters'] / 2) % args.model_args['groups'] != 0:                             # args.py:170-171
+        raise AssertionError('Base filters must be a multiple of {} for group normalization at lowest spatial level.'.format(
+            args.model_args['groups'] * 2))
+    if args.model_args['base_filters'] % args.model_args['reduction'] != 0:                                # args.py:173-174
+        raise AssertionError('Base filters must be a multiple of {} for squeeze-excitation reduction.'.format(
+            args.model_args['reduction']))
+    args.model_args['in_ch'] = args.prepro_size[3]
+    if args.load_folder:                                                                                   # args.py:180-186
+        chkpt_args = load_train_args(args.load_folder)
+        args.model_args = chkpt_args['model_args']
+        args.crop_size = [int(s) for s in chkpt_args['crop_size']]
+        assert isinstance(args.model_args, dict)
+        args.data_format = args.model_args['data_format']
+        args.save_folder = args.load_folder
+    if args.save_folder and int(os.environ.get('RANK', '0')) == 0:
+        save_train_args(args.save_folder, vars(args))
+    return args
+
+
+def run(args):
+    """the reference's train(args) (train.py:71-216) -> {'history': fit's rows, 'model', 'optimizer'}"""
+    from . import data
+    from .model import Model
+    from .util import DiceCoefficient, DiceVAELoss, ScheduledOptim
+    if not torch.cuda.is_available():
+        raise RuntimeError('python -m bts_amd.train needs a GPU (no CPU fallback exists for the product path)')
+    parallel.init_from_env()
+    dev = torch.device('cuda', torch.cuda.current_device())        # (init_from_env selected the local rank's)
+    if args.resident_gb is None:
+        resident = torch.cuda.get_device_properties(dev).total_memory // 4
+    else:
+        resident = int(args.resident_gb * 1e9)
+    sets = []
+    for loc, shuffle in ((args.train_loc, True), (args.val_loc, False)):
+        sets.append(data.prepare_dataset(loc, args.batch_size, args.prepro_size, args.crop_size, args.model_args['out_ch'],
+                                         shuffle=shuffle, data_format=args.data_format, seed=args.seed, device=dev,
+                                         resident_bytes=resident, workers=args.workers))
+    (train_data, n_train), (val_data, n_val) = sets
+    print('{} training examples.'.format(n_train), flush=True)
+    print('{} validation examples.'.format(n_val), flush=True)
+    model = Model(**args.model_args)
+    model.build((1,) + tuple(args.crop_size) + (args.model_args['in_ch'],))
+    optimizer = ScheduledOptim(learning_rate=args.lr)              # (n_epochs of the schedule stays 300, as train.py:105 leaves it)
+    if args.load_folder:
+        load_checkpoint(args.load_folder, model, optimizer)
+    if parallel.active():
+        parallel.broadcast_parameters(model)
+    print('Total number of parameters: {}'.format(int(model.n_params)), flush=True)
+    loss_fn = DiceVAELoss(data_format=args.data_format)
+    dice_fn = DiceCoefficient(data_format=args.data_format)
+    history = fit(model, optimizer, loss_fn, dice_fn, train_data, val_data, args.n_epochs, patience=args.patience,
+                  save_folder=args.save_folder or None, log=lambda s: print(s, flush=True), compute_dtype=args.dtype,
+                  eval_dtype=args.dtype)
+    return {'history': history, 'model': model, 'optimizer': optimizer}
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    print('Train args: {}'.format(args), flush=True)
+    ours = not parallel.active()                 # (a group the caller brought up is the caller's to end)
+    try:
+        run(args)
+    finally:
+        if ours and parallel.active():
+            torch.distributed.destroy_process_group()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -293,6 +293,18 @@ int bts_channel_moments(const float* x, float* mean, float* var, void* workspace
 int bts_augment_crop(const float* x, const float* y, const float* var, float* xo, float* yo, int S0, int S1, int S2, int C,
                      int T0, int T1, int T2, int o0, int o1, int o2, int flip_mask, const float* shift, const float* scale,
                      int out_ch, bts_stream_t stream);
+/* The same transformation for a whole batch in one launch, written straight into the batch tensors (no stack / permute copy
+ * afterwards).  x, y, var: HOST arrays of N device pointers (volumes, labels, variances: one per example; all volumes (S0,S1,S2,C),
+ * all crops (T0,T1,T2)); offsets: 3N host ints, flips: N host ints (bits 4|2|1), shift / scale: N*C host floats.
+ * layout 0: xo (N,T0,T1,T2,C), yo (N,T0,T1,T2,out_ch); layout 1: xo (N,C,T0,T1,T2), yo (N,out_ch,T0,T1,T2).
+ * The per-example table travels by value in the kernel arguments: bts_augment_batch_max() examples per launch, a larger N is split
+ * into several launches by the call itself.  Per element the bits of bts_augment_crop (which is this call with N = 1, layout 0):
+ * fmaf(shift, sqrtf(var), x) * scale.  BTS_ERR_SHAPE, before any HIP call, for N <= 0, C outside 1..16, out_ch <= 0, an empty crop,
+ * a layout other than 0 / 1, a NULL table, flip bits above 7 or a window that leaves its volume. */
+long bts_augment_batch_max(void);
+int bts_augment_batch(const float* const* x, const float* const* y, const float* const* var, float* xo, float* yo, int N, int S0,
+                      int S1, int S2, int C, int T0, int T1, int T2, const int* offsets, const int* flips, const float* shift,
+                      const float* scale, int out_ch, int layout, bts_stream_t stream);
 
 /* ===== dataset preprocessing on the device (preprocess.py:17-131: create_dataset, compute_norm, main) =====
  * Dense fp32 (S0,S1,S2,C) volumes, C innermost, 1 <= C <= 16.  A crop window (T0,T1,T2,C) of such a volume is addressed in place:
