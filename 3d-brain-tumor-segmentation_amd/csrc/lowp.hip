@@ -1096,7 +1096,7 @@ extern "C" long bts_lp_gn_workspace(int N, long V, int C, int G) {
 extern "C" int bts_lp_gn_stats(int dtype, const void* x, float* mean, float* rstd, void* workspace, long workspace_bytes, int N, long V,
                                int C, int G, int mode, float eps, hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || V <= 0 || C < G || C % G != 0) return BTS_ERR_SHAPE;
+  if (N <= 0 || V <= 0 || G <= 0 || C < G || C % G != 0) return BTS_ERR_SHAPE;
   const long E = V * C, L = E / G;
   if (mode == BTS_GN_SLAB && (E % G != 0 || L % 8 != 0)) return BTS_ERR_UNSUPPORTED;
   if ((((uintptr_t)x) | ((uintptr_t)workspace)) & 15) return BTS_ERR_ALIGN;
@@ -1195,7 +1195,7 @@ __global__ __launch_bounds__(256) void lp_gn_apply_chunk_kernel(const unsigned s
 extern "C" int bts_lp_gn_apply(int dtype, const void* x, void* y, const float* gamma, const float* beta, const float* mean,
                                const float* rstd, int N, long V, int C, int ldy, int G, int mode, int relu, hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || V <= 0 || C < G || C % G != 0 || C % 8 != 0 || ldy % 8 != 0 || ldy < C) return BTS_ERR_SHAPE;
+  if (N <= 0 || V <= 0 || C <= 0 || G <= 0 || C < G || C % G != 0 || C % 8 != 0 || ldy % 8 != 0 || ldy < C) return BTS_ERR_SHAPE;
   const long E = V * C, L = E / G;
   if (mode == BTS_GN_SLAB && L % 8 != 0) return BTS_ERR_UNSUPPORTED;
   if ((((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return BTS_ERR_ALIGN;
@@ -1293,7 +1293,7 @@ extern "C" long bts_lp_colsum_workspace(int N, long V, int C) {
 extern "C" int bts_lp_colsum(int dtype, const void* x, float* out, void* workspace, long workspace_bytes, int N, long V, int C, float scale,
                              hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || V <= 0 || C % 8 != 0 || C > 256 || 256 % (C / 8) != 0) return BTS_ERR_SHAPE;
+  if (N <= 0 || V <= 0 || C <= 0 || C % 8 != 0 || C > 256 || 256 % (C / 8) != 0) return BTS_ERR_SHAPE;
   if (((uintptr_t)x) & 15) return BTS_ERR_ALIGN;
   const int B = lp_colsum_blocks(V);
   if (workspace_bytes < bts_lp_colsum_workspace(N, V, C)) return BTS_ERR_WORKSPACE;
@@ -1402,7 +1402,7 @@ extern "C" int bts_lp_block_epilogue(int dtype, const void* res, const void* c2,
                                      const float* gamma, const float* beta, const float* mean, const float* rstd, int N, long V, int C,
                                      int ldo, int G, int mode, hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || V <= 0 || C % 8 != 0 || C > 256 || ((C / 8) & (C / 8 - 1)) != 0 || C % G != 0 || ldo % 8 != 0 || ldo < C) return BTS_ERR_SHAPE;
+  if (N <= 0 || V <= 0 || C <= 0 || G <= 0 || C % 8 != 0 || C > 256 || ((C / 8) & (C / 8 - 1)) != 0 || C % G != 0 || ldo % 8 != 0 || ldo < C) return BTS_ERR_SHAPE;
   const long E = V * C, L = E / G;
   if (mode == BTS_GN_SLAB && L % 8 != 0) return BTS_ERR_UNSUPPORTED;
   if ((((uintptr_t)res) & 15) || (((uintptr_t)c2) & 15) || (((uintptr_t)out) & 15)) return BTS_ERR_ALIGN;
@@ -1516,7 +1516,7 @@ extern "C" int bts_lp_block_epilogue_head(int dtype, const void* res, const void
                                           const float* gamma, const float* beta, const float* mean, const float* rstd, const float* head_w,
                                           const float* head_b, int N, long V, int C, int G, int mode, int K, int sigmoid, hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || V <= 0 || C % 8 != 0 || C > 256 || ((C / 8) & (C / 8 - 1)) != 0 || C % G != 0 || K < 1) return BTS_ERR_SHAPE;
+  if (N <= 0 || V <= 0 || C <= 0 || G <= 0 || C % 8 != 0 || C > 256 || ((C / 8) & (C / 8 - 1)) != 0 || C % G != 0 || K < 1) return BTS_ERR_SHAPE;
   const long E = V * C, L = E / G;
   const int slab = mode == BTS_GN_SLAB;
   const long Lu = slab ? L : E;
@@ -1780,7 +1780,7 @@ __global__ __launch_bounds__(256) void lp_head_oct_kernel(const unsigned short* 
 extern "C" int bts_lp_head(int dtype, const void* x, const float* w, const float* bias, float* y, long nvox, int C, int ldx, int K, int sigmoid,
                            hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (nvox <= 0 || C % 8 != 0 || K < 1 || K > 4 || ldx % 8 != 0) return BTS_ERR_SHAPE;
+  if (nvox <= 0 || C <= 0 || C % 8 != 0 || K < 1 || K > 4 || ldx % 8 != 0 || ldx < C) return BTS_ERR_SHAPE;
   if (((uintptr_t)x) & 15) return BTS_ERR_ALIGN;
   long blocks = (nvox + 255) / 256;
   if (blocks > 32768) blocks = 32768;
@@ -2155,7 +2155,7 @@ static int lp_gn_bwd_tail(int dtype, const void* x, const void* dy, void* dx, fl
 }
 static int lp_gn_bwd_check(int dtype, const void* x, const void* dy, const void* dx, const float* dx32, int N, long V, int C, int lddy, int G) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || V <= 0 || C < G || C % G != 0 || C % 8 != 0 || C > 256 || (C & (C - 1)) != 0 || lddy % 8 != 0 || lddy < C) return BTS_ERR_SHAPE;
+  if (N <= 0 || V <= 0 || G <= 0 || C < G || C % G != 0 || C % 8 != 0 || C > 256 || (C & (C - 1)) != 0 || lddy % 8 != 0 || lddy < C) return BTS_ERR_SHAPE;
   const long E = V * C, L = E / G;
   const int cg = C / G;
   if (E % G != 0 || L % 2048 != 0 || cg > 32 || 256 % cg != 0) return BTS_ERR_UNSUPPORTED;   // (the caller falls back to the fp32 kernels)
@@ -2539,7 +2539,7 @@ extern "C" int bts_lp_block_bwd(int dtype, const void* dout, int lddo, const voi
                                 float* dw2, float* dwsp, float* dgamma, float* dbeta, float* dbias_pt, float* dbias_c2, void* workspace,
                                 long workspace_bytes, int N, long V, int F, int R, int G, hipStream_t stream) {
   if (dtype != LP_F16 && dtype != LP_BF16) return BTS_ERR_UNSUPPORTED;
-  if (N <= 0 || V <= 0 || F < 8 || F < G || F % G != 0 || (F & (F - 1)) != 0 || F > 256 || lddo % 8 != 0 || lddo < F || R <= 0) return BTS_ERR_SHAPE;
+  if (N <= 0 || V <= 0 || F < 8 || G <= 0 || F < G || F % G != 0 || (F & (F - 1)) != 0 || F > 256 || lddo % 8 != 0 || lddo < F || R <= 0) return BTS_ERR_SHAPE;
   const long E = V * F, L = E / G;
   const int cg = F / G;
   if (E % G != 0 || L % 2048 != 0 || cg > 32 || 256 % cg != 0) return BTS_ERR_UNSUPPORTED;

@@ -407,7 +407,8 @@ int bts_lp_uncast(int dtype, const void* src, long ld_src, float* dst, long ld_d
  * (model.py:58, after encoder.py:71's dropout), the 2-channel VAE-output gradient and the 1-channel VAE tensor (vae.py:110-111) as
  * whole 16-channel matrix steps */
 int bts_lp_cast_pad16(int dtype, const float* src, long ld_src, void* dst, long rows, int C, bts_stream_t stream);
-/* GroupNormalization (group_norm.py:83-124), both semantics; x dense */
+/* GroupNormalization (group_norm.py:83-124), both semantics; x dense; G > 0 and G | C (BTS_ERR_SHAPE otherwise, also in the epilogues and
+ * backward passes below that take G) */
 long bts_lp_gn_workspace(int N, long V, int C, int G);
 int bts_lp_gn_stats(int dtype, const void* x, float* mean, float* rstd, void* workspace, long workspace_bytes, int N, long V, int C, int G,
                     int mode, float eps, bts_stream_t stream);
@@ -550,7 +551,8 @@ int bts_lp_maxpool2_bwd(int dtype, const void* dy, const uint8_t* idx, void* dx,
 int bts_lp_upsample2_fwd(int dtype, const void* x, void* y, int N, int D, int H, int W, int C, int ldx, int ldy, bts_stream_t stream);
 int bts_lp_upsample2_bwd(int dtype, const void* dy, void* dx, int N, int D, int H, int W, int C, int lddy, int lddx, int accumulate,
                          bts_stream_t stream);
-/* output head (decoder.py:55-63): y = sigmoid(x . W + b), W (C, K <= 4) fp32, y fp32 (the label map is taken from it) */
+/* output head (decoder.py:55-63): y = sigmoid(x . W + b), W (C, K <= 4) fp32, y fp32 (the label map is taken from it); x rows of
+ * ldx >= C elements, C > 0, C % 8 == 0 and ldx % 8 == 0 (BTS_ERR_SHAPE otherwise) */
 int bts_lp_head(int dtype, const void* x, const float* w, const float* bias, float* y, long nvox, int C, int ldx, int K, int sigmoid,
                 bts_stream_t stream);
 /* output head backward (decoder.py:55-63 under autodiff; train.py:142-151): dpre = dL/d(x . W + b) (nvox, K) fp32 (bts_sigmoid_bwd) ->
