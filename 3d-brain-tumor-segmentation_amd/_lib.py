@@ -17,7 +17,7 @@ HEADER = os.path.join(_ROOT, 'include', 'bts_hip.h')
 LIBPATH = os.environ.get('BTS_HIP_LIB') or os.path.join(_HERE, 'libbts_hip.so')  # override: A/B timing of two builds
 
 _CT = {
-    'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'uint64_t': ctypes.c_uint64,
+    'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double, 'uint64_t': ctypes.c_uint64,
     'bts_stream_t': ctypes.c_void_p,
 }
 

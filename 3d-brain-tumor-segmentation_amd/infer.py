@@ -21,8 +21,11 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
   * the score (test.py:226-232,266-270) hands a 1-channel raw label volume and a spline-zoomed label volume to DiceCoefficient, which
     expects one-hot truth and probabilities; `label_scores` gives the per-class Dice the call evidently intends, between the truth and
     the predicted label map on the scan's own grid, from a confusion matrix counted on the device (bts_label_confusion).
+  * overlap alone is what the reference's score (test.py:266-270) can report; `surface_scores` adds the distance side BraTS tables
+    carry, the 95th-percentile Hausdorff distance per class and region (bts_region_surface, bts_edt3d_sq, bts_masked_select), and
+    `region_rates_from_confusion` sensitivity and specificity of the regions.
 All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_spline_prefilter3d, bts_zoom3d,
-bts_skull_strip, bts_label_confusion, the model forward).
+bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, the model forward).
 """
 import glob
 import os
@@ -378,3 +381,114 @@ def label_scores(truth, pred, n_classes=4):
         maps.append(t.contiguous())
     counts = ops.label_confusion(maps[0], maps[1], n_classes)
     return scores_from_confusion(counts.cpu().numpy())
+
+
+BRATS_REGIONS = (('wt', (1, 2, 3)), ('tc', (1, 3)), ('et', (3,)))      # over classes min(label, 3): labels {1,2,4} / {1,4} / {4}
+
+
+def region_rates_from_confusion(confusion):
+    """4 x 4 counts [truth class, predicted class] -> {'sens_wt', 'sens_tc', 'sens_et', 'spec_wt', 'spec_tc', 'spec_et'}: sensitivity
+    TP / (TP + FN) and specificity TN / (TN + FP) of the BraTS regions, float64 on the host, nan where the denominator is zero"""
+    m = np.asarray(confusion)
+    if m.shape != (4, 4):
+        raise ValueError('confusion must be 4 x 4 (the BraTS regions are sets of classes 1..3), got shape %s' % (m.shape,))
+    m = m.astype(np.int64)
+    total = int(m.sum())
+    out = {}
+    for name, sel in BRATS_REGIONS:
+        sel = list(sel)
+        tp, t, p = int(m[np.ix_(sel, sel)].sum()), int(m[sel, :].sum()), int(m[:, sel].sum())
+        tn, neg = total - t - p + tp, total - t
+        out['sens_' + name] = tp / t if t else float('nan')
+        out['spec_' + name] = tn / neg if neg else float('nan')
+    return out
+
+
+def surface_scores(truth, pred, spacing, n_classes=4, percentile=95.0):
+    """Hausdorff distances in mm between the surfaces of two uint8 label maps (D,H,W) of equal shape (device tensors or numpy) on a
+    grid of voxel spacing `spacing` = (sd,sh,sw) -> {'hd95', 'hd', 'hd95_directed', 'surface_voxels': one entry per class 1..K-1, and for
+    n_classes == 4 'hd95_wt/tc/et', 'hd_wt/tc/et'}.  Labels >= K-1 count as class K-1.  Per region, with T / P the surface voxels (a
+    face neighbour outside the region or the volume) of truth / prediction: d(P->T) = the distances from every voxel of P to the
+    nearest voxel of T, d(T->P) likewise; hd95 = np.percentile of the two sets pooled (medpy's hd95), hd = their maximum,
+    hd95_directed = (percentile of d(P->T), of d(T->P)) (its maximum is MONAI's convention), surface_voxels = (|T|, |P|).  nan when
+    both regions are empty, inf when one is.  On the device: bts_region_surface, bts_edt3d_sq (exact, float64, mm^2),
+    bts_masked_select (exact order statistics); on the host the ranks, the square roots and the interpolation, in float64."""
+    if tuple(truth.shape) != tuple(pred.shape):
+        raise ValueError('surface_scores: truth has shape %s, the prediction %s' % (tuple(truth.shape), tuple(pred.shape)))
+    if len(truth.shape) != 3:
+        raise ValueError('surface_scores: label maps must have shape (D,H,W), got %s' % (tuple(truth.shape),))
+    q = float(percentile) / 100.0
+    if not 0.0 <= q <= 1.0:
+        raise ValueError('surface_scores: percentile must lie in [0, 100], got %r' % (percentile,))
+    spacing = tuple(float(s) for s in spacing)
+    if len(spacing) != 3:
+        raise ValueError('surface_scores: spacing must be (sd,sh,sw), got %r' % (spacing,))
+    k = int(n_classes)
+    maps = []
+    for t in (truth, pred):
+        if isinstance(t, np.ndarray):
+            if t.dtype != np.uint8:
+                raise ValueError('surface_scores: label maps must be uint8, got %s' % t.dtype)
+            if not torch.cuda.is_available():
+                raise RuntimeError('surface_scores: the distances are computed on the GPU (no CPU fallback exists for the product path)')
+            t = torch.from_numpy(np.ascontiguousarray(t)).cuda()
+        maps.append(t.contiguous())
+    tmap, pmap = maps
+    dev, shape, n = tmap.device, tuple(tmap.shape), tmap.numel()
+    names = ['class_%d' % c for c in range(1, k)]
+    masks = [1 << c for c in range(1, k)]
+    if k == 4:
+        for name, sel in BRATS_REGIONS:
+            names.append(name)
+            masks.append(sum(1 << c for c in sel))
+    uniq = sorted(set(masks))
+    # one set of buffers for every region: mask = [surface of P | surface of T], values = [dist2 to T's surface | dist2 to P's surface]
+    surf = torch.empty(2 * n, dtype=torch.uint8, device=dev)
+    dist = torch.empty(2 * n, dtype=torch.float64, device=dev)
+    sp, st = surf[:n].view(shape), surf[n:].view(shape)
+    counts = torch.zeros((len(uniq), 2), dtype=torch.int64, device=dev)
+    for i, cm in enumerate(uniq):
+        ops.region_surface(tmap, k, cm, out=st, count=counts[i, 0:1])
+        ops.region_surface(pmap, k, cm, out=sp, count=counts[i, 1:2])
+    counts = counts.cpu().numpy()                                  # the one read of the surface counts
+
+    def ranks(m):
+        pos = q * (m - 1)
+        return [int(np.floor(pos)), int(np.ceil(pos)), m - 1]
+
+    picked = torch.zeros((len(uniq), 3, 3), dtype=torch.float64, device=dev)
+    live = []
+    for i, cm in enumerate(uniq):
+        nt, npr = int(counts[i, 0]), int(counts[i, 1])
+        if nt == 0 or npr == 0:
+            continue
+        live.append(i)
+        ops.region_surface(tmap, k, cm, out=st, count=torch.zeros(1, dtype=torch.int64, device=dev))
+        ops.region_surface(pmap, k, cm, out=sp, count=torch.zeros(1, dtype=torch.int64, device=dev))
+        ops.edt3d_sq(st, spacing, out=dist[:n])
+        ops.edt3d_sq(sp, spacing, out=dist[n:])
+        ops.masked_select(dist, surf, ranks(nt + npr), out=picked[i, 0])
+        ops.masked_select(dist[:n], surf[:n], ranks(npr), out=picked[i, 1])
+        ops.masked_select(dist[n:], surf[n:], ranks(nt), out=picked[i, 2])
+    picked = np.sqrt(picked.cpu().numpy()) if live else None
+
+    def interpolate(lo, hi, m):
+        pos = q * (m - 1)
+        return float(lo + (hi - lo) * (pos - np.floor(pos)))
+
+    res = {}
+    for i, cm in enumerate(uniq):
+        nt, npr = int(counts[i, 0]), int(counts[i, 1])
+        if nt == 0 or npr == 0:
+            v = float('nan') if nt == npr else float('inf')
+            res[cm] = (v, v, (v, v), (nt, npr))
+            continue
+        a = picked[i]
+        res[cm] = (interpolate(a[0, 0], a[0, 1], nt + npr), float(a[0, 2]),
+                   (interpolate(a[1, 0], a[1, 1], npr), interpolate(a[2, 0], a[2, 1], nt)), (nt, npr))
+    per = [res[cm] for cm in masks[:k - 1]]
+    out = {'hd95': [r[0] for r in per], 'hd': [r[1] for r in per], 'hd95_directed': [r[2] for r in per],
+           'surface_voxels': [r[3] for r in per]}
+    for name, cm in zip(names[k - 1:], masks[k - 1:]):
+        out['hd95_' + name], out['hd_' + name] = res[cm][0], res[cm][1]
+    return out

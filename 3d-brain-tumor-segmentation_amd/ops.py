@@ -797,6 +797,75 @@ def label_confusion(truth, pred, n_classes=4, counts=None):
     return counts
 
 
+# ---- the distance side of the per-case score (test.py:266-270; csrc/surface.hip) ----
+def _dense(t, dtype, name, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError('%s must be a dense %s tensor on the GPU' % (name, what))
+    return t
+
+
+def region_surface(lab, n_classes=4, class_mask=0b1110, out=None, count=None):
+    """lab: dense uint8 label map (D,H,W) on the GPU; the region is the set of classes min(label, K-1) whose bit is set in class_mask
+    -> (surf uint8 (D,H,W): 1 on the region's surface voxels (a face neighbour outside the region or the volume), 0 elsewhere;
+    count: one int64 on the GPU, += their number).  out: a dense uint8 tensor of lab's size to write into; count: a zeroed (or partly
+    filled) int64 element to add into; new ones otherwise"""
+    _dense(lab, torch.uint8, 'region_surface: lab', 'uint8')
+    if lab.dim() != 3:
+        raise ValueError('region_surface: lab must have shape (D,H,W), got %s' % (tuple(lab.shape),))
+    if out is None:
+        out = torch.empty_like(lab)
+    elif _dense(out, torch.uint8, 'region_surface: out', 'uint8').numel() != lab.numel():
+        raise ValueError('region_surface: out holds %d voxels, lab %d' % (out.numel(), lab.numel()))
+    if count is None:
+        count = torch.zeros(1, dtype=torch.int64, device=lab.device)
+    elif _dense(count, torch.int64, 'region_surface: count', 'int64').numel() != 1:
+        raise ValueError('region_surface: count must be one int64 value on the GPU')
+    d, h, w = lab.shape
+    lib().call('bts_region_surface', _p(lab), _p(out), _p(count), d, h, w, int(n_classes), int(class_mask), _stream())
+    return out, count
+
+
+def edt3d_sq(feat, spacing=(1.0, 1.0, 1.0), out=None):
+    """feat: dense uint8 (D,H,W) on the GPU, spacing (sd,sh,sw) in mm -> float64 (D,H,W): the squared distance in mm^2 to the nearest
+    voxel with feat != 0 (+inf when there is none), exact.  out: a dense float64 tensor of feat's size to write into"""
+    _dense(feat, torch.uint8, 'edt3d_sq: feat', 'uint8')
+    if feat.dim() != 3:
+        raise ValueError('edt3d_sq: feat must have shape (D,H,W), got %s' % (tuple(feat.shape),))
+    sd, sh, sw = (float(s) for s in spacing)
+    if out is None:
+        out = torch.empty(tuple(feat.shape), dtype=torch.float64, device=feat.device)
+    elif _dense(out, torch.float64, 'edt3d_sq: out', 'float64').numel() != feat.numel():
+        raise ValueError('edt3d_sq: out holds %d voxels, feat %d' % (out.numel(), feat.numel()))
+    d, h, w = feat.shape
+    lib().call('bts_edt3d_sq', _p(feat), _p(out), d, h, w, sd, sh, sw, _stream())
+    return out
+
+
+def masked_select(v, mask, ranks, out=None):
+    """v: dense NON-NEGATIVE float64, mask: dense uint8 of the same size, both on the GPU; ranks: up to 8 host integers
+    -> float64 (len(ranks),) on the GPU: the ranks[i]-th smallest (0-based) of v[mask != 0], the bits np.sort gives; nan where
+    ranks[i] is not below the number of selected values.  out: a dense float64 tensor of len(ranks) values to write into"""
+    _dense(v, torch.float64, 'masked_select: v', 'float64')
+    _dense(mask, torch.uint8, 'masked_select: mask', 'uint8')
+    if v.numel() != mask.numel():
+        raise ValueError('masked_select: %d values and %d mask bytes' % (v.numel(), mask.numel()))
+    ranks = [int(r) for r in ranks]
+    nr = len(ranks)
+    if out is None:
+        out = torch.empty(nr, dtype=torch.float64, device=v.device)
+    elif _dense(out, torch.float64, 'masked_select: out', 'float64').numel() != nr:
+        raise ValueError('masked_select: out must hold %d float64 values' % nr)
+    if nr == 0:
+        return out
+    nb = lib().query('bts_masked_select_workspace', nr)
+    ws = workspace(nb, v.device)
+    rk = (ctypes.c_long * nr)(*ranks)
+    lib().call('bts_masked_select', _p(v), _p(mask), v.numel(), ctypes.cast(rk, ctypes.c_void_p), nr, _p(out), _p(ws), _stream())
+    if v.numel() == 0:
+        out.fill_(float('nan'))                                  # nothing is selected, and the call launches nothing for no values
+    return out
+
+
 # ---- training-time augmentation on the device (SURVEY 8 f-3) ----
 def channel_moments(x):
     """per-channel (mean, population variance) over all voxels of a dense (..., C) tensor, C <= 16 -> two (C,) tensors"""

@@ -11,10 +11,13 @@ threads while the device works on the previous case; `infer.segment_case` resamp
 model and the tumour model with test-time augmentation and brings the labels back to the scan's grid; `mask.nii` is written with
 the affine averaged over the modalities into the case folder (test.py:69-70), or into DIR/<case>/ with --out_loc; a labelled case
 prints the reference's line (test.py:269) from `infer.label_scores`.  With --out_loc a `scores.csv` holds one row per labelled case
-and a last row computed from the summed confusion matrix.
+and a last row computed from the summed confusion matrix.  With --surface_metrics each labelled case also gets the 95th-percentile Hausdorff
+distance (mm, on the scan's own grid with its pixdim) and the sensitivity and specificity of the regions WT, TC and ET
+(`infer.surface_scores`, `infer.region_rates_from_confusion`): nine more columns after the existing ones; the `total` row holds the mean
+of the finite distances and the rates of the summed confusion matrix.
 
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
-accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc.
+accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics.
 
 Deviations:
   * cases are visited in sorted order of their paths (the reference: the file system's order);
@@ -34,11 +37,15 @@ import numpy as np
 import torch
 
 from . import nifti
-from .infer import Interpolator, StageSpec, label_scores, scores_from_confusion, segment_case, zoom_output_shape
+from .infer import (Interpolator, StageSpec, label_scores, region_rates_from_confusion, scores_from_confusion, segment_case, surface_scores,
+                    zoom_output_shape)
 from .preprocess import load_prepro
 from .train import load_checkpoint, load_train_args
 
 N_CLASSES = 4        # background + the three BraTS labels 1, 2, 4 (4 counts as class 3, preprocess.py:36)
+HD95_KEYS = ('hd95_wt', 'hd95_tc', 'hd95_et')
+RATE_KEYS = ('sens_wt', 'sens_tc', 'sens_et', 'spec_wt', 'spec_tc', 'spec_et')
+SURFACE_KEYS = HD95_KEYS + RATE_KEYS      # the columns --surface_metrics appends to scores.csv
 
 
 def arg_parser():
@@ -62,6 +69,8 @@ def arg_parser():
     p.add_argument('--tta_batch', type=int, default=None, help='Augmented copies per forward (default: 1 in float32, 4 in 16 bits).')
     p.add_argument('--workers', type=int, default=8, help='Host threads that decode the next cases; 0 decodes in line.')
     p.add_argument('--out_loc', type=str, default='', help='Write DIR/<case>/mask.nii and DIR/scores.csv instead of into the case folders.')
+    p.add_argument('--surface_metrics', action='store_true', default=False,
+                   help='Also score each labelled case with the 95th-percentile Hausdorff distance, sensitivity and specificity of WT, TC, ET.')
     return p
 
 
@@ -160,6 +169,17 @@ def score_row(name, s):
     return [name, _fmt(s['macro']), _fmt(s['micro'])] + [_fmt(v) for v in s['dice']] + [_fmt(s[k]) for k in ('wt', 'tc', 'et')]
 
 
+def surface_row(s):
+    """the columns --surface_metrics appends to a score_row"""
+    return [_fmt(s[k]) for k in SURFACE_KEYS]
+
+
+def mean_finite(values):
+    """mean over the finite values, nan when there is none"""
+    vals = [v for v in values if np.isfinite(v)]
+    return float(np.mean(vals)) if vals else float('nan')
+
+
 def _decoded(cases, args):
     """the decoded cases in order; with workers > 0 a bounded number of them is decoded ahead by host threads"""
     if args.workers <= 0:
@@ -207,6 +227,10 @@ def run(args):
         if y is not None:
             s = label_scores(y, lab, N_CLASSES)
             total += s['confusion']
+            if args.surface_metrics:
+                hd = surface_scores(y, lab, pixdim, N_CLASSES)
+                s.update({k: hd[k] for k in HD95_KEYS})
+                s.update(region_rates_from_confusion(s['confusion']))
         where = os.path.join(args.out_loc, name) if args.out_loc else path
         os.makedirs(where, exist_ok=True)
         nifti.save(os.path.join(where, 'mask.nii'), lab.cpu().numpy(), case['affine'])
@@ -214,18 +238,30 @@ def run(args):
         if s is not None:
             scores.append((name, s))
             print('{}. Macro: {ma: 1.4f}. Micro: {mi: 1.4f}'.format(name, ma=s['macro'], mi=s['micro']), flush=True)    # test.py:269
+            if args.surface_metrics:
+                print('{}. HD95 WT: {:1.4f}. TC: {:1.4f}. ET: {:1.4f}'.format(name, *[s[k] for k in HD95_KEYS]), flush=True)
     overall = scores_from_confusion(total) if scores else None
+    n_inf = 0
+    if args.surface_metrics:
+        n_inf = sum(1 for _, s in scores for k in HD95_KEYS if np.isinf(s[k]))
+        if overall is not None:
+            overall.update({k: mean_finite([s[k] for _, s in scores]) for k in HD95_KEYS})
+            overall.update(region_rates_from_confusion(total))
     if args.out_loc:
         head = ['case', 'macro', 'micro'] + ['dice_%d' % c for c in range(1, N_CLASSES)] + ['wt', 'tc', 'et']
         rows = [head] + [score_row(n, s) for n, s in scores]
         if overall is not None:
             rows.append(score_row('total', overall))
+        if args.surface_metrics:
+            extra = [list(SURFACE_KEYS)] + [surface_row(s) for _, s in scores] + ([surface_row(overall)] if overall is not None else [])
+            rows = [r + e for r, e in zip(rows, extra)]
         with open(os.path.join(args.out_loc, 'scores.csv'), 'w') as f:
             f.write(''.join(','.join(r) + '\n' for r in rows))
     dt = time.time() - t0
     print('{} cases segmented ({} scored) in {:.1f} s, {:.2f} cases/s; {} skipped for a missing modality{}'.format(
         done, len(scores), dt, done / dt if dt > 0 else 0.0, len(skipped),
-        ': ' + ', '.join('%s (%s)' % sk for sk in skipped) if skipped else ''), flush=True)
+        (': ' + ', '.join('%s (%s)' % sk for sk in skipped) if skipped else '') +
+        ('; {} region distances infinite (a region empty in one of the two maps)'.format(n_inf) if args.surface_metrics else '')), flush=True)
     return {'cases': done, 'scored': len(scores), 'skipped': skipped, 'scores': scores, 'total': overall}
 
 

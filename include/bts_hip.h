@@ -279,6 +279,28 @@ int bts_skull_strip(const float* x, const float* p, const float* m, float* xo, f
  * int64 on the device, accumulated across calls (zero it once per score).  K = 4 folds BraTS label 4 onto class 3 (preprocess.py:36).
  * Integer atomics only: exact and bit-reproducible.  BTS_ERR_SHAPE for K outside 2..8 or nvox < 0; nvox == 0 launches nothing. */
 int bts_label_confusion(const uint8_t* truth, const uint8_t* pred, long nvox, int K, long* counts, bts_stream_t stream);
+/* The distance side of the per-case score (test.py:266-270): the 95th-percentile Hausdorff distance of a region is taken from the three
+ * calls below and a few float64 operations on the host (bts_amd.infer.surface_scores).
+ * Surface of one region of a dense uint8 label map (D,H,W): a voxel belongs to the region when bit min(label, K-1) of class_mask is set
+ * (K in 2..8, 0 <= class_mask < 2^K; WT = 14, TC = 10, ET = 8 for K = 4), and is a surface voxel when one of its six face neighbours is
+ * outside the region or outside the volume.  surf (uint8, every byte written) = 1 on surface voxels, 0 elsewhere; *count (int64 on the
+ * device, accumulated across calls) += their number.  BTS_ERR_SHAPE for a non-positive extent, K outside 2..8 or a class_mask outside
+ * its range. */
+int bts_region_surface(const uint8_t* lab, uint8_t* surf, long* count, int D, int H, int W, int K, int class_mask, bts_stream_t stream);
+/* dist2 (D,H,W) float64 = squared distance in mm^2 from each voxel to the nearest voxel with feat != 0 on a grid of spacing (sd,sh,sw)
+ * mm; +inf everywhere when there is none (test.py:266-270).  Exact and separable: along W, then H, then D, out[i] = min over all j of the
+ * line of g[j] + (s (i - j)) (s (i - j)), each product and the sum rounded once; the H and D passes run in place.  BTS_ERR_SHAPE for a
+ * non-positive extent, an extent above 8192 (a line is staged in LDS) or a spacing that is not positive and finite. */
+int bts_edt3d_sq(const uint8_t* feat, double* dist2, int D, int H, int W, double sd, double sh, double sw, bts_stream_t stream);
+/* Exact order statistics for the percentile of the score (test.py:266-270): out[i] = the ranks[i]-th smallest (0-based) of
+ * {v[j] : mask[j] != 0, j < n}, nan where ranks[i] is not below the number of selected values.  v: NON-NEGATIVE float64 (they order as
+ * their bit patterns; +inf allowed), mask: uint8, ranks: nranks <= 8 HOST values, out: nranks device doubles, work: device memory of
+ * bts_masked_select_workspace(nranks) bytes.  Radix select, 8 passes of an integer histogram and a one-workgroup pick, no host round
+ * trip: the bits of a sort, the same in every run.  BTS_ERR_SHAPE for n < 0, nranks outside 0..8 or a negative rank; n == 0 or
+ * nranks == 0 launches nothing and leaves out untouched. */
+long bts_masked_select_workspace(int nranks);
+int bts_masked_select(const double* v, const uint8_t* mask, long n, const long* ranks, int nranks, double* out, void* work,
+                      bts_stream_t stream);
 
 /* ===== training-time augmentation on the device (train.py:14-49) ===== */
 /* per-channel mean / population variance of a (nvox, C) tensor with voxel stride ld (tf.nn.moments, train.py:18);
