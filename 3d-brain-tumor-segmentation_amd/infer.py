@@ -24,8 +24,12 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
   * overlap alone is what the reference's score (test.py:266-270) can report; `surface_scores` adds the distance side BraTS tables
     carry, the 95th-percentile Hausdorff distance per class and region (bts_region_surface, bts_edt3d_sq, bts_masked_select), and
     `region_rates_from_confusion` sensitivity and specificity of the regions.
+  * the reference writes and scores the raw arg-max; `remove_components` and `postprocess_labels` add the cleaning every practical
+    pipeline applies first (small connected components removed, a tiny enhancing region relabelled, the brain mask reduced to its
+    largest piece), off by default.
 All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_spline_prefilter3d, bts_zoom3d,
-bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, the model forward).
+bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, bts_components3d, bts_component_sizes,
+bts_component_largest, bts_components_apply, bts_region_relabel, the model forward).
 """
 import glob
 import os
@@ -275,8 +279,10 @@ class StageSpec(object):
     once and kept: the 16-bit engine packs its weight images on the first forward"""
 
     def __init__(self, model, mean, std, spatial_res, spatial_tta=True, channel_tta=0, threshold=0.5, compute_dtype='float32',
-                 tta_batch=None):
+                 tta_batch=None, largest_component=False):
+        """largest_component: for a skull-stripping stage, keep only the largest connected piece of the brain it finds (segment_case)"""
         self.model, self.mean, self.std = model, mean, std
+        self.largest_component = bool(largest_component)
         self.spatial_res = int(spatial_res)
         self.spatial_tta, self.channel_tta, self.threshold = bool(spatial_tta), int(channel_tta), float(threshold)
         self.compute_dtype, self.tta_batch = compute_dtype, tta_batch
@@ -298,14 +304,53 @@ class StageSpec(object):
         return self._tta
 
 
-def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False):
+def remove_components(lab, class_mask, K=4, connectivity=26, min_voxels=0, largest_only=False, fill=0):
+    """clean one region of a dense uint8 label map (D,H,W) on the GPU, IN PLACE: the region (classes min(label, K-1) whose bit is set in
+    class_mask) is split into its connected components (6 | 18 | 26 neighbours), and every voxel of a component of fewer than
+    `min_voxels` voxels, or with `largest_only` of any component but the largest (the one that starts first among equals), becomes `fill`
+    -> {'components': found, 'removed_components', 'removed_voxels'}.  On the device: bts_components3d, bts_component_sizes,
+    bts_component_largest, bts_components_apply; one host read at the end."""
+    comp = ops.components3d(lab, class_mask, K, connectivity)
+    size, count = ops.component_sizes(comp)
+    key = ops.component_largest(size) if largest_only else None
+    removed = ops.components_apply(lab, comp, size, key, min_voxels, largest_only, fill)
+    found, vox, gone = torch.cat([count, removed]).cpu().tolist()                    # the one read
+    return {'components': int(found), 'removed_components': int(gone), 'removed_voxels': int(vox)}
+
+
+BRATS_WT_MASK, BRATS_ET_MASK = 0b1110, 0b1000       # class masks over min(label, 3)
+
+
+def postprocess_labels(lab, min_component_voxels=0, et_min_voxels=0, connectivity=26):
+    """the usual cleaning of a BraTS label map (values 0, 1, 2, 4; dense uint8 (D,H,W) on the GPU), IN PLACE:
+    (a) with min_component_voxels > 0, connected components of the whole tumour (labels 1, 2, 4 together) of fewer voxels become 0;
+    (b) then, with et_min_voxels > 0, an enhancing tumour (label 4) of 1 .. et_min_voxels - 1 voxels in all becomes label 1 (necrotic
+        core), so that a case without enhancing tumour is not scored on a few stray voxels.
+    -> {'components', 'removed_components', 'removed_voxels', 'et_relabelled'}; with both parameters 0 nothing is launched."""
+    if min_component_voxels < 0 or et_min_voxels < 0:
+        raise ValueError('postprocess_labels: the voxel counts must not be negative, got %r and %r' % (min_component_voxels, et_min_voxels))
+    out = {'components': 0, 'removed_components': 0, 'removed_voxels': 0, 'et_relabelled': 0}
+    if min_component_voxels > 0:
+        out.update(remove_components(lab, BRATS_WT_MASK, 4, connectivity, min_voxels=min_component_voxels))
+    if et_min_voxels > 0:
+        out['et_relabelled'] = int(ops.region_relabel(lab, BRATS_ET_MASK, 1, et_min_voxels, K=4).item())
+    return out
+
+
+def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False, postprocess=None):
     """test.py:235-264 for one scan, with the optional skull-stripping stage (test.py:238-248): resample to 1 mm^3 padded to the first
     model's resolution, [skull model with TTA, x * (1 - p) cropped and padded again to the tumour model's resolution,] tumour model
     with TTA, crop, resample back.  tumor, skull: StageSpec; image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz)
     -> (probabilities, uint8 labels (D,H,W)) on that grid, as segment_scan gives them; without `skull` this IS segment_scan.
     return_stages: also a dict of the device tensors each stage handed to the next -- 'x1mm', 'mask' (padded to the first model's
     resolution), 'skull_prob' (masked mean probability, same extent), 'x_stripped', 'mask_repadded' (padded to the tumour model's
-    resolution), 'prob_1mm' (the tumour model's cropped probabilities on the 1 mm^3 grid, channels last); None where a stage did not run."""
+    resolution), 'prob_1mm' (the tumour model's cropped probabilities on the 1 mm^3 grid, channels last); None where a stage did not run.
+    A skull stage with `largest_component` set: the candidate brain, (mask > 0) & (p < threshold) on the padded 1 mm^3 grid, is reduced
+    to its largest 26-connected component (eye sockets, neck fragments go), and p is set to 1 at the candidates outside it before the
+    hand-over; 'brain_kept' is that uint8 map, 'brain_counts' remove_components' counts; 'skull_prob' stays the stage's own output.
+    postprocess: keyword arguments of `postprocess_labels`, applied to the labels on the scan's own grid (the returned probabilities
+    are unchanged); 'postprocess' holds its counts.  These three keys exist only where their option is on (`stages.get(key)` is None
+    otherwise): with the options off the dict is the one callers have always got, every value of a two-stage call a tensor."""
     if skull is not None:
         out_ch = getattr(getattr(skull.model, 'decoder', None), 'out_ch', None)
         if out_ch != 1:
@@ -320,9 +365,16 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False)
         if skull.data_format == 'channels_first':
             p = p.permute(1, 2, 3, 0)
         p = p.contiguous()
+        stages['skull_prob'] = p
+        if skull.largest_component:
+            cand = ((mp > 0) & (p < skull.threshold)).to(torch.uint8).reshape(tuple(p.shape[:3]))
+            kept = cand.clone()
+            stages['brain_counts'] = remove_components(kept, 2, K=2, connectivity=26, largest_only=True, fill=0)
+            stages['brain_kept'] = kept
+            p = torch.where((cand != kept).unsqueeze(-1), torch.ones_like(p), p).contiguous()
         res = tumor.spatial_res
         xp, mp = ops.skull_strip(xp, p, mp, orig, tuple(s + res - (s % res) for s in orig))
-        stages.update(skull_prob=p, x_stripped=xp, mask_repadded=mp)
+        stages.update(x_stripped=xp, mask_repadded=mp)
     df = tumor.data_format
     tta = tumor.augmentor()
     y = tta(xp, mp)
@@ -334,6 +386,9 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False)
         lab = tta.labels()[:orig[0], :orig[1], :orig[2]]
     else:
         y, lab = interp.reverse(y, threshold=tumor.threshold)
+    if postprocess is not None:
+        lab = lab.contiguous()
+        stages['postprocess'] = postprocess_labels(lab, **postprocess)
     if df == 'channels_first':
         y = y.permute(3, 0, 1, 2)
     return (y, lab, stages) if return_stages else (y, lab)

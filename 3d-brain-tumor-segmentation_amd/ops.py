@@ -866,6 +866,93 @@ def masked_select(v, mask, ranks, out=None):
     return out
 
 
+# ---- connected components of a region of a label map (csrc/components.hip) ----
+def components3d(lab, class_mask, K=4, connectivity=26, out=None):
+    """lab: dense uint8 label map (D,H,W) on the GPU; the region is the set of classes min(label, K-1) whose bit is set in class_mask;
+    connectivity 6 | 18 | 26 (scipy's generate_binary_structure(3, 1 | 2 | 3))
+    -> comp int32 (D,H,W): 0 outside the region, 1 + the smallest linear index of the voxel's component inside (the same bytes in
+    every run; comp[v] == v + 1 marks a root).  out: a dense int32 tensor of lab's size to write into"""
+    _dense(lab, torch.uint8, 'components3d: lab', 'uint8')
+    if lab.dim() != 3:
+        raise ValueError('components3d: lab must have shape (D,H,W), got %s' % (tuple(lab.shape),))
+    if out is None:
+        out = torch.empty(tuple(lab.shape), dtype=torch.int32, device=lab.device)
+    elif _dense(out, torch.int32, 'components3d: out', 'int32').numel() != lab.numel():
+        raise ValueError('components3d: out holds %d voxels, lab %d' % (out.numel(), lab.numel()))
+    d, h, w = lab.shape
+    lib().call('bts_components3d', _p(lab), _p(out), d, h, w, int(K), int(class_mask), int(connectivity), _stream())
+    return out
+
+
+def component_sizes(comp, out=None, count=None):
+    """comp: the int32 map of components3d -> (size int32 (comp.numel(),): size[r] = voxels of the component whose root is r, 0
+    elsewhere; count: one int64 on the GPU, += the number of components).  out: a dense int32 tensor of that size to write into (the
+    call zeroes it); count: a zeroed (or partly filled) int64 element to add into; new ones otherwise"""
+    _dense(comp, torch.int32, 'component_sizes: comp', 'int32')
+    n = comp.numel()
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=comp.device)
+    elif _dense(out, torch.int32, 'component_sizes: out', 'int32').numel() != n:
+        raise ValueError('component_sizes: out holds %d values, comp %d' % (out.numel(), n))
+    if count is None:
+        count = torch.zeros(1, dtype=torch.int64, device=comp.device)
+    elif _dense(count, torch.int64, 'component_sizes: count', 'int64').numel() != 1:
+        raise ValueError('component_sizes: count must be one int64 value on the GPU')
+    lib().call('bts_component_sizes', _p(comp), n, _p(out), _p(count), _stream())
+    return out, count
+
+
+def component_largest(size, out=None):
+    """size: the int32 sizes of component_sizes -> key: one int64 on the GPU holding (size << 32) | (0xFFFFFFFF - root) of the largest
+    component, the smallest root among equal sizes; 0 when there is none.  out: an int64 element to write into"""
+    _dense(size, torch.int32, 'component_largest: size', 'int32')
+    if out is None:
+        out = torch.zeros(1, dtype=torch.int64, device=size.device)
+    elif _dense(out, torch.int64, 'component_largest: out', 'int64').numel() != 1:
+        raise ValueError('component_largest: out must be one int64 value on the GPU')
+    lib().call('bts_component_largest', _p(size), size.numel(), _p(out), _stream())
+    return out
+
+
+def components_apply(lab, comp, size, key=None, min_voxels=0, largest_only=False, fill=0, removed=None):
+    """in place on the dense uint8 map `lab`: every voxel of a component (comp, size as above) that fails `size >= min_voxels and (not
+    largest_only or it is the component of key)` becomes `fill`; no other voxel is written
+    -> removed: two int64 on the GPU, += (voxels, components) removed.  removed: a zeroed (or partly filled) pair to add into"""
+    _dense(lab, torch.uint8, 'components_apply: lab', 'uint8')
+    _dense(comp, torch.int32, 'components_apply: comp', 'int32')
+    _dense(size, torch.int32, 'components_apply: size', 'int32')
+    n = lab.numel()
+    if comp.numel() != n or size.numel() != n:
+        raise ValueError('components_apply: lab holds %d voxels, comp %d, size %d' % (n, comp.numel(), size.numel()))
+    if largest_only and key is None:
+        raise ValueError('components_apply: largest_only needs the key of component_largest')
+    if key is not None and _dense(key, torch.int64, 'components_apply: key', 'int64').numel() != 1:
+        raise ValueError('components_apply: key must be one int64 value on the GPU')
+    if removed is None:
+        removed = torch.zeros(2, dtype=torch.int64, device=lab.device)
+    elif _dense(removed, torch.int64, 'components_apply: removed', 'int64').numel() != 2:
+        raise ValueError('components_apply: removed must be two int64 values on the GPU')
+    lib().call('bts_components_apply', _p(lab), _p(comp), _p(size), _p(key), n, int(min_voxels), 1 if largest_only else 0, int(fill),
+               _p(removed[0:1]), _p(removed[1:2]), _stream())
+    return removed
+
+
+def region_relabel(lab, class_mask, fill, limit, K=4, changed=None):
+    """in place on the dense uint8 map `lab`: when the region (K, class_mask as in components3d) holds between 1 and limit - 1 voxels,
+    each becomes `fill` -> changed: one int64 on the GPU, += their number.  The count is taken on the device (label_confusion of the map
+    with itself) and the decision is made there.  changed: a zeroed (or partly filled) int64 element to add into"""
+    _dense(lab, torch.uint8, 'region_relabel: lab', 'uint8')
+    if changed is None:
+        changed = torch.zeros(1, dtype=torch.int64, device=lab.device)
+    elif _dense(changed, torch.int64, 'region_relabel: changed', 'int64').numel() != 1:
+        raise ValueError('region_relabel: changed must be one int64 value on the GPU')
+    flat = lab.view(-1)
+    conf = label_confusion(flat, flat, K)
+    lib().call('bts_region_relabel', _p(lab), lab.numel(), int(K), int(class_mask), int(fill), _p(conf), int(limit), _p(changed),
+               _stream())
+    return changed
+
+
 # ---- training-time augmentation on the device (SURVEY 8 f-3) ----
 def channel_moments(x):
     """per-channel (mean, population variance) over all voxels of a dense (..., C) tensor, C <= 16 -> two (C,) tensors"""

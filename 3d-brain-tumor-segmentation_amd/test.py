@@ -2,6 +2,7 @@
 
     python -m bts_amd.test --in_locs a,b --modalities t1ce,flair --tumor_model DIR --tumor_prepro DIR/prepro.npy
                            [--skull_model DIR --skull_prepro FILE] [--truth seg] [--out_loc DIR] [--dtype float16]
+                           [--min_component_voxels N] [--et_min_voxels N] [--component_connectivity 26] [--skull_largest_component]
 
 This module is named after the reference's script and is NOT a pytest module: pytest's `test_*.py` pattern does not match `test.py`
 and `testpaths` points at tests/, so it is never collected.
@@ -16,8 +17,16 @@ distance (mm, on the scan's own grid with its pixdim) and the sensitivity and sp
 (`infer.surface_scores`, `infer.region_rates_from_confusion`): nine more columns after the existing ones; the `total` row holds the mean
 of the finite distances and the rates of the summed confusion matrix.
 
+Post-processing of the label map, off by default (`infer.postprocess_labels`, connected components on the device): with
+--min_component_voxels N connected pieces of the whole tumour (labels 1, 2 and 4 together; 6, 18 or 26 neighbours by
+--component_connectivity) of fewer than N voxels become background, and with --et_min_voxels N an enhancing tumour (label 4) of fewer
+than N voxels in all becomes label 1; --skull_largest_component reduces the brain the skull-stripping model finds to its largest
+connected piece before the tumour model sees the scan.  `mask.nii` and every score are of the post-processed map, and one more line per
+case prints what was removed.  The columns of scores.csv do not change.
+
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
-accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics.
+accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
+--min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component.
 
 Deviations:
   * cases are visited in sorted order of their paths (the reference: the file system's order);
@@ -71,11 +80,24 @@ def arg_parser():
     p.add_argument('--out_loc', type=str, default='', help='Write DIR/<case>/mask.nii and DIR/scores.csv instead of into the case folders.')
     p.add_argument('--surface_metrics', action='store_true', default=False,
                    help='Also score each labelled case with the 95th-percentile Hausdorff distance, sensitivity and specificity of WT, TC, ET.')
+    p.add_argument('--min_component_voxels', type=int, default=0,
+                   help='Remove connected components of the whole tumour of fewer voxels than this (0: keep all).')
+    p.add_argument('--et_min_voxels', type=int, default=0,
+                   help='Relabel an enhancing tumour of fewer voxels than this in all as label 1 (0: never).')
+    p.add_argument('--component_connectivity', type=int, default=26, choices=(6, 18, 26),
+                   help='Neighbours that connect two voxels of a component: by face, edge or corner.')
+    p.add_argument('--skull_largest_component', action='store_true', default=False,
+                   help='Keep only the largest connected piece of the brain found by the skull-stripping model.')
     return p
 
 
 def parse_args(argv=None):
-    args = arg_parser().parse_args(argv)
+    parser = arg_parser()
+    args = parser.parse_args(argv)
+    if args.min_component_voxels < 0 or args.et_min_voxels < 0:
+        parser.error('--min_component_voxels and --et_min_voxels must not be negative')
+    if args.skull_largest_component and not args.skull_model:
+        parser.error('--skull_largest_component needs --skull_model')
     args.modalities = args.modalities.split(',')
     args.in_locs = args.in_locs.split(',')
     if not 0 < args.threshold < 1:                                                   # args.py:243-244
@@ -155,6 +177,14 @@ def load_stage(folder, prepro, args, shape_1mm):
                      compute_dtype=args.dtype, tta_batch=args.tta_batch)
 
 
+def postprocess_kwargs(args):
+    """-> the keyword arguments of infer.postprocess_labels the flags ask for, None when they ask for nothing"""
+    if not (getattr(args, 'min_component_voxels', 0) or getattr(args, 'et_min_voxels', 0)):
+        return None
+    return {'min_component_voxels': args.min_component_voxels, 'et_min_voxels': args.et_min_voxels,
+            'connectivity': getattr(args, 'component_connectivity', 26)}
+
+
 def require_gpu():
     """-> the current device; no CPU path: without a GPU the command ends with the Interpolator's message"""
     Interpolator._device_volume(np.zeros((1, 1, 1, 1), dtype=np.float32))
@@ -197,7 +227,8 @@ def _decoded(cases, args):
 
 def run(args):
     """-> {'cases', 'scored', 'skipped': [(name, modality)], 'scores': [(name, label_scores dict)], 'total': scores of the summed
-    confusion matrix or None}"""
+    confusion matrix or None, 'postprocess': [(name, counts)] of the cases a post-processing flag touched: the counts of
+    infer.postprocess_labels, and 'brain_*' those of the skull stage's largest-component step}"""
     dev = require_gpu()
     Interpolator(args.modalities, order=args.order, mode=args.mode)      # refuses an unsupported --order / --mode before any work
     cases = find_cases(args.in_locs, args.out_loc)
@@ -206,7 +237,9 @@ def run(args):
     if args.out_loc:
         os.makedirs(args.out_loc, exist_ok=True)
     tumor = skull = None
-    scores, skipped, done = [], [], 0
+    scores, skipped, done, cleaned = [], [], 0, []
+    post = postprocess_kwargs(args)
+    largest = bool(getattr(args, 'skull_largest_component', False))
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
     for (name, path), case in zip(cases, _decoded(cases, args)):
@@ -222,7 +255,16 @@ def run(args):
             tumor = load_stage(args.tumor_model, args.tumor_prepro, args, shape_1mm)
             if args.skull_strip:
                 skull = load_stage(args.skull_model, args.skull_prepro, args, shape_1mm)
-        _, lab = segment_case(tumor, x, pixdim, skull=skull, order=args.order)
+                if largest:
+                    skull.largest_component = True
+        if post is None and not largest:
+            _, lab = segment_case(tumor, x, pixdim, skull=skull, order=args.order)
+        else:
+            _, lab, st = segment_case(tumor, x, pixdim, skull=skull, order=args.order, return_stages=True, postprocess=post)
+            counts = dict(st.get('postprocess') or {})
+            counts.update({'brain_' + k: v for k, v in (st.get('brain_counts') or {}).items()})
+            cleaned.append((name, counts))
+            print('{}. Post-processing: {}'.format(name, ', '.join('%s %d' % kv for kv in sorted(counts.items()))), flush=True)
         s = None
         if y is not None:
             s = label_scores(y, lab, N_CLASSES)
@@ -262,7 +304,7 @@ def run(args):
         done, len(scores), dt, done / dt if dt > 0 else 0.0, len(skipped),
         (': ' + ', '.join('%s (%s)' % sk for sk in skipped) if skipped else '') +
         ('; {} region distances infinite (a region empty in one of the two maps)'.format(n_inf) if args.surface_metrics else '')), flush=True)
-    return {'cases': done, 'scored': len(scores), 'skipped': skipped, 'scores': scores, 'total': overall}
+    return {'cases': done, 'scored': len(scores), 'skipped': skipped, 'scores': scores, 'total': overall, 'postprocess': cleaned}
 
 
 def main(argv=None):

@@ -301,6 +301,33 @@ int bts_edt3d_sq(const uint8_t* feat, double* dist2, int D, int H, int W, double
 long bts_masked_select_workspace(int nranks);
 int bts_masked_select(const double* v, const uint8_t* mask, long n, const long* ranks, int nranks, double* out, void* work,
                       bts_stream_t stream);
+/* Connected components for cleaning a label map before it is written and scored (the arg-max of test.py:259-261 is used as it is by the
+ * reference; bts_amd.infer.remove_components, postprocess_labels).  The region is that of bts_region_surface: bit min(label, K-1) of
+ * class_mask; connectivity 6, 18 or 26 = scipy's generate_binary_structure(3, 1|2|3).  comp (int32 (D,H,W), every element written) = 0
+ * outside the region and 1 + the smallest linear index (d H + h) W + w of the voxel's component inside: a function of the input alone,
+ * the same bytes in every run; comp[v] == v + 1 marks a component's root.  Union-find on the device: tiles in LDS, then the tile seams
+ * with agent-scope integer atomicMin, then a flattening pass.  BTS_ERR_SHAPE for a non-positive extent, D H W >= 2^31 - 1, K outside
+ * 2..8, a class_mask outside its range or a connectivity other than 6, 18, 26. */
+int bts_components3d(const uint8_t* lab, int* comp, int D, int H, int W, int K, int class_mask, int connectivity, bts_stream_t stream);
+/* size (n int32, zeroed by the call): size[r] = the number of voxels whose root is r (comp == r + 1); *ncomp (int64 on the device,
+ * accumulated across calls) += the number of components.  BTS_ERR_SHAPE for n < 0 or n >= 2^31 - 1; n == 0 launches nothing. */
+int bts_component_sizes(const int* comp, long n, int* size, long* ncomp, bts_stream_t stream);
+/* *key (one 64-bit word on the device, zeroed by the call) = max over the components of (size << 32) | (0xFFFFFFFF - root): the largest
+ * component, the smallest root among equal sizes; 0 when there is none.  Same guards as bts_component_sizes. */
+int bts_component_largest(const int* size, long n, uint64_t* key, bts_stream_t stream);
+/* In place on the uint8 map: every voxel with comp != 0 whose component fails `size[root] >= min_voxels and (not largest_only or root ==
+ * the root of *key)` becomes `fill`, and *removed_voxels (int64 on the device, accumulated) += 1; *removed_components (may be NULL) += 1
+ * per failing component.  No other voxel is written.  key may be NULL unless largest_only.  BTS_ERR_SHAPE for n outside [0, 2^31 - 1),
+ * min_voxels < 0, fill outside 0..255 or largest_only without a key; n == 0 launches nothing. */
+int bts_components_apply(uint8_t* lab, const int* comp, const int* size, const uint64_t* key, long n, int min_voxels, int largest_only,
+                         int fill, long* removed_voxels, long* removed_components, bts_stream_t stream);
+/* In place: when the region (K, class_mask as above) holds between 1 and limit - 1 voxels, each of them becomes `fill` and *changed
+ * (int64 on the device, accumulated) += their number; the BraTS convention for a tiny enhancing region.  confusion: the K x K int64
+ * counts of bts_label_confusion(lab, lab) on the device, whose diagonal holds the class sizes, so the decision takes no host round trip.
+ * BTS_ERR_SHAPE for n < 0, K outside 2..8, a class_mask outside its range, fill outside 0..255 or limit < 0; n == 0 or limit == 0
+ * launches nothing. */
+int bts_region_relabel(uint8_t* lab, long n, int K, int class_mask, int fill, const long* confusion, long limit, long* changed,
+                       bts_stream_t stream);
 
 /* ===== training-time augmentation on the device (train.py:14-49) ===== */
 /* per-channel mean / population variance of a (nvox, C) tensor with voxel stride ld (tf.nn.moments, train.py:18);
