@@ -8,6 +8,7 @@ Activations are [N,D,H,W,C] fp32 tensors whose last-dim stride is 1 and whose vo
 import ctypes
 import weakref
 
+import numpy as np
 import torch
 
 from ._lib import ERRORS, lib
@@ -951,6 +952,152 @@ def region_relabel(lab, class_mask, fill, limit, K=4, changed=None):
     lib().call('bts_region_relabel', _p(lab), lab.numel(), int(K), int(class_mask), int(fill), _p(conf), int(limit), _p(changed),
                _stream())
     return changed
+
+
+# ---- between the labelling and the distances of a lesion-wise score (csrc/lesion.hip) ----
+def _volume3(t, dtype, name, what):
+    _dense(t, dtype, name, what)
+    if t.dim() != 3:
+        raise ValueError('%s must have shape (D,H,W), got %s' % (name, tuple(t.shape)))
+    return t
+
+
+def dilate3d(lab, class_mask, K=4, connectivity=18, iterations=1, out=None, fuse=0):
+    """lab: dense uint8 label map (D,H,W) on the GPU; the region is the set of classes min(label, K-1) whose bit is set in class_mask;
+    connectivity 6 | 18 | 26 (scipy's generate_binary_structure(3, 1 | 2 | 3)); iterations >= 0
+    -> uint8 (D,H,W): 1 where scipy.ndimage.binary_dilation(region, structure, iterations, border_value=0) is set, 0 elsewhere (the
+    region itself for 0 iterations).  out: a dense uint8 tensor of lab's size to write into, not lab itself; fuse: iterations run per
+    pass over the volume, 1..6 (0: the library's default)"""
+    _volume3(lab, torch.uint8, 'dilate3d: lab', 'uint8')
+    if out is None:
+        out = torch.empty_like(lab)
+    elif _dense(out, torch.uint8, 'dilate3d: out', 'uint8').numel() != lab.numel():
+        raise ValueError('dilate3d: out holds %d voxels, lab %d' % (out.numel(), lab.numel()))
+    elif out.data_ptr() == lab.data_ptr():
+        raise ValueError('dilate3d: out must not be lab (a tile reads its neighbours\' voxels)')
+    d, h, w = lab.shape
+    nb = lib().query('bts_dilate3d_workspace', d, h, w, int(iterations), int(fuse))
+    ws = workspace(nb, lab.device) if nb else None
+    lib().call('bts_dilate3d', _p(lab), _p(out), d, h, w, int(K), int(class_mask), int(connectivity), int(iterations), int(fuse),
+               _p(ws), _stream())
+    return out
+
+
+def lesion_pairs_capacity(n_td, n_pred):
+    """slots of the pairing table for n_td dilated lesions and n_pred predicted components: a power of two, at least four times their
+    sum (a component usually meets one lesion and a lesion a few components; a table that is too small is grown, not an error)"""
+    need = 4 * (max(int(n_td), 0) + max(int(n_pred), 0))
+    cap = 256
+    while cap < need:
+        cap *= 2
+    return cap
+
+
+def lesion_pairs(td_comp, truth, pred_comp, class_mask, K=4, counts=None, capacity=None, lesion_vox=None):
+    """td_comp, pred_comp: the int32 maps components3d gives for the dilated truth and for the prediction; truth: the dense uint8 truth
+    map of the same size, its region K / class_mask
+    -> (rows: int64 numpy (pairs, 4), one row (lesion_root, pred_root, reach, overlap) per pair of a dilated component and a predicted
+    component that share a voxel -- reach: the voxels they share, overlap: those of them that are truth -- in lexicographic order;
+    lesion_vox: int32 (n,) on the GPU, lesion_vox[r] = the truth voxels inside the dilated component of root r, 0 elsewhere).
+    counts: (dilated components, predicted components) as host integers, from which the table's capacity is derived; counted here (one
+    more host read) when neither they nor `capacity` are given.  A table that proves too small is grown and the pass run again: the rows
+    do not depend on the capacity.  One host read per pass.  lesion_vox: a dense int32 tensor of n values to write into"""
+    _dense(td_comp, torch.int32, 'lesion_pairs: td_comp', 'int32')
+    _dense(pred_comp, torch.int32, 'lesion_pairs: pred_comp', 'int32')
+    _dense(truth, torch.uint8, 'lesion_pairs: truth', 'uint8')
+    n = td_comp.numel()
+    if pred_comp.numel() != n or truth.numel() != n:
+        raise ValueError('lesion_pairs: td_comp holds %d voxels, truth %d, pred_comp %d' % (n, truth.numel(), pred_comp.numel()))
+    if lesion_vox is None:
+        lesion_vox = torch.empty(n, dtype=torch.int32, device=td_comp.device)
+    elif _dense(lesion_vox, torch.int32, 'lesion_pairs: lesion_vox', 'int32').numel() != n:
+        raise ValueError('lesion_pairs: lesion_vox holds %d values, td_comp %d' % (lesion_vox.numel(), n))
+    if capacity is None:
+        if counts is None:
+            both = torch.zeros(2, dtype=torch.int64, device=td_comp.device)
+            scratch = torch.empty(n, dtype=torch.int32, device=td_comp.device)
+            component_sizes(td_comp, out=scratch, count=both[0:1])
+            component_sizes(pred_comp, out=scratch, count=both[1:2])
+            counts = both.cpu().tolist()
+        capacity = lesion_pairs_capacity(*counts)
+    capacity = int(capacity)
+    if capacity < 1:
+        raise ValueError('lesion_pairs: the capacity must be positive, got %r' % (capacity,))
+    while True:
+        lib().query('bts_lesion_pairs_table_bytes', capacity)
+        buf = torch.empty(2 + 2 * capacity, dtype=torch.int64, device=td_comp.device)       # status, keys, (reach, overlap) pairs
+        lib().call('bts_lesion_pairs', _p(td_comp), _p(truth), _p(pred_comp), n, int(K), int(class_mask), _p(lesion_vox), _p(buf[2:]),
+                   capacity, _p(buf[0:2]), _stream())
+        host = buf.cpu().numpy()                                                            # the one read of this pass
+        stored, refused = int(host[0]), int(host[1])
+        if refused == 0:
+            break
+        capacity = lesion_pairs_capacity(stored + refused, 0)                               # enough by construction: one rerun
+    keys = host[2:2 + capacity]
+    cnt = host[2 + capacity:].view(np.int32).reshape(capacity, 2)
+    used = np.nonzero(keys)[0]
+    rows = np.empty((len(used), 4), dtype=np.int64)
+    rows[:, 0] = (keys[used] >> 32) - 1
+    rows[:, 1] = (keys[used] & 0xFFFFFFFF) - 1
+    rows[:, 2:] = cnt[used]
+    if len(used) != stored:
+        raise RuntimeError('lesion_pairs: the table holds %d pairs, its status word says %d' % (len(used), stored))
+    return rows[np.lexsort((rows[:, 1], rows[:, 0]))], lesion_vox
+
+
+def _roots(roots, name, device):
+    """-> (dense int32 tensor on the GPU or None, length); a host sequence is checked to ascend and uploaded"""
+    if isinstance(roots, torch.Tensor):
+        _dense(roots, torch.int32, name, 'int32')
+        return (roots if roots.numel() else None), roots.numel()
+    r = np.asarray(roots, dtype=np.int64).reshape(-1)
+    if len(r) and (r[0] < 0 or r[-1] >= 2 ** 31 - 1 or (np.diff(r) <= 0).any()):
+        raise ValueError('%s must ascend strictly inside [0, 2^31 - 1)' % name)
+    return (torch.from_numpy(r.astype(np.int32)).to(device) if len(r) else None), len(r)
+
+
+def component_boxes(comp, roots, out=None):
+    """comp: the int32 map (D,H,W) of components3d; roots: ASCENDING roots, a dense int32 tensor on the GPU or a host sequence
+    -> int32 (len(roots), 6) on the GPU: the half-open bounding box (d0,h0,w0,d1,h1,w1) of each root's component.  out: a dense int32
+    tensor of that size to write into"""
+    _volume3(comp, torch.int32, 'component_boxes: comp', 'int32')
+    rt, m = _roots(roots, 'component_boxes: roots', comp.device)
+    if out is None:
+        out = torch.empty((m, 6), dtype=torch.int32, device=comp.device)
+    elif _dense(out, torch.int32, 'component_boxes: out', 'int32').numel() != 6 * m:
+        raise ValueError('component_boxes: out must hold %d int32 values' % (6 * m))
+    d, h, w = comp.shape
+    lib().call('bts_component_boxes', _p(comp), d, h, w, _p(rt), m, _p(out), _stream())
+    return out
+
+
+def lesion_crop(td_comp, truth, pred_comp, class_mask, box, td_root, roots, K=4, out=None):
+    """td_comp, truth, pred_comp as in lesion_pairs, shape (D,H,W); box: host (d0,h0,w0,d1,h1,w1), half-open and inside the volume;
+    td_root: the root of one dilated component; roots: ASCENDING roots of predicted components (tensor or host sequence)
+    -> (g, m): dense uint8 maps of the box's extent; g = 1 where the voxel is truth inside that dilated component, m = 1 where the
+    voxel's predicted component is one of `roots`.  out: a pair of dense uint8 tensors of the box's size to write into"""
+    _volume3(td_comp, torch.int32, 'lesion_crop: td_comp', 'int32')
+    _volume3(pred_comp, torch.int32, 'lesion_crop: pred_comp', 'int32')
+    _volume3(truth, torch.uint8, 'lesion_crop: truth', 'uint8')
+    if tuple(td_comp.shape) != tuple(truth.shape) or tuple(pred_comp.shape) != tuple(truth.shape):
+        raise ValueError('lesion_crop: the three maps differ in shape: %s, %s, %s' %
+                         (tuple(td_comp.shape), tuple(truth.shape), tuple(pred_comp.shape)))
+    d, h, w = truth.shape
+    box = tuple(int(v) for v in box)
+    if len(box) != 6 or min(box[:3]) < 0 or any(b1 <= b0 for b0, b1 in zip(box[:3], box[3:])) or any(b1 > s for b1, s in zip(box[3:], (d, h, w))):
+        raise ValueError('lesion_crop: box must be a non-empty half-open (d0,h0,w0,d1,h1,w1) inside %s, got %r' % ((d, h, w), box))
+    ext = tuple(b1 - b0 for b0, b1 in zip(box[:3], box[3:]))
+    nbox = ext[0] * ext[1] * ext[2]
+    rt, m = _roots(roots, 'lesion_crop: roots', truth.device)
+    if out is None:
+        out = (torch.empty(ext, dtype=torch.uint8, device=truth.device), torch.empty(ext, dtype=torch.uint8, device=truth.device))
+    else:
+        for t, name in zip(out, ('g', 'm')):
+            if _dense(t, torch.uint8, 'lesion_crop: out ' + name, 'uint8').numel() != nbox:
+                raise ValueError('lesion_crop: out %s holds %d voxels, the box %d' % (name, t.numel(), nbox))
+    lib().call('bts_lesion_crop', _p(td_comp), _p(truth), _p(pred_comp), d, h, w, int(K), int(class_mask), *box, int(td_root), _p(rt), m,
+               _p(out[0]), _p(out[1]), _stream())
+    return out
 
 
 # ---- training-time augmentation on the device (SURVEY 8 f-3) ----

@@ -3,6 +3,7 @@
     python -m bts_amd.test --in_locs a,b --modalities t1ce,flair --tumor_model DIR --tumor_prepro DIR/prepro.npy
                            [--skull_model DIR --skull_prepro FILE] [--truth seg] [--out_loc DIR] [--dtype float16]
                            [--min_component_voxels N] [--et_min_voxels N] [--component_connectivity 26] [--skull_largest_component]
+                           [--lesionwise] [--lesion_dilation 3] [--lesion_min_voxels 50] [--lesion_penalty_mm 374]
 
 This module is named after the reference's script and is NOT a pytest module: pytest's `test_*.py` pattern does not match `test.py`
 and `testpaths` points at tests/, so it is never collected.
@@ -24,9 +25,16 @@ than N voxels in all becomes label 1; --skull_largest_component reduces the brai
 connected piece before the tumour model sees the scan.  `mask.nii` and every score are of the post-processed map, and one more line per
 case prints what was removed.  The columns of scores.csv do not change.
 
+With --lesionwise each labelled case also gets the lesion-wise Dice and HD95 of WT, TC and ET (`infer.lesionwise_scores`, the BraTS 2023
+ranking: every truth lesion scored on its own, a missed lesion 0 and --lesion_penalty_mm, a predicted component on no lesion a false
+positive; --lesion_dilation iterations join truth pieces into one lesion, lesions below --lesion_min_voxels are ignored), taken on the
+mask as written: fifteen more columns at the end of the row (after those of --surface_metrics), lw_dice_*, lw_hd95_*, and the counts
+lw_lesions_*, lw_fn_*, lw_fp_*; the `total` row holds the mean of the finite scores and the sums of the counts; one more line per case.
+
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
 accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
---min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component.
+--min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component, --lesionwise, --lesion_dilation,
+--lesion_min_voxels, --lesion_penalty_mm.
 
 Deviations:
   * cases are visited in sorted order of their paths (the reference: the file system's order);
@@ -46,8 +54,8 @@ import numpy as np
 import torch
 
 from . import nifti
-from .infer import (Interpolator, StageSpec, label_scores, region_rates_from_confusion, scores_from_confusion, segment_case, surface_scores,
-                    zoom_output_shape)
+from .infer import (BRATS_REGIONS, Interpolator, StageSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
+                    scores_from_confusion, segment_case, surface_scores, zoom_output_shape)
 from .preprocess import load_prepro
 from .train import load_checkpoint, load_train_args
 
@@ -55,6 +63,10 @@ N_CLASSES = 4        # background + the three BraTS labels 1, 2, 4 (4 counts as 
 HD95_KEYS = ('hd95_wt', 'hd95_tc', 'hd95_et')
 RATE_KEYS = ('sens_wt', 'sens_tc', 'sens_et', 'spec_wt', 'spec_tc', 'spec_et')
 SURFACE_KEYS = HD95_KEYS + RATE_KEYS      # the columns --surface_metrics appends to scores.csv
+LESION_SCORE_KEYS = tuple('lw_%s_%s' % (what, name) for what in ('dice', 'hd95') for name, _ in BRATS_REGIONS)
+LESION_COUNT_KEYS = tuple('lw_%s_%s' % (what, name) for what in ('lesions', 'fn', 'fp') for name, _ in BRATS_REGIONS)
+LESION_KEYS = LESION_SCORE_KEYS + LESION_COUNT_KEYS      # the columns --lesionwise appends to scores.csv, after the others
+LESION_DEFAULTS = {'lesion_dilation': 3, 'lesion_min_voxels': 50, 'lesion_penalty_mm': 374.0}
 
 
 def arg_parser():
@@ -88,6 +100,16 @@ def arg_parser():
                    help='Neighbours that connect two voxels of a component: by face, edge or corner.')
     p.add_argument('--skull_largest_component', action='store_true', default=False,
                    help='Keep only the largest connected piece of the brain found by the skull-stripping model.')
+    # the lesion-wise flags exist in the namespace only where the command line gives them (tests/test_components_host.py pins the
+    # attributes a plain command line parses to); `lesion_kwargs` supplies LESION_DEFAULTS
+    p.add_argument('--lesionwise', action='store_true', default=argparse.SUPPRESS,
+                   help='Also score each labelled case with the lesion-wise Dice and HD95 of WT, TC, ET (the BraTS 2023 ranking).')
+    p.add_argument('--lesion_dilation', type=int, default=argparse.SUPPRESS,
+                   help='Dilation iterations that join truth pieces into one lesion (default: %d).' % LESION_DEFAULTS['lesion_dilation'])
+    p.add_argument('--lesion_min_voxels', type=int, default=argparse.SUPPRESS,
+                   help='Truth lesions of fewer voxels than this are ignored (default: %d).' % LESION_DEFAULTS['lesion_min_voxels'])
+    p.add_argument('--lesion_penalty_mm', type=float, default=argparse.SUPPRESS,
+                   help='HD95 charged for a missed lesion or a false positive (default: %g).' % LESION_DEFAULTS['lesion_penalty_mm'])
     return p
 
 
@@ -96,6 +118,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.min_component_voxels < 0 or args.et_min_voxels < 0:
         parser.error('--min_component_voxels and --et_min_voxels must not be negative')
+    if not all(getattr(args, k, v) >= 0 for k, v in LESION_DEFAULTS.items()):
+        parser.error('--lesion_dilation, --lesion_min_voxels and --lesion_penalty_mm must not be negative')
     if args.skull_largest_component and not args.skull_model:
         parser.error('--skull_largest_component needs --skull_model')
     args.modalities = args.modalities.split(',')
@@ -185,6 +209,15 @@ def postprocess_kwargs(args):
             'connectivity': getattr(args, 'component_connectivity', 26)}
 
 
+def lesion_kwargs(args):
+    """-> the keyword arguments of infer.lesionwise_scores the flags ask for, None without --lesionwise"""
+    if not getattr(args, 'lesionwise', False):
+        return None
+    return {'dilation': getattr(args, 'lesion_dilation', LESION_DEFAULTS['lesion_dilation']),
+            'min_lesion_voxels': getattr(args, 'lesion_min_voxels', LESION_DEFAULTS['lesion_min_voxels']),
+            'penalty_mm': getattr(args, 'lesion_penalty_mm', LESION_DEFAULTS['lesion_penalty_mm'])}
+
+
 def require_gpu():
     """-> the current device; no CPU path: without a GPU the command ends with the Interpolator's message"""
     Interpolator._device_volume(np.zeros((1, 1, 1, 1), dtype=np.float32))
@@ -202,6 +235,21 @@ def score_row(name, s):
 def surface_row(s):
     """the columns --surface_metrics appends to a score_row"""
     return [_fmt(s[k]) for k in SURFACE_KEYS]
+
+
+def lesion_columns(lw):
+    """infer.lesionwise_scores' dict -> the values of LESION_KEYS by name"""
+    out = {}
+    for name, _ in BRATS_REGIONS:
+        c = lw['lw_counts_' + name]
+        out.update({'lw_dice_' + name: lw['lw_dice_' + name], 'lw_hd95_' + name: lw['lw_hd95_' + name], 'lw_lesions_' + name: c['lesions'],
+                    'lw_fn_' + name: c['false_negatives'], 'lw_fp_' + name: c['false_positives']})
+    return out
+
+
+def lesion_row(s):
+    """the columns --lesionwise appends to a score_row"""
+    return [_fmt(s[k]) for k in LESION_SCORE_KEYS] + ['%d' % s[k] for k in LESION_COUNT_KEYS]
 
 
 def mean_finite(values):
@@ -240,6 +288,8 @@ def run(args):
     scores, skipped, done, cleaned = [], [], 0, []
     post = postprocess_kwargs(args)
     largest = bool(getattr(args, 'skull_largest_component', False))
+    lesion = lesion_kwargs(args)
+    lesionwise = lesion is not None
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
     for (name, path), case in zip(cases, _decoded(cases, args)):
@@ -273,6 +323,8 @@ def run(args):
                 hd = surface_scores(y, lab, pixdim, N_CLASSES)
                 s.update({k: hd[k] for k in HD95_KEYS})
                 s.update(region_rates_from_confusion(s['confusion']))
+            if lesionwise:
+                s.update(lesion_columns(lesionwise_scores(y, lab, pixdim, N_CLASSES, **lesion)))
         where = os.path.join(args.out_loc, name) if args.out_loc else path
         os.makedirs(where, exist_ok=True)
         nifti.save(os.path.join(where, 'mask.nii'), lab.cpu().numpy(), case['affine'])
@@ -282,6 +334,11 @@ def run(args):
             print('{}. Macro: {ma: 1.4f}. Micro: {mi: 1.4f}'.format(name, ma=s['macro'], mi=s['micro']), flush=True)    # test.py:269
             if args.surface_metrics:
                 print('{}. HD95 WT: {:1.4f}. TC: {:1.4f}. ET: {:1.4f}'.format(name, *[s[k] for k in HD95_KEYS]), flush=True)
+            if lesionwise:
+                print('{}. Lesion-wise Dice WT: {:1.4f}. TC: {:1.4f}. ET: {:1.4f}. HD95 WT: {:1.4f}. TC: {:1.4f}. ET: {:1.4f}. '
+                      'Lesions (missed, false positives) WT: {:d} ({:d}, {:d}). TC: {:d} ({:d}, {:d}). ET: {:d} ({:d}, {:d})'.format(
+                          name, *([s[k] for k in LESION_SCORE_KEYS] +
+                                  [s['lw_%s_%s' % (what, r)] for r, _ in BRATS_REGIONS for what in ('lesions', 'fn', 'fp')])), flush=True)
     overall = scores_from_confusion(total) if scores else None
     n_inf = 0
     if args.surface_metrics:
@@ -289,6 +346,9 @@ def run(args):
         if overall is not None:
             overall.update({k: mean_finite([s[k] for _, s in scores]) for k in HD95_KEYS})
             overall.update(region_rates_from_confusion(total))
+    if lesionwise and overall is not None:
+        overall.update({k: mean_finite([s[k] for _, s in scores]) for k in LESION_SCORE_KEYS})
+        overall.update({k: sum(s[k] for _, s in scores) for k in LESION_COUNT_KEYS})
     if args.out_loc:
         head = ['case', 'macro', 'micro'] + ['dice_%d' % c for c in range(1, N_CLASSES)] + ['wt', 'tc', 'et']
         rows = [head] + [score_row(n, s) for n, s in scores]
@@ -296,6 +356,9 @@ def run(args):
             rows.append(score_row('total', overall))
         if args.surface_metrics:
             extra = [list(SURFACE_KEYS)] + [surface_row(s) for _, s in scores] + ([surface_row(overall)] if overall is not None else [])
+            rows = [r + e for r, e in zip(rows, extra)]
+        if lesionwise:
+            extra = [list(LESION_KEYS)] + [lesion_row(s) for _, s in scores] + ([lesion_row(overall)] if overall is not None else [])
             rows = [r + e for r, e in zip(rows, extra)]
         with open(os.path.join(args.out_loc, 'scores.csv'), 'w') as f:
             f.write(''.join(','.join(r) + '\n' for r in rows))

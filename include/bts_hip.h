@@ -328,6 +328,42 @@ int bts_components_apply(uint8_t* lab, const int* comp, const int* size, const u
  * launches nothing. */
 int bts_region_relabel(uint8_t* lab, long n, int K, int class_mask, int fill, const long* confusion, long limit, long* changed,
                        bts_stream_t stream);
+/* Lesion-wise scores (the BraTS 2023 ranking; bts_amd.infer.lesionwise_scores): what lies between the labelling above and the distances
+ * of bts_region_surface / bts_edt3d_sq / bts_masked_select.  Regions (K, class_mask) and connectivities are those of bts_components3d.
+ * out (uint8 (D,H,W), every byte written, must not overlap lab) = 1 where scipy.ndimage.binary_dilation(region,
+ * generate_binary_structure(3, 1|2|3), iterations, border_value=0) is set, 0 elsewhere; iterations == 0 gives the region itself.  A tiled
+ * stencil on bit rows in LDS; a pass runs `fuse` iterations on a tile with a halo of as many voxels (0: the default, 3; at most 6) and
+ * ceil(iterations / fuse) passes alternate between out and work, device memory of bts_dilate3d_workspace(...) bytes (0 for one pass; work
+ * may then be NULL).  BTS_ERR_SHAPE, before any HIP call, for a non-positive extent, D H W >= 2^31 - 1, iterations outside 0..4096, fuse
+ * outside 0..6, K outside 2..8, a class_mask outside its range or a connectivity other than 6, 18, 26; BTS_ERR_WORKSPACE for a missing
+ * workspace. */
+long bts_dilate3d_workspace(int D, int H, int W, int iterations, int fuse);
+int bts_dilate3d(const uint8_t* lab, uint8_t* out, int D, int H, int W, int K, int class_mask, int connectivity, int iterations, int fuse,
+                 void* work, bts_stream_t stream);
+/* One pass over n voxels of td_comp (bts_components3d of the dilated truth), truth (uint8, region K / class_mask) and pred_comp
+ * (bts_components3d of the prediction).  lesion_vox (n int32, zeroed by the call, the layout of bts_component_sizes): lesion_vox[r] = the
+ * truth voxels inside the dilated component of root r.  table (bts_lesion_pairs_table_bytes(capacity) = 16 capacity bytes, zeroed by the
+ * call): `capacity` 64-bit keys (td_comp << 32) | pred_comp, 0 = empty, then `capacity` int32 pairs (reach, overlap) in the keys' slots:
+ * for every distinct pair of a dilated component and a predicted component that share a voxel, the voxels they share and those of them
+ * that are truth.  Integer atomics only: the counts are exact, the slot a pair lands in is not fixed.  status (two int64 on the device,
+ * zeroed by the call): [0] = pairs stored, [1] = insertions that found no room.  A table that is too small is NO error: status[1] > 0,
+ * status[0] + status[1] slots are enough for a rerun, every stored pair still holds its complete counts and lesion_vox is complete.
+ * BTS_ERR_SHAPE for n outside [0, 2^31 - 1), K outside 2..8, a class_mask outside its range or a capacity outside 1..2^32. */
+long bts_lesion_pairs_table_bytes(long capacity);
+int bts_lesion_pairs(const int* td_comp, const uint8_t* truth, const int* pred_comp, long n, int K, int class_mask, int* lesion_vox,
+                     void* table, long capacity, long* status, bts_stream_t stream);
+/* boxes (nroots x 6 int32, every element written) = the half-open bounding box (d0,h0,w0,d1,h1,w1) of the component of comp (int32
+ * (D,H,W) of bts_components3d) whose root is roots[i]; roots: nroots ASCENDING int32 on the device; (INT_MAX x 3, 0 x 3) for a root the
+ * map does not hold.  BTS_ERR_SHAPE for a non-positive extent, D H W >= 2^31 - 1 or nroots outside 0..2^28; nroots == 0 launches nothing. */
+int bts_component_boxes(const int* comp, int D, int H, int W, const int* roots, int nroots, int* boxes, bts_stream_t stream);
+/* Two dense uint8 maps of the half-open box [d0,d1) x [h0,h1) x [w0,w1) of the volume (D,H,W), every byte written: g = 1 where the
+ * voxel is of the truth region (K, class_mask) and of the dilated component of root td_root (td_comp == td_root + 1); m = 1 where
+ * pred_comp's root is one of roots (nroots ASCENDING int32 on the device; nroots == 0: m is all 0 and roots may be NULL).  They feed
+ * bts_region_surface(K = 2, class_mask = 2), bts_edt3d_sq and bts_masked_select.  BTS_ERR_SHAPE for a non-positive extent, D H W >=
+ * 2^31 - 1, a box that is empty or leaves the volume, td_root outside the volume, K or class_mask as above, nroots outside 0..2^28. */
+int bts_lesion_crop(const int* td_comp, const uint8_t* truth, const int* pred_comp, int D, int H, int W, int K, int class_mask, int d0,
+                    int h0, int w0, int d1, int h1, int w1, int td_root, const int* roots, int nroots, uint8_t* g, uint8_t* m,
+                    bts_stream_t stream);
 
 /* ===== training-time augmentation on the device (train.py:14-49) ===== */
 /* per-channel mean / population variance of a (nvox, C) tensor with voxel stride ld (tf.nn.moments, train.py:18);
