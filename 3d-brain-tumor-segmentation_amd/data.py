@@ -76,6 +76,70 @@ def augment_example(x, y, crop_size, out_ch, draws):
     return ops.augment_crop(x, y, var, crop_size, draws.offsets, draws.flip_mask, draws.shift, draws.scale, out_ch)
 
 
+class SpatialConfig(object):
+    """spatial augmentation of a training example (bts_augment_spatial_batch): with probability `prob` the crop is rotated about
+    axes 0, 1, 2 by angles uniform in +-rotate_deg[k] degrees (one number: the same bound for all three), zoomed by z uniform in
+    zoom = (lo, hi) (z > 1 magnifies) and, with elastic_sigma > 0, deformed by a cubic B-spline free-form field whose control
+    nodes, elastic_spacing voxels apart, are N(0, elastic_sigma^2) displacements in voxels.  Voxels from outside the volume carry
+    `fill` (one number or one per channel) before the intensity shift / scale; labels there are background."""
+
+    def __init__(self, prob, rotate_deg=(15.0, 15.0, 15.0), zoom=(0.9, 1.1), elastic_sigma=0.0, elastic_spacing=32, fill=0.0):
+        deg = [float(rotate_deg)] * 3 if np.isscalar(rotate_deg) else [float(a) for a in rotate_deg]
+        self.prob, self.rotate_deg, self.zoom = float(prob), tuple(deg), (float(zoom[0]), float(zoom[1]))
+        self.elastic_sigma, self.elastic_spacing = float(elastic_sigma), int(elastic_spacing)
+        self.fill = float(fill) if np.isscalar(fill) else [float(v) for v in fill]
+        if not 0.0 <= self.prob <= 1.0 or len(deg) != 3 or self.elastic_sigma < 0 or self.elastic_spacing < 1:
+            raise ValueError('SpatialConfig: prob in [0,1], three angles, elastic_sigma >= 0 and elastic_spacing >= 1 are needed')
+        if not 0.0 < self.zoom[0] <= self.zoom[1]:
+            raise ValueError('SpatialConfig: zoom must be 0 < lo <= hi, got %r' % (self.zoom,))
+
+    def fill_of(self, c):
+        return [self.fill] * c if isinstance(self.fill, float) else list(self.fill)
+
+
+class SpatialDraw(object):
+    """the spatial draws of one example: `on` (False: the plain copy), the 3x3 float64 `matrix` M, the control field `phi`
+    (host float32 (G0,G1,G2,3), or None) and its `spacing`"""
+    __slots__ = ('on', 'matrix', 'phi', 'spacing', 'angles', 'zoom')
+
+    def __init__(self, on, matrix, phi, spacing, angles, zoom):
+        self.on, self.matrix, self.phi, self.spacing, self.angles, self.zoom = bool(on), matrix, phi, int(spacing), angles, zoom
+
+
+def spatial_matrix(angles, zoom):
+    """M = R0(a0) R1(a1) R2(a2) / zoom in float64; R_k rotates about axis k by a_k radians (counter-clockwise in the plane of the two
+    other axes taken in cyclic order)"""
+    def rot(axis, a):
+        i, j = (axis + 1) % 3, (axis + 2) % 3
+        r = np.eye(3)
+        r[i, i], r[i, j], r[j, i], r[j, j] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
+        return r
+    return rot(0, angles[0]).dot(rot(1, angles[1])).dot(rot(2, angles[2])) / float(zoom)
+
+
+def control_grid(crop_size, spacing):
+    """nodes per axis of the free-form field of a crop: G_k = (T_k - 1) // spacing + 4"""
+    return tuple((int(t) - 1) // int(spacing) + 4 for t in crop_size)
+
+
+def draw_spatial(gen, cfg, crop_size):
+    """The spatial draws of one example, taken right after draw().  For a given config the same number of values is consumed whatever
+    they turn out to be (an example that stays untransformed still draws its angles, zoom and field), so the position in the stream
+    never depends on a draw.  Order: torch.rand(5, float64) = [u_prob, u_a0, u_a1, u_a2, u_z] with on = (u_prob < prob),
+    angle_k = (2 u_ak - 1) rotate_deg[k], z = lo + u_z (hi - lo); then, only if elastic_sigma > 0, torch.randn(G0, G1, G2, 3, float32)
+    scaled by elastic_sigma (3 G0 G1 G2 standard normals, node-major, component last)."""
+    u = torch.rand(5, generator=gen, dtype=torch.float64).tolist()
+    phi = None
+    if cfg.elastic_sigma > 0:
+        phi = torch.randn(control_grid(crop_size, cfg.elastic_spacing) + (3,), generator=gen, dtype=torch.float32) * cfg.elastic_sigma
+    on = u[0] < cfg.prob
+    angles = [np.deg2rad((2.0 * u[1 + k] - 1.0) * cfg.rotate_deg[k]) for k in range(3)]
+    zoom = cfg.zoom[0] + u[4] * (cfg.zoom[1] - cfg.zoom[0])
+    if not on:
+        return SpatialDraw(False, np.eye(3), None, cfg.elastic_spacing, angles, zoom)
+    return SpatialDraw(True, spatial_matrix(angles, zoom), phi, cfg.elastic_spacing, angles, zoom)
+
+
 class _Dataset(object):
     """re-iterable epoch of (x, y) device batches.  Data parallel: every rank draws the SAME permutation from
     the shared shuffle generator and keeps positions rank, rank+world, ... of it, truncated to len // world examples so
@@ -90,12 +154,16 @@ class _Dataset(object):
         offset tables leave the host.  A rank keeps what it visits;
       * with workers > 0 host threads read the epoch's next non-resident examples ahead, consumed in visiting order.
     All draws stay on the iterating thread in visiting order, so for a given seed the batches are bit-identical whatever the two
-    arguments are; residency is not state (state_dict is the two generators)."""
+    arguments are; residency is not state (state_dict is the two generators).
+
+    spatial (a SpatialConfig, or None: nothing below happens and not one extra value is drawn): draw_spatial() follows every draw(), on
+    the same generator, and both paths go through bts_augment_spatial_batch (the per-example path with N = 1), so the batches are
+    still the same on either path and the state is still the two generators."""
 
     channels_first = False
 
     def __init__(self, files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, device, rank=0, world=1,
-                 resident_bytes=0, workers=0):
+                 resident_bytes=0, workers=0, spatial=None):
         self.files, self.batch_size, self.prepro_size = files, int(batch_size), tuple(prepro_size)
         self.crop_size, self.out_ch, self.shuffle = tuple(crop_size), int(out_ch), shuffle
         self.rank, self.world = int(rank), max(1, int(world))
@@ -104,6 +172,7 @@ class _Dataset(object):
         self.device = device
         self.resident_bytes, self.workers = max(0, int(resident_bytes)), max(0, int(workers))
         self._resident, self._resident_used = {}, 0           # file index -> (x, y, var) on the device; bytes of their x + y
+        self.spatial = spatial
 
     def _per_rank(self):
         return len(self.files) // self.world if self.world > 1 else len(self.files)
@@ -147,7 +216,13 @@ class _Dataset(object):
         for i in order:
             xh, yh = self._read(i)
             x, y = torch.from_numpy(xh).to(self.device), torch.from_numpy(yh).to(self.device)
-            xa, ya = augment_example(x, y, self.crop_size, self.out_ch, draw(self.gen, c, (h, w, d), self.crop_size))
+            dr = draw(self.gen, c, (h, w, d), self.crop_size)
+            if self.spatial is None:
+                xa, ya = augment_example(x, y, self.crop_size, self.out_ch, dr)
+            else:
+                sd = draw_spatial(self.gen, self.spatial, self.crop_size)
+                xa, ya = self._augment_spatial([(x, y, ops.channel_moments(x)[1])], [dr], [sd], False)
+                xa, ya = xa[0], ya[0]
             xs.append(xa)
             ys.append(ya)
             if len(xs) == self.batch_size:
@@ -178,7 +253,7 @@ class _Dataset(object):
         h, w, d, c = self.prepro_size
         # an index occurs once per epoch and the resident set only grows: what this epoch has to read is known now
         host = self._host_examples([i for i in order if i not in self._resident])
-        batch, draws = [], []
+        batch, draws, sdraws = [], [], []
         for i in order:
             ex = self._resident.get(i)
             if ex is None:
@@ -192,13 +267,27 @@ class _Dataset(object):
                     self._resident_used += nbytes
             batch.append(ex)
             draws.append(draw(self.gen, c, (h, w, d), self.crop_size))
+            if self.spatial is not None:
+                sdraws.append(draw_spatial(self.gen, self.spatial, self.crop_size))
             if len(batch) == self.batch_size:
-                yield self._augment(batch, draws)
-                batch, draws = [], []
+                yield self._augment(batch, draws, sdraws)
+                batch, draws, sdraws = [], [], []
         if batch:
-            yield self._augment(batch, draws)
+            yield self._augment(batch, draws, sdraws)
 
-    def _augment(self, batch, draws):
+    def _augment_spatial(self, batch, draws, sdraws, channels_first):
+        # (the fields are uploaded on the current stream, ahead of the launch that reads them)
+        phis = [None if sd.phi is None else sd.phi.to(self.device) for sd in sdraws]
+        c = self.prepro_size[3]
+        return ops.augment_spatial_batch([b[0] for b in batch], [b[1] for b in batch], [b[2] for b in batch], self.crop_size,
+                                         [dr.offsets for dr in draws], [dr.flip_mask for dr in draws], [dr.shift for dr in draws],
+                                         [dr.scale for dr in draws], self.out_ch, [sd.on for sd in sdraws],
+                                         [sd.matrix.reshape(-1).tolist() for sd in sdraws], phis, [sd.spacing for sd in sdraws],
+                                         [self.spatial.fill_of(c)] * len(batch), channels_first)
+
+    def _augment(self, batch, draws, sdraws=()):
+        if self.spatial is not None:
+            return self._augment_spatial(batch, draws, sdraws, self.channels_first)
         return ops.augment_batch([b[0] for b in batch], [b[1] for b in batch], [b[2] for b in batch], self.crop_size,
                                  [dr.offsets for dr in draws], [dr.flip_mask for dr in draws], [dr.shift for dr in draws],
                                  [dr.scale for dr in draws], self.out_ch, self.channels_first)
@@ -214,11 +303,12 @@ class _ChannelsFirstDataset(_Dataset):
 
 
 def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=True, data_format='channels_last', seed=0,
-                    device=None, rank=None, world=None, resident_bytes=0, workers=0):
+                    device=None, rank=None, world=None, resident_bytes=0, workers=0, spatial=None):
     """-> (re-iterable dataset of (x, y) device batches, number of examples)   [train.py:12-64]
     rank / world default to the process group's (one shard of the examples per rank, see _Dataset).
     resident_bytes: budget of example bytes kept on the device after their first read; workers: host threads reading ahead
-    (see _Dataset; the batches do not depend on either)."""
+    (see _Dataset; the batches do not depend on either).  spatial: a SpatialConfig (rotation, zoom and elastic deformation of the
+    crops, on the device in the same launch) or None, which leaves every draw and every batch as it was."""
     if data_format not in ('channels_last', 'channels_first'):
         raise ValueError('unknown data_format %r' % (data_format,))
     from . import parallel
@@ -227,4 +317,4 @@ def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=Tru
     files = sorted(os.path.join(loc, f) for f in os.listdir(loc) if f.endswith('.npz'))
     dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
     cls = _Dataset if data_format == 'channels_last' else _ChannelsFirstDataset
-    return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world, resident_bytes, workers), len(files)
+    return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world, resident_bytes, workers, spatial), len(files)

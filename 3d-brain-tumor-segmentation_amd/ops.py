@@ -1173,6 +1173,79 @@ def augment_batch(xs, ys, variances, crop, offsets, flip_masks, shifts, scales, 
     return xo, yo
 
 
+def augment_spatial_batch_max():
+    """examples one launch of bts_augment_spatial_batch carries (ops.augment_spatial_batch takes any number: the call splits)"""
+    return int(lib().query('bts_augment_spatial_batch_max'))
+
+
+def augment_spatial_batch(xs, ys, variances, crop, offsets, flip_masks, shifts, scales, out_ch, spatial, matrices, phis, spacings,
+                          fills=None, channels_first=False, out=None):
+    """augment_batch with a spatial transform per example (bts_augment_spatial_batch: s = o + (T-1)/2 + M (t~ - (T-1)/2) + u(t~),
+    trilinear image with `fill` outside the volume, nearest labels).  The arguments of augment_batch plus, per example: spatial (a
+    false flag: the plain copy, bit-equal to augment_batch), matrices (9 floats, row-major, or a 3x3 nesting), phis (a dense fp32
+    (G0,G1,G2,3) device tensor with G_k = (T_k-1)//spacing + 4, or None for no elastic part), spacings (ints >= 1) and fills (C floats
+    each; None: zeros) -> the tensors of augment_batch"""
+    n = len(xs)
+    if n == 0 or not (len(ys) == len(variances) == len(offsets) == len(flip_masks) == len(shifts) == len(scales) == n):
+        raise ValueError('augment_spatial_batch: %d examples need as many labels, variances and draws' % n)
+    if not (len(spatial) == len(matrices) == len(phis) == len(spacings) == n) or (fills is not None and len(fills) != n):
+        raise ValueError('augment_spatial_batch: %d examples need as many flags, matrices, fields, spacings and fills' % n)
+    s0, s1, s2, c = xs[0].shape
+    for x, y, v in zip(xs, ys, variances):
+        _check(x, 'x'), _check(y, 'y'), _check(v, 'var')
+        if tuple(x.shape) != (s0, s1, s2, c) or y.numel() != s0 * s1 * s2 or v.numel() != c:
+            raise ValueError('augment_spatial_batch: every example must be a (%d,%d,%d,%d) volume with its labels and %d variances'
+                             % (s0, s1, s2, c, c))
+        if not (x.is_contiguous() and y.is_contiguous() and v.is_contiguous()):
+            raise ValueError('augment_spatial_batch: dense tensors only')
+    t0, t1, t2 = (int(t) for t in crop)
+    mats = []
+    for m in matrices:
+        flat = [float(v) for row in m for v in row] if len(m) == 3 else [float(v) for v in m]
+        if len(flat) != 9:
+            raise ValueError('augment_spatial_batch: a matrix is 9 floats')
+        mats += flat
+    for ph, sp in zip(phis, spacings):
+        if int(sp) < 1:
+            raise ValueError('augment_spatial_batch: spacing must be >= 1, got %r' % (sp,))
+        if ph is None:
+            continue
+        _check(ph, 'phi')
+        g = tuple((t - 1) // int(sp) + 4 for t in (t0, t1, t2)) + (3,)
+        if tuple(ph.shape) != g or not ph.is_contiguous():
+            raise ValueError('augment_spatial_batch: phi must be a dense %s tensor for spacing %d, got %s' % (g, int(sp), tuple(ph.shape)))
+    if fills is None:
+        fills = [[0.0] * c] * n
+    if any(len(f) != c for f in fills):
+        raise ValueError('augment_spatial_batch: a fill is %d floats' % c)
+    dev = xs[0].device
+    xshape = (n, c, t0, t1, t2) if channels_first else (n, t0, t1, t2, c)
+    yshape = (n, out_ch, t0, t1, t2) if channels_first else (n, t0, t1, t2, out_ch)
+    if out is None:
+        xo = torch.empty(xshape, dtype=torch.float32, device=dev)
+        yo = torch.empty(yshape, dtype=torch.float32, device=dev)
+    else:
+        xo, yo = out
+        _check(xo, 'out x'), _check(yo, 'out y')
+        if tuple(xo.shape) != xshape or tuple(yo.shape) != yshape or not (xo.is_contiguous() and yo.is_contiguous()):
+            raise ValueError('augment_spatial_batch: out must be dense %s and %s tensors' % (xshape, yshape))
+    ptrs = ctypes.c_void_p * n
+    off = (ctypes.c_int * (3 * n))(*[int(o) for tri in offsets for o in tri])
+    fl = (ctypes.c_int * n)(*[int(f) for f in flip_masks])
+    sh = (ctypes.c_float * (n * c))(*[float(v) for row in shifts for v in row])
+    sc = (ctypes.c_float * (n * c))(*[float(v) for row in scales for v in row])
+    on = (ctypes.c_int * n)(*[1 if f else 0 for f in spatial])
+    mm = (ctypes.c_float * (9 * n))(*mats)
+    spc = (ctypes.c_int * n)(*[int(v) for v in spacings])
+    fi = (ctypes.c_float * (n * c))(*[float(v) for row in fills for v in row])
+    as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)      # noqa: E731
+    lib().call('bts_augment_spatial_batch', as_p(ptrs(*[x.data_ptr() for x in xs])), as_p(ptrs(*[y.data_ptr() for y in ys])),
+               as_p(ptrs(*[v.data_ptr() for v in variances])), _p(xo), _p(yo), n, s0, s1, s2, c, t0, t1, t2, as_p(off), as_p(fl), as_p(sh),
+               as_p(sc), as_p(on), as_p(mm), as_p(ptrs(*[None if ph is None else ph.data_ptr() for ph in phis])), as_p(spc), as_p(fi),
+               int(out_ch), 1 if channels_first else 0, _stream())
+    return xo, yo
+
+
 # ---- dataset preprocessing on the device (preprocess.py:17-131) ----
 def _window(v, c, name):
     """(st0, st1) of a view made by slicing a dense (S0,S1,S2,c) parent on its three spatial axes; no copy is ever made here"""

@@ -19,7 +19,9 @@ The command (the reference's train.py:219-223 with args.py:86-196):
                             [--dtype bfloat16] [--batch_size 8] [--load_folder OUT] ...
 
 The flags and defaults are the reference's TrainArgParser (args.py:91-143), its two size checks included (args.py:170-174).  --gpu is
-accepted and implied: there is no CPU path.  Added: --dtype (training AND validation type), --workers, --resident_gb, --seed.
+accepted and implied: there is no CPU path.  Added: --dtype (training AND validation type), --workers, --resident_gb, --seed, and
+the spatial augmentation of the TRAINING examples (add_spatial_arguments: --spatial_prob, --rotate_deg, --zoom_range, --elastic_sigma,
+--elastic_spacing; off by default, never applied to --val_loc; data.SpatialConfig).
 Examples are the `.npz` files `python -m bts_amd.preprocess` writes; with a process group in the environment (torchrun) every rank
 runs the command, takes its shard and rank 0 writes the files.
 
@@ -28,7 +30,8 @@ Deviations:
   * an empty --val_loc is refused (the reference ends in os.listdir(''));
   * an empty --save_folder writes no files (the reference ends in os.mkdir(''));
   * --load_folder reads `crop_size` as the key of the pickled dict it is (args.py:184 asks the dict for an attribute) and resumes
-    at the container's `next_epoch` with the optimiser state (see above);
+    at the container's `next_epoch` with the optimiser state (see above); the spatial augmentation flags are restored with the crop
+    (a train_args.pkl from before they existed has none of them and means "off");
   * `train_args.pkl` is the plain dict of the arguments (`model_args` with `in_ch`, `crop_size`, ...), written by rank 0 alone.
 """
 import argparse
@@ -409,11 +412,56 @@ def arg_parser():
     return p
 
 
+SPATIAL_KEYS = ('spatial_prob', 'rotate_deg', 'zoom_range', 'elastic_sigma', 'elastic_spacing')
+
+
+def add_spatial_arguments(p):
+    """the flags of the spatial training augmentation (data.SpatialConfig), a group of their own: arg_parser() stays the reference's
+    flag set plus the run's, which tests/golden/train_cli_flags.json is held against"""
+    g = p.add_argument_group('spatial augmentation of the training examples')
+    g.add_argument('--spatial_prob', type=float, default=0.0,
+                   help='Probability that a training example is rotated, zoomed and deformed; 0: off.')
+    g.add_argument('--rotate_deg', type=str, default='15', help='Largest rotation in degrees about each axis: a or a0,a1,a2.')
+    g.add_argument('--zoom_range', type=str, default='0.9,1.1', help='Zoom is uniform in lo,hi; above 1 magnifies.')
+    g.add_argument('--elastic_sigma', type=float, default=0.0,
+                   help='Standard deviation, in voxels, of the control-node displacements of the elastic deformation; 0: none.')
+    g.add_argument('--elastic_spacing', type=int, default=32, help='Voxels between control nodes of the elastic deformation.')
+    return p
+
+
+def full_parser():
+    """what the command parses: arg_parser() and the spatial augmentation group"""
+    return add_spatial_arguments(arg_parser())
+
+
+def _floats(text, counts, flag):
+    try:
+        vals = [float(v) for v in str(text).split(',')]
+    except ValueError:
+        vals = []
+    if len(vals) not in counts:
+        raise ValueError('%s: expected %s comma-separated numbers, got %r' % (flag, ' or '.join(str(n) for n in counts), text))
+    return vals
+
+
+def spatial_config(args):
+    """the data.SpatialConfig of the parsed (or unpickled) arguments, None when spatial_prob is 0 or absent"""
+    a = args if isinstance(args, dict) else vars(args)
+    if not a.get('spatial_prob'):
+        return None
+    from .data import SpatialConfig
+    return SpatialConfig(a['spatial_prob'], rotate_deg=a['rotate_deg'], zoom=a['zoom_range'], elastic_sigma=a['elastic_sigma'],
+                         elastic_spacing=a['elastic_spacing'])
+
+
 def parse_args(argv=None):
     """args.py:145-196: model_args.* folded into a dict, crop split, sizes from the prepro dump, the two size checks, --load_folder;
     writes train_args.pkl (rank 0, when there is a save folder)"""
     from .preprocess import load_prepro
-    args = arg_parser().parse_args(argv)
+    args = full_parser().parse_args(argv)
+    deg = _floats(args.rotate_deg, (1, 3), '--rotate_deg')
+    args.rotate_deg = deg * 3 if len(deg) == 1 else deg
+    args.zoom_range = _floats(args.zoom_range, (2,), '--zoom_range')
     args.model_args = {}
     for key in [k for k in vars(args) if k.startswith('model_args.')]:                                    # args.py:24-38
         args.model_args[key.split('.', 1)[1]] = getattr(args, key)
@@ -440,6 +488,11 @@ def parse_args(argv=None):
         assert isinstance(args.model_args, dict)
         args.data_format = args.model_args['data_format']
         args.save_folder = args.load_folder
+        args.spatial_prob = 0.0 if 'spatial_prob' not in chkpt_args else chkpt_args['spatial_prob']      # (an older pickle: off)
+        for key in SPATIAL_KEYS[1:]:
+            if key in chkpt_args:
+                setattr(args, key, chkpt_args[key])
+    spatial_config(args)                      # (a bad range or probability is refused here, not at the first batch)
     if args.save_folder and int(os.environ.get('RANK', '0')) == 0:
         save_train_args(args.save_folder, vars(args))
     return args
@@ -459,10 +512,11 @@ def run(args):
     else:
         resident = int(args.resident_gb * 1e9)
     sets = []
-    for loc, shuffle in ((args.train_loc, True), (args.val_loc, False)):
+    spatial = spatial_config(args)
+    for loc, shuffle, extra in ((args.train_loc, True, {'spatial': spatial} if spatial is not None else {}), (args.val_loc, False, {})):
         sets.append(data.prepare_dataset(loc, args.batch_size, args.prepro_size, args.crop_size, args.model_args['out_ch'],
                                          shuffle=shuffle, data_format=args.data_format, seed=args.seed, device=dev,
-                                         resident_bytes=resident, workers=args.workers))
+                                         resident_bytes=resident, workers=args.workers, **extra))
     (train_data, n_train), (val_data, n_val) = sets
     print('{} training examples.'.format(n_train), flush=True)
     print('{} validation examples.'.format(n_val), flush=True)

@@ -390,6 +390,32 @@ long bts_augment_batch_max(void);
 int bts_augment_batch(const float* const* x, const float* const* y, const float* const* var, float* xo, float* yo, int N, int S0,
                       int S1, int S2, int C, int T0, int T1, int T2, const int* offsets, const int* flips, const float* shift,
                       const float* scale, int out_ch, int layout, bts_stream_t stream);
+/* bts_augment_batch with a spatial transform per example: rotation + zoom + free-form deformation, as a gather in place of the copy,
+ * in the same single launch.  For an output voxel t of a crop of extent T, from a source volume of extent S at window origin o:
+ *   t~_k = flip_k ? T_k-1-t_k : t_k (the flip is undone first, as in bts_augment_batch), q = t~ - (T-1)/2,
+ *   s = o + (T-1)/2 + M q + u(t~);  M = R0(th0) R1(th1) R2(th2) / z: rotations about axes 0, 1, 2 and the zoom z (z > 1 magnifies), built
+ *   by the host in float64 and passed as 9 floats, row-major;
+ *   u: a free-form deformation on a control grid of `spacing` voxels: g = t~/spacing, i = floor(g), f = g - i,
+ *      u = sum_{a,b,c=0..3} B_a(f0) B_b(f1) B_c(f2) phi[i0+a, i1+b, i2+c, :], B the uniform cubic B-spline basis; phi has
+ *      G_k = (T_k-1)/spacing + 4 (integer division) nodes per axis and 3 components, in source voxels, dense fp32 (G0,G1,G2,3) in DEVICE
+ *      memory; NULL: no elastic part;
+ *   image channels: trilinear at s, a corner outside the volume contributes fill[c] (scipy.ndimage mode='grid-constant'; a voxel
+ *      whose eight corners are all outside is exactly fill[c]), then
+ *      fmaf(shift, sqrtf(var), v) * scale on the interpolated value (var stays the variance of the whole untransformed volume);
+ *   labels: the nearest voxel floor(s + 0.5), label 0 outside the volume; one-hot without the background as in bts_augment_batch.
+ * An example whose spatial flag is 0 is copied inside the same launch, bit-equal to bts_augment_batch; one with M = I and phi = NULL
+ * that takes the gather is bit-equal too (exact integer coordinates, weights exactly 0 and 1; finite volumes).  Coordinates are fp32; the
+ * order of operations is written out above augment_spatial_batch_kernel (csrc/augment.hip) and bounds the error.
+ * Arguments of bts_augment_batch plus per-example HOST arrays: spatial (N ints, 0 = copy), M (9N floats), phi (N device pointers or
+ * NULLs), spacing (N ints), fill (N*C floats).  bts_augment_spatial_batch_max() examples per launch (the table entry is larger than
+ * bts_augment_batch's); a larger N is split by the call itself.  No atomics: deterministic.  BTS_ERR_SHAPE, before any HIP call, for
+ * everything bts_augment_batch rejects, a NULL table, a spacing < 1, a non-finite entry of M (every example is checked, whatever its
+ * flag), or a phi with more than 256 nodes along axis 2. */
+long bts_augment_spatial_batch_max(void);
+int bts_augment_spatial_batch(const float* const* x, const float* const* y, const float* const* var, float* xo, float* yo, int N, int S0,
+                              int S1, int S2, int C, int T0, int T1, int T2, const int* offsets, const int* flips, const float* shift,
+                              const float* scale, const int* spatial, const float* M, const float* const* phi, const int* spacing,
+                              const float* fill, int out_ch, int layout, bts_stream_t stream);
 
 /* ===== dataset preprocessing on the device (preprocess.py:17-131: create_dataset, compute_norm, main) =====
  * Dense fp32 (S0,S1,S2,C) volumes, C innermost, 1 <= C <= 16.  A crop window (T0,T1,T2,C) of such a volume is addressed in place:
