@@ -183,8 +183,10 @@ __global__ __launch_bounds__(256) void gn_bwd_group_generic_kernel(const float* 
     const float xh = (x[(long)n * E + r] - m) * rs;
     float de = dy[((long)n * (E / C) + r / C) * lddy + c];
     if (relu && !(xh * gamma[idx] + beta[idx] > 0.f)) de = 0.f;
-    s1 += (double)(de * gamma[idx]);
-    s2 += (double)(de * gamma[idx] * xh);
+    // gamma_j B_j and gamma_j A_j as the vectorised route forms them: dE exact, dE * xh rounded once, the products with gamma in fp64
+    // (an fp32 dE * gamma put 70 eps32 on a c1 that cancels, visible in dx where dE = 0 and xh ~ 0)
+    s1 += (double)de * (double)gamma[idx];
+    s2 += (double)(de * xh) * (double)gamma[idx];
   }
   const double r1 = block_sum_f64(s1, sh);
   const double r2 = block_sum_f64(s2, sh + 4);
@@ -247,7 +249,7 @@ extern "C" int bts_gn_stats(const float* x, float* mean, float* rstd, void* work
   GnGeom g;
   int r = gn_geom(g, N, V, C, G, mode);
   if (r != BTS_OK) return r;
-  if (workspace_bytes < bts_gn_workspace(N, V, C, G, mode)) return BTS_ERR_WORKSPACE;
+  if (workspace == nullptr || workspace_bytes < bts_gn_workspace(N, V, C, G, mode)) return BTS_ERR_WORKSPACE;
   if (g.generic) {
     (void)hipGetLastError(); hipLaunchKernelGGL(gn_stats_generic_kernel, dim3(N * G), dim3(256), 0, stream, x, mean, rstd, g.E, g.L, C, G, g.cg, mode, eps);
     BTS_LAUNCH_CHECK();
@@ -725,6 +727,7 @@ extern "C" int bts_gn_bwd(const float* x, const float* dy, float* dx, const floa
   int r = gn_geom(g, N, V, C, G, mode);
   if (r != BTS_OK) return r;
   if (lddy < C) return BTS_ERR_ALIGN;
+  if (workspace == nullptr) return BTS_ERR_WORKSPACE;
   if (g.generic || lddy % 4 != 0) {
     if (workspace_bytes < (long)N * G * 2 * 4 + 64) return BTS_ERR_WORKSPACE;
     float* gc1 = reinterpret_cast<float*>(workspace);

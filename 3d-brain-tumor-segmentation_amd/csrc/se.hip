@@ -450,6 +450,7 @@ static int se_bwd_blocks(long V, int N, int F, long* vspan) {
 }
 
 extern "C" long bts_se_bwd_workspace(int N, long V, int F, int R) {
+  if (N <= 0 || V <= 0 || R <= 0 || F < 4 || (F & (F - 1)) || F > 256) return -1;      // (se_bwd_blocks divides by N and by F / 4)
   long vspan;
   const int B = se_bwd_blocks(V, N, F, &vspan);
   return (long)N * B * F * 2 * 8 + ((long)N * F * 3 + (long)N * R) * 8 + 128;
@@ -460,8 +461,8 @@ extern "C" int bts_se_bwd(const float* dout, const float* res, const float* sp, 
                           const float* ch, const float* w1, const float* w2, const float* wsp, float* dres, float* ds,
                           float* dgap, float* dw1, float* dw2, float* dwsp, void* workspace, long workspace_bytes, int N,
                           long V, int F, int R, int lddo, int accumulate_params, hipStream_t stream) {
-  if (N <= 0 || V <= 0 || F < 4 || (F & (F - 1)) || F > 256 || lddo < F || lddo % 4) return BTS_ERR_SHAPE;
-  if (workspace_bytes < bts_se_bwd_workspace(N, V, F, R)) return BTS_ERR_WORKSPACE;
+  if (N <= 0 || V <= 0 || R <= 0 || F < 4 || (F & (F - 1)) || F > 256 || lddo < F || lddo % 4) return BTS_ERR_SHAPE;
+  if (workspace == nullptr || workspace_bytes < bts_se_bwd_workspace(N, V, F, R)) return BTS_ERR_WORKSPACE;
   if (((uintptr_t)workspace) & 15) return BTS_ERR_ALIGN;     // (the partial reduce reads double2)
   long vspan;
   const int B = se_bwd_blocks(V, N, F, &vspan);

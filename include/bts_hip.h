@@ -109,6 +109,9 @@ int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, float* dw, 
                           int dup_start, int dup_shift, int accumulate, bts_stream_t stream);
 
 /* ===== GroupNormalization (layers/group_norm.py:83-124) ===== */
+/* Statuses, all before any launch: BTS_ERR_SHAPE for a non-positive size, C < G or G not dividing C (the queries return -1);
+ * BTS_ERR_ALIGN for ldy / lddy < C and, on a vectorisable shape (C a power of two in [4, 1024], group length a multiple of 4, row
+ * stride a multiple of 4), for x, y, dy or dx off a 16-byte boundary; BTS_ERR_WORKSPACE for a NULL or short workspace. */
 long bts_gn_workspace(int N, long V, int C, int G, int mode);
 long bts_gn_bwd_workspace(int N, long V, int C, int G, int mode);
 /* mean,rstd: (N*G) floats. x dense NDHWC (ld == C). */
@@ -131,6 +134,10 @@ int bts_se_mlp_fwd(const float* gap, const float* w1, const float* w2, float* h,
 int bts_block_epilogue_fwd(const float* res, const float* c2, float* out, float* sp, const float* wsp, const float* ch,
                            const float* gamma, const float* beta, const float* mean, const float* rstd, int N, long V,
                            int F, int ldo, int G, int mode, bts_stream_t stream);
+/* F a power of two in [4, 256] and lddo >= F a multiple of 4, N, V, R positive: BTS_ERR_SHAPE otherwise (the query returns -1);
+ * BTS_ERR_WORKSPACE for a NULL or short workspace, BTS_ERR_ALIGN for one off a 16-byte boundary; all before any launch.
+ * bts_block_epilogue_fwd: BTS_ERR_SHAPE for the same F rule, ldo < F, ldo % 4 != 0 or (with c2) G not dividing F; BTS_ERR_ALIGN for
+ * res, out or c2 off a 16-byte boundary. */
 long bts_se_bwd_workspace(int N, long V, int F, int R);
 int bts_se_bwd(const float* dout, const float* res, const float* sp, const float* gap, const float* h, const float* ch,
                const float* w1, const float* w2, const float* wsp, float* dres, float* ds, float* dgap, float* dw1,
