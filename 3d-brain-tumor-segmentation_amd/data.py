@@ -140,6 +140,88 @@ def draw_spatial(gen, cfg, crop_size):
     return SpatialDraw(True, spatial_matrix(angles, zoom), phi, cfg.elastic_spacing, angles, zoom)
 
 
+class IntensityConfig(object):
+    """intensity augmentation of a training example (bts_intensity_batch), the nnU-Net / batchgenerators set with its defaults:
+    Gaussian noise of standard deviation s ~ U(noise_sigma) with probability noise_prob; Gaussian blur with probability blur_prob,
+    then per channel with probability blur_channel_prob and sigma ~ U(blur_sigma); a brightness factor m ~ U(brightness) with
+    probability brightness_prob; a contrast factor f from `contrast` with probability contrast_prob; a gamma from `gamma` with
+    probability gamma_prob, applied to the negated image with probability gamma_invert_prob.  f and gamma follow batchgenerators'
+    rule for a range (lo, hi): with lo < 1 and a side draw < 0.5 the value is U(lo, 1), otherwise U(max(lo, 1), hi).  s, sigma, m, f
+    and gamma are drawn per channel."""
+
+    def __init__(self, noise_prob=0.1, noise_sigma=(0.0, 0.1), blur_prob=0.2, blur_sigma=(0.5, 1.0), blur_channel_prob=0.5,
+                 brightness_prob=0.15, brightness=(0.75, 1.25), contrast_prob=0.15, contrast=(0.75, 1.25), gamma_prob=0.3,
+                 gamma=(0.7, 1.5), gamma_invert_prob=0.1):
+        def pair(v, name, positive):
+            try:
+                lo, hi = (float(a) for a in v)
+            except (TypeError, ValueError):
+                raise ValueError('IntensityConfig: %s must be a pair (lo, hi), got %r' % (name, v))
+            if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi and (lo > 0.0 if positive else lo >= 0.0)):
+                raise ValueError('IntensityConfig: %s must be finite with %s lo <= hi, got %r' % (name, '0 <' if positive else '0 <=', v))
+            return lo, hi
+        self.noise_sigma = pair(noise_sigma, 'noise_sigma', False)
+        self.blur_sigma = pair(blur_sigma, 'blur_sigma', True)
+        self.brightness = pair(brightness, 'brightness', True)
+        self.contrast = pair(contrast, 'contrast', True)
+        self.gamma = pair(gamma, 'gamma', True)
+        if int(4.0 * float(np.float32(self.blur_sigma[1])) + 0.5) > 16:
+            raise ValueError('IntensityConfig: blur_sigma %r needs a radius int(4 sigma + 0.5) above 16' % (blur_sigma,))
+        for name, v in (('noise_prob', noise_prob), ('blur_prob', blur_prob), ('blur_channel_prob', blur_channel_prob),
+                        ('brightness_prob', brightness_prob), ('contrast_prob', contrast_prob), ('gamma_prob', gamma_prob),
+                        ('gamma_invert_prob', gamma_invert_prob)):
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                v = float('nan')
+            if not 0.0 <= v <= 1.0:
+                raise ValueError('IntensityConfig: %s must be a probability in [0, 1]' % name)
+            setattr(self, name, v)
+
+
+class IntensityDraw(object):
+    """the intensity draws of one example: `params`, one (flags, s, sigma, m, f, gamma) per channel as ops.intensity_batch takes
+    them (every number is kept, whatever its flag), and the Philox `key` (k0, k1) of its noise"""
+    __slots__ = ('params', 'key')
+
+    def __init__(self, params, key):
+        self.params, self.key = params, key
+
+
+def _two_sided(rng, side, u):
+    """batchgenerators' draw of a contrast factor or gamma from rng = (lo, hi)"""
+    lo, hi = rng
+    if side < 0.5 and lo < 1.0:
+        return lo + u * (1.0 - lo)
+    lo = max(lo, 1.0)
+    return lo + u * (hi - lo)
+
+
+def draw_intensity(gen, cfg, c):
+    """The intensity draws of one example of c channels, taken after draw() (and after draw_spatial() when there is one) on the same
+    generator.  For a given config the same number of values is consumed whatever they turn out to be.  Order:
+    torch.rand(6 + 8c, float64) = [u_noise, u_blur, u_brightness, u_contrast, u_gamma, u_invert], then for each channel
+    [noise s, blur-channel, blur sigma, brightness m, contrast side, contrast value, gamma side, gamma value];
+    then torch.randint(0, 2**32, (2,), int64) = the noise key (k0, k1).
+    A stage is on when its u < its probability (blur: and the channel's u < blur_channel_prob; invert: u_invert <
+    gamma_invert_prob, with gamma on); a range draw is lo + u (hi - lo), f and gamma by the two-sided rule of IntensityConfig."""
+    u = torch.rand(6 + 8 * c, generator=gen, dtype=torch.float64).tolist()
+    key = torch.randint(0, 2 ** 32, (2,), generator=gen, dtype=torch.int64).tolist()
+    lin = lambda rng, v: rng[0] + v * (rng[1] - rng[0])      # noqa: E731
+    noise, blur, bright = u[0] < cfg.noise_prob, u[1] < cfg.blur_prob, u[2] < cfg.brightness_prob
+    contrast, gamma = u[3] < cfg.contrast_prob, u[4] < cfg.gamma_prob
+    invert = gamma and u[5] < cfg.gamma_invert_prob
+    params = []
+    for j in range(c):
+        v = u[6 + 8 * j:14 + 8 * j]
+        flags = ((ops.INTENSITY_NOISE if noise else 0) | (ops.INTENSITY_BLUR if blur and v[1] < cfg.blur_channel_prob else 0) |
+                 (ops.INTENSITY_BRIGHT if bright else 0) | (ops.INTENSITY_CONTRAST if contrast else 0) |
+                 (ops.INTENSITY_GAMMA if gamma else 0) | (ops.INTENSITY_INVERT if invert else 0))
+        params.append((flags, lin(cfg.noise_sigma, v[0]), lin(cfg.blur_sigma, v[2]), lin(cfg.brightness, v[3]),
+                       _two_sided(cfg.contrast, v[4], v[5]), _two_sided(cfg.gamma, v[6], v[7])))
+    return IntensityDraw(params, (int(key[0]), int(key[1])))
+
+
 class _Dataset(object):
     """re-iterable epoch of (x, y) device batches.  Data parallel: every rank draws the SAME permutation from
     the shared shuffle generator and keeps positions rank, rank+world, ... of it, truncated to len // world examples so
@@ -158,12 +240,17 @@ class _Dataset(object):
 
     spatial (a SpatialConfig, or None: nothing below happens and not one extra value is drawn): draw_spatial() follows every draw(), on
     the same generator, and both paths go through bts_augment_spatial_batch (the per-example path with N = 1), so the batches are
-    still the same on either path and the state is still the two generators."""
+    still the same on either path and the state is still the two generators.
+
+    intensity (an IntensityConfig, or None: nothing below happens and not one extra value is drawn): draw_intensity() follows draw()
+    and draw_spatial(), on the same generator, and both paths run bts_intensity_batch on what the augment launch returned (the
+    per-example path with N = 1, channels last).  Its result depends neither on N nor on the layout, so the batches are again the
+    same on either path."""
 
     channels_first = False
 
     def __init__(self, files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, device, rank=0, world=1,
-                 resident_bytes=0, workers=0, spatial=None):
+                 resident_bytes=0, workers=0, spatial=None, intensity=None):
         self.files, self.batch_size, self.prepro_size = files, int(batch_size), tuple(prepro_size)
         self.crop_size, self.out_ch, self.shuffle = tuple(crop_size), int(out_ch), shuffle
         self.rank, self.world = int(rank), max(1, int(world))
@@ -173,6 +260,7 @@ class _Dataset(object):
         self.resident_bytes, self.workers = max(0, int(resident_bytes)), max(0, int(workers))
         self._resident, self._resident_used = {}, 0           # file index -> (x, y, var) on the device; bytes of their x + y
         self.spatial = spatial
+        self.intensity = intensity
 
     def _per_rank(self):
         return len(self.files) // self.world if self.world > 1 else len(self.files)
@@ -223,6 +311,9 @@ class _Dataset(object):
                 sd = draw_spatial(self.gen, self.spatial, self.crop_size)
                 xa, ya = self._augment_spatial([(x, y, ops.channel_moments(x)[1])], [dr], [sd], False)
                 xa, ya = xa[0], ya[0]
+            if self.intensity is not None:
+                idr = draw_intensity(self.gen, self.intensity, c)
+                ops.intensity_batch(xa.unsqueeze(0), [idr.params], [idr.key], False)
             xs.append(xa)
             ys.append(ya)
             if len(xs) == self.batch_size:
@@ -253,7 +344,7 @@ class _Dataset(object):
         h, w, d, c = self.prepro_size
         # an index occurs once per epoch and the resident set only grows: what this epoch has to read is known now
         host = self._host_examples([i for i in order if i not in self._resident])
-        batch, draws, sdraws = [], [], []
+        batch, draws, sdraws, idraws = [], [], [], []
         for i in order:
             ex = self._resident.get(i)
             if ex is None:
@@ -269,11 +360,18 @@ class _Dataset(object):
             draws.append(draw(self.gen, c, (h, w, d), self.crop_size))
             if self.spatial is not None:
                 sdraws.append(draw_spatial(self.gen, self.spatial, self.crop_size))
+            if self.intensity is not None:
+                idraws.append(draw_intensity(self.gen, self.intensity, c))
             if len(batch) == self.batch_size:
-                yield self._augment(batch, draws, sdraws)
-                batch, draws, sdraws = [], [], []
+                yield self._intensity(self._augment(batch, draws, sdraws), idraws)
+                batch, draws, sdraws, idraws = [], [], [], []
         if batch:
-            yield self._augment(batch, draws, sdraws)
+            yield self._intensity(self._augment(batch, draws, sdraws), idraws)
+
+    def _intensity(self, xy, idraws):
+        if self.intensity is not None:
+            ops.intensity_batch(xy[0], [d.params for d in idraws], [d.key for d in idraws], self.channels_first)
+        return xy
 
     def _augment_spatial(self, batch, draws, sdraws, channels_first):
         # (the fields are uploaded on the current stream, ahead of the launch that reads them)
@@ -303,12 +401,13 @@ class _ChannelsFirstDataset(_Dataset):
 
 
 def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=True, data_format='channels_last', seed=0,
-                    device=None, rank=None, world=None, resident_bytes=0, workers=0, spatial=None):
+                    device=None, rank=None, world=None, resident_bytes=0, workers=0, spatial=None, intensity=None):
     """-> (re-iterable dataset of (x, y) device batches, number of examples)   [train.py:12-64]
     rank / world default to the process group's (one shard of the examples per rank, see _Dataset).
     resident_bytes: budget of example bytes kept on the device after their first read; workers: host threads reading ahead
     (see _Dataset; the batches do not depend on either).  spatial: a SpatialConfig (rotation, zoom and elastic deformation of the
-    crops, on the device in the same launch) or None, which leaves every draw and every batch as it was."""
+    crops, on the device in the same launch) or None, which leaves every draw and every batch as it was.  intensity: an
+    IntensityConfig (noise, blur, brightness, contrast and gamma on the augmented batch, on the device) or None, likewise."""
     if data_format not in ('channels_last', 'channels_first'):
         raise ValueError('unknown data_format %r' % (data_format,))
     from . import parallel
@@ -317,4 +416,5 @@ def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=Tru
     files = sorted(os.path.join(loc, f) for f in os.listdir(loc) if f.endswith('.npz'))
     dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
     cls = _Dataset if data_format == 'channels_last' else _ChannelsFirstDataset
-    return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world, resident_bytes, workers, spatial), len(files)
+    return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world, resident_bytes, workers, spatial,
+               intensity), len(files)

@@ -1246,6 +1246,52 @@ def augment_spatial_batch(xs, ys, variances, crop, offsets, flip_masks, shifts, 
     return xo, yo
 
 
+# ---- intensity augmentation of an augmented batch (bts_intensity_batch) ----
+INTENSITY_NOISE, INTENSITY_BLUR, INTENSITY_BRIGHT, INTENSITY_CONTRAST, INTENSITY_GAMMA, INTENSITY_INVERT = 1, 2, 4, 8, 16, 32
+
+
+def intensity_blur_weights(sigma):
+    """(radius, the radius + 1 float weights w[|j|]) of the Gaussian blur of `sigma` as bts_intensity_batch applies it (host only)"""
+    buf = (ctypes.c_float * 17)()
+    r = lib().probe('bts_intensity_blur_weights', float(sigma), ctypes.cast(buf, ctypes.c_void_p))
+    if r < 0:
+        raise ValueError('intensity_blur_weights: sigma must be positive with a radius int(4 sigma + 0.5) <= 16, got %r' % (sigma,))
+    return int(r), [float(buf[k]) for k in range(r + 1)]
+
+
+def intensity_batch(x, params, keys, channels_first=False):
+    """Gaussian noise, Gaussian blur, brightness, contrast and gamma on the batch an augment launch wrote, IN PLACE (-> x).
+    x: dense fp32 (N,T0,T1,T2,C), or (N,C,T0,T1,T2) with channels_first.  params: N rows of C entries
+    (flags, s, sigma, m, f, gamma), flags a sum of INTENSITY_*; a stage whose flag is off ignores its number.  keys: N pairs
+    (k0, k1) of uint32, the Philox key of each example's noise.  The semantics are written above bts_intensity_batch in
+    include/bts_hip.h; an (n, c) without a flag is not written."""
+    _check(x, 'x')
+    if x.dtype != torch.float32 or x.dim() != 5 or not x.is_contiguous():
+        raise ValueError('intensity_batch: x must be a dense float32 batch of five dimensions, got %s %s' % (x.dtype, tuple(x.shape)))
+    if channels_first:
+        n, c, t0, t1, t2 = x.shape
+    else:
+        n, t0, t1, t2, c = x.shape
+    if n == 0 or len(params) != n or len(keys) != n:
+        raise ValueError('intensity_batch: %d examples need as many parameter rows and keys' % n)
+    fl, pr, ky = [], [], []
+    for row, key in zip(params, keys):
+        if len(row) != c or len(key) != 2:
+            raise ValueError('intensity_batch: a parameter row has %d entries of (flags, s, sigma, m, f, gamma), a key two words' % c)
+        for e in row:
+            if len(e) != 6:
+                raise ValueError('intensity_batch: an entry is (flags, s, sigma, m, f, gamma)')
+            fl.append(int(e[0]))
+            pr.extend(float(v) for v in e[1:])
+        ky.extend(int(k) & 0xffffffff for k in key)
+    nb = lib().query('bts_intensity_batch_workspace', n, t0, t1, t2, c)
+    ws = workspace(nb, x.device)
+    as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)      # noqa: E731
+    lib().call('bts_intensity_batch', _p(x), n, t0, t1, t2, c, 1 if channels_first else 0, as_p((ctypes.c_int * len(fl))(*fl)),
+               as_p((ctypes.c_float * len(pr))(*pr)), as_p((ctypes.c_uint32 * len(ky))(*ky)), _p(ws), ws.numel(), _stream())
+    return x
+
+
 # ---- dataset preprocessing on the device (preprocess.py:17-131) ----
 def _window(v, c, name):
     """(st0, st1) of a view made by slicing a dense (S0,S1,S2,c) parent on its three spatial axes; no copy is ever made here"""

@@ -21,7 +21,9 @@ The command (the reference's train.py:219-223 with args.py:86-196):
 The flags and defaults are the reference's TrainArgParser (args.py:91-143), its two size checks included (args.py:170-174).  --gpu is
 accepted and implied: there is no CPU path.  Added: --dtype (training AND validation type), --workers, --resident_gb, --seed, and
 the spatial augmentation of the TRAINING examples (add_spatial_arguments: --spatial_prob, --rotate_deg, --zoom_range, --elastic_sigma,
---elastic_spacing; off by default, never applied to --val_loc; data.SpatialConfig).
+--elastic_spacing; off by default, never applied to --val_loc; data.SpatialConfig), and their intensity augmentation
+(add_intensity_arguments: --intensity_aug and the --noise_*, --blur_*, --brightness_*, --contrast_* and --gamma_* flags; off by
+default, never applied to --val_loc; data.IntensityConfig).
 Examples are the `.npz` files `python -m bts_amd.preprocess` writes; with a process group in the environment (torchrun) every rank
 runs the command, takes its shard and rank 0 writes the files.
 
@@ -30,8 +32,8 @@ Deviations:
   * an empty --val_loc is refused (the reference ends in os.listdir(''));
   * an empty --save_folder writes no files (the reference ends in os.mkdir(''));
   * --load_folder reads `crop_size` as the key of the pickled dict it is (args.py:184 asks the dict for an attribute) and resumes
-    at the container's `next_epoch` with the optimiser state (see above); the spatial augmentation flags are restored with the crop
-    (a train_args.pkl from before they existed has none of them and means "off");
+    at the container's `next_epoch` with the optimiser state (see above); the spatial and intensity augmentation flags are restored with the
+    crop (a train_args.pkl from before they existed has none of them and means "off");
   * `train_args.pkl` is the plain dict of the arguments (`model_args` with `in_ch`, `crop_size`, ...), written by rank 0 alone.
 """
 import argparse
@@ -429,9 +431,35 @@ def add_spatial_arguments(p):
     return p
 
 
+INTENSITY_KEYS = ('intensity_aug', 'noise_prob', 'noise_sigma', 'blur_prob', 'blur_sigma', 'blur_channel_prob', 'brightness_prob',
+                  'brightness_range', 'contrast_prob', 'contrast_range', 'gamma_prob', 'gamma_range', 'gamma_invert_prob')
+_INTENSITY_RANGES = ('noise_sigma', 'blur_sigma', 'brightness_range', 'contrast_range', 'gamma_range')
+
+
+def add_intensity_arguments(p):
+    """the flags of the intensity training augmentation (data.IntensityConfig, whose defaults these are), a group of their own like
+    the spatial one"""
+    g = p.add_argument_group('intensity augmentation of the training examples')
+    g.add_argument('--intensity_aug', action='store_true',
+                   help='Gaussian noise, Gaussian blur, brightness, contrast and gamma on the training crops (off by default).')
+    g.add_argument('--noise_prob', type=float, default=0.1, help='Probability of Gaussian noise.')
+    g.add_argument('--noise_sigma', type=str, default='0,0.1', help='Standard deviation of the noise is uniform in lo,hi.')
+    g.add_argument('--blur_prob', type=float, default=0.2, help='Probability of Gaussian blur.')
+    g.add_argument('--blur_sigma', type=str, default='0.5,1.0', help='Sigma of the blur, in voxels, is uniform in lo,hi per channel.')
+    g.add_argument('--blur_channel_prob', type=float, default=0.5, help='Probability that a channel of a blurred example is blurred.')
+    g.add_argument('--brightness_prob', type=float, default=0.15, help='Probability of a multiplicative brightness change.')
+    g.add_argument('--brightness_range', type=str, default='0.75,1.25', help='The brightness factor is uniform in lo,hi.')
+    g.add_argument('--contrast_prob', type=float, default=0.15, help='Probability of a contrast change.')
+    g.add_argument('--contrast_range', type=str, default='0.75,1.25', help='The contrast factor lies in lo,hi (either side of 1 equally likely).')
+    g.add_argument('--gamma_prob', type=float, default=0.3, help='Probability of a gamma transform.')
+    g.add_argument('--gamma_range', type=str, default='0.7,1.5', help='Gamma lies in lo,hi (either side of 1 equally likely).')
+    g.add_argument('--gamma_invert_prob', type=float, default=0.1, help='Probability that a gamma transform acts on the negated image.')
+    return p
+
+
 def full_parser():
-    """what the command parses: arg_parser() and the spatial augmentation group"""
-    return add_spatial_arguments(arg_parser())
+    """what the command parses: arg_parser() and the spatial and intensity augmentation groups"""
+    return add_intensity_arguments(add_spatial_arguments(arg_parser()))
 
 
 def _floats(text, counts, flag):
@@ -454,6 +482,18 @@ def spatial_config(args):
                          elastic_spacing=a['elastic_spacing'])
 
 
+def intensity_config(args):
+    """the data.IntensityConfig of the parsed (or unpickled) arguments, None when intensity_aug is off or absent"""
+    a = args if isinstance(args, dict) else vars(args)
+    if not a.get('intensity_aug'):
+        return None
+    from .data import IntensityConfig
+    return IntensityConfig(noise_prob=a['noise_prob'], noise_sigma=a['noise_sigma'], blur_prob=a['blur_prob'], blur_sigma=a['blur_sigma'],
+                           blur_channel_prob=a['blur_channel_prob'], brightness_prob=a['brightness_prob'],
+                           brightness=a['brightness_range'], contrast_prob=a['contrast_prob'], contrast=a['contrast_range'],
+                           gamma_prob=a['gamma_prob'], gamma=a['gamma_range'], gamma_invert_prob=a['gamma_invert_prob'])
+
+
 def parse_args(argv=None):
     """args.py:145-196: model_args.* folded into a dict, crop split, sizes from the prepro dump, the two size checks, --load_folder;
     writes train_args.pkl (rank 0, when there is a save folder)"""
@@ -462,6 +502,8 @@ def parse_args(argv=None):
     deg = _floats(args.rotate_deg, (1, 3), '--rotate_deg')
     args.rotate_deg = deg * 3 if len(deg) == 1 else deg
     args.zoom_range = _floats(args.zoom_range, (2,), '--zoom_range')
+    for key in _INTENSITY_RANGES:
+        setattr(args, key, _floats(getattr(args, key), (2,), '--' + key))
     args.model_args = {}
     for key in [k for k in vars(args) if k.startswith('model_args.')]:                                    # args.py:24-38
         args.model_args[key.split('.', 1)[1]] = getattr(args, key)
@@ -492,7 +534,12 @@ def parse_args(argv=None):
         for key in SPATIAL_KEYS[1:]:
             if key in chkpt_args:
                 setattr(args, key, chkpt_args[key])
+        args.intensity_aug = bool(chkpt_args.get('intensity_aug', False))                                  # (an older pickle: off)
+        for key in INTENSITY_KEYS[1:]:
+            if key in chkpt_args:
+                setattr(args, key, chkpt_args[key])
     spatial_config(args)                      # (a bad range or probability is refused here, not at the first batch)
+    intensity_config(args)
     if args.save_folder and int(os.environ.get('RANK', '0')) == 0:
         save_train_args(args.save_folder, vars(args))
     return args
@@ -512,8 +559,11 @@ def run(args):
     else:
         resident = int(args.resident_gb * 1e9)
     sets = []
-    spatial = spatial_config(args)
-    for loc, shuffle, extra in ((args.train_loc, True, {'spatial': spatial} if spatial is not None else {}), (args.val_loc, False, {})):
+    spatial, intensity = spatial_config(args), intensity_config(args)
+    train_extra = {} if spatial is None else {'spatial': spatial}
+    if intensity is not None:
+        train_extra['intensity'] = intensity
+    for loc, shuffle, extra in ((args.train_loc, True, train_extra), (args.val_loc, False, {})):
         sets.append(data.prepare_dataset(loc, args.batch_size, args.prepro_size, args.crop_size, args.model_args['out_ch'],
                                          shuffle=shuffle, data_format=args.data_format, seed=args.seed, device=dev,
                                          resident_bytes=resident, workers=args.workers, **extra))

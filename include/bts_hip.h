@@ -424,6 +424,46 @@ int bts_augment_spatial_batch(const float* const* x, const float* const* y, cons
                               const float* scale, const int* spatial, const float* M, const float* const* phi, const int* spacing,
                               const float* fill, int out_ch, int layout, bts_stream_t stream);
 
+/* Intensity augmentation of the batch that bts_augment_batch / bts_augment_spatial_batch wrote: Gaussian noise, Gaussian blur,
+ * brightness, contrast and gamma (the nnU-Net / batchgenerators set; train.py:19-20 has only the shift and scale).  x: dense fp32
+ * (N,T0,T1,T2,C) (layout 0) or (N,C,T0,T1,T2) (layout 1), 1 <= C <= 16, changed IN PLACE; labels are not touched.  The unit is one
+ * (example n, channel c) volume v of T0*T1*T2 voxels, background included.  HOST tables: flags (N*C ints, a sum of BTS_INTENSITY_*),
+ * params (N*C*5 floats: s, sigma, m, f, gamma), keys (2N uint32: the Philox key (k0,k1) of each example).  Stages in this order, each
+ * on the output of the one before:
+ *   NOISE     v[t] += s * z[e], s >= 0;  e = ((t0*T1 + t1)*T2 + t2)*C + c, the element's channels-last index in EITHER layout (so both
+ *             layouts get the same noise);  z: Philox4x32-10 of key (k0,k1) and counter (q & 0xffffffff, q >> 32, 0, 0), q = e >> 2,
+ *             element e takes output word e & 3; words (0,1) and (2,3) are Box-Muller pairs: u1 = ((w_a >> 8) + 1) 2^-24,
+ *             u2 = (w_b >> 8) 2^-24, r = sqrt(-2 ln u1), z_a = r cos(2 pi u2), z_b = r sin(2 pi u2)  (logf / sinf / cosf, not the fast
+ *             intrinsics; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85);
+ *   BLUR      scipy.ndimage.gaussian_filter(v, sigma) with its defaults: separable, radius r = int(4 sigma + 0.5), weights
+ *             exp(-j^2 / (2 sigma^2)) normalised in float64 on the host (bts_intensity_blur_weights) and passed as floats,
+ *             mode='reflect' (d c b a | a b c d | d c b a, period 2n when r >= n); r <= 16; out of place through the workspace;
+ *   BRIGHT    v *= m, m > 0  (alone: bit-equal to the fp32 product);
+ *   CONTRAST  batchgenerators augment_contrast, preserve_range: mu = mean(v), lo = min(v), hi = max(v),
+ *             v = clip((v - mu) f + mu, lo, hi);
+ *   GAMMA     batchgenerators augment_gamma, retain_stats, epsilon 1e-7: with INVERT v = -v;  mu, sd = mean, population std of v,
+ *             lo = min(v), R = max(v) - lo;  v = ((v - lo) / (R + 1e-7))^gamma R + lo;  v = (v - mean(v)) / (std(v) + 1e-8) sd + mu;
+ *             with INVERT v = -v.  A constant volume comes out unchanged up to the rounding of the last line.
+ * Means and deviations are fp64 sums of v - v[0] and its square in a fixed order (a constant volume has deviation exactly 0), min and
+ * max are exact; no floating-point atomics.  The result of an example depends neither on N, nor on its place in the batch, nor on the
+ * layout, nor on how many launches the call makes (the job table travels by value, 32 (n,c) volumes per launch; any N works); two
+ * runs are bit-identical.  An (n,c) without a flag is not written.  The fp32 order of operations is written out at the head of
+ * csrc/intensity.hip and bounds the error.
+ * BTS_ERR_SHAPE, before any HIP call: N <= 0, C outside 1..16, an empty crop (or one of about 2^31 / C voxels or more), a layout other than 0 / 1, a NULL x, table or key array,
+ * a workspace smaller than bts_intensity_batch_workspace(), an unknown flag bit, and on an enabled stage a non-finite or negative s,
+ * sigma <= 0 or r > 16, a non-finite or non-positive m, f or gamma. */
+#define BTS_INTENSITY_NOISE 1
+#define BTS_INTENSITY_BLUR 2
+#define BTS_INTENSITY_BRIGHT 4
+#define BTS_INTENSITY_CONTRAST 8
+#define BTS_INTENSITY_GAMMA 16
+#define BTS_INTENSITY_INVERT 32
+long bts_intensity_batch_workspace(int N, int T0, int T1, int T2, int C);
+/* host only: the blur radius of sigma (-1: sigma <= 0, not finite, or r > 16) and, unless NULL, its r + 1 weights w[|j|] */
+long bts_intensity_blur_weights(float sigma, float* weights);
+int bts_intensity_batch(float* x, int N, int T0, int T1, int T2, int C, int layout, const int* flags, const float* params,
+                        const uint32_t* keys, void* workspace, long workspace_bytes, bts_stream_t stream);
+
 /* ===== dataset preprocessing on the device (preprocess.py:17-131: create_dataset, compute_norm, main) =====
  * Dense fp32 (S0,S1,S2,C) volumes, C innermost, 1 <= C <= 16.  A crop window (T0,T1,T2,C) of such a volume is addressed in place:
  * `xwin` points at its origin, st0 / st1 are the element strides of the two outer axes, the voxel stride is C. */
