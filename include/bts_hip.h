@@ -6,6 +6,18 @@
  * a tensor may be a channel slice of a wider slab (virtual Concatenate).
  * Weights are passed in the reference's Keras layouts and re-packed by bts_conv_pack().
  *
+ * What a result may depend on -- the operand views, and nothing else:
+ *   - a `workspace` is scratch: its contents on entry are never read before the call has written them, so it need not be initialised
+ *     (or cleared between calls); a call that needs zeros there writes them itself;
+ *   - an output that is not accumulated into (no BTS_CONV_FLAG_ACCUM / `accumulate` argument set) need not be initialised either: every
+ *     element of its view is written, none is read first;
+ *   - with ld > C, the ld - C floats between two voxels' channels belong to other tensors of the slab: they are neither written nor do they
+ *     influence a result -- a lane outside [0, C) is masked at the load, not loaded and cancelled by a zero weight (Inf * 0 is NaN);
+ *   - memory before the first and behind the last voxel of a view is neither read into a result nor written (halo taps outside the
+ *     volume are zeros by construction, not loads).
+ * The caching allocator of a training process hands out blocks that hold an earlier step's bytes, Inf / NaN after an fp16 overflow step
+ * included; tests/test_poison_gpu.py runs every path with such bytes reading NaN and requires bit-identical, finite results.
+ *
  * The reference (vliu15/3d-brain-tumor-segmentation) has no FFI of its own: its boundary is the Keras
  * layer protocol. Each function below cites the reference call site whose arithmetic it replaces.
  */

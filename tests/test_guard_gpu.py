@@ -11,97 +11,17 @@ What runs under it: complete training steps of small models through every conv-f
 Winograd, implicit GEMM incl. split-K, upm / k1s / dsc / c2 forced on by their thresholds, Winograd / direct / streaming weight
 gradients), at ragged and minimum crops and with batch 2; the 16-bit forward and training step; and the 16-bit kernels with their own
 tiling floors (LDS-DMA stride-1 conv, streaming 1x1x1, transposed form, strided weight gradients) on slab views with ld > C."""
-import importlib
-
 import pytest
 import torch
 
+from guard_alloc import FILL, PAD, Guarded, install  # noqa: F401  (tests/guard_alloc.py: the allocator, shared with the poison tests)
+
 pytestmark = pytest.mark.gpu
-
-PAD = 4096
-FILL = 0xA5
-
-
-class Guarded(object):
-    """stand-in for the `torch` module inside bts_amd: allocation calls return views into guard-banded buffers"""
-
-    def __init__(self):
-        self.live = []
-
-    def __getattr__(self, name):
-        return getattr(torch, name)
-
-    def _alloc(self, shape, dtype, device, zero=False, value=None):
-        if isinstance(shape, int):
-            shape = (shape,)
-        shape = tuple(int(s) for s in shape)
-        dtype = dtype or torch.float32
-        numel = 1
-        for s in shape:
-            numel *= s
-        nbytes = numel * torch.empty((), dtype=dtype).element_size()
-        big = torch.full((nbytes + 2 * PAD,), FILL, dtype=torch.uint8, device=device if device is not None else 'cpu')
-        view = big[PAD:PAD + nbytes].view(dtype).view(shape)
-        if zero:
-            view.zero_()
-        if value is not None:
-            view.fill_(value)
-        if big.is_cuda:
-            self.live.append((big, nbytes))
-        return view
-
-    def empty(self, *shape, dtype=None, device=None, **kw):
-        if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)):
-            shape = shape[0]
-        return self._alloc(shape, dtype, device)
-
-    def zeros(self, *shape, dtype=None, device=None, **kw):
-        if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)):
-            shape = shape[0]
-        return self._alloc(shape, dtype, device, zero=True)
-
-    def full(self, shape, value, dtype=None, device=None, **kw):
-        return self._alloc(shape, dtype, device, value=value)
-
-    def empty_like(self, t, dtype=None, **kw):
-        return self._alloc(tuple(t.shape), dtype or t.dtype, t.device)
-
-    def zeros_like(self, t, dtype=None, **kw):
-        return self._alloc(tuple(t.shape), dtype or t.dtype, t.device, zero=True)
-
-    def check(self):
-        torch.cuda.synchronize()
-        bad = 0
-        for big, nbytes in self.live:
-            if not bool((big[:PAD] == FILL).all()) or not bool((big[PAD + nbytes:] == FILL).all()):
-                bad += 1
-        n = len(self.live)
-        self.live = []
-        assert bad == 0, '%d of %d guarded buffers were written outside their bounds' % (bad, n)
-        return n
 
 
 @pytest.fixture
 def guard(monkeypatch):
-    import bts_amd
-    from bts_amd import ops
-    g = Guarded()
-    import sys
-    for name in ('model', 'util', 'tape', 'ops', 'lowp', 'lowp_train', 'parallel', 'data', 'infer', 'train', 'layers._base', 'layers.resnet',
-                 'layers.group_norm', 'layers.downsample', 'layers.upsample', 'layers.vae', 'layers.encoder', 'layers.decoder'):
-        importlib.import_module('bts_amd.' + name)
-    mods = [m for n, m in list(sys.modules.items()) if n == 'bts_amd' or n.startswith('bts_amd.')]
-    for m in mods:
-        if getattr(m, 'torch', None) is torch:
-            monkeypatch.setattr(m, 'torch', g)
-
-    def exact_workspace(nbytes, device):       # exactly what the *_workspace query asked for -- no 1 MB floor, no reuse
-        return g._alloc((max(int(nbytes), 1),), torch.uint8, device)
-    monkeypatch.setattr(ops, 'workspace', exact_workspace)
-    from bts_amd import lowp
-    if getattr(lowp, 'ops', None) is ops:
-        pass
-    yield g
+    yield install(monkeypatch, FILL)
 
 
 def _fresh_model(kw, shape, seed=3):
