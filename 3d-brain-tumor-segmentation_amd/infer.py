@@ -32,6 +32,10 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
     detail, that definition holds: the HD95 of a lesion is `surface_scores`' (pooled directed distances, np.percentile, face-neighbour
     surfaces), a component reaching a lesion's dilated halo alone matches it, a component on a lesion ignored for its size is no
     false positive, two empty maps score (1, 0), and a region in which nothing is left to score gives nan.
+  * the reference runs the network over the whole padded volume (test.py:128-134), an extent no training step produced; with a
+    `WindowSpec` the `TestTimeAugmentor` predicts windows of the training crop instead and blends them with a Gaussian importance map,
+    as nnU-Net and MONAI's sliding_window_inference do (`window_plan`; bts_window_gather, bts_window_accumulate, bts_window_occupancy),
+    off by default.
 All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_spline_prefilter3d, bts_zoom3d,
 bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, bts_components3d, bts_component_sizes,
 bts_component_largest, bts_components_apply, bts_region_relabel, bts_dilate3d, bts_lesion_pairs, bts_component_boxes, bts_lesion_crop, the
@@ -73,11 +77,88 @@ def augment_axes(spatial_tta=True):
     return out
 
 
+WINDOW_MODES = ('gaussian', 'constant')
+
+
+def _window_axis(extent, window, overlap, mode, sigma_scale):
+    """one axis of `window_plan` -> (starts, float64 table (windows, window))"""
+    s, r = int(extent), int(window)
+    interval = max(1, int(r * (1 - overlap)))
+    count = 1 if s <= r else -(-(s - r) // interval) + 1
+    starts = [min(i * interval, max(s - r, 0)) for i in range(count)]
+    pos = np.arange(r, dtype=np.float64)
+    if mode == 'gaussian':
+        g = np.exp(-(pos - (r - 1) / 2.0) ** 2 / (2.0 * (float(sigma_scale) * r) ** 2))
+    else:
+        g = np.ones(r, dtype=np.float64)
+    total = np.zeros(max(s, r), dtype=np.float64)         # S_a(p): the importance of every window that covers p
+    for st in starts:
+        total[st:st + r] += g
+    table = np.zeros((count, r), dtype=np.float64)
+    for i, st in enumerate(starts):
+        inside = min(r, s - st)                           # beyond the volume's end the weight is 0
+        table[i, :inside] = g[:inside] / total[st:st + inside]
+    return starts, table
+
+
+def window_plan(shape, roi, overlap=0.5, mode='gaussian', sigma_scale=0.125):
+    """the windows of a sliding-window pass over a volume of spatial extent `shape` with windows of extent `roi`
+    -> (starts, tables): per axis the list of window starts and a float64 table n[i][r], one row per window, one entry per position.
+    Starts (MONAI's rule), with S the extent and R the window: interval = max(1, int(R (1 - overlap))), 1 window when S <= R and
+    ceil((S - R) / interval) + 1 otherwise, start_i = min(i interval, max(S - R, 0)): the last window is shifted back to end at the
+    volume's end, and a volume shorter than the window gets one window at 0 that hangs over.  Importance: g(r) =
+    exp(-(r - (R-1)/2)^2 / (2 (sigma_scale R)^2)) for 'gaussian', 1 for 'constant'; a voxel's weight in a window is gz gy gx.  The windows
+    are the Cartesian product of the per-axis starts, so the sum of all windows' weights at a voxel is Sz(z) Sy(y) Sx(x) with S_a(p) =
+    sum_i g(p - start_i), and n[i][r] = g(r) / S_a(start_i + r) inside the volume, 0 beyond its end: the weights nz ny nx of all windows
+    at any voxel sum to 1.  No weight volume, no division on the device."""
+    try:
+        roi = tuple(int(r) for r in roi)
+    except TypeError:
+        roi = ()
+    if len(roi) != 3 or min(roi) < 1:
+        raise ValueError('window_plan: roi must have three positive entries, got %r' % (roi,))
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError('window_plan: shape must have three positive entries, got %r' % (shape,))
+    if not 0 <= overlap < 1:
+        raise ValueError('window_plan: overlap must lie in [0, 1), got %r' % (overlap,))
+    if mode not in WINDOW_MODES:
+        raise ValueError('window_plan: mode must be one of %s, got %r' % (WINDOW_MODES, mode))
+    if not sigma_scale > 0:
+        raise ValueError('window_plan: sigma_scale must be positive, got %r' % (sigma_scale,))
+    axes = [_window_axis(s, r, overlap, mode, sigma_scale) for s, r in zip(shape, roi)]
+    return [a[0] for a in axes], [a[1] for a in axes]
+
+
+class WindowSpec(object):
+    """how a TestTimeAugmentor windows a volume: roi (the window, a multiple of the model's spatial resolution per axis), overlap, mode,
+    sigma_scale as in `window_plan`; batch: jobs (windows x augmented copies) per forward, None = the augmentor's tta_batch;
+    skip_empty: windows without a brain-mask voxel are not run (tta_finish zeroes those voxels anyway)"""
+
+    def __init__(self, roi, overlap=0.5, mode='gaussian', sigma_scale=0.125, batch=None, skip_empty=True):
+        window_plan(roi, roi, overlap, mode, sigma_scale)                 # the checks, on a one-window volume
+        if batch is not None and int(batch) < 1:
+            raise ValueError('WindowSpec: batch must be positive, got %r' % (batch,))
+        self.roi = tuple(int(r) for r in roi)
+        self.overlap, self.mode, self.sigma_scale = float(overlap), mode, float(sigma_scale)
+        self.batch = None if batch is None else int(batch)
+        self.skip_empty = bool(skip_empty)
+
+    def check_resolution(self, spatial_res):
+        """the network halves every axis `depth` times: a window must be a multiple of the model's spatial resolution"""
+        if any(r % int(spatial_res) for r in self.roi):
+            raise ValueError('window roi %s must be a multiple of the model\'s spatial resolution %d on every axis' % (self.roi, spatial_res))
+
+    def __repr__(self):
+        return 'WindowSpec(roi=%r, overlap=%r, mode=%r, sigma_scale=%r, batch=%r, skip_empty=%r)' % (
+            self.roi, self.overlap, self.mode, self.sigma_scale, self.batch, self.skip_empty)
+
+
 class TestTimeAugmentor(object):
     __test__ = False  # not a pytest class
 
     def __init__(self, mean, std, model, model_data_format='channels_last', spatial_tta=True, channel_tta=0, threshold=0.5,
-                 seed=0, compute_dtype='float32', tta_batch=None):
+                 seed=0, compute_dtype='float32', tta_batch=None, window=None):
         """compute_dtype: 'float32' (the engine's parity path) | 'float16' | 'bfloat16' -- 16-bit STORAGE of activations and
         weight images with fp32 sums (bts_amd.lowp; BASELINE configs[4] runs the forwards in fp16)"""
         if model_data_format not in ('channels_last', 'channels_first'):
@@ -103,12 +184,19 @@ class TestTimeAugmentor(object):
         if tta_batch is None:
             tta_batch = 1 if compute_dtype in ('float32', 'fp32', 'f32') else 4
         self.tta_batch = max(1, int(tta_batch))
+        # window: a WindowSpec -> the volume is predicted in windows of that extent, blended by their importance (`_call_windowed`);
+        # None: the whole volume per forward, as the reference does.  After a windowed call `window_counts` = (run, skipped).
+        self.window = window
+        self.window_counts = None
+        self._lowp = compute_dtype not in ('float32', 'fp32', 'f32')
 
     def _dev(self, t, like):
         return torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(like.device).contiguous()
 
     def __call__(self, x, bmask):
         """x: (D,H,W,C) raw intensities, bmask: (D,H,W,1) -> masked mean probability map (D,H,W,out_ch)"""
+        if self.window is not None:
+            return self._call_windowed(x, bmask)
         xs = x.unsqueeze(0).contiguous()
         mean, std = self._dev(self.mean, xs), self._dev(self.std, xs)
         acc = None
@@ -146,20 +234,82 @@ class TestTimeAugmentor(object):
         y, _ = ops.tta_finish(acc, self._mask, self.threshold, want_probabilities=True, want_labels=False)
         return y[0].permute(3, 0, 1, 2) if self.model_data_format == 'channels_first' else y[0]   # (test.py:112-114: the model's layout)
 
+    def _call_windowed(self, x, bmask):
+        """__call__ with a WindowSpec: every augmented copy of every window is a job; jobs go through the network `batch` at a time
+        (gather -> forward -> accumulate), weighted by the normalised importance tables, so `acc` ends as the blended mean"""
+        spec = self.window
+        xv = x.to(torch.float32).contiguous()
+        mask = bmask.to(torch.float32).contiguous()
+        dev, c = xv.device, xv.shape[-1]
+        roi = spec.roi
+        starts, tables = window_plan(tuple(xv.shape[:3]), roi, spec.overlap, spec.mode, spec.sigma_scale)
+        tables = [torch.from_numpy(t.astype(np.float32)).to(dev) for t in tables]
+        wins = [(iz, iy, ix) for iz in range(len(starts[0])) for iy in range(len(starts[1])) for ix in range(len(starts[2]))]
+        run = wins
+        if spec.skip_empty:
+            occ = ops.window_occupancy(mask, roi, starts).cpu().numpy()              # the one read of the counts
+            run = [w for w in wins if occ[w] > 0]
+        self.window_counts = (len(run), len(wins) - len(run))
+        mean = torch.as_tensor(self.mean, dtype=torch.float32).reshape(-1).cpu()   # the job table is built on the host
+        std = torch.as_tensor(self.std, dtype=torch.float32).reshape(-1).cpu()
+        sig = None
+        if self.channel_tta:                          # the deviation of the WHOLE normalised volume, read once; one draw per copy
+            xn = ops.flip_affine(xv.unsqueeze(0), 0, mean.to(dev).contiguous(), std.to(dev).contiguous())
+            sig = torch.sqrt(ops.channel_moments(xn[0])[1]).cpu()
+        copies = []                                   # (flip, mean, std) of every augmented copy, in the reference's order
+        for flip in self.flips:
+            copies.append((flip, mean.tolist(), std.tolist()))
+            for _ in range(self.channel_tta):
+                shift = (torch.rand(c, generator=self._gen) * 0.2 - 0.1) * sig
+                scale = torch.rand(c, generator=self._gen) * 0.2 + 0.9
+                copies.append((flip, (mean - shift * std).tolist(), (std / scale).tolist()))
+        count = len(copies)
+        jobs = [(w, cp) for w in run for cp in copies]
+        batch = min(self.tta_batch if spec.batch is None else spec.batch, ops.window_batch_max())
+        cf = self.model_data_format == 'channels_first'
+        aug = torch.empty((min(batch, len(jobs)),) + roi + (c,), dtype=torch.float32, device=dev) if jobs else None
+        acc = None
+        for j0 in range(0, len(jobs), batch):
+            chunk = jobs[j0:j0 + batch]
+            at = [tuple(starts[a][w[a]] for a in range(3)) for w, _ in chunk]
+            flips = [cp[0] for _, cp in chunk]
+            ops.window_gather(xv, roi, at, flips, [cp[1] for _, cp in chunk], [cp[2] for _, cp in chunk], out=aug[:len(chunk)])
+            if self._lowp:
+                y = self._forward(aug[:len(chunk)].permute(0, 4, 1, 2, 3) if cf else aug[:len(chunk)])
+                y = y.permute(0, 2, 3, 4, 1) if cf else y
+            else:
+                y = self._forward(aug[:len(chunk)])
+            yt = (y.t if isinstance(y, Tensor) else y).contiguous()
+            if acc is None:
+                acc = torch.zeros(tuple(xv.shape[:3]) + (yt.shape[-1],), dtype=torch.float32, device=dev)
+            ops.window_accumulate(yt, acc, tables, at, flips, [w for w, _ in chunk], scale=1.0 / count)
+        if acc is None:                               # every window empty: the mask is zero everywhere, and so is the result
+            out_ch = getattr(getattr(self.model, 'decoder', None), 'out_ch', None)
+            acc = torch.zeros(tuple(xv.shape[:3]) + (int(out_ch),), dtype=torch.float32, device=dev)
+        acc = acc.unsqueeze(0)
+        self._prob = acc
+        self._mask = mask.unsqueeze(0)
+        y, _ = ops.tta_finish(acc, self._mask, self.threshold, want_probabilities=True, want_labels=False)
+        return y[0].permute(3, 0, 1, 2) if self.model_data_format == 'channels_first' else y[0]
+
     def labels(self):
         """uint8 label map (D,H,W) of the last call: argmax+1, >=3 -> 4, 0 = background / masked / below threshold"""
         _, lab = ops.tta_finish(self._prob, self._mask, self.threshold, want_probabilities=False, want_labels=True)
         return lab[0]
 
 
-def segment_volume(model, x, mask, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None):
+def segment_volume(model, x, mask, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
+                   window=None):
     """test.py:246-261 for one volume: pad to the model's spatial resolution, TTA inference, crop back.
     x (D,H,W,C), mask (D,H,W,1) channels_last (test.py:109) -> (probabilities, uint8 labels (D,H,W)); the probabilities are
-    (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'"""
+    (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  window: a WindowSpec -> the padded volume
+    is predicted in blended windows of that extent"""
+    if window is not None:
+        window.check_resolution(spatial_res)
     xp, mp, orig = pad_to_spatial_res(spatial_res, x, mask)
     df = getattr(model, 'data_format', 'channels_last')
     tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch)
+                            tta_batch=tta_batch, window=window)
     y = tta(xp, mp)
     lab = tta.labels()
     y = y[:, :orig[0], :orig[1], :orig[2]] if df == 'channels_first' else y[:orig[0], :orig[1], :orig[2]]
@@ -259,16 +409,18 @@ class Interpolator(object):
 
 
 def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
-                 order=3):
+                 order=3, window=None):
     """test.py:235-264 for one scan: resample to 1 mm^3 with mask and padding in one pass, TTA inference, crop, resample back.
     image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz) -> (probabilities, uint8 labels (D,H,W)) on that grid; the probabilities
     are (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  With pixdim (1,1,1) this is
-    segment_volume with the reference's mask, bit for bit."""
+    segment_volume with the reference's mask, bit for bit.  window: a WindowSpec, as in segment_volume."""
+    if window is not None:
+        window.check_resolution(spatial_res)
     interp = Interpolator(None, order=order)
     xp, mp, orig = interp.resample(image, pixdim, pad_res=spatial_res)
     df = getattr(model, 'data_format', 'channels_last')
     tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch)
+                            tta_batch=tta_batch, window=window)
     y = tta(xp, mp)
     if all(f == 1.0 for f in interp.factors):
         lab = tta.labels()
@@ -285,8 +437,12 @@ class StageSpec(object):
     once and kept: the 16-bit engine packs its weight images on the first forward"""
 
     def __init__(self, model, mean, std, spatial_res, spatial_tta=True, channel_tta=0, threshold=0.5, compute_dtype='float32',
-                 tta_batch=None, largest_component=False):
-        """largest_component: for a skull-stripping stage, keep only the largest connected piece of the brain it finds (segment_case)"""
+                 tta_batch=None, largest_component=False, window=None):
+        """largest_component: for a skull-stripping stage, keep only the largest connected piece of the brain it finds (segment_case);
+        window: a WindowSpec -> this stage predicts blended windows of that extent (a multiple of spatial_res per axis)"""
+        if window is not None:
+            window.check_resolution(spatial_res)
+        self.window = window
         self.model, self.mean, self.std = model, mean, std
         self.largest_component = bool(largest_component)
         self.spatial_res = int(spatial_res)
@@ -298,15 +454,23 @@ class StageSpec(object):
     def data_format(self):
         return getattr(self.model, 'data_format', 'channels_last')
 
-    def augmentor(self):
+    @property
+    def window_counts(self):
+        """(windows run, windows skipped as empty) of the stage's last windowed call, None before one"""
+        return None if self._tta is None else self._tta.window_counts
+
+    def augmentor(self, window=None):
         """the stage's TestTimeAugmentor, with the channel-TTA generator back at its seed: every case draws what a fresh augmentor
-        would (segment_scan builds one per call)"""
+        would (segment_scan builds one per call).  window: a WindowSpec for this call in place of the stage's own"""
+        if window is not None:
+            window.check_resolution(self.spatial_res)
         if self._tta is not None:
             self._tta._gen.manual_seed(0)
         if self._tta is None:
             self._tta = TestTimeAugmentor(self.mean, self.std, self.model, self.data_format, spatial_tta=self.spatial_tta,
                                           channel_tta=self.channel_tta, threshold=self.threshold, compute_dtype=self.compute_dtype,
                                           tta_batch=self.tta_batch)
+        self._tta.window = self.window if window is None else window
         return self._tta
 
 
@@ -343,7 +507,7 @@ def postprocess_labels(lab, min_component_voxels=0, et_min_voxels=0, connectivit
     return out
 
 
-def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False, postprocess=None):
+def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False, postprocess=None, window=None):
     """test.py:235-264 for one scan, with the optional skull-stripping stage (test.py:238-248): resample to 1 mm^3 padded to the first
     model's resolution, [skull model with TTA, x * (1 - p) cropped and padded again to the tumour model's resolution,] tumour model
     with TTA, crop, resample back.  tumor, skull: StageSpec; image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz)
@@ -356,7 +520,14 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
     hand-over; 'brain_kept' is that uint8 map, 'brain_counts' remove_components' counts; 'skull_prob' stays the stage's own output.
     postprocess: keyword arguments of `postprocess_labels`, applied to the labels on the scan's own grid (the returned probabilities
     are unchanged); 'postprocess' holds its counts.  These three keys exist only where their option is on (`stages.get(key)` is None
-    otherwise): with the options off the dict is the one callers have always got, every value of a two-stage call a tensor."""
+    otherwise): with the options off the dict is the one callers have always got, every value of a two-stage call a tensor.
+    window: each stage predicts in windows when its StageSpec carries a WindowSpec; a WindowSpec given here takes the place of both
+    stages' own for this call (checked against each stage's resolution).  After the call `stage.window_counts` is (windows run,
+    windows skipped as empty) of that stage."""
+    if window is not None:
+        for stage in (tumor, skull):
+            if stage is not None:
+                window.check_resolution(stage.spatial_res)
     if skull is not None:
         out_ch = getattr(getattr(skull.model, 'decoder', None), 'out_ch', None)
         if out_ch != 1:
@@ -367,7 +538,7 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
     xp, mp, orig = interp.resample(image, pixdim, pad_res=first.spatial_res)
     stages = {'x1mm': xp, 'mask': mp, 'skull_prob': None, 'x_stripped': None, 'mask_repadded': None, 'prob_1mm': None}
     if skull is not None:
-        p = skull.augmentor()(xp, mp)
+        p = skull.augmentor(window)(xp, mp)
         if skull.data_format == 'channels_first':
             p = p.permute(1, 2, 3, 0)
         p = p.contiguous()
@@ -382,7 +553,7 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
         xp, mp = ops.skull_strip(xp, p, mp, orig, tuple(s + res - (s % res) for s in orig))
         stages.update(x_stripped=xp, mask_repadded=mp)
     df = tumor.data_format
-    tta = tumor.augmentor()
+    tta = tumor.augmentor(window)
     y = tta(xp, mp)
     if df == 'channels_first':
         y = y.permute(1, 2, 3, 0)

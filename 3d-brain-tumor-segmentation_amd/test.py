@@ -4,6 +4,7 @@
                            [--skull_model DIR --skull_prepro FILE] [--truth seg] [--out_loc DIR] [--dtype float16]
                            [--min_component_voxels N] [--et_min_voxels N] [--component_connectivity 26] [--skull_largest_component]
                            [--lesionwise] [--lesion_dilation 3] [--lesion_min_voxels 50] [--lesion_penalty_mm 374]
+                           [--window D,H,W|crop] [--window_overlap 0.5] [--window_mode gaussian] [--window_batch N]
 
 This module is named after the reference's script and is NOT a pytest module: pytest's `test_*.py` pattern does not match `test.py`
 and `testpaths` points at tests/, so it is never collected.
@@ -31,10 +32,16 @@ positive; --lesion_dilation iterations join truth pieces into one lesion, lesion
 mask as written: fifteen more columns at the end of the row (after those of --surface_metrics), lw_dice_*, lw_hd95_*, and the counts
 lw_lesions_*, lw_fn_*, lw_fp_*; the `total` row holds the mean of the finite scores and the sums of the counts; one more line per case.
 
+With --window D,H,W both models predict windows of that extent in place of the whole padded volume and blend them where they overlap
+(`infer.WindowSpec`, `infer.window_plan`: --window_overlap is the fraction two neighbouring windows share, --window_mode the importance
+map, `gaussian` or `constant`, --window_batch the windows and augmented copies per forward); --window crop takes each model's recorded
+crop size.  A window must be a multiple of each model's spatial resolution.  Windows without a brain-mask voxel are not run, and one
+more line per case prints the windows run and skipped per stage.  Without --window nothing changes.
+
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
 accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
 --min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component, --lesionwise, --lesion_dilation,
---lesion_min_voxels, --lesion_penalty_mm.
+--lesion_min_voxels, --lesion_penalty_mm, --window, --window_overlap, --window_mode, --window_batch.
 
 Deviations:
   * cases are visited in sorted order of their paths (the reference: the file system's order);
@@ -54,7 +61,7 @@ import numpy as np
 import torch
 
 from . import nifti
-from .infer import (BRATS_REGIONS, Interpolator, StageSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
+from .infer import (BRATS_REGIONS, WINDOW_MODES, Interpolator, StageSpec, WindowSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
                     scores_from_confusion, segment_case, surface_scores, zoom_output_shape)
 from .preprocess import load_prepro
 from .train import load_checkpoint, load_train_args
@@ -67,6 +74,20 @@ LESION_SCORE_KEYS = tuple('lw_%s_%s' % (what, name) for what in ('dice', 'hd95')
 LESION_COUNT_KEYS = tuple('lw_%s_%s' % (what, name) for what in ('lesions', 'fn', 'fp') for name, _ in BRATS_REGIONS)
 LESION_KEYS = LESION_SCORE_KEYS + LESION_COUNT_KEYS      # the columns --lesionwise appends to scores.csv, after the others
 LESION_DEFAULTS = {'lesion_dilation': 3, 'lesion_min_voxels': 50, 'lesion_penalty_mm': 374.0}
+WINDOW_DEFAULTS = {'window_overlap': 0.5, 'window_mode': 'gaussian', 'window_batch': None}
+
+
+def _window_arg(text):
+    """--window: 'crop' or three positive integers D,H,W"""
+    if text == 'crop':
+        return text
+    try:
+        roi = tuple(int(v) for v in text.split(','))
+    except ValueError:
+        roi = ()
+    if len(roi) != 3 or min(roi) < 1:
+        raise argparse.ArgumentTypeError("expected D,H,W (three positive integers) or 'crop', got %r" % (text,))
+    return roi
 
 
 def arg_parser():
@@ -110,6 +131,15 @@ def arg_parser():
                    help='Truth lesions of fewer voxels than this are ignored (default: %d).' % LESION_DEFAULTS['lesion_min_voxels'])
     p.add_argument('--lesion_penalty_mm', type=float, default=argparse.SUPPRESS,
                    help='HD95 charged for a missed lesion or a false positive (default: %g).' % LESION_DEFAULTS['lesion_penalty_mm'])
+    # likewise the sliding-window flags: `window_kwargs` supplies WINDOW_DEFAULTS
+    p.add_argument('--window', type=_window_arg, default=argparse.SUPPRESS,
+                   help="Predict blended windows of this extent D,H,W instead of the whole volume; 'crop': each model's recorded crop size.")
+    p.add_argument('--window_overlap', type=float, default=argparse.SUPPRESS,
+                   help='Fraction of a window shared with its neighbour, in [0, 1) (default: %g).' % WINDOW_DEFAULTS['window_overlap'])
+    p.add_argument('--window_mode', type=str, choices=WINDOW_MODES, default=argparse.SUPPRESS,
+                   help='Importance of a voxel inside its window (default: %s).' % WINDOW_DEFAULTS['window_mode'])
+    p.add_argument('--window_batch', type=int, default=argparse.SUPPRESS,
+                   help='Windows and augmented copies per forward (default: as --tta_batch).')
     return p
 
 
@@ -120,6 +150,12 @@ def parse_args(argv=None):
         parser.error('--min_component_voxels and --et_min_voxels must not be negative')
     if not all(getattr(args, k, v) >= 0 for k, v in LESION_DEFAULTS.items()):
         parser.error('--lesion_dilation, --lesion_min_voxels and --lesion_penalty_mm must not be negative')
+    if not hasattr(args, 'window') and any(hasattr(args, k) for k in WINDOW_DEFAULTS):
+        parser.error('--window_overlap, --window_mode and --window_batch need --window')
+    if not 0 <= getattr(args, 'window_overlap', 0.5) < 1:
+        parser.error('--window_overlap must lie in [0, 1)')
+    if getattr(args, 'window_batch', 1) < 1:
+        parser.error('--window_batch must be positive')
     if args.skull_largest_component and not args.skull_model:
         parser.error('--skull_largest_component needs --skull_model')
     args.modalities = args.modalities.split(',')
@@ -197,8 +233,15 @@ def load_stage(folder, prepro, args, shape_1mm):
     _, mean, std = load_prepro(prepro)
     if mean.size != kw['in_ch']:
         raise ValueError('%s holds statistics of %d channels, the model of %s takes %d' % (prepro, mean.size, folder, kw['in_ch']))
+    window = window_kwargs(args)
+    if window is not None:
+        if window['roi'] == 'crop':
+            if not crop:
+                raise ValueError('--window crop: the train_args.pkl of %s records no crop_size; give --window D,H,W' % folder)
+            window['roi'] = tuple(int(s) for s in crop)
+        window = WindowSpec(**window)
     return StageSpec(model, mean, std, res, spatial_tta=args.spatial_tta, channel_tta=args.channel_tta, threshold=args.threshold,
-                     compute_dtype=args.dtype, tta_batch=args.tta_batch)
+                     compute_dtype=args.dtype, tta_batch=args.tta_batch, window=window)
 
 
 def postprocess_kwargs(args):
@@ -216,6 +259,16 @@ def lesion_kwargs(args):
     return {'dilation': getattr(args, 'lesion_dilation', LESION_DEFAULTS['lesion_dilation']),
             'min_lesion_voxels': getattr(args, 'lesion_min_voxels', LESION_DEFAULTS['lesion_min_voxels']),
             'penalty_mm': getattr(args, 'lesion_penalty_mm', LESION_DEFAULTS['lesion_penalty_mm'])}
+
+
+def window_kwargs(args):
+    """-> the keyword arguments of infer.WindowSpec the flags ask for ('roi' may still be 'crop': load_stage resolves it per model), None
+    without --window"""
+    if getattr(args, 'window', None) is None:
+        return None
+    return {'roi': args.window, 'overlap': getattr(args, 'window_overlap', WINDOW_DEFAULTS['window_overlap']),
+            'mode': getattr(args, 'window_mode', WINDOW_DEFAULTS['window_mode']),
+            'batch': getattr(args, 'window_batch', WINDOW_DEFAULTS['window_batch'])}
 
 
 def require_gpu():
@@ -290,6 +343,7 @@ def run(args):
     largest = bool(getattr(args, 'skull_largest_component', False))
     lesion = lesion_kwargs(args)
     lesionwise = lesion is not None
+    windowed = window_kwargs(args) is not None
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
     for (name, path), case in zip(cases, _decoded(cases, args)):
@@ -315,6 +369,10 @@ def run(args):
             counts.update({'brain_' + k: v for k, v in (st.get('brain_counts') or {}).items()})
             cleaned.append((name, counts))
             print('{}. Post-processing: {}'.format(name, ', '.join('%s %d' % kv for kv in sorted(counts.items()))), flush=True)
+        if windowed:
+            print('{}. Windows run (skipped as empty): {}'.format(name, '. '.join(
+                '%s %d (%d)' % ((what,) + stage.window_counts) for what, stage in (('skull', skull), ('tumor', tumor)) if stage is not None)),
+                flush=True)
         s = None
         if y is not None:
             s = label_scores(y, lab, N_CLASSES)

@@ -384,6 +384,36 @@ int bts_lesion_crop(const int* td_comp, const uint8_t* truth, const int* pred_co
                     int h0, int w0, int d1, int h1, int w1, int td_root, const int* roots, int nroots, uint8_t* g, uint8_t* m,
                     bts_stream_t stream);
 
+/* ===== sliding-window inference with blended overlapping windows (the windowed form of test.py:128-148 and :164-178) =====
+ * A launch carries B jobs, 1 <= B <= bts_window_batch_max(); a job is one augmented copy of one window: starts (3B HOST ints, (z0,y0,x0)
+ * per job, each inside the volume; a window may hang over the volume's end), flips (B HOST ints, bits 4|2|1 = D|H|W as in bts_flip_affine).
+ * The job table travels by value in the kernel arguments.  All tensors dense fp32, channels innermost.  BTS_ERR_SHAPE, before any HIP
+ * call, for a non-positive extent, flip bits above 7, a start < 0 or >= its extent, a NULL table; BTS_ERR_UNSUPPORTED for B outside the cap. */
+long bts_window_batch_max(void);
+/* The input side of a windowed forward (test.py:164-178 pad, :107 normalise, :128-148 tf.reverse, for windows): from x (D,H,W,C),
+ * out (B,R0,R1,R2,C): out[b, fd(d), fh(h), fw(w), c] = (v - mean[b,c]) / stdv[b,c] with v = x[z0+d, y0+h, x0+w, c] inside the volume and
+ * v = 0 beyond its end (the raw intensities are padded BEFORE they are normalised, test.py:107,175: the overhang holds -mean/std).
+ * mean, stdv: B*C HOST floats, a pair per job (channel TTA moves them per copy).  C <= 16 (BTS_ERR_UNSUPPORTED above).  Every element of
+ * out is written; the window is read once per job. */
+int bts_window_gather(const float* x, float* out, int D, int H, int W, int C, int R0, int R1, int R2, int B, const int* starts,
+                      const int* flips, const float* mean, const float* stdv, bts_stream_t stream);
+/* The output side (test.py:139-151 un-flip and average, with a window's importance): pred (B,R0,R1,R2,K) the network's output for the
+ * jobs, still flipped; acc (D,H,W,K); nz (n0,R0), ny (n1,R1), nx (n2,R2) the normalised per-axis importance tables of
+ * bts_amd.infer.window_plan on the device; rows (3B HOST ints): the table rows (iz,iy,ix) of each job's window.  For every voxel of a
+ * job's window inside the volume: acc[z0+d, y0+h, x0+w, k] += ((scale * nz[iz][d]) * ny[iy][h]) * nx[ix][w] * pred[b, fd(d), fh(h), fw(w), k].
+ * Owner computes: one thread owns an accumulator voxel, adds the jobs that hold it in list order and writes it once; no atomics, no race
+ * between overlapping jobs, products and sums never contracted: one launch of B jobs gives the bits of B launches of one job.  Voxels
+ * outside every window of the launch are not written.  BTS_ERR_UNSUPPORTED when acc and pred share memory; BTS_ERR_SHAPE also for a
+ * table row outside its table. */
+int bts_window_accumulate(const float* pred, float* acc, const float* nz, const float* ny, const float* nx, int n0, int n1, int n2, int D,
+                          int H, int W, int K, int R0, int R1, int R2, int B, const int* starts, const int* flips, const int* rows,
+                          float scale, bts_stream_t stream);
+/* counts (n0*n1*n2 int32 on the device, zeroed by the call, window (iz,iy,ix) at (iz n1 + iy) n2 + ix) = the voxels with mask > 0 inside
+ * each window of the plan, clipped to the volume: a window that counts 0 lies on voxels bts_tta_finish zeroes (test.py:154-155) and need
+ * not be run.  mask (D,H,W) fp32; starts: n0+n1+n2 int32 ON THE DEVICE, the z, then y, then x starts.  Integer atomics: exact. */
+int bts_window_occupancy(const float* mask, const int* starts, int* counts, int n0, int n1, int n2, int D, int H, int W, int R0, int R1,
+                         int R2, bts_stream_t stream);
+
 /* ===== training-time augmentation on the device (train.py:14-49) ===== */
 /* per-channel mean / population variance of a (nvox, C) tensor with voxel stride ld (tf.nn.moments, train.py:18);
  * C <= 16; mean may be NULL; fp64 partials of x minus the first voxel's value (no cancellation against the mean: a constant volume
