@@ -222,6 +222,9 @@ def draw_intensity(gen, cfg, c):
     return IntensityDraw(params, (int(key[0]), int(key[1])))
 
 
+TARGETS = ('labels', 'regions')
+
+
 class _Dataset(object):
     """re-iterable epoch of (x, y) device batches.  Data parallel: every rank draws the SAME permutation from
     the shared shuffle generator and keeps positions rank, rank+world, ... of it, truncated to len // world examples so
@@ -245,12 +248,21 @@ class _Dataset(object):
     intensity (an IntensityConfig, or None: nothing below happens and not one extra value is drawn): draw_intensity() follows draw()
     and draw_spatial(), on the same generator, and both paths run bts_intensity_batch on what the augment launch returned (the
     per-example path with N = 1, channels last).  Its result depends neither on N nor on the layout, so the batches are again the
-    same on either path."""
+    same on either path.
+
+    targets ('labels': nothing below happens): with 'regions' the label batch goes through bts_region_targets right after the augment
+    launch (before the intensity stage, which does not touch y), so y holds the nested BraTS regions (WT, TC, ET) in place of the
+    disjoint one-hot labels.  No value is drawn for it: x and the generator states are those of 'labels'."""
 
     channels_first = False
 
     def __init__(self, files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, device, rank=0, world=1,
-                 resident_bytes=0, workers=0, spatial=None, intensity=None):
+                 resident_bytes=0, workers=0, spatial=None, intensity=None, targets='labels'):
+        if targets not in TARGETS:
+            raise ValueError('unknown targets %r: one of %s' % (targets, TARGETS))
+        if targets == 'regions' and int(out_ch) != 3:
+            raise ValueError("targets='regions' are the three BraTS regions WT, TC, ET: out_ch must be 3, got %r" % (out_ch,))
+        self.targets = targets
         self.files, self.batch_size, self.prepro_size = files, int(batch_size), tuple(prepro_size)
         self.crop_size, self.out_ch, self.shuffle = tuple(crop_size), int(out_ch), shuffle
         self.rank, self.world = int(rank), max(1, int(world))
@@ -311,6 +323,8 @@ class _Dataset(object):
                 sd = draw_spatial(self.gen, self.spatial, self.crop_size)
                 xa, ya = self._augment_spatial([(x, y, ops.channel_moments(x)[1])], [dr], [sd], False)
                 xa, ya = xa[0], ya[0]
+            if self.targets == 'regions':
+                ops.region_targets(ya)
             if self.intensity is not None:
                 idr = draw_intensity(self.gen, self.intensity, c)
                 ops.intensity_batch(xa.unsqueeze(0), [idr.params], [idr.key], False)
@@ -385,10 +399,14 @@ class _Dataset(object):
 
     def _augment(self, batch, draws, sdraws=()):
         if self.spatial is not None:
-            return self._augment_spatial(batch, draws, sdraws, self.channels_first)
-        return ops.augment_batch([b[0] for b in batch], [b[1] for b in batch], [b[2] for b in batch], self.crop_size,
-                                 [dr.offsets for dr in draws], [dr.flip_mask for dr in draws], [dr.shift for dr in draws],
-                                 [dr.scale for dr in draws], self.out_ch, self.channels_first)
+            xy = self._augment_spatial(batch, draws, sdraws, self.channels_first)
+        else:
+            xy = ops.augment_batch([b[0] for b in batch], [b[1] for b in batch], [b[2] for b in batch], self.crop_size,
+                                   [dr.offsets for dr in draws], [dr.flip_mask for dr in draws], [dr.shift for dr in draws],
+                                   [dr.scale for dr in draws], self.out_ch, self.channels_first)
+        if self.targets == 'regions':
+            ops.region_targets(xy[1], self.channels_first)
+        return xy
 
 
 class _ChannelsFirstDataset(_Dataset):
@@ -401,13 +419,16 @@ class _ChannelsFirstDataset(_Dataset):
 
 
 def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=True, data_format='channels_last', seed=0,
-                    device=None, rank=None, world=None, resident_bytes=0, workers=0, spatial=None, intensity=None):
+                    device=None, rank=None, world=None, resident_bytes=0, workers=0, spatial=None, intensity=None,
+                    targets='labels'):
     """-> (re-iterable dataset of (x, y) device batches, number of examples)   [train.py:12-64]
     rank / world default to the process group's (one shard of the examples per rank, see _Dataset).
     resident_bytes: budget of example bytes kept on the device after their first read; workers: host threads reading ahead
     (see _Dataset; the batches do not depend on either).  spatial: a SpatialConfig (rotation, zoom and elastic deformation of the
     crops, on the device in the same launch) or None, which leaves every draw and every batch as it was.  intensity: an
-    IntensityConfig (noise, blur, brightness, contrast and gamma on the augmented batch, on the device) or None, likewise."""
+    IntensityConfig (noise, blur, brightness, contrast and gamma on the augmented batch, on the device) or None, likewise.
+    targets: 'labels' (y = one-hot labels minus the background, as the reference trains) or 'regions' (y = the nested BraTS regions
+    WT, TC, ET: bts_region_targets on the label batch; out_ch must be 3); x and every draw are the same in both."""
     if data_format not in ('channels_last', 'channels_first'):
         raise ValueError('unknown data_format %r' % (data_format,))
     from . import parallel
@@ -417,4 +438,4 @@ def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=Tru
     dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
     cls = _Dataset if data_format == 'channels_last' else _ChannelsFirstDataset
     return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world, resident_bytes, workers, spatial,
-               intensity), len(files)
+               intensity, targets), len(files)

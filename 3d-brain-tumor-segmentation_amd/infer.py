@@ -36,7 +36,12 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
     `WindowSpec` the `TestTimeAugmentor` predicts windows of the training crop instead and blends them with a Gaussian importance map,
     as nnU-Net and MONAI's sliding_window_inference do (`window_plan`; bts_window_gather, bts_window_accumulate, bts_window_occupancy),
     off by default.
-All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_spline_prefilter3d, bts_zoom3d,
+  * the reference trains its per-channel sigmoids on disjoint one-hot labels and decodes an arg-max (train.py:38-41, test.py:259-261),
+    although its model is the paper's, whose three channels are the nested regions; with `targets='regions'` (a network trained by
+    `python -m bts_amd.train --targets regions`) the channels are read as WT, TC, ET and decoded by the overwrite rule of the usual
+    BraTS conversions, 4 where et >= threshold, else 1 where tc >= threshold, else 2 where wt >= threshold (bts_region_finish), to the
+    same {0,1,2,4} map everything downstream takes; 'labels', the default, is the arg-max as before.
+All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_region_finish, bts_spline_prefilter3d, bts_zoom3d,
 bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, bts_components3d, bts_component_sizes,
 bts_component_largest, bts_components_apply, bts_region_relabel, bts_dilate3d, bts_lesion_pairs, bts_component_boxes, bts_lesion_crop, the
 model forward).
@@ -48,6 +53,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .data import TARGETS      # ('labels', 'regions'): disjoint labels decoded by an arg-max | the nested regions WT, TC, ET
 from .tape import Tensor
 
 
@@ -78,6 +84,20 @@ def augment_axes(spatial_tta=True):
 
 
 WINDOW_MODES = ('gaussian', 'constant')
+
+
+def _finish_of(targets, model=None):
+    """the probabilities -> (masked probabilities, label map) call of a target encoding: ops.tta_finish | ops.region_finish"""
+    if targets not in TARGETS:
+        raise ValueError('unknown targets %r: one of %s' % (targets, TARGETS))
+    if targets == 'labels':
+        return ops.tta_finish
+    if model is not None:
+        out_ch = getattr(getattr(model, 'decoder', None), 'out_ch', None)
+        if out_ch != 3:
+            raise ValueError("targets='regions' reads the output channels as the three BraTS regions WT, TC, ET; the model has "
+                             'out_ch = %r' % (out_ch,))
+    return ops.region_finish
 
 
 def _window_axis(extent, window, overlap, mode, sigma_scale):
@@ -158,9 +178,12 @@ class TestTimeAugmentor(object):
     __test__ = False  # not a pytest class
 
     def __init__(self, mean, std, model, model_data_format='channels_last', spatial_tta=True, channel_tta=0, threshold=0.5,
-                 seed=0, compute_dtype='float32', tta_batch=None, window=None):
+                 seed=0, compute_dtype='float32', tta_batch=None, window=None, targets='labels'):
         """compute_dtype: 'float32' (the engine's parity path) | 'float16' | 'bfloat16' -- 16-bit STORAGE of activations and
-        weight images with fp32 sums (bts_amd.lowp; BASELINE configs[4] runs the forwards in fp16)"""
+        weight images with fp32 sums (bts_amd.lowp; BASELINE configs[4] runs the forwards in fp16)
+        targets: 'labels' | 'regions' -- how the mean probabilities are decoded (`_finish_of`); the probabilities do not depend on it"""
+        self._finish = _finish_of(targets, model)
+        self.targets = targets
         if model_data_format not in ('channels_last', 'channels_first'):
             raise ValueError('unknown data_format %r' % (model_data_format,))
         self.model = model
@@ -231,7 +254,7 @@ class TestTimeAugmentor(object):
                     ops.flip_affine(yt[i:i + 1], flip, scale=1.0 / count, out=acc, accumulate=True)
         self._prob = acc
         self._mask = bmask.unsqueeze(0).to(torch.float32).contiguous()
-        y, _ = ops.tta_finish(acc, self._mask, self.threshold, want_probabilities=True, want_labels=False)
+        y, _ = self._finish(acc, self._mask, self.threshold, want_probabilities=True, want_labels=False)
         return y[0].permute(3, 0, 1, 2) if self.model_data_format == 'channels_first' else y[0]   # (test.py:112-114: the model's layout)
 
     def _call_windowed(self, x, bmask):
@@ -289,27 +312,28 @@ class TestTimeAugmentor(object):
         acc = acc.unsqueeze(0)
         self._prob = acc
         self._mask = mask.unsqueeze(0)
-        y, _ = ops.tta_finish(acc, self._mask, self.threshold, want_probabilities=True, want_labels=False)
+        y, _ = self._finish(acc, self._mask, self.threshold, want_probabilities=True, want_labels=False)
         return y[0].permute(3, 0, 1, 2) if self.model_data_format == 'channels_first' else y[0]
 
     def labels(self):
-        """uint8 label map (D,H,W) of the last call: argmax+1, >=3 -> 4, 0 = background / masked / below threshold"""
-        _, lab = ops.tta_finish(self._prob, self._mask, self.threshold, want_probabilities=False, want_labels=True)
+        """uint8 label map (D,H,W) of the last call: argmax+1, >=3 -> 4, 0 = background / masked / below threshold; with
+        targets='regions' 4 where et >= threshold, else 1 where tc, else 2 where wt, else 0"""
+        _, lab = self._finish(self._prob, self._mask, self.threshold, want_probabilities=False, want_labels=True)
         return lab[0]
 
 
 def segment_volume(model, x, mask, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
-                   window=None):
+                   window=None, targets='labels'):
     """test.py:246-261 for one volume: pad to the model's spatial resolution, TTA inference, crop back.
     x (D,H,W,C), mask (D,H,W,1) channels_last (test.py:109) -> (probabilities, uint8 labels (D,H,W)); the probabilities are
     (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  window: a WindowSpec -> the padded volume
-    is predicted in blended windows of that extent"""
+    is predicted in blended windows of that extent; targets: 'labels' | 'regions', the decode of the label map (TestTimeAugmentor)"""
     if window is not None:
         window.check_resolution(spatial_res)
     xp, mp, orig = pad_to_spatial_res(spatial_res, x, mask)
     df = getattr(model, 'data_format', 'channels_last')
     tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch, window=window)
+                            tta_batch=tta_batch, window=window, targets=targets)
     y = tta(xp, mp)
     lab = tta.labels()
     y = y[:, :orig[0], :orig[1], :orig[2]] if df == 'channels_first' else y[:orig[0], :orig[1], :orig[2]]
@@ -388,10 +412,12 @@ class Interpolator(object):
         self.affine = np.mean(affine, axis=0, dtype=np.float32)
         return self.resample(np.stack(image, axis=-1), self.pixdim[1:4], pad_res=pad_res)
 
-    def reverse(self, prob, mask=None, path=None, threshold=0.5):
+    def reverse(self, prob, mask=None, path=None, threshold=0.5, targets='labels'):
         """prob (D1,H1,W1,K): cropped probability map on the 1 mm^3 grid, mask (D1,H1,W1,1) (default: the last resample's)
         -> (probabilities (D,H,W,K), uint8 labels (D,H,W)) on the scan's native grid; with `path`, writes mask.nii there
-        (test.py:69-70) with the affine averaged in __call__ (identity if the scan came through resample())"""
+        (test.py:69-70) with the affine averaged in __call__ (identity if the scan came through resample()).  targets: 'labels' (the
+        arg-max of bts_tta_finish) | 'regions' (K == 3, the decode of bts_region_finish), taken on the native grid either way"""
+        finish = _finish_of(targets)
         if self.native_shape is None:
             raise RuntimeError('Interpolator.reverse: no scan has been resampled yet')
         mask = self.mask if mask is None else mask
@@ -400,7 +426,7 @@ class Interpolator(object):
         if not all(f == 1.0 for f in self.factors):
             p = self._zoom(p, self.native_shape, self.order)
             m = self._zoom(m, self.native_shape, 0)
-        y, lab = ops.tta_finish(p.unsqueeze(0), m.unsqueeze(0), threshold)
+        y, lab = finish(p.unsqueeze(0), m.unsqueeze(0), threshold)
         y, lab = y[0], lab[0]
         if path is not None:
             from . import nifti
@@ -409,18 +435,18 @@ class Interpolator(object):
 
 
 def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
-                 order=3, window=None):
+                 order=3, window=None, targets='labels'):
     """test.py:235-264 for one scan: resample to 1 mm^3 with mask and padding in one pass, TTA inference, crop, resample back.
     image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz) -> (probabilities, uint8 labels (D,H,W)) on that grid; the probabilities
     are (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  With pixdim (1,1,1) this is
-    segment_volume with the reference's mask, bit for bit.  window: a WindowSpec, as in segment_volume."""
+    segment_volume with the reference's mask, bit for bit.  window: a WindowSpec, targets: 'labels' | 'regions', as in segment_volume."""
     if window is not None:
         window.check_resolution(spatial_res)
     interp = Interpolator(None, order=order)
     xp, mp, orig = interp.resample(image, pixdim, pad_res=spatial_res)
     df = getattr(model, 'data_format', 'channels_last')
     tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch, window=window)
+                            tta_batch=tta_batch, window=window, targets=targets)
     y = tta(xp, mp)
     if all(f == 1.0 for f in interp.factors):
         lab = tta.labels()
@@ -428,7 +454,7 @@ def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True,
         return y, lab[:orig[0], :orig[1], :orig[2]]
     if df == 'channels_first':
         y = y.permute(1, 2, 3, 0)
-    y, lab = interp.reverse(y[:orig[0], :orig[1], :orig[2]], threshold=threshold)
+    y, lab = interp.reverse(y[:orig[0], :orig[1], :orig[2]], threshold=threshold, targets=targets)
     return (y.permute(3, 0, 1, 2) if df == 'channels_first' else y), lab
 
 
@@ -437,9 +463,13 @@ class StageSpec(object):
     once and kept: the 16-bit engine packs its weight images on the first forward"""
 
     def __init__(self, model, mean, std, spatial_res, spatial_tta=True, channel_tta=0, threshold=0.5, compute_dtype='float32',
-                 tta_batch=None, largest_component=False, window=None):
+                 tta_batch=None, largest_component=False, window=None, targets='labels'):
         """largest_component: for a skull-stripping stage, keep only the largest connected piece of the brain it finds (segment_case);
-        window: a WindowSpec -> this stage predicts blended windows of that extent (a multiple of spatial_res per axis)"""
+        window: a WindowSpec -> this stage predicts blended windows of that extent (a multiple of spatial_res per axis);
+        targets: 'labels' | 'regions' -- what the tumour model was trained on (train_args.pkl's `targets`), i.e. how segment_case
+        decodes its label map; a skull-stripping stage (out_ch == 1) is always 'labels'"""
+        _finish_of(targets, model)
+        self.targets = targets
         if window is not None:
             window.check_resolution(spatial_res)
         self.window = window
@@ -469,7 +499,7 @@ class StageSpec(object):
         if self._tta is None:
             self._tta = TestTimeAugmentor(self.mean, self.std, self.model, self.data_format, spatial_tta=self.spatial_tta,
                                           channel_tta=self.channel_tta, threshold=self.threshold, compute_dtype=self.compute_dtype,
-                                          tta_batch=self.tta_batch)
+                                          tta_batch=self.tta_batch, targets=self.targets)
         self._tta.window = self.window if window is None else window
         return self._tta
 
@@ -562,7 +592,7 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
     if all(f == 1.0 for f in interp.factors):
         lab = tta.labels()[:orig[0], :orig[1], :orig[2]]
     else:
-        y, lab = interp.reverse(y, threshold=tumor.threshold)
+        y, lab = interp.reverse(y, threshold=tumor.threshold, targets=tumor.targets)
     if postprocess is not None:
         lab = lab.contiguous()
         stages['postprocess'] = postprocess_labels(lab, **postprocess)

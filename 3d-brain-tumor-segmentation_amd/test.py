@@ -48,7 +48,10 @@ Deviations:
   * each model is built at the crop size recorded in its train_args.pkl, as test.py:186-188 does, so that the checkpoint's
     VAE variables (tied to that extent, vae.py:101-111) load; a train_args.pkl without one builds at the first case's padded shape;
   * a case with a missing modality is reported by name and skipped (the reference's glob(...)[0] ends the run with an IndexError);
-  * the score is `infer.label_scores` (see bts_amd.infer on why the reference's call is not functional).
+  * the score is `infer.label_scores` (see bts_amd.infer on why the reference's call is not functional);
+  * a model trained with `python -m bts_amd.train --targets regions` (its train_args.pkl says so; there is no flag here) is decoded
+    as the nested regions WT, TC, ET (`infer.StageSpec(targets='regions')`, bts_region_finish) to the same {0,1,2,4} label map that
+    post-processing, `mask.nii` and every score take; any other model by the arg-max, as before.
 """
 import argparse
 import glob
@@ -218,7 +221,9 @@ def upload_case(case, dev):
 
 def load_stage(folder, prepro, args, shape_1mm):
     """checkpoint folder + prepro.npy -> StageSpec: the model rebuilt from train_args.pkl's model_args (args.py:250-260), built, filled
-    with load_checkpoint; spatial_res = 2 ** depth; mean / std from the prepro dump.  shape_1mm: the first case's extent on the
+    with load_checkpoint; spatial_res = 2 ** depth; mean / std from the prepro dump; `targets` (how the label map is decoded: the
+    arg-max of a network trained on labels, or the regions WT, TC, ET of one trained with --targets regions) from train_args.pkl too,
+    'labels' where it records none.  shape_1mm: the first case's extent on the
     1 mm^3 grid, the build shape (padded to the resolution) where train_args.pkl records no crop size"""
     from .model import Model
     targs = load_train_args(folder)
@@ -241,7 +246,7 @@ def load_stage(folder, prepro, args, shape_1mm):
             window['roi'] = tuple(int(s) for s in crop)
         window = WindowSpec(**window)
     return StageSpec(model, mean, std, res, spatial_tta=args.spatial_tta, channel_tta=args.channel_tta, threshold=args.threshold,
-                     compute_dtype=args.dtype, tta_batch=args.tta_batch, window=window)
+                     compute_dtype=args.dtype, tta_batch=args.tta_batch, window=window, targets=targs.get('targets', 'labels'))
 
 
 def postprocess_kwargs(args):

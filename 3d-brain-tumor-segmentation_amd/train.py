@@ -23,7 +23,10 @@ accepted and implied: there is no CPU path.  Added: --dtype (training AND valida
 the spatial augmentation of the TRAINING examples (add_spatial_arguments: --spatial_prob, --rotate_deg, --zoom_range, --elastic_sigma,
 --elastic_spacing; off by default, never applied to --val_loc; data.SpatialConfig), and their intensity augmentation
 (add_intensity_arguments: --intensity_aug and the --noise_*, --blur_*, --brightness_*, --contrast_* and --gamma_* flags; off by
-default, never applied to --val_loc; data.IntensityConfig).
+default, never applied to --val_loc; data.IntensityConfig), and --targets (add_target_arguments: `labels`, the default, trains the
+output channels on the disjoint labels as the reference does; `regions` trains them on the nested BraTS regions WT, TC, ET, for both
+datasets, and the Dice columns of train.log are then util.RegionDiceCoefficient's; the mode is stored in train_args.pkl, restored by
+--load_folder and read by `python -m bts_amd.test`).
 Examples are the `.npz` files `python -m bts_amd.preprocess` writes; with a process group in the environment (torchrun) every rank
 runs the command, takes its shard and rank 0 writes the files.
 
@@ -457,9 +460,18 @@ def add_intensity_arguments(p):
     return p
 
 
+def add_target_arguments(p):
+    """the flag of the target encoding (data.TARGETS), a group of its own like the augmentation ones"""
+    g = p.add_argument_group('target encoding')
+    g.add_argument('--targets', type=str, default='labels', choices=('labels', 'regions'),
+                   help='What the output channels are trained on: the disjoint labels 1, 2, 4 (the reference), or the nested BraTS '
+                        'regions whole tumour, tumour core, enhancing tumour (needs --out_ch 3).')
+    return p
+
+
 def full_parser():
-    """what the command parses: arg_parser() and the spatial and intensity augmentation groups"""
-    return add_intensity_arguments(add_spatial_arguments(arg_parser()))
+    """what the command parses: arg_parser() and the spatial augmentation, intensity augmentation and target groups"""
+    return add_target_arguments(add_intensity_arguments(add_spatial_arguments(arg_parser())))
 
 
 def _floats(text, counts, flag):
@@ -538,8 +550,12 @@ def parse_args(argv=None):
         for key in INTENSITY_KEYS[1:]:
             if key in chkpt_args:
                 setattr(args, key, chkpt_args[key])
+        args.targets = chkpt_args.get('targets', 'labels')                                                 # (an older pickle: labels)
     spatial_config(args)                      # (a bad range or probability is refused here, not at the first batch)
     intensity_config(args)
+    if args.targets == 'regions' and int(args.model_args['out_ch']) != 3:
+        raise ValueError('--targets regions trains the three BraTS regions WT, TC, ET: --out_ch must be 3, got %r' %
+                         (args.model_args['out_ch'],))
     if args.save_folder and int(os.environ.get('RANK', '0')) == 0:
         save_train_args(args.save_folder, vars(args))
     return args
@@ -549,7 +565,7 @@ def run(args):
     """the reference's train(args) (train.py:71-216) -> {'history': fit's rows, 'model', 'optimizer'}"""
     from . import data
     from .model import Model
-    from .util import DiceCoefficient, DiceVAELoss, ScheduledOptim
+    from .util import DiceCoefficient, DiceVAELoss, RegionDiceCoefficient, ScheduledOptim
     if not torch.cuda.is_available():
         raise RuntimeError('python -m bts_amd.train needs a GPU (no CPU fallback exists for the product path)')
     parallel.init_from_env()
@@ -559,6 +575,7 @@ def run(args):
     else:
         resident = int(args.resident_gb * 1e9)
     sets = []
+    targets = getattr(args, 'targets', 'labels')
     spatial, intensity = spatial_config(args), intensity_config(args)
     train_extra = {} if spatial is None else {'spatial': spatial}
     if intensity is not None:
@@ -566,7 +583,7 @@ def run(args):
     for loc, shuffle, extra in ((args.train_loc, True, train_extra), (args.val_loc, False, {})):
         sets.append(data.prepare_dataset(loc, args.batch_size, args.prepro_size, args.crop_size, args.model_args['out_ch'],
                                          shuffle=shuffle, data_format=args.data_format, seed=args.seed, device=dev,
-                                         resident_bytes=resident, workers=args.workers, **extra))
+                                         resident_bytes=resident, workers=args.workers, targets=targets, **extra))
     (train_data, n_train), (val_data, n_val) = sets
     print('{} training examples.'.format(n_train), flush=True)
     print('{} validation examples.'.format(n_val), flush=True)
@@ -579,7 +596,7 @@ def run(args):
         parallel.broadcast_parameters(model)
     print('Total number of parameters: {}'.format(int(model.n_params)), flush=True)
     loss_fn = DiceVAELoss(data_format=args.data_format)
-    dice_fn = DiceCoefficient(data_format=args.data_format)
+    dice_fn = (RegionDiceCoefficient if targets == 'regions' else DiceCoefficient)(data_format=args.data_format)
     history = fit(model, optimizer, loss_fn, dice_fn, train_data, val_data, args.n_epochs, patience=args.patience,
                   save_folder=args.save_folder or None, log=lambda s: print(s, flush=True), compute_dtype=args.dtype,
                   eval_dtype=args.dtype)

@@ -77,6 +77,30 @@ class DiceCoefficient(object):
         return Tensor(out[0:1], requires_grad=False), Tensor(out[1:2], requires_grad=False)
 
 
+class RegionDiceCoefficient(object):
+    """Hard Dice of the nested BraTS regions, for a network trained with targets='regions' (channels WT, TC, ET; no reference
+    counterpart).  The call signature and return of DiceCoefficient: (macro, micro) as 1-element Tensors by the same two formulae
+    (util.py:54-55), macro = mean_r (2 I_r + 1) / (P_r + T_r + 1), micro = sum I / (sum P + sum T), with P_r = #(p_r > 0.5), T_r =
+    #(t_r > 0.5) and ONE cell per region in either data format.  .last_labels: the decoded map of the last call (uint8; 3 = ET over
+    1 = TC over 2 = WT over 0, the overwrite rule of ops.region_finish in DiceCoefficient's coding)."""
+
+    def __init__(self, name='region_dice', data_format='channels_last'):
+        if data_format not in ('channels_last', 'channels_first'):
+            raise ValueError('unknown data_format %r' % (data_format,))
+        self.name = name
+        self.data_format = data_format
+        self.last_labels = None
+
+    def __call__(self, y_true, y_pred):
+        y_true, y_pred = as_tensor(y_true, data_format=self.data_format), as_tensor(y_pred, data_format=self.data_format)
+        w, c = y_pred.shape[3], y_pred.shape[4]
+        table, labels = ops.region_dice_sums(y_true.t, y_pred.t, True)
+        parallel.all_reduce_sum(table)
+        out = ops.dice_metric_value(table, w, c, False)
+        self.last_labels = labels
+        return Tensor(out[0:1], requires_grad=False), Tensor(out[1:2], requires_grad=False)
+
+
 class ScheduledOptim(object):
     """Keras Adam with a per-epoch polynomial schedule (util.py:60-84): optimizer(epoch) sets
     lr = init_lr*(1-epoch/n_epochs)**0.9; apply_gradients() is the TF-form update (epsilon un-corrected),

@@ -506,6 +506,32 @@ long bts_intensity_blur_weights(float sigma, float* weights);
 int bts_intensity_batch(float* x, int N, int T0, int T1, int T2, int C, int layout, const int* flags, const float* params,
                         const uint32_t* keys, void* workspace, long workspace_bytes, bts_stream_t stream);
 
+/* ===== the nested BraTS regions as targets and as the decoded prediction (no reference counterpart: train.py:38-41 trains its
+ * per-channel sigmoids on disjoint one-hot labels, test.py:259-261 decodes an arg-max) =====
+ * Channels are (WT, TC, ET) = labels {1,2,4}, {1,4}, {4}, the order of bts_amd.infer.BRATS_REGIONS.  All three calls are single streaming
+ * passes defined for C == 3 only: another C returns BTS_ERR_UNSUPPORTED, a non-positive extent or a voxel stride below C BTS_ERR_SHAPE,
+ * both before any HIP call.  A channels-last voxel is 12 bytes: a lane takes four voxels as three 16-byte accesses where the base
+ * pointers are 16-byte aligned, the last (voxels mod 4) voxels and unaligned views (a batch inside a larger buffer) go voxel by voxel;
+ * the results do not depend on the path. */
+/* y, the dense label batch bts_augment_crop / bts_augment_batch / bts_augment_spatial_batch wrote (one-hot minus the background), IN
+ * PLACE: (l1, l2, l3) -> ((l1 + l2) + l3, l1 + l3, l3).  channels_first 0: (N, V, 3); 1: (N, 3, V), V the voxels of one example; 16-byte
+ * accesses along the planes of every example whose three plane starts are aligned.  A NULL y is BTS_ERR_SHAPE. */
+int bts_region_targets(float* y, int N, long V, int C, int channels_first, bts_stream_t stream);
+/* the hard Dice counts of the regions: per region r, P_r = #(p_r > 0.5), T_r = #(t_r > 0.5), I_r = # of voxels where both hold;
+ * table[3r + 0..2] = (I_r, P_r, T_r) as doubles (zeroed by the call): what bts_dice_metric_value(table, out, W, 3, 0) reduces, one cell
+ * per region, to macro = mean_r (2 I_r + 1) / (P_r + T_r + 1) and micro = sum I / (sum P + sum T) (util.py:54-55).  y_true, y_pred: NV
+ * voxels, channel stride 1, voxel strides ldt, ldp.  Counted in integer registers, summed over wave and workgroup, one add per
+ * workgroup and entry: integers below 2^53, so the table is exact and bit-identical from run to run.  labels (NV uint8, or NULL): the
+ * decode of bts_region_finish with p > 0.5 in the coding of bts_dice_metric_sums' map: 0, 1, 2, and 3 (not 4) for ET. */
+int bts_region_dice_sums(const float* y_true, const float* y_pred, uint8_t* labels, double* table, long NV, int C, int ldt, int ldp,
+                         bts_stream_t stream);
+/* the counterpart of bts_tta_finish for a network trained on regions: y = prob * bmask and/or the label map by the overwrite rule of
+ * the BraTS conversions, on the masked probabilities: 4 if et >= threshold, else 1 if tc >= threshold, else 2 if wt >= threshold, else
+ * 0, and 0 wherever bmask == 0.  Deliberately NOT the nested rule (ET only inside TC inside WT).  decode(encode(L)) = L for every map L
+ * over {0,1,2,4}.  prob, y: dense (nvox, 3); bmask: one float per voxel; y and labels may each be NULL. */
+int bts_region_finish(const float* prob, const float* bmask, float* y, uint8_t* labels, long nvox, int C, float threshold,
+                      bts_stream_t stream);
+
 /* ===== dataset preprocessing on the device (preprocess.py:17-131: create_dataset, compute_norm, main) =====
  * Dense fp32 (S0,S1,S2,C) volumes, C innermost, 1 <= C <= 16.  A crop window (T0,T1,T2,C) of such a volume is addressed in place:
  * `xwin` points at its origin, st0 / st1 are the element strides of the two outer axes, the voxel stride is C. */
