@@ -847,36 +847,38 @@ static int plan_wgrad(WgradPlan& pl, int ntaps, int s, int neg, int N, int Dp, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Weight gradient of the 3x3x3 stride-1 convolution in Winograd form (F(2x2,3x3) over (z,y), x direct) -- the counterpart of
-// conv_wino.hip for  dW[kz,ky,kx,c,k] = sum_v P[v + (kz-1,ky-1,kx-1)][c] * Q[v][k]:
-//   dU[dx][xi] = sum over 2x2 (z,y) patches and x' of  V[xi](c; x') * T[xi](k; x' - dx + 1),
-//   V = B^T d B (the forward's input transform, of P),  T = A dY A^T (of Q),  dg[.,.,dx] = G^T dU[dx] G.
-// 48 accumulator tiles (3 x taps x 16 transform points) instead of 27, each fed a quarter as often: 12/27 of the matrix
-// instructions.  The contraction runs over voxels, so channels sit on the lanes; for packed transforms every lane handles 4
-// consecutive x of its channel: the LDS tiles are x-fastest ([row][channel][x], transposed while staging; the P rows have
-// their 16-byte cells XOR-swizzled by (c >> 2) & 3 instead of padding).  Lanes 0-31 / 32-63 take two neighbouring x quads =
-// the two voxels of an MFMA's K = 2, so one ds_read_b128 feeds four matrix instructions per (x tap, point).  The x tap only
-// selects WHICH register of a 12-wide T window is the B operand (window value 5 + j - dx): V is formed once for all three taps.
-// 4 waves = the 4 xi_z, each 3 taps x 4 xi_y = 12 accumulators (192 registers), one wave per SIMD; sub-tile 16 x 4 x 2 as
-// the direct kernel's, so plan, partial layout ([27 taps][32][32] per workgroup, written after an in-LDS combine of the
-// waves) and finalize kernels are shared.  Bias partials: wave 1 holds all four Q rows of a patch anyway.
+// Weight gradient of the 3x3x3 stride-1 convolution in Winograd form with all three axes transformed, F(2x2x2, 3x3x3) -- the
+// counterpart of conv_wino3.hip for  dW[kz,ky,kx,c,k] = sum_v P[v + (kz-1,ky-1,kx-1)][c] * Q[v][k]:
+//   dW = (G^T x G^T x G^T) sum over 2x2x2 patches of  [ (B^T x B^T x B^T) P_4x4x4 ] o [ (A x A x A) Q_2x2x2 ]
+// (B^T, G, A^T as in conv_wino3.hip's header; P = x with a one-voxel halo, Q = dy).  64 accumulator tiles, each fed one
+// patch = 8 voxels at a time: 8/27 of the direct form's matrix instructions.  The contraction runs over patches, so channels
+// sit on the lanes.  4 waves = the 4 xi_z, each 16 accumulators (xi_y, xi_x) = 256 registers, one wave per SIMD.
+// Lane = (channel, patch parity): the K = 2 of an instruction is two x-neighbouring patches, so the sub-tile 16 x 4 x 2 = 16
+// patches (the direct kernel's: plan, partial layout [27 taps][32][32] per workgroup and finalize kernels are shared) is 8 steps
+// of 16 matrix instructions.  LDS tiles are x-fastest, [row][channel][18], transposed while staging: P rows hold x = -1..16, Q
+// rows x = 0..15 (+2 unused).  A lane's four x inputs of a patch are two 8-byte reads at an 8-byte-aligned offset; the row
+// stride of 18 floats sends the 32 channels of a half wave to 32 distinct bank pairs ((9 c) mod 32 is a permutation):
+// conflict-free.  Staging slots run channel quad fastest, then x: a wave's 16-byte loads are contiguous in memory and its
+// transposing 4-byte LDS writes hit banks 8 cq + x (8 x 8 distinct).  The z combination is taken per wave in registers, then y
+// and x; xi = 3 of Q carries +q1 for the true -q1 on every axis, undone where G^T is applied (in the wave for y and x, across
+// the waves through LDS for z).  Every step is branch-free: the next sub-tile's loads go through a descriptor that is empty
+// behind the workgroup's last sub-tile.  Bias partials: the all-sum point of Q (xi = 1 on every axis, wave 1).
 // ---------------------------------------------------------------------------------------------------------------------
 typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ wg_f32x2 wgw_pk_add(wg_f32x2 a, wg_f32x2 b) { wg_f32x2 d; asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ wg_f32x2 wgw_pk_sub(wg_f32x2 a, wg_f32x2 b) { wg_f32x2 d; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ wg_f32x2 wgw_pk_fma(wg_f32x2 a, wg_f32x2 b, wg_f32x2 c) { wg_f32x2 d; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
-__device__ __forceinline__ f32x4 wgw_add4(f32x4 a, f32x4 b) { const wg_f32x2 lo = wgw_pk_add(a.xy, b.xy), hi = wgw_pk_add(a.zw, b.zw); return f32x4{lo.x, lo.y, hi.x, hi.y}; }
-__device__ __forceinline__ f32x4 wgw_sub4(f32x4 a, f32x4 b) { const wg_f32x2 lo = wgw_pk_sub(a.xy, b.xy), hi = wgw_pk_sub(a.zw, b.zw); return f32x4{lo.x, lo.y, hi.x, hi.y}; }
-__device__ __forceinline__ f32x4 wgw_fma4(f32x4 a, wg_f32x2 s, f32x4 c) { const wg_f32x2 lo = wgw_pk_fma(a.xy, s, c.xy), hi = wgw_pk_fma(a.zw, s, c.zw); return f32x4{lo.x, lo.y, hi.x, hi.y}; }
+// (a.x + b.y, a.x - b.y)
+__device__ __forceinline__ wg_f32x2 wgw_pk_addsub(wg_f32x2 a, wg_f32x2 b) { wg_f32x2 d; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ float wgw_acc_rd(float a) { float v; asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a)); return v; }
 
-#define WGW_QSTR 28                          /* floats per (row, channel) of the Q tile: x = -1..16 at entries 3..20 */
-#define WGW_PTILE (24 * 32 * 16)             /* 4 z-rows x 6 y-rows */
-#define WGW_QTILE (8 * 32 * WGW_QSTR)        /* 2 z-rows x 4 y-rows */
-#define WGW_BUF (WGW_PTILE + WGW_QTILE)      /* 19456 floats = 76 KB, double buffered */
-#define WGW_NPS 12
-#define WGW_NQS 5
 #define WGW_THREADS 256
+#define WGW_RS 18
+#define WGW_PTILE (24 * 32 * WGW_RS)         /* 4 z-rows x 6 y-rows */
+#define WGW_QTILE (8 * 32 * WGW_RS)          /* 2 z-rows x 4 y-rows */
+#define WGW_BUF (WGW_PTILE + WGW_QTILE)      /* 18432 floats = 72 KB, double buffered; the two = the 4 x 9 tiles of the combine */
+#define WGW_NPS 14                           /* P slots per thread: 24 rows x 18 x x 8 channel quads = 3456 = 13.5 x 256 */
+#define WGW_NQS 4                            /* Q slots per thread: 8 rows x 16 x x 8 channel quads = 1024 */
 
 __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -888,273 +890,268 @@ __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p
   const float* pP = p.p + pct * 32;
   const float* pQ = p.q + qct * 32;
 
-  // ---- staging maps: slot id = tid + 256*i ; P: x = id & 15, channel quad = (id >> 4) & 7, row = id >> 7 = (tid >> 7) + 2i.
-  //      Byte offsets relative to the tile origin are computed once; a slot outside the image gets a 2 GB offset = outside
-  //      the buffer descriptor, the load returns zeros (border tiles only: 4 flag bits per slot against 4 per tile) ----
-  const int sxx = tid & 15, scq = (tid >> 4) & 7, srow0 = tid >> 7;
-  const int p_lds0 = (srow0 * 32 + scq * 4) * 16 + ((((sxx >> 2) ^ (scq & 3)) << 2) | (sxx & 3));
-  unsigned poff[WGW_NPS], pfl0 = 0, pfl1 = 0;
+  // ---- staging maps: slot id = tid + 256*i = ((row * XW) + x) * 8 + channel quad.  Byte offsets relative to the tile origin
+  //      are computed once; a slot outside the image gets a 2 GB offset = outside the buffer descriptor, the load returns
+  //      zeros (border tiles only: 6 face bits per slot against 6 per tile) ----
+  int p_lds[WGW_NPS];
+  unsigned poff[WGW_NPS], pfl[3] = {0u, 0u, 0u};
 #pragma unroll
   for (int i = 0; i < WGW_NPS; ++i) {
-    const int row = srow0 + 2 * i;
-    const int zr = row / 6, yr = row - zr * 6;
-    poff[i] = (unsigned)(((zr * p.Hp + yr) * p.Wp + sxx) * p.ldp + scq * 4) * 4u;
-    const unsigned fl = (zr == 0 ? 1u : 0u) | (zr == 3 ? 2u : 0u) | (yr == 0 ? 4u : 0u) | (yr == 5 ? 8u : 0u);
-    if (i < 8) pfl0 |= fl << (4 * i); else pfl1 |= fl << (4 * (i - 8));
+    const int id = tid + WGW_THREADS * i;
+    // (the half-filled last slot: its idle threads load nothing and write their zeros to the unused x = 16, 17 of the Q rows)
+    const int idle = id - 24 * 18 * 8;
+    p_lds[i] = WGW_PTILE + ((idle >> 4) * 32 + ((idle >> 1) & 7) * 4) * WGW_RS + 16 + (idle & 1);
+    poff[i] = 0x80000000u;
+    if (id < 24 * 18 * 8) {
+      const int cq = id & 7, vox = id >> 3;
+      const int row = vox / 18, xx = vox - row * 18;
+      const int zr = row / 6, yr = row - zr * 6;
+      p_lds[i] = (row * 32 + cq * 4) * WGW_RS + xx;
+      poff[i] = (unsigned)(((zr * p.Hp + yr) * p.Wp + xx) * p.ldp + cq * 4) * 4u;
+      const unsigned fl = (zr == 0 ? 1u : 0u) | (zr == 3 ? 2u : 0u) | (yr == 0 ? 4u : 0u) | (yr == 5 ? 8u : 0u) |
+                          (xx == 0 ? 16u : 0u) | (xx == 17 ? 32u : 0u);
+      pfl[i / 5] |= fl << (6 * (i % 5));
+    }
   }
   int q_lds[WGW_NQS];
-  unsigned qoff[WGW_NQS], qfl = 0;
+  unsigned qoff[WGW_NQS];
 #pragma unroll
   for (int i = 0; i < WGW_NQS; ++i) {
     const int id = tid + WGW_THREADS * i;
-    q_lds[i] = -1; qoff[i] = 0x80000000u;
-    if (id < 1152) {
-      const int xx = id % 18, kq = (id / 18) & 7, row = id / 144;   // x = x0 - 1 + xx ; row = oz*4 + oy
-      q_lds[i] = WGW_PTILE + (row * 32 + kq * 4) * WGW_QSTR + xx + 3;
-      qoff[i] = (unsigned)((((row >> 2) * p.Hq + (row & 3)) * p.Wq + xx) * p.ldq + kq * 4) * 4u;
-      qfl |= ((xx == 0 ? 1u : 0u) | (xx == 17 ? 2u : 0u)) << (2 * i);
-    }
+    const int cq = id & 7, xx = (id >> 3) & 15, row = id >> 7;   // row = oz*4 + oy
+    q_lds[i] = WGW_PTILE + (row * 32 + cq * 4) * WGW_RS + xx;
+    qoff[i] = (unsigned)((((row >> 2) * p.Hq + (row & 3)) * p.Wq + xx) * p.ldq + cq * 4) * 4u;
   }
+  const int t0 = blockIdx.x * p.sub_per_wg;
+  int t1 = t0 + p.sub_per_wg;
+  if (t1 > p.nsub) t1 = p.nsub;
   // coordinates of the NEXT sub-tile to fetch (sub-tiles of a workgroup are consecutive: incremental, no division in the loop)
   int ftx, fty, ftz, fn;
   {
-    int t = blockIdx.x * p.sub_per_wg;
+    int t = t0;
     ftx = t % p.ntx; t /= p.ntx;
     fty = t % p.nty; t /= p.nty;
     ftz = t % p.ntz;
     fn = t / p.ntz;
   }
-  // The 17 slots of the next sub-tile are fetched in four quarters (P 0-2 + Q 0-1 | P 3-5 + Q 2 | P 6-8 + Q 3 | P 9-11 + Q 4),
-  // quarter k issued at step k of the current sub-tile and written to the OTHER LDS buffer one step later: the staging
-  // registers of a quarter live for one step only and the ds_writes spread over the matrix instructions.
+  // The 18 slots of the next sub-tile are fetched in six groups of three (P 0-2 | 3-5 | 6-8 | 9-11 | P 12-13 + Q 0 | Q 1-3),
+  // group k issued at step k of the current sub-tile and written to the OTHER LDS buffer one step later.
   f32x4 pre[WGW_NPS + WGW_NQS];
   __amdgpu_buffer_rsrc_t f_pr, f_qr;
-  unsigned f_tm = 0, f_qm = 0;
-  auto fetch_begin = [&]() {
+  unsigned f_tm = 0;
+  auto fetch_begin = [&](bool live) {   // live = false: empty descriptors, every load returns zeros without traffic
     const int z0 = 2 * ftz, y0 = 4 * fty, x0 = 16 * ftx;
-    const float* pb = pP + ((((long)fn * p.Dp + z0 - 1) * p.Hp + y0 - 1) * p.Wp + x0) * p.ldp;
-    const float* qb = pQ + ((((long)fn * p.Dq + z0) * p.Hq + y0) * p.Wq + x0 - 1) * p.ldq;
-    f_pr = __builtin_amdgcn_make_buffer_rsrc((void*)pb, 0, 0x7fffffff, 0x00020000);
-    f_qr = __builtin_amdgcn_make_buffer_rsrc((void*)qb, 0, 0x7fffffff, 0x00020000);
-    f_tm = (ftz == 0 ? 1u : 0u) | (ftz == p.ntz - 1 ? 2u : 0u) | (fty == 0 ? 4u : 0u) | (fty == p.nty - 1 ? 8u : 0u);
-    f_qm = (ftx == 0 ? 1u : 0u) | (ftx == p.ntx - 1 ? 2u : 0u);
-    if (++ftx == p.ntx) { ftx = 0; if (++fty == p.nty) { fty = 0; if (++ftz == p.ntz) { ftz = 0; ++fn; } } }
+    const float* pb = pP + ((((long)fn * p.Dp + z0 - 1) * p.Hp + y0 - 1) * p.Wp + x0 - 1) * p.ldp;
+    const float* qb = pQ + ((((long)fn * p.Dq + z0) * p.Hq + y0) * p.Wq + x0) * p.ldq;
+    f_pr = __builtin_amdgcn_make_buffer_rsrc((void*)pb, 0, live ? 0x7fffffff : 0, 0x00020000);
+    f_qr = __builtin_amdgcn_make_buffer_rsrc((void*)qb, 0, live ? 0x7fffffff : 0, 0x00020000);
+    f_tm = (ftz == 0 ? 1u : 0u) | (ftz == p.ntz - 1 ? 2u : 0u) | (fty == 0 ? 4u : 0u) | (fty == p.nty - 1 ? 8u : 0u) |
+           (ftx == 0 ? 16u : 0u) | (ftx == p.ntx - 1 ? 32u : 0u);
+    const int cx = (ftx + 1 == p.ntx) ? 1 : 0;   // (selects, no branches: the call sits inside a scheduled step)
+    ftx = cx ? 0 : ftx + 1;
+    const int cy = (fty + cx == p.nty) ? 1 : 0;
+    fty = cy ? 0 : fty + cx;
+    const int cz = (ftz + cy == p.ntz) ? 1 : 0;
+    ftz = cz ? 0 : ftz + cy;
+    fn += cz;
   };
-  auto fetch_p = [&](auto ic) {
+  auto fetch_slot = [&](auto ic) {
     constexpr int i = decltype(ic)::value;
-    constexpr int sh = 4 * (i & 7);
-    const unsigned fl = (((i < 8 ? pfl0 : pfl1) >> sh) & 15u) & f_tm;
-    pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_pr, fl ? 0x80000000u : poff[i], 0, 0));
-  };
-  auto fetch_q = [&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    const unsigned fl = ((qfl >> (2 * i)) & 3u) & f_qm;
-    pre[WGW_NPS + i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_qr, fl ? 0x80000000u : qoff[i], 0, 0));
-  };
-  auto commit_p = [&](float* buf, auto ic) {
-    constexpr int i = decltype(ic)::value;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) buf[p_lds0 + i * (2 * 32 * 16) + e * 16] = pre[i][e];
-  };
-  auto commit_q = [&](float* buf, auto ic) {
-    constexpr int i = decltype(ic)::value;
-    if (q_lds[i] >= 0) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) buf[q_lds[i] + e * WGW_QSTR] = pre[WGW_NPS + i][e];
+    if constexpr (i < WGW_NPS) {
+      const unsigned fl = ((pfl[i / 5] >> (6 * (i % 5))) & 63u) & f_tm;
+      pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_pr, fl ? 0x80000000u : poff[i], 0, 0));
+    } else {
+      pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_qr, qoff[i - WGW_NPS], 0, 0));
     }
   };
-  auto fetch_quarter = [&](auto kc) {
-    constexpr int k = decltype(kc)::value;
-    fetch_p(IC<3 * k>{}); fetch_p(IC<3 * k + 1>{}); fetch_p(IC<3 * k + 2>{});
-    if constexpr (k == 0) { fetch_q(IC<0>{}); fetch_q(IC<1>{}); } else fetch_q(IC<k + 1>{});
+  auto commit_slot = [&](float* buf, auto ic) {
+    constexpr int i = decltype(ic)::value;
+    if constexpr (i < WGW_NPS) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) buf[p_lds[i] + e * WGW_RS] = pre[i][e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) buf[q_lds[i - WGW_NPS] + e * WGW_RS] = pre[i][e];
+    }
   };
-  auto commit_quarter = [&](float* buf, auto kc) {
+  auto fetch_group = [&](auto kc) {
     constexpr int k = decltype(kc)::value;
-    commit_p(buf, IC<3 * k>{}); commit_p(buf, IC<3 * k + 1>{}); commit_p(buf, IC<3 * k + 2>{});
-    if constexpr (k == 0) { commit_q(buf, IC<0>{}); commit_q(buf, IC<1>{}); } else commit_q(buf, IC<k + 1>{});
+    fetch_slot(IC<3 * k>{}); fetch_slot(IC<3 * k + 1>{}); fetch_slot(IC<3 * k + 2>{});
+  };
+  auto commit_group = [&](float* buf, auto kc) {
+    constexpr int k = decltype(kc)::value;
+    commit_slot(buf, IC<3 * k>{}); commit_slot(buf, IC<3 * k + 1>{}); commit_slot(buf, IC<3 * k + 2>{});
   };
 
-  // ---- wave roles: xi_z: 0: d0 - d2 | 1: d1 + d2 | 2: d2 - d1 | 3: d1 - d3 ;  c = P[ra] + s * P[rb] ----
+  // ---- wave roles: xi_z of P: c = P[ra] + sp * P[rb]; of Q: a = X + sq * Y (xi_z = 3: +q1) ----
   const int ra = (wave == 0) ? 0 : (wave == 2) ? 2 : 1;
   const int rb = (wave == 0) ? 2 : (wave == 1) ? 2 : (wave == 2) ? 1 : 3;
   const float sp = (wave == 1) ? 1.f : -1.f;
   const wg_f32x2 sp2 = {sp, sp};
-  // T z-part: a = X + sq * Y over the two z-rows of Q:  0: q0 | 1: q0 + q1 | 2: q0 - q1 | 3: +q1 (the true -q1 is undone in the
-  // tap combine) -- X = row oz 0 (wave 3: oz 1), Y = row oz 1, sq = 0 / +1 / -1 / 0: the same instructions for every wave
   const float sq = (wave == 1) ? 1.f : (wave == 2) ? -1.f : 0.f;
   const wg_f32x2 sq2 = {sq, sq};
-  const int qX = (wave == 3) ? 4 * 32 * WGW_QSTR : 0;
-  const int pswz = (ch >> 2) & 3;
-  const int pA = (ra * 6 * 32 + ch) * 16, pB = (rb * 6 * 32 + ch) * 16;
+  const int pA = (ra * 6 * 32 + ch) * WGW_RS + 2 * hh, pB = (rb * 6 * 32 + ch) * WGW_RS + 2 * hh;
+  const int qXa = WGW_PTILE + ((wave == 3 ? 4 : 0) * 32 + ch) * WGW_RS + 2 * hh;
+  const int qYa = WGW_PTILE + (4 * 32 + ch) * WGW_RS + 2 * hh;
   const bool bias = p.want_bias && pct == 0 && wave == 1;
   double bsum = 0.0;
+  float bs = 0.f;   // the all-sum point of Q (xi = 1 on every axis; wave 1) over one sub-tile
 
-  f32x16 acc[3][4];
+  f32x16 acc[4][4];   // [xi_y][xi_x]
 #pragma unroll
-  for (int a = 0; a < 3; ++a)
+  for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.f;
 
-  // operands of one step (patch py2, x-quad pair s): V = 4 quads (A operand), T = the middle quad of the 12-wide window in
-  // full (window 4..7) and its two neighbours (window 3 and 8) as scalars
-  struct WgwOps {
-    f32x4 v[4];
-    f32x4 a0, a1, u1, u2;
-    float a0s[2], a1s[2], u1s[2], u2s[2];
-  };
+  struct WgwOps { float v[4][4], t[4][4]; };
+  // operands of step st = (patch row py, x patch pair sx): this lane's patch is px = 2 sx + hh
   auto form = [&](const float* cur, auto stc, WgwOps& o) {
     constexpr int st = decltype(stc)::value;
-    constexpr int py2 = st >> 1, sx = st & 1;
-    const int xq = 2 * sx + hh;               // logical x quad of this lane
-    const int xo = 4 * xq;
-    const int pq = (xq ^ pswz) << 2;          // physical cell inside the 16-float row
-    f32x4 c[4];
+    constexpr int py = st >> 2, sx = st & 3;
+    wg_f32x2 cl[4], cx[4];   // z-combined rows: x inputs 0,1 | 2,3
 #pragma unroll
     for (int yr = 0; yr < 4; ++yr) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(cur + pA + (2 * py2 + yr) * 512 + pq);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(cur + pB + (2 * py2 + yr) * 512 + pq);
-      c[yr] = wgw_fma4(b, sp2, a);
+      const float* a = cur + pA + (2 * py + yr) * 32 * WGW_RS + 4 * sx;
+      const float* b = cur + pB + (2 * py + yr) * 32 * WGW_RS + 4 * sx;
+      cl[yr] = wgw_pk_fma(*reinterpret_cast<const wg_f32x2*>(b), sp2, *reinterpret_cast<const wg_f32x2*>(a));
+      cx[yr] = wgw_pk_fma(*reinterpret_cast<const wg_f32x2*>(b + 2), sp2, *reinterpret_cast<const wg_f32x2*>(a + 2));
     }
-    o.v[0] = wgw_sub4(c[0], c[2]);
-    o.v[1] = wgw_add4(c[1], c[2]);
-    o.v[2] = wgw_sub4(c[2], c[1]);
-    o.v[3] = wgw_sub4(c[1], c[3]);
-    const float* qb = cur + WGW_PTILE + ((2 * py2) * 32 + ch) * WGW_QSTR + xo;
-    {  // middle quad, packed
-      const f32x4 x0q = *reinterpret_cast<const f32x4*>(qb + qX + 4);
-      const f32x4 x1q = *reinterpret_cast<const f32x4*>(qb + qX + 32 * WGW_QSTR + 4);
-      const f32x4 y0q = *reinterpret_cast<const f32x4*>(qb + (4 * 32) * WGW_QSTR + 4);
-      const f32x4 y1q = *reinterpret_cast<const f32x4*>(qb + (5 * 32) * WGW_QSTR + 4);
-      o.a0 = wgw_fma4(y0q, sq2, x0q);
-      o.a1 = wgw_fma4(y1q, sq2, x1q);
-      o.u1 = wgw_add4(o.a0, o.a1);
-      o.u2 = wgw_sub4(o.a0, o.a1);
-      if (bias) bsum += (double)((o.u1[0] + o.u1[1]) + (o.u1[2] + o.u1[3]));   // wave 1: the four Q rows of this lane's own 4 x
-    }
-    // window 3 and 8 (the x neighbours of the quad).  Thirty-two lanes reading ONE column of 32 channel rows with 4-byte reads hit
-    // 8 banks (the row stride is a multiple of 4 floats; 4-byte reads bank on 32): those 4-way conflicts on eight reads per step
-    // were 45 % of this kernel's LDS cycles (profiles/r02e_pmc_wino.txt).  Read the neighbouring CELLS with 16-byte reads instead
-    // (conflict-free like the middle quad's: 16 lanes x 16 bytes cover the 64 banks once) and use one element of each.
+    wg_f32x2 vl[4], vx[4];
+    vl[0] = wgw_pk_sub(cl[0], cl[2]); vx[0] = wgw_pk_sub(cx[0], cx[2]);
+    vl[1] = wgw_pk_add(cl[1], cl[2]); vx[1] = wgw_pk_add(cx[1], cx[2]);
+    vl[2] = wgw_pk_sub(cl[2], cl[1]); vx[2] = wgw_pk_sub(cx[2], cx[1]);
+    vl[3] = wgw_pk_sub(cl[1], cl[3]); vx[3] = wgw_pk_sub(cx[1], cx[3]);
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int off = e == 0 ? 0 : 8, el = e == 0 ? 3 : 0;
-      f32x4 xs0 = *reinterpret_cast<const f32x4*>(qb + qX + off);
-      f32x4 xs1 = *reinterpret_cast<const f32x4*>(qb + qX + 32 * WGW_QSTR + off);
-      f32x4 ys0 = *reinterpret_cast<const f32x4*>(qb + (4 * 32) * WGW_QSTR + off);
-      f32x4 ys1 = *reinterpret_cast<const f32x4*>(qb + (5 * 32) * WGW_QSTR + off);
-      asm volatile("" : "+v"(xs0), "+v"(xs1), "+v"(ys0), "+v"(ys1));     // (keeps the four reads 16 bytes wide)
-      o.a0s[e] = fmaf(ys0[el], sq, xs0[el]);
-      o.a1s[e] = fmaf(ys1[el], sq, xs1[el]);
-      o.u1s[e] = o.a0s[e] + o.a1s[e];
-      o.u2s[e] = o.a0s[e] - o.a1s[e];
+    for (int a = 0; a < 4; ++a) {   // x: e0 - e2 | e1 + e2 | e2 - e1 | e1 - e3
+      const wg_f32x2 d = wgw_pk_sub(vl[a], vx[a]), m = wgw_pk_addsub(vx[a], vl[a]);
+      o.v[a][0] = d.x;
+      o.v[a][1] = m.x;
+      o.v[a][2] = m.y;
+      o.v[a][3] = d.y;
     }
+    wg_f32x2 qa[2];
+#pragma unroll
+    for (int yr = 0; yr < 2; ++yr) {
+      const wg_f32x2 X = *reinterpret_cast<const wg_f32x2*>(cur + qXa + (2 * py + yr) * 32 * WGW_RS + 4 * sx);
+      const wg_f32x2 Y = *reinterpret_cast<const wg_f32x2*>(cur + qYa + (2 * py + yr) * 32 * WGW_RS + 4 * sx);
+      qa[yr] = wgw_pk_fma(Y, sq2, X);
+    }
+    const wg_f32x2 ty[4] = {qa[0], wgw_pk_add(qa[0], qa[1]), wgw_pk_sub(qa[0], qa[1]), qa[1]};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {   // x: e0 | e0 + e1 | e0 - e1 | + e1
+      const wg_f32x2 m = wgw_pk_addsub(ty[a], ty[a]);
+      o.t[a][0] = ty[a].x;
+      o.t[a][1] = m.x;
+      o.t[a][2] = m.y;
+      o.t[a][3] = ty[a].y;
+    }
+    bs += o.t[1][1];
   };
-  auto mfma48 = [&](const WgwOps& o) {
+  auto mfma16 = [&](const WgwOps& o) {
 #pragma unroll
-    for (int dx = 0; dx < 3; ++dx)
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int w = 5 + j - dx;   // window value paired with this lane's x quad element j
-        const float b0 = w == 3 ? o.a0s[0] : w == 8 ? o.a0s[1] : o.a0[(w - 4) & 3];
-        const float b1 = w == 3 ? o.u1s[0] : w == 8 ? o.u1s[1] : o.u1[(w - 4) & 3];
-        const float b2 = w == 3 ? o.u2s[0] : w == 8 ? o.u2s[1] : o.u2[(w - 4) & 3];
-        const float b3 = w == 3 ? o.a1s[0] : w == 8 ? o.a1s[1] : o.a1[(w - 4) & 3];   // true t3 = -a1
-        acc[dx][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.v[0][j], b0, acc[dx][0], 0, 0, 0);
-        acc[dx][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.v[1][j], b1, acc[dx][1], 0, 0, 0);
-        acc[dx][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.v[2][j], b2, acc[dx][2], 0, 0, 0);
-        acc[dx][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.v[3][j], b3, acc[dx][3], 0, 0, 0);
-      }
+      for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.v[a][b], o.t[a][b], acc[a][b], 0, 0, 0);
   };
-  // one slot of the schedule per matrix instruction: the MFMA, then up to two vector-ALU operations and one memory operation
-  // of the work that shares the step (next step's operands, the staging quarter)
+  // one slot of the schedule per matrix instruction: the MFMA, then up to four vector-ALU operations and three memory operations
+  // of the work that shares the step (next step's operands, the staging group)
 #define WGW_SCHED_STEP()                                   \
-  _Pragma("unroll") for (int q_ = 0; q_ < 48; ++q_) {      \
+  _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {      \
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     \
-    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);     \
-    __builtin_amdgcn_sched_group_barrier(0x320, 1, 0);     \
+    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);     \
+    __builtin_amdgcn_sched_group_barrier(0x320, 3, 0);     \
   }
+#define WGW_STEP_END()                       \
+  WGW_SCHED_STEP();                          \
+  __builtin_amdgcn_sched_barrier(0);         \
+  asm volatile("s_nop 1" ::: "memory");   /* hand-written VALU -> MFMA operand: the compiler does not track that hazard */
 
-  const int t0 = blockIdx.x * p.sub_per_wg;
-  int t1 = t0 + p.sub_per_wg;
-  if (t1 > p.nsub) t1 = p.nsub;
-  if (t0 < t1) {
-    fetch_begin();
-    fetch_quarter(IC<0>{}); fetch_quarter(IC<1>{}); fetch_quarter(IC<2>{}); fetch_quarter(IC<3>{});
-    commit_quarter(lds, IC<0>{}); commit_quarter(lds, IC<1>{}); commit_quarter(lds, IC<2>{}); commit_quarter(lds, IC<3>{});
-  }
+  fetch_begin(t0 < t1);
+  fetch_group(IC<0>{}); fetch_group(IC<1>{}); fetch_group(IC<2>{}); fetch_group(IC<3>{}); fetch_group(IC<4>{}); fetch_group(IC<5>{});
+  commit_group(lds, IC<0>{}); commit_group(lds, IC<1>{}); commit_group(lds, IC<2>{}); commit_group(lds, IC<3>{});
+  commit_group(lds, IC<4>{}); commit_group(lds, IC<5>{});
   __syncthreads();
   WgwOps opA, opB;
+  form(lds, IC<0>{}, opA);
+  fetch_begin((t0 + 1) < t1);
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_nop 3" ::: "memory");
   for (int t = t0; t < t1; ++t) {
     const float* cur = lds + ((t - t0) & 1) * WGW_BUF;
     float* nxt = lds + ((t - t0 + 1) & 1) * WGW_BUF;
-    const bool more = (t + 1) < t1;
-    form(cur, IC<0>{}, opA);
-    if (more) fetch_begin();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 3" ::: "memory");   // hand-written VALU -> MFMA operand: the compiler does not track that hazard
-    // step 0: MFMA(opA) | form step 1 | fetch quarter 0
-    if (more) fetch_quarter(IC<0>{});
-    form(cur, IC<1>{}, opB);
-    mfma48(opA);
-    WGW_SCHED_STEP();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    // step 1: MFMA(opB) | form step 2 | commit quarter 0, fetch quarter 1
-    if (more) { commit_quarter(nxt, IC<0>{}); fetch_quarter(IC<1>{}); }
-    form(cur, IC<2>{}, opA);
-    mfma48(opB);
-    WGW_SCHED_STEP();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    // step 2: MFMA(opA) | form step 3 | commit quarter 1, fetch quarter 2
-    if (more) { commit_quarter(nxt, IC<1>{}); fetch_quarter(IC<2>{}); }
-    form(cur, IC<3>{}, opB);
-    mfma48(opA);
-    WGW_SCHED_STEP();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    // step 3: MFMA(opB) | commit quarter 2, fetch quarter 3
-    if (more) { commit_quarter(nxt, IC<2>{}); fetch_quarter(IC<3>{}); }
-    mfma48(opB);
-    WGW_SCHED_STEP();
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) commit_quarter(nxt, IC<3>{});
+    form(cur, IC<1>{}, opB); fetch_group(IC<0>{});
+    mfma16(opA);
+    WGW_STEP_END();
+    form(cur, IC<2>{}, opA); commit_group(nxt, IC<0>{}); fetch_group(IC<1>{});
+    mfma16(opB);
+    WGW_STEP_END();
+    form(cur, IC<3>{}, opB); commit_group(nxt, IC<1>{}); fetch_group(IC<2>{});
+    mfma16(opA);
+    WGW_STEP_END();
+    form(cur, IC<4>{}, opA); commit_group(nxt, IC<2>{}); fetch_group(IC<3>{});
+    mfma16(opB);
+    WGW_STEP_END();
+    form(cur, IC<5>{}, opB); commit_group(nxt, IC<3>{}); fetch_group(IC<4>{});
+    mfma16(opA);
+    WGW_STEP_END();
+    form(cur, IC<6>{}, opA); commit_group(nxt, IC<4>{}); fetch_group(IC<5>{});
+    mfma16(opB);
+    WGW_STEP_END();
+    form(cur, IC<7>{}, opB); commit_group(nxt, IC<5>{});
+    mfma16(opA);
+    WGW_STEP_END();
+    bsum += (double)bs;   // (step 0's share was added when it was formed, under the previous sub-tile's last step)
+    bs = 0.f;
+    // the barrier sits before the LAST step: step 0 of the next sub-tile is formed under this step's matrix instructions (behind
+    // the workgroup's last sub-tile the other buffer holds zeros or stale data and the operands formed from it are dropped)
     __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    form(nxt, IC<0>{}, opA);
+    fetch_begin((t + 2) < t1);   // descriptors and face bits of the sub-tile after the next, fetched during the next
+    mfma16(opB);
+    WGW_STEP_END();
   }
 
-  // ---- G^T dU G: y part in the wave (u3 carries the opposite sign) -> LDS [xi_z][dx*3+ky][c][k]; z part across the waves ----
+  // ---- G^T dU G: y and x part in the wave (xi = 3 carries the opposite sign) -> LDS [xi_z][ky*3+kx][c][k]; z part across the waves ----
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+  __syncthreads();   // (the last step formed operands from the other buffer)
   float* xl = lds + wave * 9 * 1024;
 #pragma unroll
-  for (int dx = 0; dx < 3; ++dx)
+  for (int r = 0; r < 16; ++r) {
+    float m[3][4];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float u0 = wgw_acc_rd(acc[dx][0][r]), u1 = wgw_acc_rd(acc[dx][1][r]), u2 = wgw_acc_rd(acc[dx][2][r]),
-                  u3 = wgw_acc_rd(acc[dx][3][r]);
+    for (int b = 0; b < 4; ++b) {
+      const float u0 = wgw_acc_rd(acc[0][b][r]), u1 = wgw_acc_rd(acc[1][b][r]), u2 = wgw_acc_rd(acc[2][b][r]),
+                  u3 = wgw_acc_rd(acc[3][b][r]);
       const float hs = 0.5f * (u1 + u2), hd = 0.5f * (u1 - u2);
-      const int crow = 8 * (r >> 2) + 4 * hh + (r & 3);
-      float* o = xl + (dx * 3) * 1024 + crow * 32 + ch;
-      o[0] = u0 + hs;
-      o[1024] = hd;
-      o[2048] = hs - u3;
+      m[0][b] = u0 + hs;
+      m[1][b] = hd;
+      m[2][b] = hs - u3;
     }
+    const int crow = 8 * (r >> 2) + 4 * hh + (r & 3);
+    float* o = xl + crow * 32 + ch;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const float hs = 0.5f * (m[ky][1] + m[ky][2]), hd = 0.5f * (m[ky][1] - m[ky][2]);
+      o[(ky * 3 + 0) * 1024] = m[ky][0] + hs;
+      o[(ky * 3 + 1) * 1024] = hd;
+      o[(ky * 3 + 2) * 1024] = hs - m[ky][3];
+    }
+  }
   __syncthreads();
-  // taps (kz, ky, dx): kz 0: L0 + .5 L1 + .5 L2 | kz 1: .5 L1 - .5 L2 | kz 2: .5 L1 + .5 L2 - L3   (L3 accumulated with +q1)
+  // taps (kz, ky, kx): kz 0: L0 + .5 L1 + .5 L2 | kz 1: .5 L1 - .5 L2 | kz 2: .5 L1 + .5 L2 - L3   (L3 accumulated with +q1)
   float* out = p.partial + ((((long)blockIdx.x * gridDim.y + pct) * gridDim.z + qct) * 27) * 1024;
   for (int e = tid; e < 9 * 1024; e += WGW_THREADS) {
-    const int g = e >> 10, ck = e & 1023;       // g = dx*3 + ky
-    const int dx = g / 3, ky = g - dx * 3;
-    const float l0 = lds[(0 * 9 + g) * 1024 + ck], l1 = lds[(1 * 9 + g) * 1024 + ck], l2 = lds[(2 * 9 + g) * 1024 + ck],
-                l3 = lds[(3 * 9 + g) * 1024 + ck];
+    const float l0 = lds[0 * 9 * 1024 + e], l1 = lds[1 * 9 * 1024 + e], l2 = lds[2 * 9 * 1024 + e], l3 = lds[3 * 9 * 1024 + e];
     const float hs = 0.5f * (l1 + l2), hd = 0.5f * (l1 - l2);
-    out[((0 * 3 + ky) * 3 + dx) * 1024 + ck] = l0 + hs;
-    out[((1 * 3 + ky) * 3 + dx) * 1024 + ck] = hd;
-    out[((2 * 3 + ky) * 3 + dx) * 1024 + ck] = hs - l3;
+    out[0 * 9 * 1024 + e] = l0 + hs;   // e = (ky*3 + kx) * 1024 + c * 32 + k
+    out[1 * 9 * 1024 + e] = hd;
+    out[2 * 9 * 1024 + e] = hs - l3;
   }
   if (bias) {
-    const double o = __shfl_xor(bsum, 32, 64);   // the two x-quad halves of the wave
+    const double o = __shfl_xor(bsum, 32, 64);   // the two patch parities of the wave
     if (lane < 32) p.partial_b[((long)blockIdx.x * gridDim.z + qct) * 32 + ch] = bsum + o;
   }
 }
@@ -1256,6 +1253,26 @@ static int wgrad_roles(WgradRoles& r, int kind, int D, int H, int W, int Cin, in
   return BTS_OK;
 }
 
+// The kernel variant of a planned call: 0 register staging | 1 LDS-DMA staging | 2, 3 the fixed-geometry sweeps (stride 1, 2).
+// vec: both operands are 16-byte granular (leading dimensions, channel counts, base addresses).  Drops p.fastf / p.fixg where
+// the 32-bit staging offsets would not reach.
+static int wgrad_variant(WgradParams& p, bool vec) {
+  if (p.fastf && ((double)p.IZ * p.Hp * p.Wp * p.ldp * 4.0 >= 4.0e9 || (double)p.TZ * p.Hq * p.Wq * p.ldq * 4.0 >= 4.0e9 || !vec))
+    p.fastf = p.fixg = 0;
+  return !vec ? 0 : (p.fastf ? 1 + p.fixg : 1);
+}
+// The form that takes the call: stride-1 whole-tile layers run in Winograd form, all three axes (BTS_FORM_WG3); BTS_WGW=0: the
+// direct fixed-geometry kernel, which also takes everything else.  (BTS_FORM_WG2, Winograd over (z, y) with x direct, was the form
+// before and lost at every layer shape: DESIGN section 9.)  The switch is read per call: tests and A/B runs toggle it.
+enum { BTS_FORM_DIRECT = 0, BTS_FORM_WG2 = 2, BTS_FORM_WG3 = 3 };
+static int wgrad_form(const WgradParams& p, const WgradRoles& ro, int variant) {
+  if (variant != 2 || ro.ntaps != 27 || ro.s != 1) return BTS_FORM_DIRECT;
+  const char* e = getenv("BTS_WGW");
+  if (e && atoi(e) == 0) return BTS_FORM_DIRECT;
+  if (!(5.0 * p.Hp * p.Wp * p.ldp * 4.0 < 2.0e9 && 3.0 * p.Hq * p.Wq * p.ldq * 4.0 < 2.0e9)) return BTS_FORM_DIRECT;  // 31-bit tile offsets
+  return BTS_FORM_WG3;
+}
+
 extern "C" int bts_colsum(const float* x, float* out, void* workspace, long workspace_bytes, int N, long rows, int C,
                           int ld, float scale, int sum_over_n, int accumulate, hipStream_t stream);
 extern "C" long bts_colsum_workspace(int N, long rows, int C);
@@ -1268,6 +1285,24 @@ extern "C" long bts_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, i
   if (plan_wgrad(pl, r.ntaps, r.s, r.neg, N, r.Dp, r.Hp, r.Wp, r.Cp, r.Dq, r.Hq, r.Wq, r.Cq) != BTS_OK) return -1;
   const long base = ((pl.partial_floats * 4 + pl.partial_b_doubles * 8 + 256 + 15) & ~15L);
   return base + (r.swapped ? bts_colsum_workspace(N, (long)D * H * W, Cout) : 0) + 128;
+}
+
+// Host only: the form bts_conv3d_bwd_weight takes for the described call -- 0 direct | 3 Winograd F(2x2x2,3x3x3) (2, Winograd
+// F(2x2,3x3) x direct, is no longer taken) -- or the negative status of a call it does not take.  aligned: bit 0 x, bit 1 dy on a
+// 16-byte boundary.
+extern "C" int bts_conv3d_bwd_weight_form(int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int aligned) {
+  WgradRoles ro;
+  int r = wgrad_roles(ro, kind, D, H, W, Cin, Cout);
+  if (r != BTS_OK) return r;
+  WgradPlan pl;
+  r = plan_wgrad(pl, ro.ntaps, ro.s, ro.neg, N, ro.Dp, ro.Hp, ro.Wp, ro.Cp, ro.Dq, ro.Hq, ro.Wq, ro.Cq);
+  if (r != BTS_OK) return r;
+  WgradParams& p = pl.p;
+  const bool pIsDy = ro.transposed || ro.swapped;
+  p.ldp = pIsDy ? lddy : ldx;
+  p.ldq = pIsDy ? ldx : lddy;
+  const bool vec = (p.ldp % 4 == 0) && (p.Cp % 4 == 0) && (p.ldq % 4 == 0) && (p.Cq % 4 == 0) && (aligned & 3) == 3;
+  return wgrad_form(p, ro, wgrad_variant(p, vec));
 }
 
 // dw is in the reference layout with Cin_ref = Cin + dup_shift input channels; db may be null.
@@ -1310,19 +1345,12 @@ extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, 
   p.zeros = reinterpret_cast<const float*>(ztail);
   const bool glds = (p.ldp % 4 == 0) && (p.Cp % 4 == 0) && ((((uintptr_t)p.p) & 15) == 0) && (p.ldq % 4 == 0) &&
                     (p.Cq % 4 == 0) && ((((uintptr_t)p.q) & 15) == 0);
-  if (p.fastf && ((double)p.IZ * p.Hp * p.Wp * p.ldp * 4.0 >= 4.0e9 || (double)p.TZ * p.Hq * p.Wq * p.ldq * 4.0 >= 4.0e9 || !glds))
-    p.fastf = p.fixg = 0;
+  const int kidx = wgrad_variant(p, glds);
+  const int form = wgrad_form(p, ro, kidx);
   const bool prof = bts_prof_on();
   if (glds && !p.fastf) {  // only the general LDS-DMA staging reads the zero source
     hipError_t e = hipMemsetAsync(ztail, 0, 64, stream);
     if (e != hipSuccess) return (int)e;
-  }
-  const int kidx = !glds ? 0 : (p.fastf ? 1 + p.fixg : 1);
-  // stride-1 whole-tile layers: Winograd form (BTS_WGW=0: the direct fixed-geometry kernel)
-  bool use_wgw = false;
-  if (kidx == 2 && ro.ntaps == 27 && ro.s == 1) {
-    const char* e = getenv("BTS_WGW");
-    use_wgw = !(e && atoi(e) == 0) && 5.0 * p.Hp * p.Wp * p.ldp * 4.0 < 2.0e9 && 3.0 * p.Hq * p.Wq * p.ldq * 4.0 < 2.0e9;  // 31-bit tile offsets
   }
   // 1x1x1 convs on big grids: streaming kernel (BTS_K1W=0: the staged kernel)
   bool use_k1w = false;
@@ -1338,7 +1366,7 @@ extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, 
     hipLaunchKernelGGL(k1w_kernel, dim3(pl.nsp, pl.npct, pl.nqct), dim3(K1W_THREADS), 0, stream, p, NVall, chunk);
     if (prof) bts_prof_end(stream);
     BTS_LAUNCH_CHECK();
-  } else if (use_wgw) {
+  } else if (form != BTS_FORM_DIRECT) {
     static bool wattr = false;
     if (!wattr) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

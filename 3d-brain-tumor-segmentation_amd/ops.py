@@ -398,6 +398,13 @@ def conv_bwd_weight(kind, x, dy, dw, db, dup_start=0, dup_shift=0, accumulate=Fa
                    cout, ld_of(dy), dup_start, dup_shift, 1 if accumulate else 0, _stream())
 
 
+def conv_bwd_weight_form(kind, x, dy):
+    """the form conv_bwd_weight takes for these operands (host-only query): 0 direct | 2 Winograd over (z, y) | 3 Winograd over all axes"""
+    n, d, h, w, cin = x.shape
+    aligned = (1 if x.data_ptr() % 16 == 0 else 0) | (2 if dy.data_ptr() % 16 == 0 else 0)
+    return lib().probe('bts_conv3d_bwd_weight_form', kind, n, d, h, w, cin, ld_of(x), dy.shape[4], ld_of(dy), aligned)
+
+
 def gn_stats(x, groups, mode, eps=1e-5):
     """x dense [N,D,H,W,C] -> (mean, rstd) each (N*G,)"""
     if not x.is_contiguous():

@@ -119,6 +119,11 @@ long bts_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int C
 int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, float* dw, float* db, void* workspace,
                           long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy,
                           int dup_start, int dup_shift, int accumulate, bts_stream_t stream);
+/* Host only: the form bts_conv3d_bwd_weight takes for the described call -- 0 the direct kernels | 3 Winograd F(2x2x2,3x3x3), profile
+ * symbol 24 (2 stood for Winograd F(2x2,3x3) over (z,y) with x direct, which no call takes any more) -- or the negative status of a
+ * call it does not take.  aligned: bit 0 x, bit 1 dy lies on a 16-byte boundary.  The BTS_WGW environment switch is read per call, as
+ * the launch reads it. */
+int bts_conv3d_bwd_weight_form(int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int aligned);
 
 /* ===== GroupNormalization (layers/group_norm.py:83-124) ===== */
 /* Statuses, all before any launch: BTS_ERR_SHAPE for a non-positive size, C < G or G not dividing C (the queries return -1);
