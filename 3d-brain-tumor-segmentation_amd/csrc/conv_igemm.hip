@@ -1765,7 +1765,7 @@ static int launch_igemm(const ConvCall& c, const ConvChoice& ch, const ConvPtrs&
 
 // The kernel of a call, in the order the forms were always offered: 3x3x3 stride 1 -- the direct kernel (no second weight set), the
 // two-channel kernel (Cin == 2, no second input), the Winograd forms (never with the sigmoid; the second form then runs as a 1x1x1 launch
-// of its own: ch.second); 1x1x1 -- the streaming kernel; transposed -- the merged-class kernel (both without a second form); then the tiled
+// of its own: ch.second -- except the second INPUT of a large unsplit w3 launch, which w3_accept takes into the launch); 1x1x1 -- the streaming kernel; transposed -- the merged-class kernel (both without a second form); then the tiled
 // kernel, whose status is that of a call no kernel takes.
 static int conv_choose(const ConvCall& c, ConvChoice& ch) {
   ch = ConvChoice{};
@@ -2004,20 +2004,40 @@ extern "C" long bts_conv3d_bwd_data_pair_workspace(int N, int D, int H, int W, i
   if (a < 0 || b < 0) return -1;
   return a > b ? a : b;
 }
+// The 3x3x3 call of a pair: 1 -- c carries the second input (one engine call), 0 -- c is the plain 3x3x3 call and the 1x1x1 gradient is a
+// call of its own, < 0 -- a status.
+static int pair_call_of(int N, int D, int H, int W, int Cin, int lddx, int Cout, int lddy, int lddy2, int flags, bool dy2_16, ConvCall& c) {
+  if (conv_call_of(1, BTS_CONV_K3S1, N, D, H, W, Cin, lddx, Cout, lddy, flags, c) != BTS_OK || lddy2 < Cout) return BTS_ERR_SHAPE;
+  const long need = conv_ws_query(1, BTS_CONV_K3S1, N, D, H, W, Cin, Cout);
+  if (need < 0) return BTS_ERR_SHAPE;
+  const bool fuse = need == 0 && (Cout % 8 == 0) && (lddy2 % 4 == 0) && dy2_16 && Cin > 4 && getenv("BTS_IGEMM_NOPAIR") == nullptr;
+  if (fuse) { c.second = CONV_X2; c.ld2 = lddy2; }
+  return fuse;
+}
+// Host only: the convolution launches bts_conv3d_bwd_data_pair makes for the described call (bts_hip.h) -- 1: one kernel forms both
+// terms (the tiled kernel, or w3_kernel with the second input in its output side), 2: the 1x1x1 term is a launch of its own.
+extern "C" int bts_conv3d_bwd_data_pair_launches(int N, int D, int H, int W, int Cin, int lddx, int Cout, int lddy, int lddy2, int flags,
+                                                 int aligned, long workspace_bytes) {
+  ConvCall c;
+  ConvChoice ch;
+  const int fuse = pair_call_of(N, D, H, W, Cin, lddx, Cout, lddy, lddy2, flags, (aligned >> 2) & 1, c);
+  if (fuse < 0) return fuse;
+  if (!fuse) return 2;
+  c.x16 = aligned & 1; c.y16 = (aligned >> 1) & 1; c.p2_16 = 1; c.ws16 = (aligned >> 3) & 1;
+  c.ws_bytes = workspace_bytes < 0 ? LONG_MAX : workspace_bytes;
+  const int r = conv_choose(c, ch);
+  return r != BTS_OK ? r : ch.second ? 2 : 1;
+}
 extern "C" int bts_conv3d_bwd_data_pair(const float* dy, const float* wp_bwd, const float* dy2, const float* wp2_bwd, float* dx,
                                         void* workspace, long workspace_bytes, int N, int D, int H, int W, int Cin, int lddx,
                                         int Cout, int lddy, int lddy2, int flags, hipStream_t stream) {
   ConvCall c;
-  if (conv_call_of(1, BTS_CONV_K3S1, N, D, H, W, Cin, lddx, Cout, lddy, flags, c) != BTS_OK || lddy2 < Cout) return BTS_ERR_SHAPE;
-  const long need = conv_ws_query(1, BTS_CONV_K3S1, N, D, H, W, Cin, Cout);
-  if (need < 0) return BTS_ERR_SHAPE;
+  const int fuse = pair_call_of(N, D, H, W, Cin, lddx, Cout, lddy, lddy2, flags, (((uintptr_t)dy2) & 15) == 0, c);
+  if (fuse < 0) return fuse;
   c.ws_bytes = workspace_bytes;
   ConvPtrs q = {};
   q.x = dy; q.wp = wp_bwd; q.y = dx; q.ws = workspace;
-  const bool fuse = need == 0 && (Cout % 8 == 0) && (lddy2 % 4 == 0) && ((((uintptr_t)dy2) & 15) == 0) && Cin > 4 &&
-                    getenv("BTS_IGEMM_NOPAIR") == nullptr;
   if (fuse) {
-    c.second = CONV_X2; c.ld2 = lddy2;
     q.x2 = dy2; q.wp2 = wp2_bwd;
     return conv_run(c, q, stream);
   }

@@ -38,7 +38,7 @@ struct ConvChoice {
   union { WinoPlan w; UpmPlan u; IgemmPlan g; };      // the plan of `kernel` (dsc, c2, k1s: a grid that follows from the call)
   long ws;                // workspace bytes the launch uses (its split-K partials; 0: none)
   long gn_B;              // GroupNorm partial slots per (sample, group) it writes; 0: it cannot, or none asked for
-  int second;             // c.second where the kernel leaves it to a 1x1x1 launch of its own (the Winograd forms), else 0
+  int second;             // c.second where the kernel leaves it to a 1x1x1 launch of its own (the Winograd forms; w3 takes CONV_X2 itself where w3_accept says so), else 0
 };
 // the operands of a launch (NULL: absent); wp = the whole image, wp2 = the K1 image of the second form, gnp = the partial slots
 struct ConvPtrs { const float *x, *wp, *bias; float* y; const float *wp2, *bias2; float* y2; const float* x2; void* ws; double* gnp; };

@@ -50,6 +50,10 @@ struct W3Params {
   float* part;
   int nb, ntiles, tiles_per_xcd;
   int T;   // (tile, cout block) items one workgroup walks back to back
+  // second input (w3_kernel<true> only): y += 1x1x1 conv of x2 (rows of ld2, KG2 k-groups of 8 channels) with the K1 image wp2
+  const float* x2;
+  const float* wp2;
+  int ld2, KG2;
 };
 
 #define W3S 12                    // dwords per staged voxel: 8 channels + 4 pad
@@ -63,6 +67,10 @@ struct W3Params {
 // patch-relative LDS offset (dwords) of row j, column k of a plane
 #define W3OFF(j, k) ((((j) * W3LX) + ((k) & 1) * 10 + ((k) >> 1)) * W3S)
 
+// X2: the output side also forms the 1x1x1 conv of a second input over the item's own 256 voxels (a direct K2-deep GEMM on the
+// matrix pipe, in the register layout of the outputs) and adds it before the store: the data-gradient pair of a ResNet block
+// (resnet.py:118,134) in one pass over dx.
+template <bool X2>
 __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
@@ -243,10 +251,37 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
   const int ld = raw ? p.Npad : p.ldy;
   const int clim = raw ? p.Npad : p.Cout;
   const bool acc_in = p.accum && !raw;
+  // second input: the fragments of 2 k-groups per buffer -- A: lane (h, cout) reads 4 channels of its cout from the K1 image
+  // [k-group][half][Npad][4]; B: lane (h, patch) reads channels kg*8 + h*4 + 0..3 of its own voxel's row, one per oz
+  f32x4 wf[2][2], xf[2][2][2];
+  __amdgpu_buffer_rsrc_t x2r, w2r;
+  unsigned x2o[2], w2o = 0x80000000u;
+  // (always all the requests of a buffer: a k-group beyond KG2, a voxel outside the volume and a cout beyond Cout are out of range -- zeros, no traffic)
+  auto x2_req = [&](int b, int kg0) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int oz = 0; oz < 2; ++oz) xf[b][k][oz] = bufload(x2r, kg0 + k < p.KG2 ? x2o[oz] : 0x80000000u, (unsigned)(kg0 + k) * 32u);
+  };
+  auto w2_req = [&](int b, int kg0) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) wf[b][k] = bufload(w2r, kg0 + k < p.KG2 ? w2o : 0x80000000u, (unsigned)(kg0 + k) * (unsigned)(p.Npad * 32));
+  };
   auto finish = [&](const Item& o, int bslot) {
     const float* obase = raw ? p.part + ((long)blockIdx.z * p.N + o.n) * p.D * p.H * p.W * (long)p.Npad
                              : p.y + (long)o.n * p.D * p.H * p.W * (long)p.ldy;
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)obase, 0, 0x7fffffff, 0x00020000);
+    if (X2) {  // x2 (HBM) is requested here, a whole (y, x) transform ahead of its use: wave w finishes (oy, ox) = w of every patch
+      const int yy = o.ty * 4 + 2 * pty + (wave >> 1), xx = o.tx * 16 + 2 * ptx + (wave & 1), zb = o.tz * 4 + 2 * ptz;
+      x2r = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 + (long)o.n * p.D * p.H * p.W * (long)p.ld2), 0, 0x7fffffff, 0x00020000);
+      w2r = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp2, 0, (unsigned)p.KG2 * (unsigned)(p.Npad * 32), 0x00020000);
+#pragma unroll
+      for (int oz = 0; oz < 2; ++oz)
+        x2o[oz] = (xx < p.W && yy < p.H && (zb + oz) < p.D) ? (unsigned)(((((zb + oz) * p.H + yy) * p.W + xx) * p.ld2 + 4 * h) * 4) : 0x80000000u;
+      w2o = (o.cb * 32 + l32 < p.Cout) ? (unsigned)((h * p.Npad + o.cb * 32 + l32) * 16) : 0x80000000u;
+      x2_req(0, 0);
+      x2_req(1, 2);
+    }
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
 #pragma unroll
     for (int g = 0; g < 4; ++g) {  // one register quad (4 couts) of all 16 accumulators at a time
@@ -267,6 +302,11 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
         *reinterpret_cast<f32x4*>(ex + (((wave * 4 + g) * 4 + 0 + ox) * 64 + lane) * 4) = m0;
         *reinterpret_cast<f32x4*>(ex + (((wave * 4 + g) * 4 + 2 + ox) * 64 + lane) * 4) = m1;
       }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (X2) {  // the weight fragments (L2): requested ahead of the barrier and of the old output's reads, which return behind them
+      w2_req(0, 0);
+      w2_req(1, 2);
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
@@ -291,6 +331,30 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
           const bool cok = o.cb * 32 + 8 * g + 4 * h < clim;
           old[g][oz] = bufload(yr, (acc_in && cok) ? yo[oz] + 32u * g : 0x80000000u, 0);
         }
+      // second input: out[cout][voxel] += sum_k Wp2[k][cout] * x2[voxel][k], k-groups in ascending order; where more than 4
+      // k-groups are to come, a buffer is requested again (4 k-groups on) as soon as its matrix instructions are issued
+      f32x16 a2[2];
+      if (X2) {
+        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int kg0 = 0; kg0 < p.KG2; kg0 += 4) {
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            if (b == 0 || kg0 + 2 < p.KG2) {
+#pragma unroll
+              for (int k = 0; k < 2; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                  for (int oz = 0; oz < 2; ++oz)
+                    a2[oz] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[b][k][j], xf[b][k][oz][j], (kg0 | b | k | j) ? a2[oz] : zero16, 0, 0, 0);
+            }
+            if (kg0 + 4 < p.KG2) {
+              w2_req(b, kg0 + 4 + 2 * b);
+              x2_req(b, kg0 + 4 + 2 * b);
+            }
+          }
+        }
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4 m[4];
@@ -306,6 +370,7 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
           const unsigned off = cok ? yo[oz] : 0x80000000u;
           const bool live = off != 0x80000000u;
           f32x4 w = ov[oz];
+          if (X2) w = add4(w, f32x4{a2[oz][4 * g], a2[oz][4 * g + 1], a2[oz][4 * g + 2], a2[oz][4 * g + 3]});
           if (gn_on) {   // (wave-uniform) masked positions contribute nothing to the GroupNorm sums
             const f32x4 tt = live ? w : f32x4{0.f, 0.f, 0.f, 0.f};
             gn_s2 = pk_add(pk_add(gn_s2, tt.xy), tt.zw);
@@ -350,7 +415,7 @@ __global__ __launch_bounds__(256, 1) void w3_kernel(const W3Params p) {
     const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, 0, 0x00020000);
     f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < 8; ++i) z += bufload(none, 0x80000000u + 16u * i, 0);
+    for (int i = 0; i < (X2 ? 20 : 8); ++i) z += bufload(none, 0x80000000u + 16u * i, 0);
 #pragma unroll
     for (int i = 0; i < 9; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, z), none, 0x80000000u + 16u * i, 0, 0);
     const float dummy = bias_of(cur);   // (stands for the successor's bias request of a later item)
@@ -419,10 +484,18 @@ long w3_ws_need(const ConvCall& c) {
   W3Plan q;
   return w3_enabled() && w3_plan(q, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout) ? q.need : 0;
 }
+// A second input (CONV_X2) is taken into the launch itself (ch.second = 0) where the plan does not split K, x2 can be read with
+// 16-byte requests at 31-bit offsets, and the 1x1x1 call left over would otherwise be the streaming kernel's (at least
+// BTS_IGEMM_K1S_MIN voxels); everywhere else it stays a 1x1x1 launch of its own, as for conv_wino.hip.
 bool w3_accept(const ConvCall& c, ConvChoice& ch) {
   if (!w3_enabled() || !wino_call_ok(c) || !w3_plan(ch.w, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout)) return false;
   ch.sym = 27;
-  return wino_plan_ok(c, ch);
+  if (!wino_plan_ok(c, ch)) return false;
+  const long nvox = (long)c.N * c.Di * c.Hi * c.Wi;
+  if (c.second == CONV_X2 && ch.w.ksplit == 1 && c.ld2 % 4 == 0 && c.p2_16 &&      // (whole k-groups of x2: w3_plan's Cin % 8 == 0)
+      nvox >= conv_env_long("BTS_IGEMM_K1S_MIN", 256 * 256) && ((long)c.Di * c.Hi * c.Wi + 64) * (long)c.ld2 * 4 < 0x7fffffffL)
+    ch.second = 0;
+  return true;
 }
 
 // The launch w3_accept planned.  q.wp: the K3S1 packed image; its third part starts (27 + 48) x the padded (cin, cout) pairs in
@@ -440,6 +513,8 @@ int bts_w3_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, h
   p.ksplit = pl.ksplit; p.kg_per = pl.kg_per; p.Npad = pl.nb * 32; p.part = reinterpret_cast<float*>(q.ws);
   p.nb = pl.nb; p.ntiles = N * pl.ntz * pl.nty * pl.ntx; p.tiles_per_xcd = (p.ntiles + 7) / 8;
   p.gnp = pl.gn_zt ? q.gnp : nullptr; p.gn_G = pl.gn_zt ? c.G : 0; p.gn_zt = pl.gn_zt ? pl.gn_zt : 1;
+  const bool x2 = c.second == CONV_X2 && ch.second == 0;   // (w3_accept took the second input: never with a k-split)
+  p.x2 = x2 ? q.x2 : nullptr; p.wp2 = x2 ? q.wp2 : nullptr; p.ld2 = x2 ? c.ld2 : 0; p.KG2 = x2 ? Cin / 8 : 0;
   static bool attr_done = false;
   const size_t shmem = (2 * W3BUF + W3EX + 64 + 16) * sizeof(float);
   // items per workgroup (chaining needs two stages per item): each XCD runs 32 workgroups at a time (one per CU), so a launch
@@ -461,15 +536,18 @@ int bts_w3_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, h
   }
   const long wgs_per_xcd = ((long)p.tiles_per_xcd * pl.nb + p.T - 1) / p.T;
   if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(w3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(w3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(w3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  const double flops = 2.0 * 27 * Cin * Cout * (double)N * D * H * W;
+  const double flops = 2.0 * 27 * Cin * Cout * (double)N * D * H * W;   // (the 3x3x3 call's; a fused second input's 1/27th more is not counted)
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(27, flops, stream);
   (void)hipGetLastError();
-  hipLaunchKernelGGL(w3_kernel, dim3((unsigned)(8L * wgs_per_xcd), 1, pl.ksplit), dim3(256), shmem, stream, p);
+  if (x2) hipLaunchKernelGGL(w3_kernel<true>, dim3((unsigned)(8L * wgs_per_xcd), 1, 1), dim3(256), shmem, stream, p);
+  else hipLaunchKernelGGL(w3_kernel<false>, dim3((unsigned)(8L * wgs_per_xcd), 1, pl.ksplit), dim3(256), shmem, stream, p);
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
   if (pl.ksplit == 1) return BTS_OK;

@@ -114,6 +114,13 @@ int bts_conv3d_bwd_data_config(int kind, int N, int D, int H, int W, int Cin, in
  * environment switches are read per call, as the launches read them. */
 int bts_conv3d_kernel(int dir, int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int ldy, int flags, int second,
                       int ld2, int G, int aligned, long workspace_bytes);
+/* Host only: the convolution launches bts_conv3d_bwd_data_pair makes for the described call -- 1: one kernel forms both terms (the
+ * tiled kernel, or the Winograd F(2x2x2,3x3x3) kernel with the 1x1x1 term in its output side), 2: the 1x1x1 term is a launch of its
+ * own (two calls, or a Winograd kernel that leaves it over) -- or the negative status of a call no kernel takes.  Sizes, strides and
+ * flags as bts_conv3d_bwd_data_pair's.  aligned: bit 0 dy, 1 dx, 2 dy2, 3 the workspace lies on a 16-byte boundary.  workspace_bytes:
+ * what the call may use, 0 none, < 0 as much as it asks for.  The environment switches are read per call, as the launch reads them. */
+int bts_conv3d_bwd_data_pair_launches(int N, int D, int H, int W, int Cin, int lddx, int Cout, int lddy, int lddy2, int flags,
+                                      int aligned, long workspace_bytes);
 long bts_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout);
 /* dw in the reference layout (Cin_ref = Cin + dup_shift); db (may be NULL; not produced for K3S2T: use bts_colsum). */
 int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, float* dw, float* db, void* workspace,
