@@ -757,16 +757,38 @@ __global__ __launch_bounds__(256) void wgrad_finalize_flat_kernel(const WfinPara
 
 static int ilog2w(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-struct WgradPlan {
-  WgradParams p;
+// ---- ONE choice per call: which kernel takes it, on which grid, and where its workspace areas lie.  wgrad_choose makes it; the
+// queries and the launch answer from it ----
+struct WgCall {           // kind, shape, strides (elements) and what the operands allow -- no pointers
+  int kind;
+  int N, D, H, W;         // the forward INPUT dims
+  int Cin, ldx, Cout, lddy;      // Cin: the slab (folded) count
+  int dup_shift;
+  int want_db;
+  int x16, dy16;          // x / dy on a 16-byte boundary
+};
+struct WgradRoles {
+  int ntaps, s, neg, swapped, transposed;
+  int Dp, Hp, Wp, Cp, Dq, Hq, Wq, Cq;
+};
+struct WgChoice {
+  WgradRoles ro;
+  WgradParams p;          // as planned, without its pointers
   int nsp, npct, nqct;
   size_t shmem;
-  long partial_floats;
-  long partial_b_doubles;
+  int variant;            // staging of wgrad_kernel: 0 register | 1 LDS-DMA | 2, 3 the fixed-geometry sweeps (stride 1, 2)
+  int sym;                // profile symbol of the kernel that runs: 100 | 104 | 109 | 110 wgrad_kernel of `variant` (100 + (MODE << 2 | FIXG)) |
+                          // 24 wgw_kernel | 26 k1w_kernel
+  long NV;                // voxels of Q: the contraction length
+  double flops;           // what the launch is profiled with
+  int clear_zeros;        // the kernel reads the zero tail: the padding lanes of the general LDS-DMA staging (104) only
+  // workspace, byte offsets: partials | bias partials | column sums of dy (swapped form's db; colsum_bytes of them) | 64 zero bytes; ws: all
+  long ws_partial, ws_partial_b, ws_colsum, colsum_bytes, ws_zeros, ws;
 };
 
-// neg: tap offsets are negated (swapped-role form, s == 1 only)
-static int plan_wgrad(WgradPlan& pl, int ntaps, int s, int neg, int N, int Dp, int Hp, int Wp_, int Cp, int Dq, int Hq,
+// Tiling and K-split of the roles: pl.p (no pointers, no strides), nsp / npct / nqct, shmem.  neg: tap offsets are negated (swapped-role
+// form, s == 1 only)
+static int plan_wgrad(WgChoice& pl, int ntaps, int s, int neg, int N, int Dp, int Hp, int Wp_, int Cp, int Dq, int Hq,
                       int Wq, int Cq) {
   WgradParams& p = pl.p;
   p.N = N; p.Dp = Dp; p.Hp = Hp; p.Wp = Wp_; p.Cp = Cp;
@@ -841,8 +863,6 @@ static int plan_wgrad(WgradPlan& pl, int ntaps, int s, int neg, int N, int Dp, i
     p.sub_per_wg = (int)((p.nsub + best - 1) / best);
     pl.nsp = (p.nsub + p.sub_per_wg - 1) / p.sub_per_wg;
   }
-  pl.partial_floats = (long)pl.nsp * pl.npct * pl.nqct * p.ntiles * 1024;
-  pl.partial_b_doubles = (long)pl.nsp * pl.nqct * 32;
   return BTS_OK;
 }
 
@@ -1232,11 +1252,6 @@ __global__ __launch_bounds__(K1W_THREADS, 2) void k1w_kernel(const WgradParams p
   }
 }
 
-struct WgradRoles {
-  int ntaps, s, neg, swapped, transposed;
-  int Dp, Hp, Wp, Cp, Dq, Hq, Wq, Cq;
-};
-
 static int wgrad_roles(WgradRoles& r, int kind, int D, int H, int W, int Cin, int Cout) {
   r.ntaps = (kind == BTS_CONV_K1) ? 1 : 27;
   r.s = 1; r.neg = 0; r.swapped = 0; r.transposed = 0;
@@ -1253,83 +1268,85 @@ static int wgrad_roles(WgradRoles& r, int kind, int D, int H, int W, int Cin, in
   return BTS_OK;
 }
 
-// The kernel variant of a planned call: 0 register staging | 1 LDS-DMA staging | 2, 3 the fixed-geometry sweeps (stride 1, 2).
-// vec: both operands are 16-byte granular (leading dimensions, channel counts, base addresses).  Drops p.fastf / p.fixg where
-// the 32-bit staging offsets would not reach.
-static int wgrad_variant(WgradParams& p, bool vec) {
-  if (p.fastf && ((double)p.IZ * p.Hp * p.Wp * p.ldp * 4.0 >= 4.0e9 || (double)p.TZ * p.Hq * p.Wq * p.ldq * 4.0 >= 4.0e9 || !vec))
-    p.fastf = p.fixg = 0;
-  return !vec ? 0 : (p.fastf ? 1 + p.fixg : 1);
-}
-// The form that takes the call: stride-1 whole-tile layers run in Winograd form, all three axes (BTS_FORM_WG3); BTS_WGW=0: the
-// direct fixed-geometry kernel, which also takes everything else.  (BTS_FORM_WG2, Winograd over (z, y) with x direct, was the form
-// before and lost at every layer shape: DESIGN section 9.)  The switch is read per call: tests and A/B runs toggle it.
-enum { BTS_FORM_DIRECT = 0, BTS_FORM_WG2 = 2, BTS_FORM_WG3 = 3 };
-static int wgrad_form(const WgradParams& p, const WgradRoles& ro, int variant) {
-  if (variant != 2 || ro.ntaps != 27 || ro.s != 1) return BTS_FORM_DIRECT;
-  const char* e = getenv("BTS_WGW");
-  if (e && atoi(e) == 0) return BTS_FORM_DIRECT;
-  if (!(5.0 * p.Hp * p.Wp * p.ldp * 4.0 < 2.0e9 && 3.0 * p.Hq * p.Wq * p.ldq * 4.0 < 2.0e9)) return BTS_FORM_DIRECT;  // 31-bit tile offsets
-  return BTS_FORM_WG3;
-}
-
 extern "C" int bts_colsum(const float* x, float* out, void* workspace, long workspace_bytes, int N, long rows, int C,
                           int ld, float scale, int sum_over_n, int accumulate, hipStream_t stream);
 extern "C" long bts_colsum_workspace(int N, long rows, int C);
 
-// workspace bytes for bts_conv3d_bwd_weight; (D,H,W) are the forward INPUT dims, Cin the slab (folded) count
+static bool wg_switch_on(const char* name) {      // (read per call: tests and A/B runs toggle them)
+  const char* e = getenv(name);
+  return !(e && atoi(e) == 0);
+}
+
+// The status bts_conv3d_bwd_weight returns for the call before it looks at its workspace, and for BTS_OK the choice.
+static int wgrad_choose(const WgCall& c, WgChoice& ch) {
+  WgradRoles& ro = ch.ro;
+  int r = wgrad_roles(ro, c.kind, c.D, c.H, c.W, c.Cin, c.Cout);
+  if (r != BTS_OK) return r;
+  if (c.dup_shift > 0 && (c.kind == BTS_CONV_K3S2 || c.kind == BTS_CONV_K3S2T)) return BTS_ERR_UNSUPPORTED;
+  r = plan_wgrad(ch, ro.ntaps, ro.s, ro.neg, c.N, ro.Dp, ro.Hp, ro.Wp, ro.Cp, ro.Dq, ro.Hq, ro.Wq, ro.Cq);
+  if (r != BTS_OK) return r;
+  WgradParams& p = ch.p;
+  const bool pIsDy = ro.transposed || ro.swapped;
+  p.p = p.q = p.zeros = nullptr; p.partial = nullptr; p.partial_b = nullptr;      // (the launch's to fill in)
+  p.ldp = pIsDy ? c.lddy : c.ldx;
+  p.ldq = pIsDy ? c.ldx : c.lddy;
+  // bias gradient = column sums of dy: dy is Q in the plain form only (the swapped form's comes from bts_colsum, the transposed has none)
+  p.want_bias = (c.want_db && !pIsDy) ? 1 : 0;
+  ch.ws_partial = 0;      // [nsp][npct][nqct][ntiles][32][32] floats, then [nsp][nqct][32] doubles
+  ch.ws_partial_b = (long)ch.nsp * ch.npct * ch.nqct * p.ntiles * 1024 * 4;
+  ch.ws_colsum = (ch.ws_partial_b + (long)ch.nsp * ch.nqct * 32 * 8 + 256 + 15) & ~15L;
+  ch.colsum_bytes = ro.swapped ? bts_colsum_workspace(c.N, (long)c.D * c.H * c.W, c.Cout) : 0;
+  ch.ws = ch.ws_colsum + ch.colsum_bytes + 128;
+  ch.ws_zeros = (ch.ws - 64) & ~15L;
+  // both operands 16-byte granular (leading dimensions, channel counts, base addresses)?  Without that, register staging; the fast
+  // staging (p.fastf / p.fixg) also goes where its 32-bit offsets would not reach.
+  const bool vec = (p.ldp % 4 == 0) && (p.Cp % 4 == 0) && (p.ldq % 4 == 0) && (p.Cq % 4 == 0) && c.x16 && c.dy16;
+  if (p.fastf && ((double)p.IZ * p.Hp * p.Wp * p.ldp * 4.0 >= 4.0e9 || (double)p.TZ * p.Hq * p.Wq * p.ldq * 4.0 >= 4.0e9 || !vec))
+    p.fastf = p.fixg = 0;
+  ch.variant = !vec ? 0 : (p.fastf ? 1 + p.fixg : 1);
+  static const int ksym[4] = {100, 104, 109, 110};
+  ch.sym = ksym[ch.variant];
+  ch.NV = (long)c.N * ro.Dq * ro.Hq * ro.Wq;
+  ch.flops = 2.0 * ro.ntaps * (double)ro.Cp * ro.Cq * (double)ch.NV;
+  // 1x1x1 convs on big grids, plain form: the streaming kernel (BTS_K1W=0: the staged kernel).  Stride-1 3x3x3 layers of whole
+  // sub-tiles and 32-channel groups whose tile offsets fit 31 bits: Winograd form, all three axes (BTS_WGW=0: the direct fixed sweep).
+  if (ro.ntaps == 1 && !pIsDy && p.ntiles == 1 && ch.NV >= 32768) {
+    if (wg_switch_on("BTS_K1W")) ch.sym = 26;
+  } else if (ch.variant == 2 && ro.ntaps == 27 && ro.s == 1 && wg_switch_on("BTS_WGW") &&
+             5.0 * p.Hp * p.Wp * p.ldp * 4.0 < 2.0e9 && 3.0 * p.Hq * p.Wq * p.ldq * 4.0 < 2.0e9) {
+    ch.sym = 24;
+  }
+  ch.clear_zeros = ch.sym == 104;
+  return BTS_OK;
+}
+
+static WgCall wgrad_query_call(int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int aligned) {
+  return WgCall{kind, N, D, H, W, Cin, ldx, Cout, lddy, 0, 0, aligned & 1, (aligned >> 1) & 1};
+}
+
+// workspace bytes for bts_conv3d_bwd_weight; (D,H,W) are the forward INPUT dims, Cin the slab (folded) count.  The shape alone decides.
 extern "C" long bts_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout) {
-  WgradRoles r;
-  if (wgrad_roles(r, kind, D, H, W, Cin, Cout) != BTS_OK) return -1;
-  WgradPlan pl;
-  if (plan_wgrad(pl, r.ntaps, r.s, r.neg, N, r.Dp, r.Hp, r.Wp, r.Cp, r.Dq, r.Hq, r.Wq, r.Cq) != BTS_OK) return -1;
-  const long base = ((pl.partial_floats * 4 + pl.partial_b_doubles * 8 + 256 + 15) & ~15L);
-  return base + (r.swapped ? bts_colsum_workspace(N, (long)D * H * W, Cout) : 0) + 128;
+  WgChoice ch;
+  return wgrad_choose(wgrad_query_call(kind, N, D, H, W, Cin, Cin, Cout, Cout, 3), ch) == BTS_OK ? ch.ws : -1;
 }
 
-// Host only: the form bts_conv3d_bwd_weight takes for the described call -- 0 direct | 3 Winograd F(2x2x2,3x3x3) (2, Winograd
-// F(2x2,3x3) x direct, is no longer taken) -- or the negative status of a call it does not take.  aligned: bit 0 x, bit 1 dy on a
-// 16-byte boundary.
+// Host only: the profile symbol of the kernel bts_conv3d_bwd_weight runs for the described call -- 100 | 104 | 109 | 110 wgrad_kernel
+// (register staging | LDS-DMA staging | the fixed-geometry sweeps of stride 1 | 2), 24 wgw_kernel, 26 k1w_kernel -- or the negative
+// status of a call it does not take.  aligned: bit 0 x, bit 1 dy on a 16-byte boundary.
+extern "C" int bts_conv3d_bwd_weight_kernel(int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int aligned) {
+  WgChoice ch;
+  const int r = wgrad_choose(wgrad_query_call(kind, N, D, H, W, Cin, ldx, Cout, lddy, aligned), ch);
+  return r != BTS_OK ? r : ch.sym;
+}
+
+// Host only: the form of that kernel -- 3 Winograd F(2x2x2,3x3x3) (wgw_kernel) | 0 every other -- or the negative status.
 extern "C" int bts_conv3d_bwd_weight_form(int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int aligned) {
-  WgradRoles ro;
-  int r = wgrad_roles(ro, kind, D, H, W, Cin, Cout);
-  if (r != BTS_OK) return r;
-  WgradPlan pl;
-  r = plan_wgrad(pl, ro.ntaps, ro.s, ro.neg, N, ro.Dp, ro.Hp, ro.Wp, ro.Cp, ro.Dq, ro.Hq, ro.Wq, ro.Cq);
-  if (r != BTS_OK) return r;
-  WgradParams& p = pl.p;
-  const bool pIsDy = ro.transposed || ro.swapped;
-  p.ldp = pIsDy ? lddy : ldx;
-  p.ldq = pIsDy ? ldx : lddy;
-  const bool vec = (p.ldp % 4 == 0) && (p.Cp % 4 == 0) && (p.ldq % 4 == 0) && (p.Cq % 4 == 0) && (aligned & 3) == 3;
-  return wgrad_form(p, ro, wgrad_variant(p, vec));
+  const int k = bts_conv3d_bwd_weight_kernel(kind, N, D, H, W, Cin, ldx, Cout, lddy, aligned);
+  return k < 0 ? k : (k == 24 ? 3 : 0);
 }
 
-// dw is in the reference layout with Cin_ref = Cin + dup_shift input channels; db may be null.
-extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, float* dw, float* db, void* workspace,
-                                     long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout,
-                                     int lddy, int dup_start, int dup_shift, int accumulate, hipStream_t stream) {
-  WgradRoles ro;
-  int r = wgrad_roles(ro, kind, D, H, W, Cin, Cout);
-  if (r != BTS_OK) return r;
-  if (dup_shift > 0 && (kind == BTS_CONV_K3S2 || kind == BTS_CONV_K3S2T)) return BTS_ERR_UNSUPPORTED;
-  WgradPlan pl;
-  r = plan_wgrad(pl, ro.ntaps, ro.s, ro.neg, N, ro.Dp, ro.Hp, ro.Wp, ro.Cp, ro.Dq, ro.Hq, ro.Wq, ro.Cq);
-  if (r != BTS_OK) return r;
-  const long need = bts_conv3d_bwd_weight_workspace(kind, N, D, H, W, Cin, Cout);
-  if (workspace_bytes < need || workspace == nullptr) return BTS_ERR_WORKSPACE;
-  WgradParams& p = pl.p;
-  const bool pIsDy = ro.transposed || ro.swapped;
-  p.p = pIsDy ? dy : x;
-  p.q = pIsDy ? x : dy;
-  p.ldp = pIsDy ? lddy : ldx;
-  p.ldq = pIsDy ? ldx : lddy;
-  p.partial = reinterpret_cast<float*>(workspace);
-  uintptr_t pb = (uintptr_t)(p.partial + pl.partial_floats);
-  pb = (pb + 15) & ~(uintptr_t)15;
-  p.partial_b = reinterpret_cast<double*>(pb);
-  // bias gradient = column sums of dy: dy is Q in the plain form only
-  p.want_bias = (db != nullptr && !pIsDy) ? 1 : 0;
+// p: ch.p with the call's pointers
+static int wgrad_launch(const WgChoice& ch, const WgradParams& p, hipStream_t stream) {
   typedef void (*WgKernel)(const WgradParams);
   static const WgKernel kernels[4] = {wgrad_kernel<0, 0>, wgrad_kernel<1, 0>, wgrad_kernel<2, 1>, wgrad_kernel<2, 2>};
   static bool attr_done = false;
@@ -1340,54 +1357,58 @@ extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, 
     }
     attr_done = true;
   }
-  // 64 zero bytes at the tail of the workspace feed the padding lanes of the LDS-DMA staging
-  char* ztail = reinterpret_cast<char*>(workspace) + ((need - 64) & ~15L);
-  p.zeros = reinterpret_cast<const float*>(ztail);
-  const bool glds = (p.ldp % 4 == 0) && (p.Cp % 4 == 0) && ((((uintptr_t)p.p) & 15) == 0) && (p.ldq % 4 == 0) &&
-                    (p.Cq % 4 == 0) && ((((uintptr_t)p.q) & 15) == 0);
-  const int kidx = wgrad_variant(p, glds);
-  const int form = wgrad_form(p, ro, kidx);
-  const bool prof = bts_prof_on();
-  if (glds && !p.fastf) {  // only the general LDS-DMA staging reads the zero source
-    hipError_t e = hipMemsetAsync(ztail, 0, 64, stream);
+  if (ch.clear_zeros) {
+    hipError_t e = hipMemsetAsync(const_cast<float*>(p.zeros), 0, 64, stream);
     if (e != hipSuccess) return (int)e;
   }
-  // 1x1x1 convs on big grids: streaming kernel (BTS_K1W=0: the staged kernel)
-  bool use_k1w = false;
-  const long NVall = (long)N * ro.Dq * ro.Hq * ro.Wq;
-  if (ro.ntaps == 1 && !pIsDy && p.ntiles == 1 && NVall >= 32768) {
-    const char* e = getenv("BTS_K1W");
-    use_k1w = !(e && atoi(e) == 0);
+  static bool wattr = false;
+  if (ch.sym == 24 && !wattr) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    wattr = true;
   }
-  if (use_k1w) {
-    const long chunk = (((NVall + pl.nsp - 1) / pl.nsp) + 15) & ~15L;
-    if (prof) bts_prof_begin(26, 2.0 * (double)ro.Cp * ro.Cq * (double)NVall, stream);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k1w_kernel, dim3(pl.nsp, pl.npct, pl.nqct), dim3(K1W_THREADS), 0, stream, p, NVall, chunk);
-    if (prof) bts_prof_end(stream);
-    BTS_LAUNCH_CHECK();
-  } else if (form != BTS_FORM_DIRECT) {
-    static bool wattr = false;
-    if (!wattr) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      wattr = true;
-    }
-    if (prof) bts_prof_begin(24, 2.0 * ro.ntaps * (double)ro.Cp * ro.Cq * (double)N * ro.Dq * ro.Hq * ro.Wq, stream);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(wgw_kernel, dim3(pl.nsp, pl.npct, pl.nqct), dim3(WGW_THREADS), (size_t)2 * WGW_BUF * sizeof(float), stream, p);
-    if (prof) bts_prof_end(stream);
-    BTS_LAUNCH_CHECK();
-  } else {
-  static const int ksym[4] = {100, 104, 109, 110};  // 100 + (MODE << 2 | FIXG)
-  if (prof) bts_prof_begin(ksym[kidx], 2.0 * ro.ntaps * (double)ro.Cp * ro.Cq * (double)N * ro.Dq * ro.Hq * ro.Wq, stream);
-  (void)hipGetLastError(); hipLaunchKernelGGL(kernels[kidx], dim3(pl.nsp, pl.npct, pl.nqct), dim3(WG_THREADS), pl.shmem, stream, p);
+  const dim3 grid(ch.nsp, ch.npct, ch.nqct);
+  const bool prof = bts_prof_on();
+  if (prof) bts_prof_begin(ch.sym, ch.flops, stream);
+  (void)hipGetLastError();
+  switch (ch.sym) {
+    case 26:
+      hipLaunchKernelGGL(k1w_kernel, grid, dim3(K1W_THREADS), 0, stream, p, ch.NV, (((ch.NV + ch.nsp - 1) / ch.nsp) + 15) & ~15L);
+      break;
+    case 24:
+      hipLaunchKernelGGL(wgw_kernel, grid, dim3(WGW_THREADS), (size_t)2 * WGW_BUF * sizeof(float), stream, p);
+      break;
+    default:
+      hipLaunchKernelGGL(kernels[ch.variant], grid, dim3(WG_THREADS), ch.shmem, stream, p);
+  }
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
-  }
+  return BTS_OK;
+}
+
+// dw is in the reference layout with Cin_ref = Cin + dup_shift input channels; db may be null.
+extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, float* dw, float* db, void* workspace,
+                                     long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout,
+                                     int lddy, int dup_start, int dup_shift, int accumulate, hipStream_t stream) {
+  const WgCall c{kind, N, D, H, W, Cin, ldx, Cout, lddy, dup_shift, db != nullptr, (((uintptr_t)x) & 15) == 0, (((uintptr_t)dy) & 15) == 0};
+  WgChoice ch;
+  int r = wgrad_choose(c, ch);
+  if (r != BTS_OK) return r;
+  if (workspace_bytes < ch.ws || workspace == nullptr) return BTS_ERR_WORKSPACE;
+  const WgradRoles& ro = ch.ro;
+  const bool pIsDy = ro.transposed || ro.swapped;
+  char* ws = reinterpret_cast<char*>(workspace);
+  WgradParams p = ch.p;
+  p.p = pIsDy ? dy : x;
+  p.q = pIsDy ? x : dy;
+  p.partial = reinterpret_cast<float*>(ws + ch.ws_partial);
+  p.partial_b = reinterpret_cast<double*>(((uintptr_t)(ws + ch.ws_partial_b) + 15) & ~(uintptr_t)15);      // (a workspace off its boundary)
+  p.zeros = reinterpret_cast<const float*>(ws + ch.ws_zeros);
+  r = wgrad_launch(ch, p, stream);
+  if (r != BTS_OK) return r;
   WfinParams f;
   f.partial = p.partial; f.partial_b = p.partial_b; f.dw = dw; f.db = p.want_bias ? db : nullptr;
-  f.nsp = pl.nsp; f.npct = pl.npct; f.nqct = pl.nqct; f.ntaps = ro.ntaps; f.ntiles = p.ntiles; f.cpad = p.cpad;
+  f.nsp = ch.nsp; f.npct = ch.npct; f.nqct = ch.nqct; f.ntaps = ro.ntaps; f.ntiles = p.ntiles; f.cpad = p.cpad;
   f.Cp = ro.Cp; f.Cq = ro.Cq;
   const int Cin_ref = Cin + dup_shift;
   f.sT = (long)Cin_ref * Cout;
@@ -1397,8 +1418,8 @@ extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, 
   f.shift = dup_shift;
   f.dup_start = dup_shift > 0 ? dup_start : (1 << 30);
   f.accum = accumulate;
-  long rows = (long)ro.ntaps * ro.Cp * pl.nqct;
-  if (pl.nsp <= 16) {
+  long rows = (long)ro.ntaps * ro.Cp * ch.nqct;
+  if (ch.nsp <= 16) {
     long blocks = (rows * 32 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     (void)hipGetLastError(); hipLaunchKernelGGL(wgrad_finalize_flat_kernel, dim3((int)blocks), dim3(256), 0, stream, f);
@@ -1407,10 +1428,7 @@ extern "C" int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, 
     (void)hipGetLastError(); hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(blocks), dim3(256), 0, stream, f);
   }
   BTS_LAUNCH_CHECK();
-  if (db != nullptr && ro.swapped) {  // bias gradient of the swapped form: plain column sum of dy
-    char* cw = reinterpret_cast<char*>(workspace) + ((pl.partial_floats * 4 + pl.partial_b_doubles * 8 + 256 + 15) & ~15L);
-    const long rowsv = (long)D * H * W;
-    return bts_colsum(dy, db, cw, bts_colsum_workspace(N, rowsv, Cout), N, rowsv, Cout, lddy, 1.0f, 1, accumulate, stream);
-  }
+  if (db != nullptr && ro.swapped)      // bias gradient of the swapped form: plain column sum of dy
+    return bts_colsum(dy, db, ws + ch.ws_colsum, ch.colsum_bytes, N, (long)D * H * W, Cout, lddy, 1.0f, 1, accumulate, stream);
   return BTS_OK;
 }

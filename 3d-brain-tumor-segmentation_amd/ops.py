@@ -327,9 +327,8 @@ def conv_fwd(kind, x, wp, bias, cout, out=None, sigmoid=False):
         out = torch.empty(conv_out_shape(kind, x.shape, cout), dtype=torch.float32, device=x.device)
     nb = lib().query('bts_conv3d_fwd_workspace', kind, n, d, h, w, cin, cout)
     ws = workspace(nb, x.device) if nb > 0 else None
-    if True:
-        lib().call('bts_conv3d_fwd', kind, _p(x), _p(wp), _p(bias), _p(out), _p(ws), nb, n, d, h, w, cin, ld_of(x), cout,
-                   ld_of(out), FLAG_SIGMOID if sigmoid else 0, _stream())
+    lib().call('bts_conv3d_fwd', kind, _p(x), _p(wp), _p(bias), _p(out), _p(ws), nb, n, d, h, w, cin, ld_of(x), cout,
+               ld_of(out), FLAG_SIGMOID if sigmoid else 0, _stream())
     return out
 
 
@@ -382,9 +381,8 @@ def conv_bwd_data(kind, dy, wp_bwd, dx, accumulate):
     cout = dy.shape[4]
     nb = lib().query('bts_conv3d_bwd_data_workspace', kind, n, d, h, w, cin, cout)
     ws = workspace(nb, dy.device) if nb > 0 else None
-    if True:
-        lib().call('bts_conv3d_bwd_data', kind, _p(dy), _p(wp_bwd), _p(dx), _p(ws), nb, n, d, h, w, cin, ld_of(dx), cout,
-                   ld_of(dy), FLAG_ACCUM if accumulate else 0, _stream())
+    lib().call('bts_conv3d_bwd_data', kind, _p(dy), _p(wp_bwd), _p(dx), _p(ws), nb, n, d, h, w, cin, ld_of(dx), cout,
+               ld_of(dy), FLAG_ACCUM if accumulate else 0, _stream())
     return dx
 
 
@@ -393,16 +391,25 @@ def conv_bwd_weight(kind, x, dy, dw, db, dup_start=0, dup_shift=0, accumulate=Fa
     cout = dy.shape[4]
     nb = lib().query('bts_conv3d_bwd_weight_workspace', kind, n, d, h, w, cin, cout)
     ws = workspace(nb, x.device)
-    if True:
-        lib().call('bts_conv3d_bwd_weight', kind, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nb, n, d, h, w, cin, ld_of(x),
-                   cout, ld_of(dy), dup_start, dup_shift, 1 if accumulate else 0, _stream())
+    lib().call('bts_conv3d_bwd_weight', kind, _p(x), _p(dy), _p(dw), _p(db), _p(ws), nb, n, d, h, w, cin, ld_of(x),
+               cout, ld_of(dy), dup_start, dup_shift, 1 if accumulate else 0, _stream())
+
+
+def _conv_bwd_weight_query(name, kind, x, dy):
+    n, d, h, w, cin = x.shape
+    aligned = (1 if x.data_ptr() % 16 == 0 else 0) | (2 if dy.data_ptr() % 16 == 0 else 0)
+    return lib().probe(name, kind, n, d, h, w, cin, ld_of(x), dy.shape[4], ld_of(dy), aligned)
 
 
 def conv_bwd_weight_form(kind, x, dy):
-    """the form conv_bwd_weight takes for these operands (host-only query): 0 direct | 2 Winograd over (z, y) | 3 Winograd over all axes"""
-    n, d, h, w, cin = x.shape
-    aligned = (1 if x.data_ptr() % 16 == 0 else 0) | (2 if dy.data_ptr() % 16 == 0 else 0)
-    return lib().probe('bts_conv3d_bwd_weight_form', kind, n, d, h, w, cin, ld_of(x), dy.shape[4], ld_of(dy), aligned)
+    """the form conv_bwd_weight takes for these operands (host-only query): 3 Winograd over all axes | 0 every other kernel"""
+    return _conv_bwd_weight_query('bts_conv3d_bwd_weight_form', kind, x, dy)
+
+
+def conv_bwd_weight_kernel(kind, x, dy):
+    """the profile symbol of the kernel conv_bwd_weight runs for these operands (host-only query): 100 | 104 | 109 | 110 the direct kernel's
+    variants, 24 wgw_kernel, 26 k1w_kernel"""
+    return _conv_bwd_weight_query('bts_conv3d_bwd_weight_kernel', kind, x, dy)
 
 
 def gn_stats(x, groups, mode, eps=1e-5):

@@ -126,10 +126,15 @@ long bts_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int C
 int bts_conv3d_bwd_weight(int kind, const float* x, const float* dy, float* dw, float* db, void* workspace,
                           long workspace_bytes, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy,
                           int dup_start, int dup_shift, int accumulate, bts_stream_t stream);
-/* Host only: the form bts_conv3d_bwd_weight takes for the described call -- 0 the direct kernels | 3 Winograd F(2x2x2,3x3x3), profile
- * symbol 24 (2 stood for Winograd F(2x2,3x3) over (z,y) with x direct, which no call takes any more) -- or the negative status of a
- * call it does not take.  aligned: bit 0 x, bit 1 dy lies on a 16-byte boundary.  The BTS_WGW environment switch is read per call, as
- * the launch reads it. */
+/* Host only: the profile symbol (bts_profile_get) of the kernel bts_conv3d_bwd_weight runs for the described call -- the direct kernel
+ * with 100 register staging | 104 LDS-DMA staging | 109, 110 the fixed-geometry sweeps of stride 1, 2; 24 Winograd F(2x2x2,3x3x3)
+ * (wgw_kernel); 26 the streaming 1x1x1 kernel (k1w_kernel) -- or the negative status of a call it does not take.  The counterpart of
+ * bts_conv3d_kernel: the launch, this query, bts_conv3d_bwd_weight_form and bts_conv3d_bwd_weight_workspace answer from one choice.
+ * Sizes and strides as bts_conv3d_bwd_weight's.  aligned: bit 0 x, bit 1 dy lies on a 16-byte boundary.  The BTS_WGW and BTS_K1W
+ * environment switches are read per call, as the launch reads them. */
+int bts_conv3d_bwd_weight_kernel(int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int aligned);
+/* Host only: the form of that kernel -- 3 Winograd F(2x2x2,3x3x3) where it is 24, 0 for every other (the direct kernels and the
+ * streaming 1x1x1 kernel, which bts_conv3d_bwd_weight_kernel tells apart) -- or the negative status. */
 int bts_conv3d_bwd_weight_form(int kind, int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int aligned);
 
 /* ===== GroupNormalization (layers/group_norm.py:83-124) ===== */

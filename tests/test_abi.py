@@ -71,6 +71,8 @@ def test_argument_validation_without_gpu(cdll):
     assert 'bts_conv3d_kernel' in declared_symbols()
     assert L._bts_conv3d_kernel(0, 1, 1, 128, 128, 128, 32, 32, 32, 32, 0, 0, 0, 0, 15, -1) == 27
     assert L._bts_conv3d_kernel(0, 1, 0, 128, 128, 128, 32, 32, 32, 32, 0, 0, 0, 0, 15, -1) == -1
+    # ... and its counterpart for the weight gradient: the Winograd F(2x2x2,3x3x3) form, symbol 24
+    assert 'bts_conv3d_bwd_weight_kernel' in declared_symbols() and L._bts_conv3d_bwd_weight_kernel(1, 1, 128, 128, 128, 32, 32, 32, 32, 3) == 24
     # split-K planning is host-only: the VAE's 1024->16 stride-2 conv on 16^3 needs a workspace, the 128^3 convs do not
     assert L._bts_conv3d_fwd_workspace(2, 1, 16, 16, 16, 1024, 16) > 0
     assert L._bts_conv3d_fwd_workspace(1, 1, 128, 128, 128, 32, 32) == 0

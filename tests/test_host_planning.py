@@ -369,3 +369,74 @@ def test_conv_kernel_query_sees_what_the_operands_allow(L, default_switches):
     # statuses come back as they do from the launch: odd extents under stride 2, rows narrower than the channels
     assert conv_kernel(L, FWD, 2, 1, 7, 8, 8, 32, 32) == -1 and conv_kernel(L, FWD, 1, *S, 32, 32, ldx=16) == -1
     assert conv_kernel(L, FWD, 2, 1, 8, 8, 8, 32, 32, second=Y2) == -1          # the second forms exist for 3x3x3 stride 1 only
+
+
+# ---- the fp32 weight gradient's dispatch: bts_conv3d_bwd_weight_kernel answers from the choice the launch runs on ----
+WG_DIRECT = (100, 104, 109, 110)      # wgrad_kernel: register staging | LDS-DMA staging | the fixed-geometry sweeps of stride 1 | 2
+WGW, K1W = 24, 26
+WG_SWITCHES = ('BTS_WGW', 'BTS_K1W')
+
+
+def wg_query(L, name, kind, N, D, H, W, ci, co, aligned=3, ldx=None, lddy=None):
+    """a bts_conv3d_bwd_weight_* query on dense rows unless told otherwise; aligned: bit 0 x, bit 1 dy on a 16-byte boundary"""
+    return getattr(L, '_bts_conv3d_bwd_weight_' + name)(kind, N, D, H, W, ci, ldx or ci, co, lddy or co, aligned)
+
+
+def wg_kernel(L, *a, **kw):
+    return wg_query(L, 'kernel', *a, **kw)
+
+
+@pytest.fixture
+def default_wg_switches(monkeypatch):
+    for name in WG_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    return monkeypatch
+
+
+@pytest.mark.parametrize('grid', GRIDS, ids=lambda g: '%dx%dx%dx%d' % g)
+def test_weight_gradient_kernel_query_is_deterministic_and_follows_its_switches(L, grid, default_wg_switches):
+    """every layer shape: the same kernel twice, a known symbol or a status, form 3 exactly where the kernel is wgw_kernel, and each
+    switch turns its own kernel into the direct kernel that stands behind it and changes nothing else: wgw_kernel into the fixed sweep
+    (109), k1w_kernel into the LDS-DMA staging (104) or, where a channel count is no whole 16 bytes (the 1- and 3-channel heads), into
+    the register staging (100)"""
+    seen = set()
+    for shape in layer_shapes(*grid):
+        k1w_behind = 104 if shape[5] % 4 == 0 and shape[6] % 4 == 0 else 100
+        k = wg_kernel(L, *shape)
+        assert k == wg_kernel(L, *shape), shape
+        assert k in WG_DIRECT + (WGW, K1W) or k < 0, (shape, k)
+        f = wg_query(L, 'form', *shape)
+        assert (f == 3) == (k == WGW) and f in (0, 3, k), (shape, k, f)
+        for switch, own, behind in (('BTS_WGW', WGW, 109), ('BTS_K1W', K1W, k1w_behind)):
+            default_wg_switches.setenv(switch, '0')
+            k0, f0 = wg_kernel(L, *shape), wg_query(L, 'form', *shape)
+            default_wg_switches.delenv(switch)
+            assert k0 == (behind if k == own else k), (shape, switch, k, k0)
+            assert (f0 == 3) == (k0 == WGW), (shape, switch, k0, f0)
+        seen.add(k)
+    assert {WGW, K1W, 100, 110} <= seen      # (every grid has layers of these sorts)
+
+
+def test_weight_gradient_dispatch_facts_of_the_plan_table(L, default_wg_switches):
+    """DESIGN "Dispatch plan", at 1 x 128^3 unless a shape is given"""
+    S = (1, 128, 128, 128)
+    K1, K3S1, K3S2, K3S2T = 0, 1, 2, 3
+    assert wg_kernel(L, K3S1, *S, 32, 32) == WGW
+    assert wg_kernel(L, K3S1, *S, 32, 32, aligned=2) == 100               # x off its boundary: register staging
+    assert wg_kernel(L, K3S1, *S, 32, 32, ldx=34) == 100                  # rows that are no whole 16 bytes
+    assert wg_kernel(L, K3S1, 1, 8, 8, 24, 32, 32) == 104                 # ragged W: the general LDS-DMA staging
+    assert wg_kernel(L, K3S1, 1, 2, 4, 16, 32, 32) == WGW                 # one sub-tile
+    assert wg_kernel(L, K3S1, *S, 2, 32) == 100
+    assert wg_kernel(L, K3S1, *S, 32, 2) == 100                           # the swapped form
+    assert wg_kernel(L, K3S2, *S, 32, 32) == 110
+    assert wg_kernel(L, K3S2T, 1, 64, 64, 64, 64, 32) == 110
+    assert wg_kernel(L, K1, *S, 32, 32) == K1W
+    assert wg_kernel(L, K1, 1, 16, 16, 16, 32, 32) == 104
+    assert wg_kernel(L, K1, 1, 32, 32, 32, 32, 32) == K1W                 # 32768 voxels: the threshold
+    assert wg_kernel(L, K1, 1, 32, 32, 31, 32, 32) == 104
+    # statuses come back as they do from the launch: odd extents under stride 2
+    assert wg_kernel(L, K3S2, 1, 7, 8, 8, 32, 32) == wg_query(L, 'form', K3S2, 1, 7, 8, 8, 32, 32) == -1
+    assert L._bts_conv3d_bwd_weight_workspace(K3S2, 1, 7, 8, 8, 32, 32) == -1
+    # the K-split is capped: the larger grid asks for no more workspace
+    need = L._bts_conv3d_bwd_weight_workspace(K3S1, *S, 32, 32)
+    assert need > 0 and need == L._bts_conv3d_bwd_weight_workspace(K3S1, 1, 160, 192, 160, 32, 32)
