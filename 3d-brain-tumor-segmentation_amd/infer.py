@@ -41,6 +41,10 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
     `python -m bts_amd.train --targets regions`) the channels are read as WT, TC, ET and decoded by the overwrite rule of the usual
     BraTS conversions, 4 where et >= threshold, else 1 where tc >= threshold, else 2 where wt >= threshold (bts_region_finish), to the
     same {0,1,2,4} map everything downstream takes; 'labels', the default, is the arg-max as before.
+  * the reference normalises every scan with one mean and deviation per channel of the training set (test.py:107), background included,
+    although the paper it implements normalises each scan on its own brain voxels; with a `norm` of mode 'case' (a prepro.npy written by
+    `python -m bts_amd.preprocess --norm case`, read by preprocess.load_norm) the `TestTimeAugmentor` does the latter, optionally after
+    clamping to robust percentiles (bts_case_norm), so that a scan of another intensity scale gives the same labels; off by default.
 All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_region_finish, bts_spline_prefilter3d, bts_zoom3d,
 bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, bts_components3d, bts_component_sizes,
 bts_component_largest, bts_components_apply, bts_region_relabel, bts_dilate3d, bts_lesion_pairs, bts_component_boxes, bts_lesion_crop, the
@@ -174,14 +178,25 @@ class WindowSpec(object):
             self.roi, self.overlap, self.mode, self.sigma_scale, self.batch, self.skip_empty)
 
 
+def check_norm(norm):
+    """None, or an object with .mode in ('dataset', 'case') and .clip (preprocess.NormSpec)"""
+    if norm is not None and getattr(norm, 'mode', None) not in ('dataset', 'case'):
+        raise ValueError("norm must be None or a NormSpec with mode 'dataset' or 'case', got %r" % (norm,))
+
+
 class TestTimeAugmentor(object):
     __test__ = False  # not a pytest class
 
     def __init__(self, mean, std, model, model_data_format='channels_last', spatial_tta=True, channel_tta=0, threshold=0.5,
-                 seed=0, compute_dtype='float32', tta_batch=None, window=None, targets='labels'):
+                 seed=0, compute_dtype='float32', tta_batch=None, window=None, targets='labels', norm=None):
         """compute_dtype: 'float32' (the engine's parity path) | 'float16' | 'bfloat16' -- 16-bit STORAGE of activations and
         weight images with fp32 sums (bts_amd.lowp; BASELINE configs[4] runs the forwards in fp16)
-        targets: 'labels' | 'regions' -- how the mean probabilities are decoded (`_finish_of`); the probabilities do not depend on it"""
+        targets: 'labels' | 'regions' -- how the mean probabilities are decoded (`_finish_of`); the probabilities do not depend on it
+        norm: None | a preprocess.NormSpec (anything with .mode and .clip).  None or mode 'dataset': (x - mean) / std with the statistics
+        given here, as the reference.  mode 'case': the volume is normalised on its own voxels inside `bmask` first (ops.case_norm, into
+        a new tensor: the caller's x is left as it is) and everything after runs with mean 0 and std 1; `mean` and `std` are not read"""
+        check_norm(norm)
+        self.norm = norm
         self._finish = _finish_of(targets, model)
         self.targets = targets
         if model_data_format not in ('channels_last', 'channels_first'):
@@ -216,12 +231,21 @@ class TestTimeAugmentor(object):
     def _dev(self, t, like):
         return torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(like.device).contiguous()
 
+    def _normalised(self, x, bmask):
+        """-> (x, mean, std) the rest of a call works with: in case mode the case-normalised volume and the identity"""
+        if self.norm is None or self.norm.mode != 'case':
+            return x, self.mean, self.std
+        c = x.shape[-1]
+        xn, _ = ops.case_norm(x.to(torch.float32), bmask.to(torch.float32), self.norm.clip)
+        return xn, np.zeros(c), np.ones(c)
+
     def __call__(self, x, bmask):
         """x: (D,H,W,C) raw intensities, bmask: (D,H,W,1) -> masked mean probability map (D,H,W,out_ch)"""
         if self.window is not None:
             return self._call_windowed(x, bmask)
+        x, mean, std = self._normalised(x, bmask)
         xs = x.unsqueeze(0).contiguous()
-        mean, std = self._dev(self.mean, xs), self._dev(self.std, xs)
+        mean, std = self._dev(mean, xs), self._dev(std, xs)
         acc = None
         count = len(self.flips) * (1 + self.channel_tta)
         sig = None
@@ -261,6 +285,7 @@ class TestTimeAugmentor(object):
         """__call__ with a WindowSpec: every augmented copy of every window is a job; jobs go through the network `batch` at a time
         (gather -> forward -> accumulate), weighted by the normalised importance tables, so `acc` ends as the blended mean"""
         spec = self.window
+        x, mean, std = self._normalised(x, bmask)
         xv = x.to(torch.float32).contiguous()
         mask = bmask.to(torch.float32).contiguous()
         dev, c = xv.device, xv.shape[-1]
@@ -273,8 +298,8 @@ class TestTimeAugmentor(object):
             occ = ops.window_occupancy(mask, roi, starts).cpu().numpy()              # the one read of the counts
             run = [w for w in wins if occ[w] > 0]
         self.window_counts = (len(run), len(wins) - len(run))
-        mean = torch.as_tensor(self.mean, dtype=torch.float32).reshape(-1).cpu()   # the job table is built on the host
-        std = torch.as_tensor(self.std, dtype=torch.float32).reshape(-1).cpu()
+        mean = torch.as_tensor(mean, dtype=torch.float32).reshape(-1).cpu()        # the job table is built on the host
+        std = torch.as_tensor(std, dtype=torch.float32).reshape(-1).cpu()
         sig = None
         if self.channel_tta:                          # the deviation of the WHOLE normalised volume, read once; one draw per copy
             xn = ops.flip_affine(xv.unsqueeze(0), 0, mean.to(dev).contiguous(), std.to(dev).contiguous())
@@ -323,17 +348,18 @@ class TestTimeAugmentor(object):
 
 
 def segment_volume(model, x, mask, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
-                   window=None, targets='labels'):
+                   window=None, targets='labels', norm=None):
     """test.py:246-261 for one volume: pad to the model's spatial resolution, TTA inference, crop back.
     x (D,H,W,C), mask (D,H,W,1) channels_last (test.py:109) -> (probabilities, uint8 labels (D,H,W)); the probabilities are
     (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  window: a WindowSpec -> the padded volume
-    is predicted in blended windows of that extent; targets: 'labels' | 'regions', the decode of the label map (TestTimeAugmentor)"""
+    is predicted in blended windows of that extent; targets: 'labels' | 'regions', the decode of the label map (TestTimeAugmentor);
+    norm: None | a NormSpec, how the volume is normalised (TestTimeAugmentor); in case mode over the voxels of `mask`"""
     if window is not None:
         window.check_resolution(spatial_res)
     xp, mp, orig = pad_to_spatial_res(spatial_res, x, mask)
     df = getattr(model, 'data_format', 'channels_last')
     tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch, window=window, targets=targets)
+                            tta_batch=tta_batch, window=window, targets=targets, norm=norm)
     y = tta(xp, mp)
     lab = tta.labels()
     y = y[:, :orig[0], :orig[1], :orig[2]] if df == 'channels_first' else y[:orig[0], :orig[1], :orig[2]]
@@ -435,18 +461,19 @@ class Interpolator(object):
 
 
 def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
-                 order=3, window=None, targets='labels'):
+                 order=3, window=None, targets='labels', norm=None):
     """test.py:235-264 for one scan: resample to 1 mm^3 with mask and padding in one pass, TTA inference, crop, resample back.
     image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz) -> (probabilities, uint8 labels (D,H,W)) on that grid; the probabilities
     are (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  With pixdim (1,1,1) this is
-    segment_volume with the reference's mask, bit for bit.  window: a WindowSpec, targets: 'labels' | 'regions', as in segment_volume."""
+    segment_volume with the reference's mask, bit for bit.  window: a WindowSpec, targets: 'labels' | 'regions', norm: None | a NormSpec, as
+    in segment_volume (in case mode the voxels of the resampled brain mask)."""
     if window is not None:
         window.check_resolution(spatial_res)
     interp = Interpolator(None, order=order)
     xp, mp, orig = interp.resample(image, pixdim, pad_res=spatial_res)
     df = getattr(model, 'data_format', 'channels_last')
     tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch, window=window, targets=targets)
+                            tta_batch=tta_batch, window=window, targets=targets, norm=norm)
     y = tta(xp, mp)
     if all(f == 1.0 for f in interp.factors):
         lab = tta.labels()
@@ -463,11 +490,16 @@ class StageSpec(object):
     once and kept: the 16-bit engine packs its weight images on the first forward"""
 
     def __init__(self, model, mean, std, spatial_res, spatial_tta=True, channel_tta=0, threshold=0.5, compute_dtype='float32',
-                 tta_batch=None, largest_component=False, window=None, targets='labels'):
+                 tta_batch=None, largest_component=False, window=None, targets='labels', norm=None):
         """largest_component: for a skull-stripping stage, keep only the largest connected piece of the brain it finds (segment_case);
         window: a WindowSpec -> this stage predicts blended windows of that extent (a multiple of spatial_res per axis);
         targets: 'labels' | 'regions' -- what the tumour model was trained on (train_args.pkl's `targets`), i.e. how segment_case
-        decodes its label map; a skull-stripping stage (out_ch == 1) is always 'labels'"""
+        decodes its label map; a skull-stripping stage (out_ch == 1) is always 'labels';
+        norm: None | a NormSpec (preprocess.load_norm of the stage's prepro.npy) -- how the stage's training examples were normalised, and
+        so its input here: None or mode 'dataset' with mean / std, mode 'case' on the scan's own voxels inside the mask the stage is
+        handed (TestTimeAugmentor)"""
+        check_norm(norm)
+        self.norm = norm
         _finish_of(targets, model)
         self.targets = targets
         if window is not None:
@@ -489,9 +521,10 @@ class StageSpec(object):
         """(windows run, windows skipped as empty) of the stage's last windowed call, None before one"""
         return None if self._tta is None else self._tta.window_counts
 
-    def augmentor(self, window=None):
+    def augmentor(self, window=None, norm=None):
         """the stage's TestTimeAugmentor, with the channel-TTA generator back at its seed: every case draws what a fresh augmentor
-        would (segment_scan builds one per call).  window: a WindowSpec for this call in place of the stage's own"""
+        would (segment_scan builds one per call).  window: a WindowSpec, norm: a NormSpec for this call in place of the stage's own"""
+        check_norm(norm)
         if window is not None:
             window.check_resolution(self.spatial_res)
         if self._tta is not None:
@@ -501,6 +534,7 @@ class StageSpec(object):
                                           channel_tta=self.channel_tta, threshold=self.threshold, compute_dtype=self.compute_dtype,
                                           tta_batch=self.tta_batch, targets=self.targets)
         self._tta.window = self.window if window is None else window
+        self._tta.norm = self.norm if norm is None else norm
         return self._tta
 
 
@@ -537,7 +571,7 @@ def postprocess_labels(lab, min_component_voxels=0, et_min_voxels=0, connectivit
     return out
 
 
-def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False, postprocess=None, window=None):
+def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False, postprocess=None, window=None, norm=None):
     """test.py:235-264 for one scan, with the optional skull-stripping stage (test.py:238-248): resample to 1 mm^3 padded to the first
     model's resolution, [skull model with TTA, x * (1 - p) cropped and padded again to the tumour model's resolution,] tumour model
     with TTA, crop, resample back.  tumor, skull: StageSpec; image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz)
@@ -553,7 +587,11 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
     otherwise): with the options off the dict is the one callers have always got, every value of a two-stage call a tensor.
     window: each stage predicts in windows when its StageSpec carries a WindowSpec; a WindowSpec given here takes the place of both
     stages' own for this call (checked against each stage's resolution).  After the call `stage.window_counts` is (windows run,
-    windows skipped as empty) of that stage."""
+    windows skipped as empty) of that stage.
+    norm: each stage normalises its input as its StageSpec's NormSpec says; a NormSpec given here takes the place of both stages' own for
+    this call.  In case mode a stage normalises into a tensor of its own over the mask it is handed ('mask' for the first stage,
+    'mask_repadded' for the tumour stage after skull stripping): 'x1mm' and 'x_stripped' stay the raw intensities, which is what
+    ops.skull_strip multiplies."""
     if window is not None:
         for stage in (tumor, skull):
             if stage is not None:
@@ -568,7 +606,7 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
     xp, mp, orig = interp.resample(image, pixdim, pad_res=first.spatial_res)
     stages = {'x1mm': xp, 'mask': mp, 'skull_prob': None, 'x_stripped': None, 'mask_repadded': None, 'prob_1mm': None}
     if skull is not None:
-        p = skull.augmentor(window)(xp, mp)
+        p = skull.augmentor(window, norm)(xp, mp)
         if skull.data_format == 'channels_first':
             p = p.permute(1, 2, 3, 0)
         p = p.contiguous()
@@ -583,7 +621,7 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
         xp, mp = ops.skull_strip(xp, p, mp, orig, tuple(s + res - (s % res) for s in orig))
         stages.update(x_stripped=xp, mask_repadded=mp)
     df = tumor.data_format
-    tta = tumor.augmentor(window)
+    tta = tumor.augmentor(window, norm)
     y = tta(xp, mp)
     if df == 'channels_first':
         y = y.permute(1, 2, 3, 0)

@@ -1528,6 +1528,59 @@ def prepro_crop_norm(v, yv, mean, std):
     return xo, yo
 
 
+# ---- per-case normalisation over the brain voxels ----
+def check_clip(clip, who='clip'):
+    """None | (lo, hi) with 0 <= lo <= hi <= 100 -> None | (float, float)"""
+    if clip is None:
+        return None
+    try:
+        lo, hi = (float(v) for v in clip)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be None or two percentiles (lo, hi), got %r' % (who, clip))
+    if not 0.0 <= lo <= hi <= 100.0:
+        raise ValueError('%s: percentiles must satisfy 0 <= lo <= hi <= 100, got %r' % (who, clip))
+    return lo, hi
+
+
+def case_norm(x, mask=None, clip=None, y=None, out=None):
+    """normalise one case on its own voxels: window x (T0,T1,T2,C) of a dense channels-last volume -> (xn, stats), or (xn, yn, stats)
+    with a label window y (T0,T1,T2,1) (labels >= 4 -> 3, as prepro_crop_norm).  mask: float32 window (T0,T1,T2) or (T0,T1,T2,1),
+    non-zero = inside; None: a voxel is inside when any of its channels is > 0.  clip: None or the percentiles (lo, hi) the inside values of
+    each channel are clamped to first.  xn (dense, `out` when given) = float32((clamp(x) - mean_c) / std_c) inside, evaluated in
+    float64, +0.0 outside, +0.0 throughout a channel whose deviation is 0; mean_c and std_c (population) over the inside voxels.
+    stats: 1 + 4C float64 on the device: n, then (mean, std, lo, hi) per channel.  Everything stays on the stream (bts_case_norm)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError('case_norm: x must be a (T0,T1,T2,C) window')
+    c = x.shape[3]
+    st0, st1 = _window(x, c, 'case_norm: x')
+    t0, t1, t2 = x.shape[:3]
+    clip = check_clip(clip, 'case_norm: clip')
+    mst0 = mst1 = 0
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or tuple(mask.shape) not in ((t0, t1, t2), (t0, t1, t2, 1)):
+            raise ValueError('case_norm: mask must have shape %s or %s' % ((t0, t1, t2), (t0, t1, t2, 1)))
+        mask = mask if mask.dim() == 4 else mask.unsqueeze(-1)
+        mst0, mst1 = _window(mask, 1, 'case_norm: mask')
+    yo, yst0, yst1 = None, 0, 0
+    if y is not None:
+        if not isinstance(y, torch.Tensor) or y.dim() != 4 or tuple(y.shape) != (t0, t1, t2, 1):
+            raise ValueError('case_norm: y must have shape %s' % ((t0, t1, t2, 1),))
+        yst0, yst1 = _window(y, 1, 'case_norm: y')
+        yo = torch.empty((t0, t1, t2, 1), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((t0, t1, t2, c), dtype=torch.float32, device=x.device)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (t0, t1, t2, c)
+          or not out.is_contiguous()):
+        raise ValueError('case_norm: out must be a dense float32 tensor of shape %s on the GPU' % ((t0, t1, t2, c),))
+    stats = torch.empty(1 + 4 * c, dtype=torch.float64, device=x.device)
+    nb = lib().query('bts_case_norm_workspace', c)
+    ws = workspace(nb, x.device)
+    lo, hi = clip if clip is not None else (0.0, 100.0)
+    lib().call('bts_case_norm', _p(x), st0, st1, _p(mask), mst0, mst1, _p(y), yst0, yst1, t0, t1, t2, c, 1 if clip is not None else 0,
+               lo, hi, _p(out), _p(yo), _p(stats), _p(ws), nb, _stream())
+    return (out, stats) if y is None else (out, yo, stats)
+
+
 # ---- non-default samplers (SURVEY 8 f-4) ----
 def maxpool2_fwd(x):
     n, d, h, w, c = x.shape

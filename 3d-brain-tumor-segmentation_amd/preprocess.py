@@ -1,6 +1,7 @@
 """Dataset preprocessing on the device: folders of NIfTI scans -> train-ready examples (reference preprocess.py:12-131).
 
     python -m bts_amd.preprocess --in_locs a,b --modalities t1ce,flair --truth seg [--create_val] [--out_loc ./data]
+                                 [--norm dataset|case] [--clip_percentiles LO,HI]
 
 The names, the argument order and the results are the reference's: `create_dataset` finds the bounding box of all non-zero voxels
 of all cases and crops every case to it, `compute_norm` gives the per-channel mean and standard deviation of the training cases,
@@ -24,9 +25,13 @@ Deviations:
     volumes in float64; on real scans the totals pass 2^24 and that float32 sum is inexact, so its mean differs from ours in the
     low digits.  On integer-valued volumes whose per-volume totals stay below 2^24 the two are bit-equal;
   * the label rule is applied by the kernel that writes the example, not to the resident volume (`remap_labels` is the eager form);
-  * examples are stored as `.npz` files with the arrays `x` and `y`, the form data.prepare_dataset reads, not as TFRecords.
+  * examples are stored as `.npz` files with the arrays `x` and `y`, the form data.prepare_dataset reads, not as TFRecords;
+  * --norm case (off by default) normalises every case on its own brain voxels instead, as the paper the model comes from does, with
+    --clip_percentiles LO,HI after clamping them to robust percentiles (`normalize_case`, ops.case_norm, csrc/casenorm.hip); prepro.npy
+    then records the mode, and `python -m bts_amd.test` normalises each scan the same way (`load_norm`).
 """
 import argparse
+import collections
 import glob
 import os
 import shutil
@@ -168,6 +173,14 @@ def normalize_example(x, y, mean, std):
     return ops.prepro_crop_norm(x, y, m, s)
 
 
+def normalize_case(x, y, clip=None):
+    """device views x (h,w,d,c), y (h,w,d,1) of ONE case -> dense device (x normalised on the case's own brain voxels, y with labels
+    >= 4 -> 3): zero mean and unit deviation per channel over the voxels where any channel is > 0 (the brain mask of test.py:53-54),
+    after clamping them to the percentiles clip = (lo, hi) when given; 0 outside the mask (ops.case_norm, one call, no host round trip)"""
+    xn, yn, _ = ops.case_norm(x, None, clip, y=y)
+    return xn, yn
+
+
 def make_dirs(out_loc):
     """the folders of PreproArgParser.parse_args (args.py:72-81): out_loc is replaced if it exists -> (train_loc, val_loc)"""
     if os.path.isdir(out_loc):
@@ -179,9 +192,9 @@ def make_dirs(out_loc):
     return train_loc, val_loc
 
 
-def _write(folder, x, y, mean_d, std_d):
+def _write(folder, x, y, mean_d, std_d, norm='dataset', clip=None):
     for i, (xv, yv) in enumerate(zip(x, y), 1):
-        xn, yn = normalize_example(xv, yv, mean_d, std_d)
+        xn, yn = normalize_example(xv, yv, mean_d, std_d) if norm == 'dataset' else normalize_case(xv, yv, clip)
         np.savez(os.path.join(folder, '{}.npz'.format(i)), x=xn.cpu().numpy(), y=yn.cpu().numpy())
 
 
@@ -193,12 +206,24 @@ def _refuse_inputs_inside(out_loc, in_locs):
             raise ValueError('out_loc %s is replaced as a whole and contains the input folder %s' % (out_loc, loc))
 
 
-def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=None, workers=8):
+NORM_MODES = ('dataset', 'case')
+
+
+def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=None, workers=8, norm='dataset', clip=None):
     """the reference's main (preprocess.py:99-131): out_loc/train/{i}.npz, out_loc/val/{i}.npz (arrays x (h,w,d,c) and y (h,w,d,1),
     float32) and out_loc/prepro.npy -> {'size', 'mean', 'std', 'n_train', 'n_val'}
     An existing out_loc is REMOVED with everything in it and created anew before any scan is read, as the reference's argument
     parser does (args.py:73-74, `make_dirs`); an out_loc that is or contains one of `in_locs` raises ValueError and removes
-    nothing."""
+    nothing.
+    norm: 'dataset' (the default: one mean and deviation per channel over the training cases, `compute_norm`, as the reference) |
+    'case' (every case on its own brain voxels, `normalize_case`, as the paper the model comes from; `compute_norm` is not run and
+    prepro.npy records the mode with an identity mean / std, so that every reader of the file keeps working).  clip: None or the
+    percentiles (lo, hi) of a case's brain voxels its intensities are clamped to first; 'case' only."""
+    if norm not in NORM_MODES:
+        raise ValueError('norm must be one of %s, got %r' % (NORM_MODES, norm))
+    clip = ops.check_clip(clip)
+    if clip is not None and norm != 'case':
+        raise ValueError("clip needs norm='case'")
     _refuse_inputs_inside(out_loc, in_locs)
     train_loc, val_loc = make_dirs(out_loc)
     x_train, y_train, size = create_dataset(in_locs, modalities, truth, device=device, workers=workers)
@@ -209,13 +234,20 @@ def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=Non
         x_train, y_train = x_train[split:], y_train[split:]
         print('{} validation examples.'.format(len(x_val)))
     print('{} training examples.'.format(len(x_train)))
-    mean, std = compute_norm(x_train, len(modalities))
-    np.save(os.path.join(out_loc, 'prepro.npy'), {'size': size, 'norm': {'mean': mean, 'std': std}})
-    dev = x_train[0].device
-    mean_d, std_d = _stats_on(dev, mean), _stats_on(dev, std)
-    _write(train_loc, x_train, y_train, mean_d, std_d)
+    if norm == 'case':
+        if not x_train:
+            raise ValueError('preprocess needs at least one training case')
+        mean, std = np.zeros((1, 1, 1, len(modalities))), np.ones((1, 1, 1, len(modalities)))
+        np.save(os.path.join(out_loc, 'prepro.npy'), {'size': size, 'norm': {'mode': 'case', 'clip': clip, 'mean': mean, 'std': std}})
+        mean_d = std_d = None
+    else:
+        mean, std = compute_norm(x_train, len(modalities))
+        np.save(os.path.join(out_loc, 'prepro.npy'), {'size': size, 'norm': {'mean': mean, 'std': std}})
+        dev = x_train[0].device
+        mean_d, std_d = _stats_on(dev, mean), _stats_on(dev, std)
+    _write(train_loc, x_train, y_train, mean_d, std_d, norm, clip)
     if create_val:
-        _write(val_loc, x_val, y_val, mean_d, std_d)
+        _write(val_loc, x_val, y_val, mean_d, std_d, norm, clip)
     return {'size': size, 'mean': mean, 'std': std, 'n_train': len(x_train), 'n_val': len(x_val)}
 
 
@@ -231,19 +263,63 @@ def load_prepro(path):
     return size, mean, std
 
 
+NormSpec = collections.namedtuple('NormSpec', ('mode', 'clip', 'mean', 'std'))
+
+
+def load_norm(path):
+    """prepro.npy -> NormSpec(mode, clip, mean (c,), std (c,)): how the examples of that dump were normalised, and so how a scan must be
+    before the model trained on them sees it (infer.TestTimeAugmentor(norm=...)).  mode 'dataset': (x - mean) / std with the dump's
+    statistics; a file that records no mode is one.  mode 'case': ops.case_norm with `clip`; mean / std are the identity."""
+    _, mean, std = load_prepro(path)
+    nd = np.load(path, allow_pickle=True).item()['norm']
+    mode = nd.get('mode', 'dataset')
+    if mode not in NORM_MODES:
+        raise ValueError('%s: unknown normalisation mode %r' % (path, mode))
+    clip = ops.check_clip(nd.get('clip'), '%s: clip' % path)
+    if clip is not None and mode != 'case':
+        raise ValueError("%s: clip percentiles with mode %r" % (path, mode))
+    return NormSpec(mode, clip, mean, std)
+
+
+def _clip_arg(text):
+    """--clip_percentiles: LO,HI with 0 <= LO <= HI <= 100"""
+    try:
+        lo, hi = (float(v) for v in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected LO,HI (two percentiles), got %r' % (text,))
+    if not 0.0 <= lo <= hi <= 100.0:
+        raise argparse.ArgumentTypeError('expected 0 <= LO <= HI <= 100, got %r' % (text,))
+    return lo, hi
+
+
 def arg_parser():
-    """the flags of the reference's PreproArgParser (args.py:51-61)"""
+    """the flags of the reference's PreproArgParser (args.py:51-61), and --norm / --clip_percentiles"""
     p = argparse.ArgumentParser(prog='python -m bts_amd.preprocess', description=__doc__.split('\n')[0])
     p.add_argument('--in_locs', type=str, required=True, help='Comma-separated list of paths to all data folders.')
     p.add_argument('--modalities', type=str, required=True, help='Comma-separated list of all input modalities to use.')
     p.add_argument('--truth', type=str, required=True, help='Truth label pattern to use.')
     p.add_argument('--create_val', action='store_true', default=False, help='Whether to create validation set.')
     p.add_argument('--out_loc', type=str, default='./data', help='Location to write preprocessed data.')
+    # the two flags below exist in the namespace only where the command line gives them: a plain command line parses to what it
+    # always has; `norm_kwargs` supplies the defaults
+    p.add_argument('--norm', type=str, choices=NORM_MODES, default=argparse.SUPPRESS,
+                   help="'dataset': one mean and deviation per channel over the training set (default); 'case': every case on its own "
+                        'brain voxels.')
+    p.add_argument('--clip_percentiles', type=_clip_arg, default=argparse.SUPPRESS, metavar='LO,HI',
+                   help='With --norm case: clamp the brain voxels of each case to these percentiles first, e.g. 0.5,99.5.')
     return p
 
 
+def norm_kwargs(args):
+    """-> the norm / clip keyword arguments of `preprocess` the flags ask for"""
+    return {'norm': getattr(args, 'norm', 'dataset'), 'clip': getattr(args, 'clip_percentiles', None)}
+
+
 def parse_args(argv=None):
-    args = arg_parser().parse_args(argv)
+    parser = arg_parser()
+    args = parser.parse_args(argv)
+    if hasattr(args, 'clip_percentiles') and getattr(args, 'norm', 'dataset') != 'case':
+        parser.error('--clip_percentiles needs --norm case')
     args.in_locs = args.in_locs.split(',')
     args.modalities = args.modalities.split(',')
     return args
@@ -252,7 +328,7 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     print('Preprocess args: {}'.format(args))
-    r = preprocess(args.in_locs, args.modalities, args.truth, args.out_loc, create_val=args.create_val)
+    r = preprocess(args.in_locs, args.modalities, args.truth, args.out_loc, create_val=args.create_val, **norm_kwargs(args))
     print('mean {} std {}'.format(r['mean'].reshape(-1), r['std'].reshape(-1)))
     return 0
 

@@ -52,6 +52,9 @@ Deviations:
   * a model trained with `python -m bts_amd.train --targets regions` (its train_args.pkl says so; there is no flag here) is decoded
     as the nested regions WT, TC, ET (`infer.StageSpec(targets='regions')`, bts_region_finish) to the same {0,1,2,4} label map that
     post-processing, `mask.nii` and every score take; any other model by the arg-max, as before.
+  * a stage whose prepro.npy was written by `python -m bts_amd.preprocess --norm case` (the file says so; there is no flag here)
+    normalises every scan on its own brain voxels, with the recorded percentile clipping (`preprocess.load_norm`,
+    `infer.StageSpec(norm=...)`, bts_case_norm); any other file means the dataset's mean and deviation, as before.
 """
 import argparse
 import glob
@@ -66,7 +69,7 @@ import torch
 from . import nifti
 from .infer import (BRATS_REGIONS, WINDOW_MODES, Interpolator, StageSpec, WindowSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
                     scores_from_confusion, segment_case, surface_scores, zoom_output_shape)
-from .preprocess import load_prepro
+from .preprocess import load_norm
 from .train import load_checkpoint, load_train_args
 
 N_CLASSES = 4        # background + the three BraTS labels 1, 2, 4 (4 counts as class 3, preprocess.py:36)
@@ -223,7 +226,8 @@ def load_stage(folder, prepro, args, shape_1mm):
     """checkpoint folder + prepro.npy -> StageSpec: the model rebuilt from train_args.pkl's model_args (args.py:250-260), built, filled
     with load_checkpoint; spatial_res = 2 ** depth; mean / std from the prepro dump; `targets` (how the label map is decoded: the
     arg-max of a network trained on labels, or the regions WT, TC, ET of one trained with --targets regions) from train_args.pkl too,
-    'labels' where it records none.  shape_1mm: the first case's extent on the
+    'labels' where it records none; `norm` (how a scan is normalised: with the dump's mean / std, or on its own brain voxels when the dump
+    was written by `python -m bts_amd.preprocess --norm case`) from the prepro dump, one line printed per stage.  shape_1mm: the first case's extent on the
     1 mm^3 grid, the build shape (padded to the resolution) where train_args.pkl records no crop size"""
     from .model import Model
     targs = load_train_args(folder)
@@ -235,7 +239,10 @@ def load_stage(folder, prepro, args, shape_1mm):
     build = tuple(int(s) for s in crop) if crop else tuple(s + res - (s % res) for s in shape_1mm)
     model.build((1,) + build + (kw['in_ch'],))
     load_checkpoint(folder, model)
-    _, mean, std = load_prepro(prepro)
+    norm = load_norm(prepro)
+    mean, std = norm.mean, norm.std
+    print('{}: normalisation {}{}'.format(folder, norm.mode, '' if norm.clip is None else ', clipped to the percentiles %g, %g' % norm.clip),
+          flush=True)
     if mean.size != kw['in_ch']:
         raise ValueError('%s holds statistics of %d channels, the model of %s takes %d' % (prepro, mean.size, folder, kw['in_ch']))
     window = window_kwargs(args)
@@ -246,7 +253,7 @@ def load_stage(folder, prepro, args, shape_1mm):
             window['roi'] = tuple(int(s) for s in crop)
         window = WindowSpec(**window)
     return StageSpec(model, mean, std, res, spatial_tta=args.spatial_tta, channel_tta=args.channel_tta, threshold=args.threshold,
-                     compute_dtype=args.dtype, tta_batch=args.tta_batch, window=window, targets=targs.get('targets', 'labels'))
+                     compute_dtype=args.dtype, tta_batch=args.tta_batch, window=window, targets=targs.get('targets', 'labels'), norm=norm)
 
 
 def postprocess_kwargs(args):

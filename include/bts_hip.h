@@ -568,6 +568,28 @@ int bts_prepro_sums(const float* xwin, long st0, long st1, int T0, int T1, int T
 int bts_prepro_crop_norm(const float* xwin, const float* ywin, long st0, long st1, long yst0, long yst1, int T0, int T1, int T2,
                          int C, const double* mean, const double* stdv, float* xo, float* yo, bts_stream_t stream);
 
+/* ===== per-case normalisation over the voxels inside a mask, with optional percentile clipping (bts_amd.ops.case_norm) =====
+ * xwin: a window (T0,T1,T2,C) addressed as above.  mask_or_null: the same window of a fp32 (S0,S1,S2) volume with element strides
+ * mst0 / mst1, non-zero = inside; NULL: a voxel is inside when any of its channels is > 0 (test.py:53-54).  n = voxels inside.  Per
+ * channel c, with s the inside values in ascending order: with clip != 0, lo_c / hi_c = s[k] + f (s[min(k+1,n-1)] - s[k]) for
+ * h = (n-1) p / 100, k = floor(h), f = h - k and p = p_lo / p_hi, in fp64; with clip == 0, -inf / +inf.  v = clamp(double(x), lo_c, hi_c),
+ * mean_c = sum v / n, std_c = sqrt(sum (v - mean_c)^2 / n) (two passes, fp64, fixed order: the same bits in every run).
+ * xo (T0,T1,T2,C), dense, every element written = float((v - mean_c) / std_c) inside (one rounding), +0.0 outside, +0.0 throughout a
+ * channel with std_c == 0 and everywhere when n == 0.  yo (T0,T1,T2) = y >= 4 ? 3 : y of the label window ywin_or_null (strides yst0 /
+ * yst1); both may be NULL.  stats: 1 + 4 C device doubles, n then (mean, std, lo, hi) per channel; all 0 when n == 0.
+ * The order statistics are exact: a four-pass radix select on the order-preserving 32-bit key of the float, all channels and both
+ * bounds in the same passes, integer histograms.  Nothing leaves the stream; no host round trip.  Inputs are expected to be finite.
+ * workspace: device memory of exactly bts_case_norm_workspace(C) bytes (negative for C outside 1..16); nothing in it need be set.
+ * bts_case_norm_blocks(): the grid cap of the voxel-owning kernels (256 voxels per workgroup and sweep, one fp64 partial each).
+ * BTS_ERR_SHAPE, before any HIP call: C outside 1..16, a non-positive extent, a stride smaller than the rows it spans, more than
+ * 2^31 - 1 voxels, a row of 2^28 floats or more, clip with a percentile outside [0,100] or p_lo > p_hi, a NULL xwin, xo or stats, ywin
+ * without yo.  BTS_ERR_WORKSPACE: a NULL or short workspace. */
+long bts_case_norm_workspace(int C);
+int bts_case_norm_blocks(void);
+int bts_case_norm(const float* xwin, long st0, long st1, const float* mask_or_null, long mst0, long mst1, const float* ywin_or_null,
+                  long yst0, long yst1, int T0, int T1, int T2, int C, int clip, double p_lo, double p_hi, float* xo, float* yo,
+                  double* stats, void* workspace, long workspace_bytes, bts_stream_t stream);
+
 /* library identification */
 const char* bts_version(void);
 
