@@ -3,7 +3,7 @@
 // main one) stream nine tensor-sized passes -- reduce: (dout, res) and (dout, c2); apply: dout -> dres and (dout, c2) -> dc2 -- and launch
 // nine kernels; here the reduce pass reads dout, res, c2 once (GroupNorm class sums + gate sums + the per-voxel spatial-gate gradient)
 // and the apply pass reads dout, c2 once and writes dres and dc2: seven passes, five kernels (reduce, one middle launch for both finalizes, SE-MLP backward, apply).  The 16-bit engine's bts_lp_block_bwd is the
-// same idea on 16-bit tensors (lowp.hip).
+// same idea on 16-bit tensors (lowp_block.hip).
 //
 //   gate (SURVEY Appendix A'):  g = dout * res per element;  t_v = sum_c g;  ds_v = t_v sp_v (1 - sp_v)
 //                               Pch[n][c] = sum_v g;  Pw[c] = sum_v ds_v res;   dres = dout (sp + ch) + ds w_sp + dgap / V

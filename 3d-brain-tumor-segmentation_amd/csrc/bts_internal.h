@@ -2,6 +2,11 @@
 #pragma once
 #include "../../include/bts_hip.h"
 
+// version.hip: the optional in-library kernel timing -- is it on; events on the launch stream right around the launch of kernel `sym`
+int bts_prof_on();
+void bts_prof_begin(int sym, double flops, hipStream_t stream);
+void bts_prof_end(hipStream_t stream);
+
 // groupnorm.hip: mean / rstd from per-block (sum, sumsq) partials laid out [N*G][B][2] (slab semantics), fixed order
 int bts_gn_finalize_partials_(const double* partial, float* mean, float* rstd, int NG, long B, double count, float eps,
                               hipStream_t stream);

@@ -97,7 +97,7 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh /*>=4*/) {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// counter-based uniform generator of the dropout mask / the VAE's eps (pointwise.hip) and of lowp.hip's fused dropout + cast: element i of a
+// counter-based uniform generator of the dropout mask / the VAE's eps (pointwise.hip) and of lowp_point.hip's fused dropout + cast: element i of a
 // stream `seed` is a pure function of (seed, i), so every kernel that draws element i gets the same value
 __device__ __forceinline__ uint32_t mix32(uint64_t z) {  // splitmix64 finaliser
   z += 0x9E3779B97F4A7C15ull;

@@ -35,10 +35,6 @@
 
 #define MAXSLOT 8
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 struct IgemmParams {
   const float* x;
   const float* wp;

@@ -20,10 +20,6 @@
 #include "common.h"
 #include "bts_internal.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 #define WG_THREADS 512
 #define WG_WAVES 8
 #define WG_MAXT 4

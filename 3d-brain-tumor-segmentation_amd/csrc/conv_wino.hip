@@ -25,10 +25,6 @@
 #include "common.h"
 #include "conv_plan.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 #include "wino_util.h"
 
 struct WinoParams {

@@ -32,10 +32,6 @@
 #include "conv_plan.h"
 #include "wino_util.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 struct W3Params {
   const float* x;
   const float* up;

@@ -23,10 +23,6 @@
 #include "bts_internal.h"
 #include "lowp_common.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 struct LpC2Params {
   const float* x;        // (N, D, H, W, 2) fp32, dense
   const float* w3;       // (3, 3, 3, 2, F) fp32
@@ -267,12 +263,12 @@ extern "C" int bts_lp_first_block_fwd(int dtype, const float* x, const float* w3
   if (prof) bts_prof_begin(40, 2.0 * 28.0 * 2.0 * F * (double)N * V, stream);
   (void)hipGetLastError();
   const long grid = blocks < 1024 ? blocks : 1024;      // four persistent workgroups per CU
-  if (dtype == LP_F16) hipLaunchKernelGGL(lp_c2_kernel<TF16>, dim3((unsigned)grid), dim3(256), 0, stream, p, blocks);
-  else hipLaunchKernelGGL(lp_c2_kernel<TBF16>, dim3((unsigned)grid), dim3(256), 0, stream, p, blocks);
+  lp_typed(dtype, [&](auto t) { hipLaunchKernelGGL(lp_c2_kernel<decltype(t)>, dim3((unsigned)grid), dim3(256), 0, stream, p, blocks); });
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
-  if (dtype == LP_F16) hipLaunchKernelGGL(lp_c2_gap_kernel<TF16>, dim3(N), dim3(1024), 0, stream, p.xsum, w1, b1, gap, (int)tiles, F, 1.0 / (double)V);
-  else hipLaunchKernelGGL(lp_c2_gap_kernel<TBF16>, dim3(N), dim3(1024), 0, stream, p.xsum, w1, b1, gap, (int)tiles, F, 1.0 / (double)V);
+  lp_typed(dtype, [&](auto t) {
+    hipLaunchKernelGGL(lp_c2_gap_kernel<decltype(t)>, dim3(N), dim3(1024), 0, stream, p.xsum, w1, b1, gap, (int)tiles, F, 1.0 / (double)V);
+  });
   BTS_LAUNCH_CHECK();
   return bts_gn_finalize_partials_(p.gnp, mean, rstd, N * G, p.gn_B, (double)(V * F / G), eps, stream);
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "common.h"
+#include "bts_internal.h"
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -33,6 +34,12 @@ struct TBF16 {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b16x8, a), __builtin_bit_cast(b16x8, b), c, 0, 0, 0);
   }
 };
+// The trait type of a run-time dtype: f(TF16{}) for LP_F16, else f(TBF16{}) (entry points answer BTS_ERR_UNSUPPORTED for any other value
+// before they get here).  f is a generic lambda -- `[&](auto t) { using T = decltype(t); ...<T>... }` -- so a typed launch is written once.
+template <typename F> inline auto lp_typed(int dtype, F&& f) {
+  if (dtype == LP_F16) return f(TF16{});
+  return f(TBF16{});
+}
 template <typename T> __device__ __forceinline__ unsigned pack2(float a, float b) {
   return (unsigned)T::st(a) | ((unsigned)T::st(b) << 16);
 }
@@ -101,7 +108,7 @@ __device__ __forceinline__ float lp_pack_src(const LpPackParams& q, int t, int k
 }
 
 // element i of the LDS-DMA stage-order part of a K3S1 image: [cout group of CBW blocks][k-step][dz][dy*3+dx][k-half][cout in group][8 cin]
-// (lowp_s1d.hip's pack kernel and lowp.hip's batched pack)
+// (lowp_s1d.hip's pack kernel and lowp_pack.hip's batched pack)
 template <typename T> __device__ __forceinline__ void lp_s1d_pack_elem(const LpPackParams& p, int CBW, long i) {
   const int e = (int)(i & 7);
   long q = i >> 3;
@@ -211,6 +218,35 @@ struct LpGnbFuse {
   long B;
 };
 
+// ---- shared block arithmetic of the non-conv passes (lowp_norm.hip, lowp_block.hip; tests/lowp_ref.py restates it) ----
+// Chunks of one (sample, slab) unit of Lu elements for the chunked apply kernels: enough workgroups for ~16 per CU, at least 4 iterations
+// each where the unit is that long.  Returns the elements per chunk, *B = chunks per unit.
+inline long lp_chunk_per(long Lu, long units, int* B, long target = 4096) {
+  const long steps = Lu / 2048;                 // 2048-element steps of a unit
+  long b = target / units;
+  if (b > steps / 4) b = steps / 4;
+  if (b < 1) b = 1;
+  const long per = (steps + b - 1) / b;
+  *B = (int)((steps + per - 1) / per);
+  return per * 2048;
+}
+// reduce-pass workgroups per (sample, group) unit of L elements of the GroupNorm backward and the fused block backward
+inline int lp_gnb_blocks(long L) {
+  long b = L / (2048 * 16);
+  if (b < 1) b = 1;
+  if (b > 256) b = 256;
+  return (int)b;
+}
+// The tiling of lp_gn_bwd_reduce / apply and of the fused block backward's kernels: whole 2048-element steps per (sample, group) unit,
+// a power-of-two C <= 256, classes (cg = C / G) that tile a 256-thread workgroup and fit the reduce pass's four lanes per wave.
+// Outside it bts_lp_gn_bwd and bts_lp_block_bwd answer BTS_ERR_UNSUPPORTED (their argument checks come first and answer BTS_ERR_SHAPE).
+inline bool lp_gn_bwd_tiled(long V, int C, int G) {
+  if (V <= 0 || G <= 0 || C < G) return false;
+  const long E = V * C, L = E / G;
+  const int cg = C / G;
+  return E % G == 0 && L % 2048 == 0 && cg <= 32 && 256 % cg == 0 && C <= 256 && (C & (C - 1)) == 0;
+}
+
 // ---- stride-1 3x3x3 convolutions: which of the three kernels takes a call (lowp_s1z.hip, lowp_s1d.hip, lowp.hip's register-staged
 // lp_conv_s1_kernel), decided ONCE per query or launch by lp_s1_choose; the workspace queries and the entry points answer from it ----
 struct LpS1Call {         // shape, strides (elements) and requested form of one call -- no pointers
@@ -266,9 +302,29 @@ bool lp_s1_accept(const LpS1Call& c, LpS1Choice& ch);
 // BTS_OK: ch = the call's kernel.  1: no kernel takes the operand form asked for (SC, FS, gna, ysplit, ldxb); ch = the choice of the same
 // call without it.  Otherwise the status of a call no kernel takes.
 int lp_s1_choose(const LpS1Call& c, LpS1Choice& ch);
+inline bool lp_s1_same(const LpS1Choice& a, const LpS1Choice& b) { return a.kernel == b.kernel && a.ws == b.ws && a.B == b.B; }
+// the query's view of a call: dense strides, aligned operands
+inline LpS1Call lp_s1_call(int N, int D, int H, int W, int Cin, int Cout) {
+  LpS1Call c{};
+  c.N = N; c.D = D; c.H = H; c.W = W; c.Cin = Cin; c.ldx = Cin; c.Cout = Cout; c.ldy = Cout;
+  c.aligned = 1;
+  return c;
+}
+// lowp.hip: launch ch's kernel (q.wp = the whole K3S1 image)
+int lp_s1_run(int dtype, const LpS1Call& c, const LpS1Choice& ch, LpS1Ptrs q, hipStream_t stream);
 inline long lp_s1z_fs_B(const S1zPlan& pl) { return (long)pl.ntx * pl.nty * pl.nzc * 8; }      // FS column-sum rows per sample
 int bts_lp_s1z_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);     // q.wp = the DMA part
 int bts_lp_s1d_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const LpS1Ptrs& q, hipStream_t stream);
+// lowp_s1d.hip: the DMA part of a K3S1 image -- its bytes, and packing it at dst
+long bts_lp_s1d_image_bytes_(int K, int N);
+int bts_lp_s1d_pack_(int dtype, const LpPackParams& p, void* dst, hipStream_t stream);
+// lowp.hip: the finish of a split-K launch, y (+)= round(bias + sum_z part[z]) in fixed order; the _gn_ form also leaves the slab-mode
+// GroupNorm partials of the rounded y, bts_lp_splitk_gn_B_ slots per (n, group) (0: it does not take the shape)
+long bts_lp_splitk_gn_B_(int N, long V, int Cout, int G);
+int bts_lp_splitk_reduce_gn_(int dtype, const float* part, const float* bias, void* y, double* gn_partial, int N, long V, int Cout, int G,
+                             int ksplit, hipStream_t stream);
+int bts_lp_splitk_reduce_(int dtype, const float* part, const float* bias, void* y, long nvox, int Cout, int Npad, int ldy, int ksplit,
+                          int accum, hipStream_t stream);
 
 // ---- 1x1x1, stride-2 and transposed convolutions and the data gradients on those geometries: which kernel takes a call (lowp_k1.hip,
 // lowp_s2t.hip, lowp_up.hip, else lowp_gather.hip), decided ONCE per query or launch by lp_g_choose; queries and entry points answer from it ----
@@ -291,9 +347,6 @@ struct LpGChoice {
 };
 // the operands of a launch (NULL: absent); wp = the whole image, part = the partial rows: [N][rows][Cout] (want_gap) | [N*G][rows][2] (G)
 struct LpGPtrs { const void *x, *wp; const float* bias; void* y; double* part; };
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
 // the A/B switches of the family (BTS_LP_K1 | UP | S2T | GATHERQ = 0: the kernel is off and the gather kernels take its calls): read per call
 inline bool lp_switch_on(const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); }
 // true: the kernel takes the call (every switch, shape, stride, alignment and 31-bit condition of its launcher) -- its plan and rows are
@@ -311,8 +364,10 @@ int bts_lp_up_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const Lp
 // One call of the family (c's alignment flags come from q): chosen, put through the common argument check and launched.  q->part holds
 // max_rows partial rows; partials that would not fit are not asked for.  q == NULL: the query's view, aligned operands, the choice only.
 int bts_lp_g_conv_(int dtype, LpGCall c, const LpGPtrs* q, long max_rows, LpGChoice& ch, hipStream_t stream);
-// lowp.hip: out[n][c] = scale * the sum of the B partial rows [n][b][c], fixed order
+// lowp_block.hip: out[n][c] = scale * the sum of the B partial rows [n][b][c], fixed order
 int bts_lp_colsum_finalize_(const double* partial, float* out, int N, int C, int B, double scale, hipStream_t stream);
+// lowp_point.hip: db[c] (+)= the sum of the nblocks partial rows part[b][c] of row length C, block order, c < ncols (lp_dbias_finalize_kernel)
+int bts_lp_dbias_finalize_(const double* part, float* db, int ncols, int nblocks, int C, int accum, hipStream_t stream);
 
 // byte offset of the DMA part inside a K3S1 / K3S2T-forward / K3S2-data-gradient image with K contraction channels and N output columns
 inline long lp_s1d_part_offset(int K, int N) { return 27L * ((K + 15) / 16) * ((N + 31) / 32) * 1024; }

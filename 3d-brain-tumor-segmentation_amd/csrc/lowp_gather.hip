@@ -340,7 +340,7 @@ static int lp_gather_run(int dtype, const LpGCall& c, const LpGChoice& ch, const
   g.x = (const unsigned short*)q.x; g.wp = (const unsigned short*)q.wp; g.bias = q.bias; g.y = (unsigned short*)q.y;
   g.N = c.N; g.Di = c.D; g.Hi = c.H; g.Wi = c.W; g.ldx = c.ldx; g.ldy = c.ldy; g.Cout = c.Cout; g.KS = c.Cin / 16; g.NB = (c.Cout + 31) / 32;
   g.accum = c.accum; g.ncg = ch.g.ncg; g.npos = ch.g.npos; g.gap_part = q.part;
-  auto run = [&]() { return dtype == LP_F16 ? lp_gather_launch<TF16>(g, ch.g, stream) : lp_gather_launch<TBF16>(g, ch.g, stream); };
+  auto run = [&]() { return lp_typed(dtype, [&](auto t) { return lp_gather_launch<decltype(t)>(g, ch.g, stream); }); };
   if (c.geo == 0) {
     g.Dg = g.Do = c.D; g.Hg = g.Ho = c.H; g.Wg = g.Wo = c.W; g.s = 1; g.os = 1; g.ooz = g.ooy = g.oox = 0; g.ntaps = 1;
     g.taps[0] = LpTap{0, 0, 0, 0};

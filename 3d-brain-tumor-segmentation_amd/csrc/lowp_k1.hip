@@ -361,8 +361,10 @@ int bts_lp_k1_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const Lp
     if (k.cb == 2) { if (gp) hipLaunchKernelGGL((KERN<T_, 2, true>), grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL((KERN<T_, 2, false>), grid, dim3(256), 0, stream, p); } \
     else { if (gp) hipLaunchKernelGGL((KERN<T_, 1, true>), grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL((KERN<T_, 1, false>), grid, dim3(256), 0, stream, p); }        \
   } while (0)
-  if (k.lf) { if (dtype == LP_F16) K1_GO(lp_k1f_kernel, TF16); else K1_GO(lp_k1f_kernel, TBF16); }
-  else { if (dtype == LP_F16) K1_GO(lp_k1_kernel, TF16); else K1_GO(lp_k1_kernel, TBF16); }
+  lp_typed(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (k.lf) K1_GO(lp_k1f_kernel, T); else K1_GO(lp_k1_kernel, T);
+  });
 #undef K1_GO
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();

@@ -28,15 +28,6 @@
 #include "bts_internal.h"
 #include "lowp_common.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-long bts_lp_splitk_gn_B_(int N, long V, int Cout, int G);
-int bts_lp_splitk_reduce_gn_(int dtype, const float* part, const float* bias, void* y, double* gn_partial, int N, long V, int Cout, int G,
-                             int ksplit, hipStream_t stream);
-int bts_lp_splitk_reduce_(int dtype, const float* part, const float* bias, void* y, long nvox, int Cout, int Npad, int ldy, int ksplit,
-                          int accum, hipStream_t stream);
-
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct LpS1dParams {
@@ -60,7 +51,7 @@ struct LpS1dParams {
   int gn_G, gn_zt;
   long gn_B;
   // SC kernels: a second contraction at the CENTRE tap only -- y += x2 (N,D,H,W,K) . w2, the 1x1x1 image [k-step][cout block][k-half][32][8]
-  // (lowp.hip's first part of a K1 image) -- the shortcut conv's data gradient riding on conv1's (resnet.py:96-103 / 80-87 under train.py:151)
+  // (lowp_pack.hip's first part of a K1 image) -- the shortcut conv's data gradient riding on conv1's (resnet.py:96-103 / 80-87 under train.py:151)
   const unsigned short* x2;
   const unsigned short* wp2;
   int ldx2;
@@ -519,8 +510,7 @@ int bts_lp_s1d_pack_(int dtype, const LpPackParams& p0, void* dst, hipStream_t s
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   (void)hipGetLastError();
-  if (dtype == LP_F16) hipLaunchKernelGGL(lp_s1d_pack_kernel<TF16>, dim3(blocks), dim3(256), 0, stream, p, cbw, ncg);
-  else hipLaunchKernelGGL(lp_s1d_pack_kernel<TBF16>, dim3(blocks), dim3(256), 0, stream, p, cbw, ncg);
+  lp_typed(dtype, [&](auto t) { hipLaunchKernelGGL(lp_s1d_pack_kernel<decltype(t)>, dim3(blocks), dim3(256), 0, stream, p, cbw, ncg); });
   BTS_LAUNCH_CHECK();
   return BTS_OK;
 }
@@ -669,16 +659,14 @@ int bts_lp_s1d_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const
   if (split_gn) { p.gnp = nullptr; p.gn_G = 0; p.gn_zt = 1; p.gn_B = 0; }
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(33 | ((1 + pl.mode * 2 + (pl.txl == 4 ? 1 : 0)) << 16), 2.0 * (sc ? 28.0 : 27.0) * Cin * (double)Cout * (double)nvox, stream);   // (bits 16+: the variant, for bench.py's per-variant table)
-  int r;
-  if (sc) {
-    if (pl.txl == 5) r = dtype == LP_F16 ? s1d_launch_t<TF16, 1, 5, true>(p, stream) : s1d_launch_t<TBF16, 1, 5, true>(p, stream);
-    else r = dtype == LP_F16 ? s1d_launch_t<TF16, 1, 4, true>(p, stream) : s1d_launch_t<TBF16, 1, 4, true>(p, stream);
-  } else
-#define S1D_CASE(M_, X_)                                                                                                  \
-  if (pl.mode == M_ && pl.txl == X_)                                                                                      \
-    r = dtype == LP_F16 ? s1d_launch_t<TF16, M_, X_>(p, stream) : s1d_launch_t<TBF16, M_, X_>(p, stream);
-  S1D_CASE(0, 5) else S1D_CASE(1, 5) else S1D_CASE(0, 4) else S1D_CASE(1, 4) else r = BTS_ERR_UNSUPPORTED;
+  const int r = lp_typed(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (sc) return pl.txl == 5 ? s1d_launch_t<T, 1, 5, true>(p, stream) : s1d_launch_t<T, 1, 4, true>(p, stream);
+#define S1D_CASE(M_, X_) if (pl.mode == M_ && pl.txl == X_) return s1d_launch_t<T, M_, X_>(p, stream);
+    S1D_CASE(0, 5) S1D_CASE(1, 5) S1D_CASE(0, 4) S1D_CASE(1, 4)
 #undef S1D_CASE
+    return BTS_ERR_UNSUPPORTED;
+  });
   if (prof) bts_prof_end(stream);
   if (r != BTS_OK) return r;
   if (split_gn) return bts_lp_splitk_reduce_gn_(dtype, p.part, q.bias, q.y, q.gnp, N, (long)D * H * W, Cout, c.G, p.ksplit, stream);

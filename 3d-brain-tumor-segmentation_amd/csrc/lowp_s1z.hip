@@ -22,10 +22,6 @@
 #include "bts_internal.h"
 #include "lowp_common.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 template <int V> using S1zIC = std::integral_constant<int, V>;
 
@@ -726,8 +722,13 @@ int bts_lp_s1z_launch_(int dtype, const LpS1Call& c, const LpS1Choice& ch, const
     } while (0)
     const bool prof = bts_prof_on();
     if (prof) bts_prof_begin(38, 2.0 * ((double)(sc ? 28 : 27) * c.Cout + (fs ? c.Cout2 : 0)) * (double)Cin * (double)c.N * c.D * c.H * c.W, stream);
-    if (dtype == LP_F16) { if (KS == 2) S1Z_LAUNCH(TF16, 2); else S1Z_LAUNCH(TF16, 1); }
-    else { if (KS == 2) S1Z_LAUNCH(TBF16, 2); else S1Z_LAUNCH(TBF16, 1); }
+    // (the launch macro's `return` on a failed hipFuncSetAttribute leaves the lambda: its status is handed on)
+    const int lr = lp_typed(dtype, [&](auto t) -> int {
+      using T = decltype(t);
+      if (KS == 2) S1Z_LAUNCH(T, 2); else S1Z_LAUNCH(T, 1);
+      return BTS_OK;
+    });
+    if (lr != BTS_OK) return lr;
 #undef S1Z_LAUNCH
 #undef S1Z_LAUNCH_
     if (prof) bts_prof_end(stream);

@@ -211,6 +211,7 @@ int bts_lp_s2t_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const L
     BTS_LAUNCH_CHECK();
     return BTS_OK;
   };
+  // (not lp_typed: the two arms differ -- each kernel has its own once-only attribute flag, and both kernels have one pointer type)
   const int r = dtype == LP_F16 ? go(lp_s2t_kernel<TF16>, attr_done[0]) : go(lp_s2t_kernel<TBF16>, attr_done[1]);
   if (prof) bts_prof_end(stream);
   return r;

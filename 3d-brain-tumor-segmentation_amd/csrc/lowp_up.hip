@@ -362,12 +362,12 @@ int bts_lp_up_launch_(int dtype, const LpGCall& c, const LpGChoice& ch, const Lp
   p.gn_B = gn_G > 0 ? ch.rows : 0;
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(35, 2.0 * 27.0 * c.Cin * (double)c.Cout * (double)c.N * c.D * c.H * c.W, stream);
-  int r;
-#define UP_CASE(M_, X_)                                                                                               \
-  if (pl.mode == M_ && pl.txl == X_)                                                                                  \
-    r = dtype == LP_F16 ? up_launch_t<TF16, M_, X_>(p, stream) : up_launch_t<TBF16, M_, X_>(p, stream);
-  UP_CASE(0, 5) else UP_CASE(1, 5) else UP_CASE(0, 4) else UP_CASE(1, 4) else r = BTS_ERR_UNSUPPORTED;
+  const int r = lp_typed(dtype, [&](auto t) -> int {
+#define UP_CASE(M_, X_) if (pl.mode == M_ && pl.txl == X_) return up_launch_t<decltype(t), M_, X_>(p, stream);
+    UP_CASE(0, 5) UP_CASE(1, 5) UP_CASE(0, 4) UP_CASE(1, 4)
 #undef UP_CASE
+    return BTS_ERR_UNSUPPORTED;
+  });
   if (prof) bts_prof_end(stream);
   return r;
 }

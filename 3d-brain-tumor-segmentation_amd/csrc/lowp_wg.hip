@@ -8,10 +8,6 @@
 #include "bts_internal.h"
 #include "lowp_common.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 // =====================================================================================================================
 // Weight gradient of the stride-1 3x3x3 and 1x1x1 convolutions on 16-bit operands (what TF autodiff derives for the Conv3D
 // kernels of resnet.py:30-37,80-87,96-103; train.py:151):  dW[t][c][k] = sum_v P[v + off_t][c] * Q[v][k],  P = the conv's input,
@@ -569,13 +565,14 @@ static int lp_wg_launch(int dtype, const LpWgCall& c, const LpWgChoice& ch, cons
   } while (0)
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(32 | ((k3 ? 1 : 2) << 16), 2.0 * p.ntaps * (double)c.Cin * c.Cout * (double)c.N * c.D * c.H * c.W, stream);   // (variant 2: 1x1x1 -- 2 FLOP per operand byte, HBM-bound)
-  if (dtype == LP_F16) {
-    if (k3) { if (nq == 2) LPW_LAUNCH(TF16, 2, true); else LPW_LAUNCH(TF16, 1, true); }
-    else { if (nq == 2) LPW_LAUNCH(TF16, 2, false); else LPW_LAUNCH(TF16, 1, false); }
-  } else {
-    if (k3) { if (nq == 2) LPW_LAUNCH(TBF16, 2, true); else LPW_LAUNCH(TBF16, 1, true); }
-    else { if (nq == 2) LPW_LAUNCH(TBF16, 2, false); else LPW_LAUNCH(TBF16, 1, false); }
-  }
+  // (the launch macro's `return` on a failed hipFuncSetAttribute leaves the lambda: its status is handed on here)
+  const int lr = lp_typed(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (k3) { if (nq == 2) LPW_LAUNCH(T, 2, true); else LPW_LAUNCH(T, 1, true); }
+    else { if (nq == 2) LPW_LAUNCH(T, 2, false); else LPW_LAUNCH(T, 1, false); }
+    return BTS_OK;
+  });
+  if (lr != BTS_OK) return lr;
 #undef LPW_LAUNCH
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
@@ -622,6 +619,16 @@ extern "C" int bts_lp_conv3d_bwd_weight(int kind, int dtype, const void* x, cons
   if (r != BTS_OK) return r;
   if (lp_wg_choose(lp_wg_dense(c), sized) != BTS_OK || workspace_bytes < sized.ws || workspace_bytes < ch.ws) return BTS_ERR_WORKSPACE;
   return lp_wg_run(dtype, c, ch, LpWgPtrs{x, dy, dw, workspace}, db, stream);
+}
+// lp_wg_args' answer for the dense, aligned, unfolded call (conventions: bts_hip.h); the stride-1 kinds are asked with a bias gradient
+extern "C" int bts_lp_conv3d_bwd_weight_args_ok(int kind, int D, int H, int W, int Cin, int Cout) {
+  const bool strided = kind == BTS_CONV_K3S2 || kind == BTS_CONV_K3S2T;
+  if (!strided && kind != BTS_CONV_K3S1 && kind != BTS_CONV_K1) return 0;
+  if (D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
+  LpWgCall c{kind, 1, D, H, W, Cin, Cin, Cout, Cout};
+  c.want_db = strided ? 0 : 1;
+  c.aligned = 1;
+  return lp_wg_args(c, strided) == BTS_OK ? 1 : 0;
 }
 // conv1's and the shortcut's weight gradients from ONE pass over the block input (K1F: the 1x1x1 gradient is one more accumulator per wave of
 // the streaming kernel; conventions: bts_hip.h).  Query -1 / call 1 (nothing launched) where that kernel does not take the shape.

@@ -28,10 +28,6 @@
 #include "bts_internal.h"
 #include "lowp_common.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 template <int V> using WgdIC = std::integral_constant<int, V>;
@@ -498,7 +494,12 @@ int bts_lp_wgd_launch_(int dtype, const LpWgCall& c, const LpWgChoice& ch, const
   } while (0)
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(37, 2.0 * (k1f ? 28.0 : 27.0) * (double)Cp * Cq * (double)c.N * c.D * c.H * c.W, stream);
-  if (dtype == LP_F16) WGD_LAUNCH(TF16); else WGD_LAUNCH(TBF16);
+  // (the launch macro's `return` on a failed hipFuncSetAttribute leaves the lambda: its status is handed on here)
+  const int lr = lp_typed(dtype, [&](auto t) -> int {
+    WGD_LAUNCH(decltype(t));
+    return BTS_OK;
+  });
+  if (lr != BTS_OK) return lr;
 #undef WGD_LAUNCH
 #undef WGD_LAUNCH_
   if (prof) bts_prof_end(stream);

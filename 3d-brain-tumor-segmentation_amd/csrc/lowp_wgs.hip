@@ -20,10 +20,6 @@
 #include "bts_internal.h"
 #include "lowp_common.h"
 
-int bts_prof_on();
-void bts_prof_begin(int sym, double flops, hipStream_t stream);
-void bts_prof_end(hipStream_t stream);
-
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
@@ -243,8 +239,13 @@ int bts_lp_wgs_launch_(int dtype, const LpWgCall& c, const LpWgChoice& ch, const
   } while (0)
   const bool prof = bts_prof_on();
   if (prof) bts_prof_begin(36, 2.0 * 27.0 * (double)r.Cp * r.Cq * (double)c.N * r.Dc * r.Hc * r.Wc, stream);
-  if (dtype == LP_F16) { if (nq == 2) WGS_LAUNCH(TF16, 2); else WGS_LAUNCH(TF16, 1); }
-  else { if (nq == 2) WGS_LAUNCH(TBF16, 2); else WGS_LAUNCH(TBF16, 1); }
+  // (the launch macro's `return` on a failed hipFuncSetAttribute leaves the lambda: its status is handed on here)
+  const int lr = lp_typed(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (nq == 2) WGS_LAUNCH(T, 2); else WGS_LAUNCH(T, 1);
+    return BTS_OK;
+  });
+  if (lr != BTS_OK) return lr;
 #undef WGS_LAUNCH
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();

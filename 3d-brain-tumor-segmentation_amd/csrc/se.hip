@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void se_mlp_bwd_param_kernel(const double* par
                                                                float* dwsp, const double* scratch, int N, int F, int R, int accum) {
   se_mlp_bwd_param_body(partial, gap, hbuf, dw1, dw2, dwsp, scratch, N, F, R, accum, blockIdx.x);
 }
-// the per-sample pass alone (dz2, dz1 into scratch, dgap): callers that run the sums over the samples themselves (lowp.hip's tail launch)
+// the per-sample pass alone (dz2, dz1 into scratch, dgap): callers that run the sums over the samples themselves (lowp_block.hip's tail launch)
 int bts_se_mlp_bwd_sample_(const double* red, double* scratch, const float* h, const float* ch, const float* w1, const float* w2, float* dgap, int N,
                            long V, int F, int R, hipStream_t stream) {
   (void)hipGetLastError();
@@ -430,7 +430,7 @@ int bts_se_mlp_bwd_(const double* red, double* scratch, const float* gap, const 
                     hipStream_t stream) {
   return se_mlp_bwd_launch(red, gap, h, ch, w1, w2, dw1, dw2, dwsp, dgap, scratch, N, B, V, F, R, accumulate_params, stream);
 }
-// stages 2a + 2 for callers that produced the per-block partials themselves (lowp.hip: 16-bit dout / res), same layouts as above
+// stages 2a + 2 for callers that produced the per-block partials themselves (lowp_block.hip: 16-bit dout / res), same layouts as above
 int bts_se_bwd_middle_(double* partial, double* red, double* scratch, const float* gap, const float* h, const float* ch, const float* w1,
                        const float* w2, float* dw1, float* dw2, float* dwsp, float* dgap, int N, int B, long V, int F, int R,
                        int accumulate_params, hipStream_t stream) {

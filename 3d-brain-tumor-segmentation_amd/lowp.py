@@ -2,7 +2,7 @@
 model.py:67-68 / test.py:128-134; the same kernels in bf16 are the forward half of configs[2]).
 
 Activations and packed weights are 16-bit, every sum is fp32: convolutions on v_mfma_f32_32x32x16_{f16,bf16}, GroupNorm
-statistics, SE gates and the sigmoid head in fp32 from the stored values (csrc/lowp.hip).  The master weights stay the
+statistics, SE gates and the sigmoid head in fp32 from the stored values (csrc/lowp*.hip).  The master weights stay the
 model's fp32 variables; 16-bit weight images are re-packed when the weights epoch changes.  The reference has no reduced
 precision mode, so the parity reference of this path is the fp32 engine (tests/test_lowp_gpu.py).
 
@@ -12,6 +12,7 @@ level slabs.  The first block reads the 2-channel input volume: a 16-channel mat
 so the volume is stored zero-padded to 16 channels (the pad multiplies zeros on both sides).
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -160,16 +161,15 @@ def conv(kind, code, tdt, x, wp, bias, cout, out=None):
     return out
 
 
+@functools.lru_cache(maxsize=None)      # (a pure function of the shape, asked per launch)
 def wgrad_supported(kind, cin, cout, extents=None):
-    """shapes the 16-bit weight-gradient kernels take, asked before anything runs (the trainer decides the fp32 route from it).  It mirrors
-    lp_wg_args of csrc/lowp_wg.hip: channel counts in whole 16-byte chunks (BTS_ERR_SHAPE otherwise) and, for the stride-1 3x3x3 / 1x1x1
-    kinds whose bias gradient comes from bts_lp_colsum, a Cout <= 256 whose chunks divide the 256-thread block.  extents: (d, h, w) of
-    the forward input, which the stride-2 kind needs -- its transposing-read kernel takes even extents only"""
-    if kind == ops.K3S2 and any(v & 1 for v in extents):
-        return False
-    if kind in (ops.K3S2, ops.K3S2T):
-        return cin % 8 == 0 and cout % 8 == 0
-    return kind in (ops.K3S1, ops.K1) and cin % 8 == 0 and cout % 8 == 0 and cout <= 256 and ((cout // 8) & (cout // 8 - 1)) == 0
+    """shapes the 16-bit weight-gradient kernels take, asked before anything runs (the trainer decides the fp32 route from it): the
+    library's own argument rules (bts_lp_conv3d_bwd_weight_args_ok, lp_wg_args of csrc/lowp_wg.hip) -- channel counts in whole 16-byte
+    chunks and, for the stride-1 3x3x3 / 1x1x1 kinds whose bias gradient comes from bts_lp_colsum, a Cout <= 256 whose chunks divide the
+    256-thread block.  extents: (d, h, w) of the forward input, which the stride-2 kind needs -- its transposing-read kernel takes even
+    extents only; the other kinds do not read them"""
+    d, h, w = extents if extents is not None else (2, 2, 2)
+    return bool(lib().probe('bts_lp_conv3d_bwd_weight_args_ok', kind, d, h, w, cin, cout))
 
 
 def conv_bwd_weight(kind, code, x, dy, dw, db, dup_start=0, dup_shift=0, accumulate=True):
@@ -363,10 +363,12 @@ def gn_apply(code, x, gamma, beta, mean, rstd, groups, mode, relu, out=None):
     return out
 
 
+@functools.lru_cache(maxsize=None)      # (a pure function of the shape, asked per launch)
 def gn_bwd_tiled(v, c, groups):
     """does the 16-bit GroupNorm-backward tiling (bts_lp_gn_bwd and the fused passes built on it) fit v voxels of c channels in `groups`
-    slab-mode groups?  Whole 2048-element chunks per group, a power-of-two c <= 256 whose groups (<= 32 channels) divide the 256-thread block"""
-    return not ((v * c) % groups or (v * c // groups) % 2048 or c // groups > 32 or 256 % (c // groups) or c > 256 or c & (c - 1))
+    slab-mode groups?  Whole 2048-element chunks per group, a power-of-two c <= 256 whose groups (<= 32 channels) divide the 256-thread block
+    (the library's rule: bts_lp_gn_bwd_tiled)"""
+    return bool(lib().probe('bts_lp_gn_bwd_tiled', v, c, groups))
 
 
 def gn_bwd(code, tdt, x, dy, gamma, beta, mean, rstd, dgamma, dbeta, groups, relu, want_f32=True, dbias=None):

@@ -3,7 +3,7 @@
 Activations and their gradients live in HBM as bf16 (or fp16), packed weight images too; every sum is fp32 and the master
 weights, their gradients and the Adam moments stay the model's flat fp32 buffers.  Where each piece of the step runs:
 
-  forward convolutions, GroupNorm, pooling, block epilogue            16-bit kernels of csrc/lowp.hip (as bts_amd.lowp)
+  forward convolutions, GroupNorm, pooling, block epilogue            16-bit kernels of csrc/lowp*.hip (as bts_amd.lowp)
   data gradients of every convolution                                  the same kernels on role-swapped weight images
                                                                        (bts_lp_conv3d_bwd_data), accumulating into slab gradients
   weight gradients of the stride-1 3x3x3 / 1x1x1 convolutions,         16-bit kernels too (bts_lp_conv3d_bwd_weight: the contraction

@@ -658,6 +658,11 @@ int bts_lp_conv3d_bwd_weight_pair(int dtype, const void* x, long x_split, const 
  * launch: a call that returns an argument status (also for a db that cannot be produced -- BTS_ERR_UNSUPPORTED where lddy != Cout,
  * BTS_ERR_SHAPE where Cout > 256 or Cout / 8 does not divide 256) has not touched dw, whatever `accumulate` says. */
 long bts_lp_conv3d_bwd_weight_workspace(int kind, int N, int D, int H, int W, int Cin, int Cout);
+/* Host-only query, asked before anything runs (a trainer decides the fp32 route from it): 1 when the argument rules above pass for the dense,
+ * aligned, unfolded call on a (D,H,W) forward input -- channel counts in whole 16-byte chunks, even extents for BTS_CONV_K3S2, and for
+ * BTS_CONV_K3S1 / BTS_CONV_K1, whose callers ask for db, a Cout <= 256 with Cout / 8 dividing 256 -- else 0, also for an unknown kind.
+ * Not a status.  (The strided kinds are asked without the db rule: their callers always were.) */
+int bts_lp_conv3d_bwd_weight_args_ok(int kind, int D, int H, int W, int Cin, int Cout);
 int bts_lp_conv3d_bwd_weight(int kind, int dtype, const void* x, const void* dy, float* dw, float* db, void* workspace, long workspace_bytes,
                              int N, int D, int H, int W, int Cin, int ldx, int Cout, int lddy, int dup_start, int dup_shift, int accumulate,
                              bts_stream_t stream);
@@ -685,6 +690,10 @@ int bts_lp_gn_apply(int dtype, const void* x, void* y, const float* gamma, const
  * whose output this layer normalised (resnet.py:80-93: conv -> GroupNormalization), taken from the same pass.
  * BTS_ERR_UNSUPPORTED for shapes outside its tiling (group length not a multiple of 2048, C/G > 32): run bts_gn_bwd on widened copies */
 long bts_lp_gn_bwd_workspace(int N, long V, int C, int G);
+/* Host-only query: 1 when V voxels of C channels in G slab-mode groups fit that tiling (whole 2048-element steps per (sample, group), a
+ * power-of-two C <= 256, C / G <= 32 dividing 256), else 0; not a status.  The same rule holds for bts_lp_conv3d_bwd_data_gn_bwd and
+ * bts_lp_block_bwd: a caller asks it before choosing between them and the fp32 kernels. */
+int bts_lp_gn_bwd_tiled(long V, int C, int G);
 int bts_lp_gn_bwd(int dtype, const void* x, const void* dy, void* dx, float* dx32, const float* gamma, const float* beta, const float* mean,
                   const float* rstd, float* dgamma, float* dbeta, void* workspace, long workspace_bytes, int N, long V, int C, int lddy, int G,
                   int relu, int accumulate_params, float* dbias, bts_stream_t stream);

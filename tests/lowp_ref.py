@@ -1,4 +1,4 @@
-"""References, fp32 restatements and error bounds for the 16-bit NON-CONV kernels of csrc/lowp.hip: bts_lp_gn_stats, bts_lp_gn_apply,
+"""References, fp32 restatements and error bounds for the 16-bit NON-CONV kernels of csrc/lowp_norm.hip, lowp_block.hip and lowp_point.hip: bts_lp_gn_stats, bts_lp_gn_apply,
 bts_lp_colsum, bts_lp_block_epilogue, bts_lp_block_epilogue_head, bts_lp_head, bts_lp_head_bwd, the samplers and the casts.  Plain
 Python on the CPU, in the pattern of tests/step_ref.py (whose EPS32, TINY, ratio and check are used, not copied).
 
@@ -182,7 +182,7 @@ def randn32(shape, seed, sd=1.0, mean=0.0):
 
 
 # ----------------------------------------------------------------------------------------------------------------
-# the host code's block arithmetic (csrc/lowp.hip), restated: the seams and the restatements follow it
+# the host code's block arithmetic (csrc/lowp_common.h, lowp_norm.hip, lowp_block.hip), restated: the seams and the restatements follow it
 # ----------------------------------------------------------------------------------------------------------------
 def gn_blocks(L):
     return max(1, min(256, L // (256 * 8 * 8)))
@@ -198,6 +198,22 @@ def chunk_per(Lu, units, target=4096):
     b = max(1, min(target // units, steps // 4))
     per = (steps + b - 1) // b
     return per * 2048, (steps + per - 1) // per
+
+
+def gn_bwd_tiled_ref(v, c, groups):
+    """the GroupNorm-backward tiling rule as bts_amd.lowp stated it before it asked the library (bts_lp_gn_bwd_tiled)"""
+    return not ((v * c) % groups or (v * c // groups) % 2048 or c // groups > 32 or 256 % (c // groups) or c > 256 or c & (c - 1))
+
+
+def wgrad_supported_ref(kind, cin, cout, extents=None):
+    """the 16-bit weight-gradient shape rule as bts_amd.lowp stated it before it asked the library (bts_lp_conv3d_bwd_weight_args_ok);
+    kinds: K1, K3S1, K3S2, K3S2T = 0, 1, 2, 3"""
+    K1, K3S1, K3S2, K3S2T = 0, 1, 2, 3
+    if kind == K3S2 and any(v & 1 for v in extents):
+        return False
+    if kind in (K3S2, K3S2T):
+        return cin % 8 == 0 and cout % 8 == 0
+    return kind in (K3S1, K1) and cin % 8 == 0 and cout % 8 == 0 and cout <= 256 and ((cout // 8) & (cout // 8 - 1)) == 0
 
 
 def takes_chunked(n, v, c, g, mode):

@@ -8,10 +8,14 @@ What is asserted: the queries are total (no crash, no negative size other than t
 deterministic (the same answer twice) and monotone where the ABI says so (a workspace for N samples is never smaller than for one)."""
 import ctypes
 import os
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)      # tests/lowp_ref.py
 
 GRIDS = [(1, 128, 128, 128), (8, 128, 128, 128), (1, 160, 192, 160)]
 F, DEPTH, G, R = 32, 4, 8, 8
@@ -221,6 +225,61 @@ def test_weight_gradient_calls_refuse_an_impossible_bias_gradient_before_any_lau
         nb = L._bts_lp_conv3d_bwd_weight_workspace(1, N, D, H, W, ci, co)
         r = L._bts_lp_conv3d_gnin_bwd_weight(BF16, P, P, P, P, P, G, P, P, P, P, nb, N, D, H, W, ci, co, lddy, 1, None)
         assert r == want, ('gnin', co, lddy, r)
+
+
+def test_gn_bwd_tiling_query_is_the_rule_the_python_side_used_to_state(L):
+    """bts_lp_gn_bwd_tiled (the one statement of the GroupNorm-backward tiling) against tests/lowp_ref.gn_bwd_tiled_ref, the expression
+    bts_amd.lowp carried before; lowp.gn_bwd_tiled is a probe of it; outside the tiling bts_lp_gn_bwd and lowp.gn_bwd decline as ever,
+    before any launch"""
+    import lowp_ref
+    from bts_amd import lowp
+    seen = set()
+    for V in (64, 512, 2048, 4096, 4097, 32768, 128 ** 3):
+        for C in (8, 16, 24, 32, 64, 128, 256, 512):
+            for g in (1, 2, 4, 8, 16, 32):
+                if C % g:
+                    continue
+                want = bool(lowp_ref.gn_bwd_tiled_ref(V, C, g))
+                assert L._bts_lp_gn_bwd_tiled(V, C, g) == int(want), (V, C, g)
+                assert lowp.gn_bwd_tiled(V, C, g) is want, (V, C, g)
+                seen.add(want)
+                if not want and C <= 256 and not C & (C - 1):      # (other C: BTS_ERR_SHAPE, as ever)
+                    P = 0x100000
+                    r = L._bts_lp_gn_bwd(2, P, P, P, None, P, P, P, P, P, P, P, 1 << 40, 1, V, C, C, g, 1, 1, None, None)
+                    assert r == -3, (V, C, g, r)
+    assert seen == {True, False}
+
+    class FakeX(object):      # lowp.gn_bwd reads the shape, asks the rule and returns None: no tensor is touched, nothing is launched
+        shape = (1, 1, 1, 4097, 32)
+    assert lowp.gn_bwd(2, None, FakeX(), None, None, None, None, None, None, None, 8, True) is None
+
+
+def test_weight_gradient_args_query_is_the_rule_the_python_side_used_to_state(L):
+    """bts_lp_conv3d_bwd_weight_args_ok (lp_wg_args' answer for the dense, aligned, unfolded call) against
+    tests/lowp_ref.wgrad_supported_ref, the expression bts_amd.lowp carried before; lowp.wgrad_supported is a probe of it, and
+    lowp.conv_bwd_weight declines (False, nothing launched) exactly where it says no"""
+    import lowp_ref
+    from bts_amd import lowp
+    chans = (4, 8, 12, 16, 24, 32, 64, 256, 264, 512)
+    seen = set()
+    for kind in (0, 1, 2, 3):
+        for ext in ((16, 16, 16), (15, 16, 16), (16, 16, 17)):
+            for ci in chans:
+                for co in chans:
+                    want = bool(lowp_ref.wgrad_supported_ref(kind, ci, co, ext))
+                    assert L._bts_lp_conv3d_bwd_weight_args_ok(kind, ext[0], ext[1], ext[2], ci, co) == int(want), (kind, ext, ci, co)
+                    assert lowp.wgrad_supported(kind, ci, co, ext) is want, (kind, ext, ci, co)
+                    seen.add(want)
+    assert seen == {True, False}
+    assert L._bts_lp_conv3d_bwd_weight_args_ok(4, 16, 16, 16, 32, 32) == 0 and L._bts_lp_conv3d_bwd_weight_args_ok(-1, 16, 16, 16, 32, 32) == 0
+    # the kinds that do not read the extents are asked without them (the paired launch's caller)
+    assert lowp.wgrad_supported(1, 64, 32) is True and lowp.wgrad_supported(1, 64, 264) is False
+
+    class Fake(object):      # lowp.conv_bwd_weight reads the two shapes, asks the rule and returns False: nothing is launched
+        def __init__(self, *shape):
+            self.shape = shape
+    for kind, ext, ci, co in ((1, (16, 16, 16), 32, 264), (0, (16, 16, 16), 12, 32), (2, (15, 16, 16), 32, 32), (3, (16, 16, 16), 32, 12)):
+        assert lowp.conv_bwd_weight(kind, 2, Fake(1, *ext, ci), Fake(1, *ext, co), None, None) is False, (kind, ext, ci, co)
 
 
 def test_paired_weight_gradient_query_at_the_split_level0_shapes(L, monkeypatch):

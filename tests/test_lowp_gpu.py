@@ -1,4 +1,4 @@
-"""-m gpu: the reduced-precision STORAGE forward (csrc/lowp.hip, bts_amd/lowp.py; BASELINE configs[4] fp16 inference, the forward
+"""-m gpu: the reduced-precision STORAGE forward (csrc/lowp*.hip, bts_amd/lowp.py; BASELINE configs[4] fp16 inference, the forward
 half of configs[2] in bf16).  The reference has no such mode; what is checked:
 
   * every kernel against the oracle's op on the SAME 16-bit-rounded operands, evaluated in fp64: the only differences left are

@@ -1,4 +1,4 @@
-"""-m gpu: the 16-bit non-conv kernels of csrc/lowp.hip against the fp64 references of tests/lowp_ref.py, at the shapes where their
+"""-m gpu: the 16-bit non-conv kernels of csrc/lowp_norm.hip, lowp_block.hip and lowp_point.hip against the fp64 references of tests/lowp_ref.py, at the shapes where their
 two forms, their block spans, their unrolled loops and their grid caps part ways.  The Ks are lowp_ref's, unchanged; outputs in the
 storage type are held to storage_interval (no u * |ref| of slack); selections and copies are compared bit for bit.  Every check
 prints its ratio first (pytest -s); where a bound is a sum of terms with a K each (the gate, the epilogue's output, the heads) the

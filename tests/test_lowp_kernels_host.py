@@ -287,7 +287,7 @@ def test_cast_edge_table_reaches_what_it_names():
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# argument statuses: every call returns before its first HIP call (read from csrc/lowp.hip); nothing is launched
+# argument statuses: every call returns before its first HIP call (read from csrc/lowp_norm.hip, lowp_block.hip and lowp_point.hip); nothing is launched
 # ---------------------------------------------------------------------------------------------------------------
 A = 4096        # a "pointer": 16-byte aligned, never dereferenced
 OFF4 = 4100     # 4 bytes off a 16-byte boundary
