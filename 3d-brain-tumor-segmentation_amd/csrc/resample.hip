@@ -10,8 +10,8 @@
 //                           index mapping, the brain mask from the same registers, zero fill of the padding region.
 #include "common.h"
 #include "bts_internal.h"
+#include "resample_taps.h"
 
-#define RS_MAXC 8
 #define RS_POLE (-0.26794919243112270647f)  // sqrt(3) - 2
 // terms of the initial-value sum: all of them for n <= 32; beyond that the dropped ones weigh |z|^32 = 5e-19 of the line
 #define RS_HORIZON 32
@@ -131,69 +131,6 @@ struct ZoomParams {
   int Din, Hin, Win, Dout, Hout, Wout, Dpad, Hpad, Wpad;
   double sd, sh, sw;  // (n - 1) / (nout - 1) per axis, as zoom() forms it
 };
-
-// half-sample symmetric reflection (-1 -> 0, n -> n-1), then clamped so that no extent can index outside the line
-__device__ __forceinline__ int rs_reflect(int i, int n) {
-  if (i < 0) i = -i - 1;
-  if (i >= n) i = 2 * n - 1 - i;
-  return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
-// taps and weights of output index o on an input line of n samples; the coordinate is formed in fp64 as zoom() does, so the tap
-// indices are SciPy's; the weights are fp32
-template <int NT>
-__device__ __forceinline__ void rs_taps(int o, double scale, int n, int* idx, float* wt) {
-  const double c = (double)o * scale;
-  if constexpr (NT == 1) {
-    idx[0] = rs_reflect((int)floor(c + 0.5), n);
-    wt[0] = 1.f;
-  } else {
-    const double fl = floor(c);
-    const int i0 = (int)fl;
-    const float t = (float)(c - fl);
-    if constexpr (NT == 2) {
-      idx[0] = rs_reflect(i0, n); idx[1] = rs_reflect(i0 + 1, n);
-      wt[0] = 1.f - t; wt[1] = 1.f - wt[0];  // zoom() forms the last weight as 1 - the others
-    } else {
-      const float u = 1.f - t;
-      wt[1] = (t * t * (t - 2.f) * 3.f + 4.f) / 6.f;
-      wt[2] = (u * u * (u - 2.f) * 3.f + 4.f) / 6.f;
-      wt[0] = u * u * u / 6.f;
-      wt[3] = 1.f - wt[0] - wt[1] - wt[2];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) idx[k] = rs_reflect(i0 - 1 + k, n);
-    }
-  }
-}
-
-template <int C>
-__device__ __forceinline__ void rs_load(const float* p, float* v) {
-  if (C % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < C / 4; ++q) {
-      const float4 t = reinterpret_cast<const float4*>(p)[q];
-      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-  } else if (C == 2) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-  } else {
-#pragma unroll
-    for (int c = 0; c < C; ++c) v[c] = p[c];
-  }
-}
-template <int C>
-__device__ __forceinline__ void rs_store(float* p, const float* v) {
-  if (C % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < C / 4; ++q) reinterpret_cast<float4*>(p)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-  } else if (C == 2) {
-    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  } else {
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] = v[c];
-  }
-}
 
 // NT taps per axis: 1 = order 0 (nearest, floor(c + 0.5)), 2 = order 1, 4 = order 3 on prefiltered coefficients.
 // Order 1 sums its 8 taps as zoom() does, ((v * wd) * wh) * ww in row-major tap order; order 3 sums separably, W innermost.

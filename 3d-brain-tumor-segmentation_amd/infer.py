@@ -45,10 +45,16 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
     although the paper it implements normalises each scan on its own brain voxels; with a `norm` of mode 'case' (a prepro.npy written by
     `python -m bts_amd.preprocess --norm case`, read by preprocess.load_norm) the `TestTimeAugmentor` does the latter, optionally after
     clamping to robust percentiles (bts_case_norm), so that a scan of another intensity scale gives the same labels; off by default.
+  * the reference stacks its modalities voxel for voxel and scales along the array axes (test.py:21-46), whatever the headers say about
+    orientation, spacing per modality or the grids of the modalities against each other: right for BraTS (all LPS, 1 mm, one grid), noise
+    for anything else, since the network is not flip- or permutation-invariant.  A `Conformer` brings every modality onto one grid of
+    a stated orientation and spacing by the affines (nifti.best_affine) -- an exact reorientation copy where the map is a signed
+    permutation, a spline resample with a general matrix otherwise (bts_reorient3d, bts_affine_resample3d) -- and the prediction back;
+    `segment_case(geometry=...)` uses it in place of the Interpolator, off by default.
 All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_region_finish, bts_spline_prefilter3d, bts_zoom3d,
 bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, bts_components3d, bts_component_sizes,
-bts_component_largest, bts_components_apply, bts_region_relabel, bts_dilate3d, bts_lesion_pairs, bts_component_boxes, bts_lesion_crop, the
-model forward).
+bts_component_largest, bts_components_apply, bts_region_relabel, bts_dilate3d, bts_lesion_pairs, bts_component_boxes, bts_lesion_crop,
+bts_reorient3d, bts_affine_resample3d, the model forward).
 """
 import glob
 import os
@@ -460,22 +466,245 @@ class Interpolator(object):
         return y, lab
 
 
+def _grid_corners(shape):
+    """the 8 corner voxels of a grid, homogeneous: (4, 8) float64"""
+    n = [float(int(v) - 1) for v in shape]
+    return np.array([[a, b, c, 1.0] for a in (0.0, n[0]) for b in (0.0, n[1]) for c in (0.0, n[2])], dtype=np.float64).T
+
+
+def _corner_shift(m_a, m_b, shape):
+    """the largest displacement, in source voxels along any axis, between two 3x4 voxel maps over the corners of a grid"""
+    c = _grid_corners(shape)
+    return float(np.abs(np.asarray(m_a)[:3] @ c - np.asarray(m_b)[:3] @ c).max())
+
+
+IDENTITY_REORIENTATION = ((0, 1, 2), (False, False, False))
+
+
+def signed_permutation(matrix, src_shape, out_shape, entry_tol=1e-6, corner_tol=1e-3):
+    """is the 3x4 voxel map output grid -> source grid an exact reorientation of the whole source array?  Every row of the 3x3 part one
+    entry within entry_tol of +-1 and the others within it of 0, the extents matching, and the map within corner_tol voxel of the
+    reorientation's own (translation 0, or n - 1 on a reversed axis) at the corners of the output grid -> (perm, flip) as
+    ops.reorient3d takes them, else None"""
+    m = np.asarray(matrix, dtype=np.float64)[:3]
+    lin = m[:, :3]
+    perm, flip, exact = [None] * 3, [False] * 3, np.zeros((3, 4), dtype=np.float64)
+    for b in range(3):                                   # source axis b is fed by output axis a
+        a = int(np.argmax(np.abs(lin[b])))
+        rest = [k for k in range(3) if k != a]
+        if abs(abs(lin[b, a]) - 1.0) > entry_tol or np.abs(lin[b, rest]).max() > entry_tol or perm[a] is not None:
+            return None
+        perm[a], flip[a] = b, bool(lin[b, a] < 0)
+        exact[b, a] = -1.0 if flip[a] else 1.0
+        exact[b, 3] = float(int(src_shape[b]) - 1) if flip[a] else 0.0
+    if any(int(out_shape[a]) != int(src_shape[perm[a]]) for a in range(3)):
+        return None
+    if _corner_shift(m, exact, out_shape) > corner_tol:
+        return None
+    return tuple(perm), tuple(flip)
+
+
+class Conformer(object):
+    """brings the modalities of a scan onto ONE grid of a stated orientation and spacing by their affines, on the device, and the
+    prediction back onto the first modality's own grid.
+
+    The reference grid is the first modality's.  The target keeps that scan's own axes -- permuted and reversed to the closest
+    `orientation` (nifti.orientation / nifti.reorientation), each rescaled to `spacing` -- and is not rotated to the scanner's axes, so an
+    oblique scan is not resliced through its field of view.  Extent per axis int(round(n * src_spacing / spacing)) (zoom_output_shape);
+    the outer faces of the two volumes coincide: source coordinate s = (o + 0.5) * (spacing / src_spacing) - 0.5.  Every modality c is
+    read through M_c = inv(A_c) @ target_affine, so modalities on other grids land where their affines say; what lies outside a
+    modality's field of view is 0."""
+
+    def __init__(self, orientation='LPS', spacing=(1.0, 1.0, 1.0), order=3):
+        from . import nifti
+        nifti.reorientation(orientation, orientation)                         # refuses a code that is none
+        if order not in (0, 1, 3):
+            raise ValueError('Conformer: order %r is not supported; supported spline orders are 0, 1 and 3' % (order,))
+        spacing = tuple(float(v) for v in spacing)
+        if len(spacing) != 3 or not all(np.isfinite(v) and v > 0 for v in spacing):
+            raise ValueError('Conformer: spacing must be three positive numbers, got %r' % (spacing,))
+        self.orientation, self.spacing, self.order = str(orientation), spacing, int(order)
+        self.last = None            # after forward: the plan of the last scan
+        self.affine = None          # the reference modality's affine (mask.nii is written with it)
+        self.native_shape = None    # the reference modality's extent
+        self.mask = None            # unpadded brain mask of the last forward, on the target grid
+
+    def plan(self, shapes, affines):
+        """host only, float64.  shapes: the (D,H,W) of every modality's array, affines: their 4x4 voxel -> world matrices
+        -> {'shape': the target extent, 'target_affine' (4,4), 'voxel_map' (4,4): target voxel -> reference voxel, 'matrices': one 3x4
+        target voxel -> source voxel map per modality, 'groups': lists of modality indices that share a map (within 1e-3 voxel at the
+        corners of the target grid) and a source extent, 'reorient': per group (perm, flip) where the map is an exact reorientation
+        (`signed_permutation`), else None, 'code': the reference's own orientation code, 'native_spacing': its voxel size per axis,
+        'shapes': the extents as given}"""
+        from . import nifti
+        shapes = [tuple(int(v) for v in sh) for sh in shapes]
+        affines = [np.asarray(a, dtype=np.float64) for a in affines]
+        if not shapes or len(shapes) != len(affines) or any(len(sh) != 3 or min(sh) < 1 for sh in shapes) \
+                or any(a.shape != (4, 4) for a in affines):
+            raise ValueError('Conformer.plan: one (D,H,W) extent and one 4x4 affine per modality, got %r and %r'
+                             % (shapes, [a.shape for a in affines]))
+        a0, n0 = affines[0], shapes[0]
+        code = nifti.orientation(a0)
+        perm, flip = nifti.reorientation(code, self.orientation)
+        native = np.sqrt((a0[:3, :3] ** 2).sum(axis=0))
+        shape = zoom_output_shape([n0[perm[a]] for a in range(3)], [native[perm[a]] / self.spacing[a] for a in range(3)])
+        if min(shape) < 1:
+            raise ValueError('Conformer.plan: extent %s at spacing %s leaves the empty target %s' % (n0, tuple(native), shape))
+        vmap = np.zeros((4, 4), dtype=np.float64)
+        vmap[3, 3] = 1.0
+        for a in range(3):
+            k = self.spacing[a] / native[perm[a]]
+            if abs(k - 1.0) <= 1e-6:          # the column norm of float32 srows: the same spacing, and then an exactly integer map
+                k = 1.0
+            start = 0.5 * k - 0.5
+            vmap[perm[a], a] = -k if flip[a] else k
+            vmap[perm[a], 3] = (n0[perm[a]] - 1) - start if flip[a] else start
+        target = a0 @ vmap
+        mats = [vmap[:3].copy() if c == 0 or np.array_equal(a, a0) else (np.linalg.inv(a) @ target)[:3] for c, a in enumerate(affines)]
+        groups = []
+        for c, m in enumerate(mats):
+            for g in groups:
+                if shapes[g[0]] == shapes[c] and _corner_shift(mats[g[0]], m, shape) <= 1e-3:
+                    g.append(c)
+                    break
+            else:
+                groups.append([c])
+        return {'shape': tuple(shape), 'target_affine': target, 'voxel_map': vmap, 'matrices': mats, 'groups': groups,
+                'reorient': [signed_permutation(mats[g[0]], shapes[g[0]], shape) for g in groups], 'code': code,
+                'native_spacing': tuple(float(v) for v in native), 'shapes': shapes}
+
+    @staticmethod
+    def _runs(group):
+        """a group's channels as runs of consecutive indices of at most 8 (one launch each)"""
+        runs = []
+        for c in group:
+            if runs and runs[-1][-1] == c - 1 and len(runs[-1]) < 8:
+                runs[-1].append(c)
+            else:
+                runs.append([c])
+        return runs
+
+    @staticmethod
+    def _device_stack(vols, run):
+        """the volumes `run` names, channels last, dense float32 on the device"""
+        out = []
+        for c in run:
+            v = vols[c]
+            if isinstance(v, np.ndarray):
+                if not torch.cuda.is_available():
+                    raise RuntimeError('Conformer: conforming runs on the GPU (no CPU fallback exists for the product path)')
+                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
+            if v.dim() != 3:
+                raise ValueError('Conformer: every modality must be a (D,H,W) volume, got shape %s' % (tuple(v.shape),))
+            out.append(v.to(torch.float32))
+        return torch.stack(out, dim=-1).contiguous()
+
+    def _gather(self, x, matrix, shape, order, **kw):
+        coef = ops.spline_prefilter3d(x) if order == 3 else x
+        return ops.affine_resample3d(coef, matrix, shape, order=order, **kw)
+
+    def forward(self, vols, affines, pad_res=None):
+        """vols: one (D,H,W) volume per modality (numpy or device tensors, each on its own grid), affines: their 4x4 matrices
+        -> (x (D,H,W,C), mask (D,H,W,1), orig_shape) on the device, on the target grid; with pad_res padded by the reference's rule
+        (pad_to_spatial_res, as Interpolator.resample) with orig_shape the unpadded extent.  A group whose map is an exact
+        reorientation goes through ops.reorient3d, any other through the prefilter (order 3) and ops.affine_resample3d; mask and padding
+        come from the resampling launch where one launch writes every channel, else from one more pass over the finished volume."""
+        plan = self.plan([tuple(v.shape) for v in vols], affines)
+        self.last, self.affine, self.native_shape = plan, np.asarray(affines[0], dtype=np.float64), plan['shapes'][0]
+        shape, nch = plan['shape'], len(vols)
+        pad_to = None if pad_res is None else tuple(s + pad_res - (s % pad_res) for s in shape)
+        launches = [(run, plan['matrices'][g[0]], ro) for g, ro in zip(plan['groups'], plan['reorient']) for run in self._runs(g)]
+        whole = None
+        if len(launches) == 1:
+            run, matrix, ro = launches[0]
+            src = self._device_stack(vols, run)
+            if ro is None:
+                x, m = self._gather(src, matrix, shape, self.order, pad_to=pad_to, want_mask=True)
+            else:
+                whole = src if ro == IDENTITY_REORIENTATION else ops.reorient3d(src, *ro)
+        else:
+            for run, matrix, ro in launches:
+                src = self._device_stack(vols, run)
+                if whole is None:
+                    whole = torch.empty(tuple(shape) + (nch,), dtype=torch.float32, device=src.device)
+                if ro is None:
+                    self._gather(src, matrix, shape, self.order, out=whole, channel=run[0])
+                else:
+                    whole[..., run[0]:run[0] + len(run)].copy_(src if ro == IDENTITY_REORIENTATION else ops.reorient3d(src, *ro))
+        if whole is not None:
+            x, m = ops.zoom3d(whole, shape, order=0, pad_to=pad_to, want_mask=True)        # order 0 onto the same grid: copy, mask, padding
+        self.mask = m if pad_to is None else m[:shape[0], :shape[1], :shape[2]]
+        return x, m, list(shape)
+
+    @property
+    def identity(self):
+        """did the reference modality of the last scan already lie on the target grid, array axes included?"""
+        return self.last is not None and self.last['reorient'][0] == IDENTITY_REORIENTATION
+
+    def reverse(self, prob, mask=None, path=None, threshold=0.5, targets='labels'):
+        """prob (D1,H1,W1,K): cropped probability map on the target grid, mask (D1,H1,W1,1) (default: the last forward's)
+        -> (probabilities (D,H,W,K), uint8 labels (D,H,W)) on the reference modality's own grid, as Interpolator.reverse: the
+        probabilities at the configured order and the mask at order 0 through the inverse map (the exact copy where the forward was a
+        reorientation), the labels taken there ('labels' | 'regions'); with `path`, writes mask.nii there with the reference modality's
+        own affine"""
+        finish = _finish_of(targets)
+        if self.last is None:
+            raise RuntimeError('Conformer.reverse: no scan has been conformed yet')
+        mask = self.mask if mask is None else mask
+        p = prob.to(torch.float32).contiguous()
+        m = mask.to(torch.float32).contiguous()
+        ro = self.last['reorient'][0]
+        if ro is None:
+            inv = np.linalg.inv(self.last['voxel_map'])[:3]
+            p = self._gather(p, inv, self.native_shape, self.order)
+            m = self._gather(m, inv, self.native_shape, 0)
+        elif ro != IDENTITY_REORIENTATION:
+            perm, flip = ro
+            back = tuple(perm.index(b) for b in range(3))                     # native axis b is the target's axis back[b]
+            p = ops.reorient3d(p, back, tuple(flip[a] for a in back))
+            m = ops.reorient3d(m, back, tuple(flip[a] for a in back))
+        y, lab = finish(p.unsqueeze(0), m.unsqueeze(0), threshold)
+        y, lab = y[0], lab[0]
+        if path is not None:
+            from . import nifti
+            nifti.save(os.path.join(path, 'mask.nii'), lab.cpu().numpy(), self.affine)
+        return y, lab
+
+
+def _conformed(geometry, pad_res):
+    """segment_scan / segment_case with `geometry` = (Conformer, volumes, affines): the forward in place of Interpolator.resample"""
+    try:
+        conf, vols, affines = geometry
+    except (TypeError, ValueError):
+        conf = None
+    if not isinstance(conf, Conformer):
+        raise ValueError('geometry must be (Conformer, one (D,H,W) volume per modality, one 4x4 affine per modality), got %r' % (geometry,))
+    return (conf,) + tuple(conf.forward(vols, affines, pad_res=pad_res))
+
+
 def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True, threshold=0.5, compute_dtype='float32', tta_batch=None,
-                 order=3, window=None, targets='labels', norm=None):
+                 order=3, window=None, targets='labels', norm=None, geometry=None):
     """test.py:235-264 for one scan: resample to 1 mm^3 with mask and padding in one pass, TTA inference, crop, resample back.
     image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz) -> (probabilities, uint8 labels (D,H,W)) on that grid; the probabilities
     are (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  With pixdim (1,1,1) this is
     segment_volume with the reference's mask, bit for bit.  window: a WindowSpec, targets: 'labels' | 'regions', norm: None | a NormSpec, as
-    in segment_volume (in case mode the voxels of the resampled brain mask)."""
+    in segment_volume (in case mode the voxels of the resampled brain mask).
+    geometry: (Conformer, one (D,H,W) volume per modality, their 4x4 affines) -> the Conformer takes the Interpolator's place, forward and
+    back; `image`, `pixdim` and `order` are not read, and the result lies on the first modality's own grid."""
     if window is not None:
         window.check_resolution(spatial_res)
-    interp = Interpolator(None, order=order)
-    xp, mp, orig = interp.resample(image, pixdim, pad_res=spatial_res)
+    if geometry is None:
+        interp = Interpolator(None, order=order)
+        xp, mp, orig = interp.resample(image, pixdim, pad_res=spatial_res)
+        same_grid = all(f == 1.0 for f in interp.factors)
+    else:
+        interp, xp, mp, orig = _conformed(geometry, spatial_res)
+        same_grid = interp.identity
     df = getattr(model, 'data_format', 'channels_last')
     tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
                             tta_batch=tta_batch, window=window, targets=targets, norm=norm)
     y = tta(xp, mp)
-    if all(f == 1.0 for f in interp.factors):
+    if same_grid:
         lab = tta.labels()
         y = y[:, :orig[0], :orig[1], :orig[2]] if df == 'channels_first' else y[:orig[0], :orig[1], :orig[2]]
         return y, lab[:orig[0], :orig[1], :orig[2]]
@@ -571,7 +800,7 @@ def postprocess_labels(lab, min_component_voxels=0, et_min_voxels=0, connectivit
     return out
 
 
-def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False, postprocess=None, window=None, norm=None):
+def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False, postprocess=None, window=None, norm=None, geometry=None):
     """test.py:235-264 for one scan, with the optional skull-stripping stage (test.py:238-248): resample to 1 mm^3 padded to the first
     model's resolution, [skull model with TTA, x * (1 - p) cropped and padded again to the tumour model's resolution,] tumour model
     with TTA, crop, resample back.  tumor, skull: StageSpec; image (D,H,W,C) on the scan's grid, pixdim (dx,dy,dz)
@@ -591,7 +820,10 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
     norm: each stage normalises its input as its StageSpec's NormSpec says; a NormSpec given here takes the place of both stages' own for
     this call.  In case mode a stage normalises into a tensor of its own over the mask it is handed ('mask' for the first stage,
     'mask_repadded' for the tumour stage after skull stripping): 'x1mm' and 'x_stripped' stay the raw intensities, which is what
-    ops.skull_strip multiplies."""
+    ops.skull_strip multiplies.
+    geometry: (Conformer, one (D,H,W) volume per modality, their 4x4 affines) -> the Conformer takes the Interpolator's place for the forward
+    and the reverse: `image`, `pixdim` and `order` are not read, 'x1mm' is the conformed scan, and probabilities and labels lie on the
+    first modality's own grid.  None: as before."""
     if window is not None:
         for stage in (tumor, skull):
             if stage is not None:
@@ -601,9 +833,14 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
         if out_ch != 1:
             raise ValueError('segment_case: the skull-stripping model must have out_ch == 1 (its probability multiplies every channel '
                              'of the scan, test.py:245), got out_ch = %r' % (out_ch,))
-    interp = Interpolator(None, order=order)
     first = tumor if skull is None else skull
-    xp, mp, orig = interp.resample(image, pixdim, pad_res=first.spatial_res)
+    if geometry is None:
+        interp = Interpolator(None, order=order)
+        xp, mp, orig = interp.resample(image, pixdim, pad_res=first.spatial_res)
+        same_grid = all(f == 1.0 for f in interp.factors)
+    else:
+        interp, xp, mp, orig = _conformed(geometry, first.spatial_res)
+        same_grid = interp.identity
     stages = {'x1mm': xp, 'mask': mp, 'skull_prob': None, 'x_stripped': None, 'mask_repadded': None, 'prob_1mm': None}
     if skull is not None:
         p = skull.augmentor(window, norm)(xp, mp)
@@ -627,7 +864,7 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
         y = y.permute(1, 2, 3, 0)
     y = y[:orig[0], :orig[1], :orig[2]]
     stages['prob_1mm'] = y
-    if all(f == 1.0 for f in interp.factors):
+    if same_grid:
         lab = tta.labels()[:orig[0], :orig[1], :orig[2]]
     else:
         y, lab = interp.reverse(y, threshold=tumor.threshold, targets=tumor.targets)

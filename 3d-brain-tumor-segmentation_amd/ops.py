@@ -767,6 +767,70 @@ def zoom3d(coef, out_shape, order=3, pad_to=None, want_mask=False, mean=None, st
     return (out, mask) if want_mask else out
 
 
+# ---- conforming a scan to an oriented grid by its affine (infer.Conformer) ----
+def reorient3d(x, perm, flip, out=None):
+    """x (D,H,W,C) -> the exact copy np.flip(np.transpose(x, perm + (3,)), [a for a in range(3) if flip[a]]): output axis a runs along
+    axis perm[a] of x, reversed where flip[a]; C <= 8"""
+    _check_volume(x, 'reorient3d: x')
+    try:
+        perm = tuple(int(v) for v in perm)
+        flip = tuple(bool(v) for v in flip)
+    except TypeError:
+        perm, flip = (), ()
+    if sorted(perm) != [0, 1, 2] or len(flip) != 3:
+        raise ValueError('reorient3d: perm must be a permutation of (0, 1, 2) and flip three booleans, got %r and %r' % (perm, flip))
+    d, h, w, c = x.shape
+    shape = tuple(x.shape[p] for p in perm) + (c,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32 or out.data_ptr() == x.data_ptr():
+        raise ValueError('reorient3d: out must be a dense float32 tensor of shape %s that is not x' % (shape,))
+    lib().call('bts_reorient3d', _p(x), _p(out), d, h, w, c, perm[0], perm[1], perm[2], 4 * flip[0] + 2 * flip[1] + 1 * flip[2],
+               _stream())
+    return out
+
+
+def affine_resample3d(coef, matrix, out_shape, order=3, pad_to=None, out=None, channel=0, want_mask=False):
+    """coef (D,H,W,C) evaluated where the 3x4 (or 4x4) float64 `matrix` sends the voxels of a grid of spatial extent out_shape: source
+    voxel coordinate = matrix @ (o0, o1, o2, 1).  order 3 takes spline_prefilter3d coefficients, orders 0 and 1 the samples themselves;
+    taps and the reflect rule are zoom3d's (order 1 is weighted and summed in float64 and rounded once).  Voxels whose coordinate lies outside [-0.5, n - 0.5] on any axis are 0, as are
+    those of pad_to >= out_shape outside out_shape.  out: a dense float32 (pad_to, K) volume, K >= channel + C, whose channels
+    channel .. channel+C-1 are written and whose others are left as they are (modalities on different grids: one call each).
+    want_mask: also (max_c value > 0) as float32 (..., 1); only a call that writes every channel of the result can give it.
+    -> volume, or (volume, mask) with want_mask"""
+    _check_volume(coef, 'affine_resample3d: coef')
+    if order not in (0, 1, 3):
+        raise ValueError('affine_resample3d: order must be 0, 1 or 3, got %r' % (order,))
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape == (4, 4):
+        m = m[:3]
+    if m.shape != (3, 4) or not np.all(np.isfinite(m)):
+        raise ValueError('affine_resample3d: matrix must be a finite 3x4 or 4x4 array, got %r' % (matrix,))
+    do, ho, wo = (int(v) for v in out_shape)
+    dp, hp, wp = (do, ho, wo) if pad_to is None else (int(v) for v in pad_to)
+    if min(do, ho, wo) < 1 or dp < do or hp < ho or wp < wo:
+        raise ValueError('affine_resample3d: out_shape %s must be positive and within pad_to %s' % ((do, ho, wo), (dp, hp, wp)))
+    d, h, w, c = coef.shape
+    c0 = int(channel)
+    if out is None:
+        if c0 != 0:
+            raise ValueError('affine_resample3d: channel %d needs an output volume to write into' % c0)
+        out = torch.empty((dp, hp, wp, c), dtype=torch.float32, device=coef.device)
+    else:
+        _check_volume(out, 'affine_resample3d: out')
+        if tuple(out.shape[:3]) != (dp, hp, wp) or c0 < 0 or c0 + c > out.shape[3]:
+            raise ValueError('affine_resample3d: out has shape %s; channels %d .. %d of a %s volume are asked for'
+                             % (tuple(out.shape), c0, c0 + c - 1, (dp, hp, wp)))
+    ld = int(out.shape[3])
+    if want_mask and (c0 != 0 or ld != c):
+        raise ValueError('affine_resample3d: the mask is the maximum over all channels; this call writes %d of %d' % (c, ld))
+    mask = torch.empty((dp, hp, wp, 1), dtype=torch.float32, device=coef.device) if want_mask else None
+    m12 = (ctypes.c_double * 12)(*[float(v) for v in m.reshape(-1)])
+    lib().call('bts_affine_resample3d', _p(coef), d, h, w, c, _p(out), ld, c0, _p(mask), do, ho, wo, dp, hp, wp, m12, int(order),
+               _stream())
+    return (out, mask) if want_mask else out
+
+
 # ---- the two-stage hand-over and the per-case score (test.py:181-270) ----
 def skull_strip(x, p, m, orig, pad_to, out=None):
     """x (Da,Ha,Wa,C), p and m (Da,Ha,Wa,1) dense float32; orig = the unpadded extent (D,H,W); pad_to = (Db,Hb,Wb) >= orig

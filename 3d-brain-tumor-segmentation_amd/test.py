@@ -5,6 +5,7 @@
                            [--min_component_voxels N] [--et_min_voxels N] [--component_connectivity 26] [--skull_largest_component]
                            [--lesionwise] [--lesion_dilation 3] [--lesion_min_voxels 50] [--lesion_penalty_mm 374]
                            [--window D,H,W|crop] [--window_overlap 0.5] [--window_mode gaussian] [--window_batch N]
+                           [--conform [CODE]]
 
 This module is named after the reference's script and is NOT a pytest module: pytest's `test_*.py` pattern does not match `test.py`
 and `testpaths` points at tests/, so it is never collected.
@@ -38,10 +39,20 @@ map, `gaussian` or `constant`, --window_batch the windows and augmented copies p
 crop size.  A window must be a multiple of each model's spatial resolution.  Windows without a brain-mask voxel are not run, and one
 more line per case prints the windows run and skipped per stage.  Without --window nothing changes.
 
+With --conform [CODE] (default LPS, the orientation of the BraTS arrays) the headers decide where the voxels are: every modality keeps its
+own shape and its best affine (`nifti.best_affine`: the sform, else the qform; a header with neither is refused), and an
+`infer.Conformer` brings them all onto one 1 mm grid of that orientation -- the first modality's axes, permuted, reversed and rescaled;
+an exact copy where that is a pure reorientation, a spline resample of --order otherwise -- and the prediction back onto the first
+modality's grid.  A RAS scan, a sagittal acquisition, or modalities exported on different grids then segment as the same scan in BraTS
+layout does.  The truth volume must lie on the first modality's grid (same shape, affine within 1e-3 voxel at the corners), else the case
+is reported and skipped.  Scores act on that native grid, with its own voxel size for the distances; `mask.nii` carries the first
+modality's affine, not a mean; one more line per case prints the native orientation code, the voxel size and the path taken.  Without
+--conform nothing changes.
+
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
 accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
 --min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component, --lesionwise, --lesion_dilation,
---lesion_min_voxels, --lesion_penalty_mm, --window, --window_overlap, --window_mode, --window_batch.
+--lesion_min_voxels, --lesion_penalty_mm, --window, --window_overlap, --window_mode, --window_batch, --conform.
 
 Deviations:
   * cases are visited in sorted order of their paths (the reference: the file system's order);
@@ -67,7 +78,7 @@ import numpy as np
 import torch
 
 from . import nifti
-from .infer import (BRATS_REGIONS, WINDOW_MODES, Interpolator, StageSpec, WindowSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
+from .infer import (BRATS_REGIONS, WINDOW_MODES, Conformer, Interpolator, StageSpec, WindowSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
                     scores_from_confusion, segment_case, surface_scores, zoom_output_shape)
 from .preprocess import load_norm
 from .train import load_checkpoint, load_train_args
@@ -94,6 +105,15 @@ def _window_arg(text):
     if len(roi) != 3 or min(roi) < 1:
         raise argparse.ArgumentTypeError("expected D,H,W (three positive integers) or 'crop', got %r" % (text,))
     return roi
+
+
+def _code_arg(text):
+    """--conform: an orientation code, one letter from each of R/L, A/P, S/I"""
+    try:
+        nifti.reorientation(text.upper(), text.upper())
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text.upper()
 
 
 def arg_parser():
@@ -146,6 +166,9 @@ def arg_parser():
                    help='Importance of a voxel inside its window (default: %s).' % WINDOW_DEFAULTS['window_mode'])
     p.add_argument('--window_batch', type=int, default=argparse.SUPPRESS,
                    help='Windows and augmented copies per forward (default: as --tta_batch).')
+    # and --conform: absent, the namespace has no such attribute and nothing changes
+    p.add_argument('--conform', type=_code_arg, nargs='?', const='LPS', default=argparse.SUPPRESS, metavar='CODE',
+                   help='Bring every modality onto one 1 mm grid of this orientation by its affine (default code: LPS), and the labels back.')
     return p
 
 
@@ -187,11 +210,12 @@ def _first(path, name):
     return found[0] if found else None
 
 
-def decode_case(path, modalities, truth):
+def decode_case(path, modalities, truth, conform=False):
     """host side of one case (test.py:21-42,226-232) -> {'vols': float32 volumes with the axes reversed (the file's own byte order, see
     preprocess._decode_case), 'pixdim', 'affine': means over the modalities, 'truth': uint8 volume (axes reversed) or None}, or
-    {'missing': name} when a modality has no file"""
-    vols, pixdim, affine = [], [], []
+    {'missing': name} when a modality has no file.  conform: also 'affines', every modality's best affine (float64), the modalities may
+    differ in shape, and {'refused': why} for a header without an orientation or a truth volume off the first modality's grid"""
+    vols, pixdim, affine, best = [], [], [], []
     for name in modalities:
         card = _first(path, name)
         if card is None:
@@ -200,12 +224,49 @@ def decode_case(path, modalities, truth):
         vols.append(np.ascontiguousarray(np.asarray(data).astype(np.float32).T))
         pixdim.append(header['pixdim'][:4])
         affine.append(header['affine'])
+        if conform:
+            try:
+                best.append(nifti.best_affine(header))
+            except ValueError as e:
+                return {'refused': '%s: %s' % (os.path.basename(card), e)}
     y = None
     card = _first(path, truth) if truth else None
     if card is not None:
-        y = np.ascontiguousarray(np.asarray(nifti.load(card)[0]).astype(np.uint8).T)
-    return {'vols': vols, 'pixdim': np.mean(pixdim, axis=0, dtype=np.float32), 'affine': np.mean(affine, axis=0, dtype=np.float32),
-            'truth': y}
+        data, header = nifti.load(card)
+        y = np.ascontiguousarray(np.asarray(data).astype(np.uint8).T)
+        if conform:
+            try:
+                off = truth_grid_shift(vols[0].shape[::-1], best[0], np.asarray(data).shape, nifti.best_affine(header))
+            except ValueError as e:
+                return {'refused': '%s: %s' % (os.path.basename(card), e)}
+            if off is None or off > 1e-3:
+                return {'refused': '%s does not lie on the grid of %s (%s)' % (os.path.basename(card), modalities[0], (
+                    'another shape' if off is None else 'up to %.3g voxel off at the corners' % off))}
+    out = {'vols': vols, 'pixdim': np.mean(pixdim, axis=0, dtype=np.float32), 'affine': np.mean(affine, axis=0, dtype=np.float32),
+           'truth': y}
+    if conform:
+        out['affines'] = best
+    return out
+
+
+def truth_grid_shift(shape, affine, truth_shape, truth_affine):
+    """how far, in voxels along any axis, the truth volume's affine moves a corner of the reference grid from where the reference's own
+    puts it; None when the shapes differ"""
+    if tuple(int(v) for v in shape) != tuple(int(v) for v in truth_shape):
+        return None
+    n = [float(int(v) - 1) for v in shape]
+    corners = np.array([[a, b, c, 1.0] for a in (0.0, n[0]) for b in (0.0, n[1]) for c in (0.0, n[2])], dtype=np.float64).T
+    moved = np.linalg.inv(np.asarray(affine, dtype=np.float64)) @ np.asarray(truth_affine, dtype=np.float64) @ corners
+    return float(np.abs(moved[:3] - corners[:3]).max())
+
+
+def upload_conform_case(case, dev):
+    """-> ([one (D,H,W) float32 view per modality, each on its own grid], truth (D,H,W) uint8 or None) on `dev`"""
+    vols = [torch.from_numpy(v).to(dev).permute(2, 1, 0) for v in case['vols']]
+    y = case['truth']
+    if y is not None:
+        y = torch.from_numpy(y).to(dev).permute(2, 1, 0).contiguous()
+    return vols, y
 
 
 def upload_case(case, dev):
@@ -325,15 +386,16 @@ def mean_finite(values):
 
 def _decoded(cases, args):
     """the decoded cases in order; with workers > 0 a bounded number of them is decoded ahead by host threads"""
+    conform = getattr(args, 'conform', None) is not None
     if args.workers <= 0:
         for _, path in cases:
-            yield decode_case(path, args.modalities, args.truth)
+            yield decode_case(path, args.modalities, args.truth, conform)
         return
     with ThreadPoolExecutor(max_workers=args.workers) as pool:
         pending, nxt = [], 0
         for _ in cases:
             while nxt < len(cases) and len(pending) < args.workers + 1:
-                pending.append(pool.submit(decode_case, cases[nxt][1], args.modalities, args.truth))
+                pending.append(pool.submit(decode_case, cases[nxt][1], args.modalities, args.truth, conform))
                 nxt += 1
             yield pending.pop(0).result()
 
@@ -356,6 +418,7 @@ def run(args):
     lesion = lesion_kwargs(args)
     lesionwise = lesion is not None
     windowed = window_kwargs(args) is not None
+    conf = Conformer(args.conform, (1.0, 1.0, 1.0), args.order) if getattr(args, 'conform', None) is not None else None
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
     for (name, path), case in zip(cases, _decoded(cases, args)):
@@ -363,20 +426,38 @@ def run(args):
             print('{}: no *{}*.nii* file, case skipped'.format(name, case['missing']), flush=True)
             skipped.append((name, case['missing']))
             continue
-        x, y = upload_case(case, dev)
-        pixdim = tuple(float(v) for v in case['pixdim'][1:4])
+        if 'refused' in case:
+            print('{}: {}, case skipped'.format(name, case['refused']), flush=True)
+            skipped.append((name, case['refused']))
+            continue
+        geometry, affine = None, case['affine']
+        if conf is None:
+            x, y = upload_case(case, dev)
+            pixdim = tuple(float(v) for v in case['pixdim'][1:4])
+        else:
+            vols, y = upload_conform_case(case, dev)
+            x, geometry, affine = None, (conf, vols, case['affines']), case['affines'][0]
+            plan = conf.plan([tuple(v.shape) for v in vols], case['affines'])
+            pixdim = plan['native_spacing']                      # the distances of the scores are taken on the native grid
+            print('{}. Orientation {} -> {}, voxel size {:.4g} x {:.4g} x {:.4g} mm, {}'.format(
+                name, plan['code'], conf.orientation, pixdim[0], pixdim[1], pixdim[2],
+                'exact reorientation' if all(ro is not None for ro in plan['reorient']) else 'resampled at order %d' % conf.order), flush=True)
         if tumor is None:
             unit = all(f == 1.0 for f in pixdim)
-            shape_1mm = tuple(x.shape[:3]) if unit else zoom_output_shape(tuple(x.shape[:3]), pixdim)
+            if conf is not None:
+                shape_1mm = plan['shape']
+            else:
+                shape_1mm = tuple(x.shape[:3]) if unit else zoom_output_shape(tuple(x.shape[:3]), pixdim)
             tumor = load_stage(args.tumor_model, args.tumor_prepro, args, shape_1mm)
             if args.skull_strip:
                 skull = load_stage(args.skull_model, args.skull_prepro, args, shape_1mm)
                 if largest:
                     skull.largest_component = True
+        geo = {} if geometry is None else {'geometry': geometry}          # without --conform the call is the one it has always been
         if post is None and not largest:
-            _, lab = segment_case(tumor, x, pixdim, skull=skull, order=args.order)
+            _, lab = segment_case(tumor, x, pixdim, skull=skull, order=args.order, **geo)
         else:
-            _, lab, st = segment_case(tumor, x, pixdim, skull=skull, order=args.order, return_stages=True, postprocess=post)
+            _, lab, st = segment_case(tumor, x, pixdim, skull=skull, order=args.order, return_stages=True, postprocess=post, **geo)
             counts = dict(st.get('postprocess') or {})
             counts.update({'brain_' + k: v for k, v in (st.get('brain_counts') or {}).items()})
             cleaned.append((name, counts))
@@ -397,7 +478,7 @@ def run(args):
                 s.update(lesion_columns(lesionwise_scores(y, lab, pixdim, N_CLASSES, **lesion)))
         where = os.path.join(args.out_loc, name) if args.out_loc else path
         os.makedirs(where, exist_ok=True)
-        nifti.save(os.path.join(where, 'mask.nii'), lab.cpu().numpy(), case['affine'])
+        nifti.save(os.path.join(where, 'mask.nii'), lab.cpu().numpy(), affine)
         done += 1
         if s is not None:
             scores.append((name, s))

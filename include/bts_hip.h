@@ -301,6 +301,26 @@ int bts_spline_prefilter3d(const float* src, float* dst, int D, int H, int W, in
 int bts_zoom3d(const float* coef, float* dst, float* bmask, const float* mean, const float* stdv, int Din, int Hin, int Win,
                int Dout, int Hout, int Wout, int C, int Dpad, int Hpad, int Wpad, int order, bts_stream_t stream);
 
+/* ===== conforming a scan to an oriented grid by its affine (infer.Conformer; the reference stacks its modalities voxel for voxel,
+ * test.py:21-42, whatever their headers say) =====
+ * Dense fp32 (D,H,W,C) tensors, C innermost, 1 <= C <= 8. */
+/* dst = the exact copy flip(transpose(src)): src is (D,H,W,C); output axis a runs along source axis perm_a (a permutation of 0, 1, 2), so
+ * dst is (S[perm0],S[perm1],S[perm2],C) with S = (D,H,W); flip_mask bits 4|2|1 reverse OUTPUT axis 0|1|2.  numpy:
+ * np.flip(np.transpose(src, (perm0, perm1, perm2, 3)), the flipped axes).  src and dst must not overlap.  BTS_ERR_SHAPE for a bad extent,
+ * permutation or mask, a NULL pointer or src == dst, BTS_ERR_ALIGN for a volume that does not start on a voxel's vector width (16 bytes
+ * for C % 4 == 0, 8 for C == 2), with nothing launched. */
+int bts_reorient3d(const float* src, float* dst, int D, int H, int W, int C, int perm0, int perm1, int perm2, int flip_mask,
+                   bts_stream_t stream);
+/* dst[o0,o1,o2, c0 .. c0+C-1] = coef (Ds,Hs,Ws,C) evaluated at the source voxel coordinate s = m12 (o0,o1,o2,1), m12 a HOST array of 12
+ * doubles (3 x 4, row-major) read during the call; s is formed in fp64.  dst is (Dp,Hp,Wp,ld_dst), ld_dst >= c0 + C; its other channels
+ * are not touched.  order 0 | 1 | 3 with the taps and reflect index mapping of bts_zoom3d (3: coef from bts_spline_prefilter3d, its
+ * fp32 weights and summation order; 1: the 8 taps weighted and summed in fp64 and rounded once).  An output voxel whose s lies outside [-0.5, n - 0.5] on any axis is 0, as are the voxels outside (Do,Ho,Wo).
+ * bmask (Dp,Hp,Wp; may be NULL) = max_c value > 0, only for a call that writes every channel (c0 == 0 and ld_dst == C).
+ * BTS_ERR_SHAPE for a bad extent, ld_dst < C, a channel range outside ld_dst, a NULL coef, dst or m12, or a bmask with other channels
+ * present, with nothing launched. */
+int bts_affine_resample3d(const float* coef, int Ds, int Hs, int Ws, int C, float* dst, int ld_dst, int c0, float* bmask, int Do, int Ho,
+                          int Wo, int Dp, int Hp, int Wp, const double* m12, int order, bts_stream_t stream);
+
 /* ===== segmenting a folder of scans end to end (test.py:181-270: main) =====
  * The skull-stripping hand-over between the two models (test.py:244-254: invert, multiply, slice, pad again) in one pass.
  * x (Da,Ha,Wa,C) fp32: the scan padded to the skull model's resolution; p (Da,Ha,Wa,1): that stage's masked mean probability; m
