@@ -19,9 +19,9 @@ int bts_se_mlp_bwd_(const double* red, double* scratch, const float* gap, const 
                     float* dw1, float* dw2, float* dwsp, float* dgap, int N, int B, long V, int F, int R, int accumulate_params,
                     hipStream_t stream);
 
-// conv_igemm.hip: y (+)= bias + sum_z part[z][voxel][Npad]  (finish of a split-K launch, fixed summation order)
-int bts_igemm_reduce_(const float* part, const float* bias, float* y, long nvox, int Cout, int Npad, int ldy, int ksplit,
-                      int with_bias, int accum, hipStream_t stream);
+// conv_igemm.hip: y (+)= act(bias + sum_z part[z][voxel][Npad])  (finish of a split-K launch, fixed summation order); flags: IG_FLAG_*
+int bts_igemm_reduce_(const float* part, const float* bias, float* y, long nvox, int Cout, int Npad, int ldy, int ksplit, int flags,
+                      hipStream_t stream);
 // se.hip: stages 2a + 2 of the gate backward (sum the per-block partials [n][b][F][{ch, w}], SE-MLP backward, dgap / V)
 int bts_se_mlp_bwd_sample_(const double* red, double* scratch, const float* h, const float* ch, const float* w1, const float* w2, float* dgap, int N,
                            long V, int F, int R, hipStream_t stream);
@@ -29,8 +29,9 @@ int bts_se_bwd_middle_(double* partial, double* red, double* scratch, const floa
                        const float* w2, float* dw1, float* dw2, float* dwsp, float* dgap, int N, int B, long V, int F, int R,
                        int accumulate_params, hipStream_t stream);
 
-// conv_igemm.hip: a kernel is about to read part `bit` (1 implicit-GEMM, 2 F(2x2,3x3) x direct, 4 F(2x2x2,3x3x3)) of the K3S1 weight image
-// that starts at `base`: packed on the spot where the last re-pack left it out (ensure, before the launch), and recorded once the launch
-// was accepted (mark_used: re-packs then write the parts in use only)
+// conv_pack.hip: the parts of a K3S1 weight image -- implicit GEMM (also read by the small-channel kernels) | F(2x2,3x3) x direct |
+// F(2x2x2,3x3x3).  A kernel is about to read part `bit` of the image that starts at `base`: packed on the spot where the last re-pack left
+// it out (ensure, before the launch), and recorded once the launch was accepted (mark_used: re-packs then write the parts in use only)
+enum : unsigned { IMG_IGEMM = 1u, IMG_WINO = 2u, IMG_W3 = 4u, IMG_ALL = 7u };
 int bts_img_ensure_(const float* base, unsigned bit, hipStream_t stream);
 void bts_img_mark_used_(const float* base, unsigned bit);

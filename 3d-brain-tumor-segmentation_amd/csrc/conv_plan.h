@@ -1,5 +1,6 @@
-// The fp32 conv engine's host-side plan (conv_igemm.hip, conv_wino.hip, conv_wino3.hip): which kernel takes a call is decided ONCE per
-// query or launch by conv_choose; queries and entry points answer from it, launchers neither decline nor re-plan.
+// The fp32 conv engine's host-side plan (conv_engine.hip; the kernels: conv_igemm.hip, conv_upm.hip, conv_k1s.hip, conv_dsc.hip, conv_c2.hip,
+// conv_wino.hip, conv_wino3.hip): which kernel takes a call is decided ONCE per query or launch by conv_choose; queries and entry points
+// answer from it, launchers neither decline nor re-plan.
 #pragma once
 #include <limits.h>
 #include <stdlib.h>
@@ -32,9 +33,11 @@ struct UpmPlan { int lgTX, lgTY, TZ, ntz, nty, ntx, IZ, IY, IX, ksplit, kg_per; 
 // the tiled kernel: cfg ids 0:(2,1,4,1) M256 N32 | 1:(2,2,4,1) M256 N64 | 2:(1,2,2,2) M64 N128 | 3:(1,1,2,2) M64 N64 | 4:(1,1,4,1) M128 N32
 struct IgemmPlan { int cfg, lgTX, lgTY, TZ, ntz, nty, ntx, IZ, IY, IX, gridy, ksplit, kg_per, gn_zt; long need; };
 enum { CONV_DSC = 1, CONV_C2, CONV_W3, CONV_WINO, CONV_K1S, CONV_UPM, CONV_IGEMM };
+// profile symbols (bts_prof_begin; names: ops.kernel_symbol); the tiled kernel's is its cfg + SYM_IGEMM_K1 * (1x1x1 staging)
+enum { SYM_IGEMM_K1 = 8, SYM_UPM = 20, SYM_K1S = 21, SYM_DSC = 22, SYM_WINO = 23, SYM_C2 = 25, SYM_W3 = 27 };
 struct ConvChoice {
   int kernel;             // CONV_DSC | C2 | W3 | WINO | K1S | UPM | IGEMM
-  int sym;                // its profile symbol: 22 | 25 | 27 | 23 | 21 | 20 | cfg + 8 * (1x1x1)
+  int sym;                // its profile symbol (SYM_*)
   union { WinoPlan w; UpmPlan u; IgemmPlan g; };      // the plan of `kernel` (dsc, c2, k1s: a grid that follows from the call)
   long ws;                // workspace bytes the launch uses (its split-K partials; 0: none)
   long gn_B;              // GroupNorm partial slots per (sample, group) it writes; 0: it cannot, or none asked for
@@ -44,6 +47,7 @@ struct ConvChoice {
 struct ConvPtrs { const float *x, *wp, *bias; float* y; const float *wp2, *bias2; float* y2; const float* x2; void* ws; double* gnp; };
 
 inline int conv_npad32(int n) { return (n + 31) / 32 * 32; }
+inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }      // of the next power of two
 inline long conv_env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }      // (read per call: tests and A/B runs toggle them)
 // z-tiles of TZ planes per GroupNorm slab group; 0: the groups do not hold whole tiles, or BTS_IGEMM_NOGNFUSE is set
 inline int conv_gn_zt(const ConvCall& c, int TZ) {
@@ -92,8 +96,18 @@ inline bool wino_plan_ok(const ConvCall& c, ConvChoice& ch) {
 // ws and gn_B are filled in, and the launcher does not decline it.  Which form goes to which kernel is conv_choose's rule.
 bool w3_accept(const ConvCall& c, ConvChoice& ch);        // conv_wino3.hip: Winograd F(2x2x2,3x3x3), the third part of the K3S1 image
 bool wino_accept(const ConvCall& c, ConvChoice& ch);      // conv_wino.hip: Winograd F(2x2,3x3) x direct, the second part
+bool upm_accept(const ConvCall& c, ConvChoice& ch);       // conv_upm.hip: the merged-class transposed form
+bool k1s_accept(const ConvCall& c, ConvChoice& ch);       // conv_k1s.hip: the streaming 1x1x1 conv
+bool dsc_accept(const ConvCall& c, ConvChoice& ch);       // conv_dsc.hip: 3x3x3 into <= 4 output channels
+bool c2_accept(const ConvCall& c, ConvChoice& ch);        // conv_c2.hip: 3x3x3 of a 2-channel input
+int igemm_accept(const ConvCall& c, ConvChoice& ch);      // conv_igemm.hip: the tiled kernel takes every call of the family, so a status
 // workspace the form's full split wants for a shape (0: none, or the form is switched off): the workspace queries size for every form
 long w3_ws_need(const ConvCall& c);
 long wino_ws_need(const ConvCall& c);
 int bts_w3_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream);
 int bts_wino_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream);
+int bts_upm_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream);
+int bts_k1s_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream);
+int bts_dsc_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream);
+int bts_c2_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream);
+int bts_igemm_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream);

@@ -7,7 +7,7 @@
 //   Y = A^T [ (G g G^T) o (B^T d B) ] A   per 2x2 (z, y) output patch, summed over the three x taps and the input channels
 //   B^T = (1 0 -1 0 | 0 1 1 0 | 0 -1 1 0 | 0 1 0 -1)   G = (1 0 0 | .5 .5 .5 | .5 -.5 .5 | 0 0 1)   A^T = (1 1 1 0 | 0 1 -1 -1)
 //
-// U = G g G^T is formed at weight-packing time (conv_igemm.hip: second part of the K3S1 image, layout
+// U = G g G^T is formed at weight-packing time (conv_pack.hip: second part of the K3S1 image, layout
 // [cout block of 32][k-group of 8 cin][x tap][xi = xi_z*4 + xi_y][half h][32 couts][4 cin]).
 //
 // Work decomposition: 256 threads = 4 waves; workgroup tile = 32 (x) x 4 (y) x 4 (z) output voxels x 32 couts; each wave
@@ -451,12 +451,13 @@ long wino_ws_need(const ConvCall& c) {
 }
 bool wino_accept(const ConvCall& c, ConvChoice& ch) {
   if (!wino_enabled() || !wino_call_ok(c) || !wino_plan(ch.w, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout)) return false;
-  ch.sym = 23;
+  ch.sym = SYM_WINO;
   return wino_plan_ok(c, ch);
 }
 
 template <int XW>
-static int wino_launch_cfg(const WinoParams& p, const WinoPlan& q, double flops, hipStream_t stream) {
+static int wino_launch_cfg(const WinoParams& p, const ConvChoice& ch, double flops, hipStream_t stream) {
+  const WinoPlan& q = ch.w;
   auto kern = wino_kernel<XW>;
   static bool attr_done = false;
   const size_t shmem = 2 * WinoGeo<XW>::BUF * sizeof(float) + 64 + 256;   // + GroupNorm partial exchange (8 doubles) + 2 x 32 bias values
@@ -466,7 +467,7 @@ static int wino_launch_cfg(const WinoParams& p, const WinoPlan& q, double flops,
     attr_done = true;
   }
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(23, flops, stream);
+  if (prof) bts_prof_begin(ch.sym, flops, stream);
   (void)hipGetLastError();
   const long wgs_per_xcd = ((long)p.tiles_per_xcd * q.nb + p.T - 1) / p.T;
   hipLaunchKernelGGL(kern, dim3((unsigned)(8L * wgs_per_xcd), 1, q.ksplit), dim3(256), shmem, stream, p);
@@ -476,7 +477,7 @@ static int wino_launch_cfg(const WinoParams& p, const WinoPlan& q, double flops,
 }
 
 // The launch wino_accept planned.  q.wp: the K3S1 packed image; its Winograd part starts 27 x the padded (cin, cout) pairs in
-// (conv_igemm.hip's image layout).  q.ws: the split-K workspace of ch.ws bytes.
+// (conv_pack.hip's image layout).  q.ws: the split-K workspace of ch.ws bytes.
 int bts_wino_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
   const WinoPlan& pl = ch.w;
   const int N = c.N, D = c.Di, H = c.Hi, W = c.Wi, Cin = c.Cin, Cout = c.Cout;
@@ -496,7 +497,8 @@ int bts_wino_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q,
   }
   p.gnp = pl.gn_zt ? q.gnp : nullptr; p.gn_G = pl.gn_zt ? c.G : 0; p.gn_zt = pl.gn_zt ? pl.gn_zt : 1;
   const double flops = 2.0 * 27 * Cin * Cout * (double)N * D * H * W;
-  const int r = (pl.xw == 32) ? wino_launch_cfg<32>(p, pl, flops, stream) : wino_launch_cfg<16>(p, pl, flops, stream);
+  const int r = (pl.xw == 32) ? wino_launch_cfg<32>(p, ch, flops, stream) : wino_launch_cfg<16>(p, ch, flops, stream);
   if (r != BTS_OK || pl.ksplit == 1) return r;
-  return bts_igemm_reduce_(p.part, bias, q.y, (long)N * D * H * W, Cout, p.Npad, c.ldy, pl.ksplit, bias != nullptr, accum, stream);
+  return bts_igemm_reduce_(p.part, bias, q.y, (long)N * D * H * W, Cout, p.Npad, c.ldy, pl.ksplit,
+                           (bias ? IG_FLAG_BIAS : 0) | (c.flags & IG_FLAG_ACCUM), stream);
 }

@@ -6,7 +6,7 @@
 //   Y = (A^T x A^T x A^T) [ ((G x G x G) g) o ((B^T x B^T x B^T) d) ]   per 2x2x2 output patch, summed over the input channels
 //   B^T = (1 0 -1 0 | 0 1 1 0 | 0 -1 1 0 | 0 1 0 -1)   G = (1 0 0 | .5 .5 .5 | .5 -.5 .5 | 0 0 1)   A^T = (1 1 1 0 | 0 1 -1 -1)
 //
-// U = (G x G x G) g is formed at weight-packing time (conv_igemm.hip: third part of the K3S1 image, layout
+// U = (G x G x G) g is formed at weight-packing time (conv_pack.hip: third part of the K3S1 image, layout
 // [cout block of 32][k-group of 8 cin][xi = (xi_z*4 + xi_y)*4 + xi_x][half h][32 couts][4 cin]).
 //
 // Work decomposition: 256 threads = 4 waves; workgroup tile = 16 (x) x 4 (y) x 4 (z) output voxels x 32 couts = 32 patches of
@@ -485,7 +485,7 @@ long w3_ws_need(const ConvCall& c) {
 // BTS_IGEMM_K1S_MIN voxels); everywhere else it stays a 1x1x1 launch of its own, as for conv_wino.hip.
 bool w3_accept(const ConvCall& c, ConvChoice& ch) {
   if (!w3_enabled() || !wino_call_ok(c) || !w3_plan(ch.w, c.N, c.Di, c.Hi, c.Wi, c.Cin, c.Cout)) return false;
-  ch.sym = 27;
+  ch.sym = SYM_W3;
   if (!wino_plan_ok(c, ch)) return false;
   const long nvox = (long)c.N * c.Di * c.Hi * c.Wi;
   if (c.second == CONV_X2 && ch.w.ksplit == 1 && c.ld2 % 4 == 0 && c.p2_16 &&      // (whole k-groups of x2: w3_plan's Cin % 8 == 0)
@@ -495,7 +495,7 @@ bool w3_accept(const ConvCall& c, ConvChoice& ch) {
 }
 
 // The launch w3_accept planned.  q.wp: the K3S1 packed image; its third part starts (27 + 48) x the padded (cin, cout) pairs in
-// (conv_igemm.hip's image layout).  q.ws: the split-K workspace of ch.ws bytes.
+// (conv_pack.hip's image layout).  q.ws: the split-K workspace of ch.ws bytes.
 int bts_w3_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, hipStream_t stream) {
   const W3Plan& pl = ch.w;
   const int N = c.N, D = c.Di, H = c.Hi, W = c.Wi, Cin = c.Cin, Cout = c.Cout;
@@ -540,12 +540,13 @@ int bts_w3_launch_(const ConvCall& c, const ConvChoice& ch, const ConvPtrs& q, h
   }
   const double flops = 2.0 * 27 * Cin * Cout * (double)N * D * H * W;   // (the 3x3x3 call's; a fused second input's 1/27th more is not counted)
   const bool prof = bts_prof_on();
-  if (prof) bts_prof_begin(27, flops, stream);
+  if (prof) bts_prof_begin(ch.sym, flops, stream);
   (void)hipGetLastError();
   if (x2) hipLaunchKernelGGL(w3_kernel<true>, dim3((unsigned)(8L * wgs_per_xcd), 1, 1), dim3(256), shmem, stream, p);
   else hipLaunchKernelGGL(w3_kernel<false>, dim3((unsigned)(8L * wgs_per_xcd), 1, pl.ksplit), dim3(256), shmem, stream, p);
   if (prof) bts_prof_end(stream);
   BTS_LAUNCH_CHECK();
   if (pl.ksplit == 1) return BTS_OK;
-  return bts_igemm_reduce_(p.part, bias, q.y, (long)N * D * H * W, Cout, p.Npad, c.ldy, pl.ksplit, bias != nullptr, accum, stream);
+  return bts_igemm_reduce_(p.part, bias, q.y, (long)N * D * H * W, Cout, p.Npad, c.ldy, pl.ksplit,
+                           (bias ? IG_FLAG_BIAS : 0) | (c.flags & IG_FLAG_ACCUM), stream);
 }

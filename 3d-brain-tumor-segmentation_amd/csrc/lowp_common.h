@@ -85,7 +85,7 @@ struct LpPackParams {
   int cin_is_k;       // 1: the (possibly folded) input-channel axis is k (forward role), 0: it is n (data-gradient role)
   int shift, dup_start;
 };
-// source value of packed position (tap t, k, n) -- same conventions as the fp32 images (conv_igemm.hip: pack_src)
+// source value of packed position (tap t, k, n) -- same conventions as the fp32 images (conv_pack.hip: pack_src)
 __device__ __forceinline__ float lp_pack_src(const LpPackParams& q, int t, int k, int n) {
   if (k >= q.K || n >= q.N) return 0.f;
   const int ts = q.flip ? (q.ntaps - 1 - t) : t;

@@ -25,6 +25,15 @@ _workspaces = {}
 _CFG = {0: '2,1,4,1', 1: '2,2,4,1', 2: '1,2,2,2', 3: '1,1,2,2', 4: '1,1,4,1'}
 
 
+# profile symbol -> kernel name (fp32 conv engine: SYM_* of csrc/conv_plan.h; the weight-gradient and 16-bit kernels name theirs at the launch)
+_SYMBOLS = {20: 'upm_kernel', 21: 'k1s_kernel', 22: 'dsc_kernel', 23: 'wino_kernel', 24: 'wgw_kernel', 25: 'c2_kernel', 26: 'k1w_kernel',
+            27: 'w3_kernel', 30: 'lp_conv_s1_kernel', 31: 'lp_conv_gather_kernel', 32: 'lp_wgrad_kernel', 33: 'lp_s1d_kernel',
+            34: 'lp_k1_kernel', 35: 'lp_up_kernel', 36: 'lp_wgs_kernel', 37: 'lp_wgd_kernel', 38: 'lp_s1z_kernel', 39: 'lp_s2t_kernel',
+            40: 'lp_c2_kernel'}
+_SYMBOLS.update({cfg + 8 * k1: 'igemm_kernel<%s,%d>' % (_CFG[cfg], 4 if k1 else 1) for cfg in _CFG for k1 in (0, 1)})      # the tiled kernel
+_SYMBOLS.update({100 + v: 'wgrad_kernel<%d,%d>' % (v >> 2, v & 3) for v in range(12)})      # 100 + (MODE << 2 | FIXG)
+
+
 _VARIANTS = {33: {1: '<0,5>', 2: '<0,4>', 3: '<1,5>', 4: '<1,4>'},          # lp_s1d_kernel<MODE, TXL>
              32: {1: '<3x3x3>', 2: '<1x1x1>'}}                                 # lp_wgrad_kernel by kernel size
 
@@ -35,47 +44,7 @@ def kernel_symbol(sym, detail=False):
     var, sym = sym >> 16, sym & 0xffff
     if var and detail and sym in _VARIANTS:
         return kernel_symbol(sym) + _VARIANTS[sym].get(var, '<%d>' % var)
-    if sym == 20:
-        return 'upm_kernel'
-    if sym == 21:
-        return 'k1s_kernel'
-    if sym == 22:
-        return 'dsc_kernel'
-    if sym == 23:
-        return 'wino_kernel'
-    if sym == 24:
-        return 'wgw_kernel'
-    if sym == 25:
-        return 'c2_kernel'
-    if sym == 26:
-        return 'k1w_kernel'
-    if sym == 27:
-        return 'w3_kernel'
-    if sym == 30:
-        return 'lp_conv_s1_kernel'
-    if sym == 31:
-        return 'lp_conv_gather_kernel'
-    if sym == 32:
-        return 'lp_wgrad_kernel'
-    if sym == 33:
-        return 'lp_s1d_kernel'
-    if sym == 34:
-        return 'lp_k1_kernel'
-    if sym == 35:
-        return 'lp_up_kernel'
-    if sym == 36:
-        return 'lp_wgs_kernel'
-    if sym == 37:
-        return 'lp_wgd_kernel'
-    if sym == 38:
-        return 'lp_s1z_kernel'
-    if sym == 39:
-        return 'lp_s2t_kernel'
-    if sym == 40:
-        return 'lp_c2_kernel'
-    if sym >= 100:  # 100 + (MODE << 2 | FIXG)
-        return 'wgrad_kernel<%d,%d>' % ((sym - 100) >> 2, (sym - 100) & 3)
-    return 'igemm_kernel<%s,%d>' % (_CFG[sym & 7], 4 if sym & 8 else 1)
+    return _SYMBOLS[sym]
 
 
 def profile_enable(on):

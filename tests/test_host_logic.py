@@ -315,3 +315,28 @@ def test_bench_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path)
     assert np.array_equal(params, np.load(str(tmp_path / 'b' / 'params.npy')))
     r = _bench(['--help'], {})
     assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout
+
+
+def test_kernel_symbol_names_every_profile_id():
+    """ops.kernel_symbol: the name of every profile id the library records (fp32 conv engine 0-4 / 8-12 / 20-27, 16-bit engine 30-40,
+    weight gradient 100-111), and the variant forms of 32 and 33 with detail=True -- the names bench.py's kernel breakdown reads"""
+    from bts_amd import ops
+    names = {0: 'igemm_kernel<2,1,4,1,1>', 1: 'igemm_kernel<2,2,4,1,1>', 2: 'igemm_kernel<1,2,2,2,1>', 3: 'igemm_kernel<1,1,2,2,1>',
+             4: 'igemm_kernel<1,1,4,1,1>', 8: 'igemm_kernel<2,1,4,1,4>', 9: 'igemm_kernel<2,2,4,1,4>', 10: 'igemm_kernel<1,2,2,2,4>',
+             11: 'igemm_kernel<1,1,2,2,4>', 12: 'igemm_kernel<1,1,4,1,4>',
+             20: 'upm_kernel', 21: 'k1s_kernel', 22: 'dsc_kernel', 23: 'wino_kernel', 24: 'wgw_kernel', 25: 'c2_kernel', 26: 'k1w_kernel',
+             27: 'w3_kernel',
+             30: 'lp_conv_s1_kernel', 31: 'lp_conv_gather_kernel', 32: 'lp_wgrad_kernel', 33: 'lp_s1d_kernel', 34: 'lp_k1_kernel',
+             35: 'lp_up_kernel', 36: 'lp_wgs_kernel', 37: 'lp_wgd_kernel', 38: 'lp_s1z_kernel', 39: 'lp_s2t_kernel', 40: 'lp_c2_kernel',
+             100: 'wgrad_kernel<0,0>', 101: 'wgrad_kernel<0,1>', 102: 'wgrad_kernel<0,2>', 103: 'wgrad_kernel<0,3>',
+             104: 'wgrad_kernel<1,0>', 105: 'wgrad_kernel<1,1>', 106: 'wgrad_kernel<1,2>', 107: 'wgrad_kernel<1,3>',
+             108: 'wgrad_kernel<2,0>', 109: 'wgrad_kernel<2,1>', 110: 'wgrad_kernel<2,2>', 111: 'wgrad_kernel<2,3>'}
+    for sym, name in names.items():
+        assert ops.kernel_symbol(sym) == name and ops.kernel_symbol(sym, detail=True) == name, sym
+    variants = {(33, 1): 'lp_s1d_kernel<0,5>', (33, 2): 'lp_s1d_kernel<0,4>', (33, 3): 'lp_s1d_kernel<1,5>', (33, 4): 'lp_s1d_kernel<1,4>',
+                (33, 5): 'lp_s1d_kernel<5>', (32, 1): 'lp_wgrad_kernel<3x3x3>', (32, 2): 'lp_wgrad_kernel<1x1x1>',
+                (32, 3): 'lp_wgrad_kernel<3>'}
+    for (sym, var), name in variants.items():
+        assert ops.kernel_symbol(var << 16 | sym, detail=True) == name, (sym, var)
+        assert ops.kernel_symbol(var << 16 | sym) == names[sym], (sym, var)
+    assert ops.kernel_symbol(2 << 16 | 27, detail=True) == 'w3_kernel'      # (a variant on a kernel that names none)

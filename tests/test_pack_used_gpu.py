@@ -1,4 +1,4 @@
-"""-m gpu: weight images are re-packed in the forms their layers READ (csrc/conv_igemm.hip, "Which parts of a K3S1 image are READ").
+"""-m gpu: weight images are re-packed in the forms their layers READ (csrc/conv_pack.hip, "Which parts of a K3S1 image are READ").
 A BTS_CONV_K3S1 image carries three forms of the same weights; after an optimiser step (train.py:152) only the forms the dispatcher has
 picked so far are rewritten, and a form picked later is packed on the spot.  Checked against the fp64 oracle's convolution on the NEW
 weights, so a stale form would show."""
