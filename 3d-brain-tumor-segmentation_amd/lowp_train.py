@@ -70,9 +70,13 @@ class LowPrecisionTrainer(object):
     finished long before): a skipped step is then counted, the optimiser's `iterations` taken back by one and the scale halved; after
     `growth_interval` clean steps it doubles.  So the scale of step k+1 still is step k's: an overflow costs two skipped steps, not one.
     State readers (checkpoints, tests) call settle() first.  bfloat16 has fp32's exponent range and runs unscaled (loss_scale = 1, no
-    check) unless a scale is asked for."""
+    check) unless a scale is asked for.
 
-    def __init__(self, model, dtype='bfloat16', loss_scale=None, growth_interval=200):
+    loss: None = the reference's loss (util.DiceVAELoss: ops.loss_sums / loss_value / loss_bwd, exactly the calls of a trainer built
+    without the argument); a util.LossSpec = the compound loss of util.CompoundVAELoss (ops.seg_loss_sums / seg_loss_value /
+    seg_loss_bwd, one pass each; the loss scale is passed as the gradient scale in the same way)."""
+
+    def __init__(self, model, dtype='bfloat16', loss_scale=None, growth_interval=200, loss=None):
         self.fwd = lowp.LowPrecisionForward(model, dtype)      # checks samplers / layout, owns the forward weight images
         self.model = model
         self.code, self.tdt = DTYPES[dtype]
@@ -82,6 +86,11 @@ class LowPrecisionTrainer(object):
         if loss_scale <= 0 or 2.0 ** round(math.log2(loss_scale)) != loss_scale:
             raise ValueError('loss_scale must be a power of two, got %r' % (loss_scale,))
         self.loss_scale = float(loss_scale)
+        if loss is not None:
+            from .util import LossSpec
+            if not isinstance(loss, LossSpec):
+                raise TypeError('loss must be a util.LossSpec or None, got %r' % (loss,))
+        self.loss_spec = loss
         self.dynamic_scale = self.tdt == torch.float16 or self.loss_scale != 1.0
         self.growth_interval = int(growth_interval)
         self._clean_steps = 0
@@ -509,9 +518,7 @@ class LowPrecisionTrainer(object):
         split_fwd, split_grad = self._level0_splits(*x.shape[:4])
         fw = self._forward(self._stage_input(x), split_fwd)
         # loss, metric (fp32: util.py:13-24,35-57, train.py:145-148)
-        sums = ops.loss_sums(fw['y_pred'], y, x, fw['y_vae'], fw['proj'])
-        parallel.all_reduce_sum(sums)
-        lt, _ = ops.loss_value(sums, fw['y_pred'].shape[-1], True)
+        sums, lt = self._loss(fw, x, y)
         l2v = ops.l2_reg_fwd(m.flat_params, m._l2_ranges) if m._l2_ranges else None
         loss_t = ops.scalar_lincomb(lt, l2v, 1.0, 1.0) if l2v is not None else lt
         macro, micro = dice_fn(Tensor(y, requires_grad=False), Tensor(fw['y_pred'], requires_grad=False))     # (engine layout already)
@@ -540,15 +547,27 @@ class LowPrecisionTrainer(object):
         x, y = x.contiguous(), y.contiguous()
         split_fwd, _ = self._level0_splits(*x.shape[:4])
         fw = self._forward(lowp.cast_padded(self.code, self.tdt, x), split_fwd)
-        sums = ops.loss_sums(fw['y_pred'], y, x, fw['y_vae'], fw['proj'])
-        parallel.all_reduce_sum(sums)
-        lt, _ = ops.loss_value(sums, fw['y_pred'].shape[-1], True)
+        sums, lt = self._loss(fw, x, y)
         l2v = ops.l2_reg_fwd(m.flat_params, m._l2_ranges) if m._l2_ranges else None
         loss_t = ops.scalar_lincomb(lt, l2v, 1.0, 1.0) if l2v is not None else lt
         macro, micro = dice_fn(Tensor(y, requires_grad=False), Tensor(fw['y_pred'], requires_grad=False))
         self.last_labels = dice_fn.last_labels
         ops.step_fence_done(fence)
         return Tensor(loss_t, requires_grad=False), macro, micro
+
+    def _loss(self, fw, x, y):
+        """-> the (all-reduced) raw sums and the loss value of the forward record"""
+        spec = self.loss_spec
+        if spec is None:
+            sums = ops.loss_sums(fw['y_pred'], y, x, fw['y_vae'], fw['proj'])
+            parallel.all_reduce_sum(sums)
+            lt, _ = ops.loss_value(sums, fw['y_pred'].shape[-1], True)
+            return sums, lt
+        gamma, w_pos, w_neg = spec.kernel_args
+        sums = ops.seg_loss_sums(fw['y_pred'], y, x, fw['y_vae'], fw['proj'], gamma, w_pos, w_neg)
+        parallel.all_reduce_sum(sums)
+        lt, _ = ops.seg_loss_value(sums, fw['y_pred'].shape[-1], True, spec.dice_weight, spec.ce_weight)
+        return sums, lt
 
     def _stage_input(self, x):
         """the fp32 volume (engine layout) -> the encoder's 16-bit input, zero-padded to a 16-channel matrix step; input dropout
@@ -665,7 +684,12 @@ class LowPrecisionTrainer(object):
         dyv = torch.empty_like(y_vae)
         dproj = torch.empty_like(proj)
         # (through the decoder's sigmoid, decoder.py:60, in the same pass: dyp IS the gradient of the head's pre-activation)
-        ops.loss_bwd(y_pred, y, x, y_vae, proj, sums, one, dyp, dyv, dproj, through_sigmoid=True)
+        spec = self.loss_spec
+        if spec is None:
+            ops.loss_bwd(y_pred, y, x, y_vae, proj, sums, one, dyp, dyv, dproj, through_sigmoid=True)
+        else:
+            ops.seg_loss_bwd(y_pred, y, x, y_vae, proj, sums, one, dyp, dyv, dproj, True, spec.dice_weight, spec.ce_weight,
+                             *spec.kernel_args)
         # slab gradients: uninitialised -- the first writer of each one writes, every later contribution accumulates.  Levels below the
         # top: the decoder block's conv1 data gradient (its view [0, cres + f) is the whole slab); the top level: the VAE's
         # down-sampling conv's data gradient (its view [0, top_used) is the whole slab, which has no spare channels)

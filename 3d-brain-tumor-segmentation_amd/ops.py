@@ -612,6 +612,43 @@ def loss_bwd(y_pred, y, x, y_vae, proj, sums, gscale, dypred, dyvae, dproj, thro
                lz, 1 if through_sigmoid else 0, _stream())
 
 
+def _seg_loss_dims(y_pred, x, y_vae, proj):
+    n, c = y_pred.shape[0], y_pred.shape[4]
+    v = y_pred.shape[1] * y_pred.shape[2] * y_pred.shape[3]
+    has_vae = x is not None
+    cx = x.shape[4] if has_vae else 0
+    lz = proj.shape[1] // 2 if proj is not None else 0
+    return n, v, c, cx, ld_of(x) if has_vae else 0, ld_of(y_vae) if has_vae else 0, lz
+
+
+def seg_loss_sums(y_pred, y, x, y_vae, proj, gamma=0.0, w_pos=1.0, w_neg=1.0):
+    """the compound loss's raw sums in one pass -> (4C+5,) float64 device tensor: loss_sums' 3C+4, the cross-entropy / focal sums per
+    channel, this shard's N*V (see include/bts_hip.h)"""
+    n, v, c, cx, ldx, ldv, lz = _seg_loss_dims(y_pred, x, y_vae, proj)
+    sums = torch.empty(4 * c + 5, dtype=torch.float64, device=y_pred.device)
+    nb = lib().query('bts_seg_loss_workspace')
+    ws = workspace(nb, y_pred.device)
+    lib().call('bts_seg_loss_sums', _p(y_pred), _p(y), _p(x), _p(y_vae), _p(proj), _p(sums), _p(ws), nb, n, v, c, ld_of(y_pred),
+               ld_of(y), cx, ldx, ldv, lz, gamma, w_pos, w_neg, _stream())
+    return sums
+
+
+def seg_loss_value(sums, c, has_vae=True, w_dice=1.0, w_ce=1.0):
+    """-> loss (1,), parts (4,) = dice, l2, kl, cross-entropy"""
+    loss = torch.empty(1, dtype=torch.float32, device=sums.device)
+    parts = torch.empty(4, dtype=torch.float32, device=sums.device)
+    lib().call('bts_seg_loss_value', _p(sums), _p(loss), _p(parts), c, 1 if has_vae else 0, w_dice, w_ce, _stream())
+    return loss, parts
+
+
+def seg_loss_bwd(y_pred, y, x, y_vae, proj, sums, gscale, dypred, dyvae, dproj, through_sigmoid=False, w_dice=1.0, w_ce=1.0,
+                 gamma=0.0, w_pos=1.0, w_neg=1.0):
+    n, v, c, cx, ldx, ldv, lz = _seg_loss_dims(y_pred, x, y_vae, proj)
+    lib().call('bts_seg_loss_bwd', _p(y_pred), _p(y), _p(x), _p(y_vae), _p(proj), _p(sums), _p(gscale), _p(dypred), _p(dyvae),
+               _p(dproj), n, v, c, ld_of(y_pred), ld_of(y), cx, ldx, ldv, lz, 1 if through_sigmoid else 0, w_dice, w_ce, gamma,
+               w_pos, w_neg, _stream())
+
+
 def dice_metric_sums(y_true, y_pred, channels_last_axes=True, want_labels=True):
     n, d, h, w, c = y_pred.shape
     cells = w if channels_last_axes else 1

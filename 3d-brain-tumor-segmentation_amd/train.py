@@ -26,7 +26,10 @@ the spatial augmentation of the TRAINING examples (add_spatial_arguments: --spat
 default, never applied to --val_loc; data.IntensityConfig), and --targets (add_target_arguments: `labels`, the default, trains the
 output channels on the disjoint labels as the reference does; `regions` trains them on the nested BraTS regions WT, TC, ET, for both
 datasets, and the Dice columns of train.log are then util.RegionDiceCoefficient's; the mode is stored in train_args.pkl, restored by
---load_folder and read by `python -m bts_amd.test`).
+--load_folder and read by `python -m bts_amd.test`), and the training loss (add_loss_arguments: --loss `dice`, the default, is the
+reference's util.DiceVAELoss; `dice_ce` and `dice_focal` add a voxel-wise binary cross-entropy or focal term on the sigmoid outputs,
+util.CompoundVAELoss, weighted by --dice_weight and --ce_weight, the focal term shaped by --focal_gamma and --focal_alpha; in both
+engines; train_loss and val_loss of train.log are then the compound loss; stored in train_args.pkl and restored by --load_folder).
 Examples are the `.npz` files `python -m bts_amd.preprocess` writes; with a process group in the environment (torchrun) every rank
 runs the command, takes its shard and rank 0 writes the files.
 
@@ -286,7 +289,10 @@ def fit(model, optimizer, loss_fn, dice_fn, train_data, val_data, n_epochs, pati
 
     compute_dtype: None / 'float32' = the fp32 engine (util.train_step); 'bfloat16' / 'float16' = the 16-bit-storage engine
     (lowp_train.LowPrecisionTrainer.step: fp32 master weights, fp32 statistics, fp16 with dynamic loss scaling) for the training
-    iterations (its loss is util.DiceVAELoss, like train.py:143-147; loss_fn is then used by fp32 validation only).
+    iterations.  That engine evaluates its loss itself: util.DiceVAELoss' (train.py:143-147) unless loss_fn carries a `.spec`
+    (util.CompoundVAELoss: a util.LossSpec), in which case the 16-bit trainer is built with that spec -- or rebuilt, if the model
+    holds one built for another loss -- and trains and validates on the same compound loss; loss_fn itself is called by the fp32
+    steps only.
     eval_dtype: None / 'float32' = validation on the fp32 engine (eval_step), whatever the training type; 'bfloat16' / 'float16' =
     validation through the same 16-bit engine (LowPrecisionTrainer.evaluate: no switch of engines, weight images and allocator
     footprint once per epoch).  Both advance the random counters alike, so the training trajectory is the same either way.
@@ -298,8 +304,9 @@ def fit(model, optimizer, loss_fn, dice_fn, train_data, val_data, n_epochs, pati
     def trainer16(dtype):
         from .lowp_train import LowPrecisionTrainer
         trainer = getattr(model, '_trainer16', None)
-        if trainer is None or trainer.dtype_name != dtype:
-            trainer = model._trainer16 = LowPrecisionTrainer(model, dtype)
+        spec = getattr(loss_fn, 'spec', None)
+        if trainer is None or trainer.dtype_name != dtype or trainer.loss_spec != spec:
+            trainer = model._trainer16 = LowPrecisionTrainer(model, dtype, loss=spec)
         return trainer
     if train_step_fn is None and compute_dtype not in (None, 'float32'):
         trainer = trainer16(compute_dtype)
@@ -469,9 +476,28 @@ def add_target_arguments(p):
     return p
 
 
+LOSS_KEYS = ('loss', 'dice_weight', 'ce_weight', 'focal_gamma', 'focal_alpha')
+LOSSES = ('dice', 'dice_ce', 'dice_focal')
+LOSS_DEFAULTS = {'loss': 'dice', 'dice_weight': 1.0, 'ce_weight': 1.0, 'focal_gamma': 2.0, 'focal_alpha': None}
+
+
+def add_loss_arguments(p):
+    """the flags of the training loss (util.LossSpec), a group of their own like the augmentation ones"""
+    g = p.add_argument_group('training loss')
+    g.add_argument('--loss', type=str, default=LOSS_DEFAULTS['loss'], choices=LOSSES,
+                   help='dice: the reference\'s soft Dice + VAE terms; dice_ce / dice_focal: plus a voxel-wise binary cross-entropy / '
+                        'focal term on the sigmoid outputs.')
+    g.add_argument('--dice_weight', type=float, default=LOSS_DEFAULTS['dice_weight'], help='Weight of the Dice term (dice_ce, dice_focal).')
+    g.add_argument('--ce_weight', type=float, default=LOSS_DEFAULTS['ce_weight'], help='Weight of the cross-entropy / focal term (dice_ce, dice_focal).')
+    g.add_argument('--focal_gamma', type=float, default=LOSS_DEFAULTS['focal_gamma'], help='Focusing exponent of the focal term, in [0, 8] (dice_focal).')
+    g.add_argument('--focal_alpha', type=float, default=LOSS_DEFAULTS['focal_alpha'],
+                   help='Weight alpha of the positive targets and 1 - alpha of the negative ones, in (0, 1) (dice_focal; default: none).')
+    return p
+
+
 def full_parser():
-    """what the command parses: arg_parser() and the spatial augmentation, intensity augmentation and target groups"""
-    return add_target_arguments(add_intensity_arguments(add_spatial_arguments(arg_parser())))
+    """what the command parses: arg_parser() and the spatial augmentation, intensity augmentation, target and loss groups"""
+    return add_loss_arguments(add_target_arguments(add_intensity_arguments(add_spatial_arguments(arg_parser()))))
 
 
 def _floats(text, counts, flag):
@@ -504,6 +530,26 @@ def intensity_config(args):
                            blur_channel_prob=a['blur_channel_prob'], brightness_prob=a['brightness_prob'],
                            brightness=a['brightness_range'], contrast_prob=a['contrast_prob'], contrast=a['contrast_range'],
                            gamma_prob=a['gamma_prob'], gamma=a['gamma_range'], gamma_invert_prob=a['gamma_invert_prob'])
+
+
+def loss_spec(args):
+    """the util.LossSpec of the parsed (or unpickled) arguments, None for `dice` (or no `loss` key: an older pickle) -- the reference's
+    loss, which has no weights: a non-default --dice_weight / --ce_weight is refused with it"""
+    a = dict(LOSS_DEFAULTS, **{k: v for k, v in (args if isinstance(args, dict) else vars(args)).items() if k in LOSS_DEFAULTS})
+    kind, dw, cw = a['loss'], a['dice_weight'], a['ce_weight']
+    if kind not in LOSSES:
+        raise ValueError('--loss: unknown loss %r, one of %s' % (kind, ', '.join(LOSSES)))
+    if kind == 'dice':
+        for flag, v in (('--dice_weight', dw), ('--ce_weight', cw)):
+            if float(v) != 1.0:
+                raise ValueError('%s %r with --loss dice: the reference\'s loss has no weights; use --loss dice_ce or dice_focal' % (flag, v))
+        return None
+    from .util import LossSpec
+    try:                                   # (dice_ce ignores the focal flags)
+        return LossSpec(kind, dw, cw, a['focal_gamma'], a['focal_alpha']) if kind == 'dice_focal' else LossSpec(kind, dw, cw)
+    except ValueError as e:                # LossSpec names the field first: say which flag set it
+        field = str(e).split(' ', 1)[0]
+        raise ValueError('--%s: %s' % ({'gamma': 'focal_gamma', 'alpha': 'focal_alpha'}.get(field, field), e))
 
 
 def parse_args(argv=None):
@@ -551,8 +597,12 @@ def parse_args(argv=None):
             if key in chkpt_args:
                 setattr(args, key, chkpt_args[key])
         args.targets = chkpt_args.get('targets', 'labels')                                                 # (an older pickle: labels)
+        args.loss = chkpt_args.get('loss', 'dice')                                                         # (an older pickle: dice)
+        for key in LOSS_KEYS[1:]:
+            setattr(args, key, chkpt_args.get(key, LOSS_DEFAULTS[key]))
     spatial_config(args)                      # (a bad range or probability is refused here, not at the first batch)
     intensity_config(args)
+    loss_spec(args)
     if args.targets == 'regions' and int(args.model_args['out_ch']) != 3:
         raise ValueError('--targets regions trains the three BraTS regions WT, TC, ET: --out_ch must be 3, got %r' %
                          (args.model_args['out_ch'],))
@@ -565,7 +615,7 @@ def run(args):
     """the reference's train(args) (train.py:71-216) -> {'history': fit's rows, 'model', 'optimizer'}"""
     from . import data
     from .model import Model
-    from .util import DiceCoefficient, DiceVAELoss, RegionDiceCoefficient, ScheduledOptim
+    from .util import CompoundVAELoss, DiceCoefficient, DiceVAELoss, RegionDiceCoefficient, ScheduledOptim
     if not torch.cuda.is_available():
         raise RuntimeError('python -m bts_amd.train needs a GPU (no CPU fallback exists for the product path)')
     parallel.init_from_env()
@@ -595,7 +645,13 @@ def run(args):
     if parallel.active():
         parallel.broadcast_parameters(model)
     print('Total number of parameters: {}'.format(int(model.n_params)), flush=True)
-    loss_fn = DiceVAELoss(data_format=args.data_format)
+    spec = loss_spec(args)
+    if spec is None:
+        loss_fn = DiceVAELoss(data_format=args.data_format)
+        print('Loss: Dice + 0.1 * l2 + 0.1 * kl (the reference\'s).', flush=True)
+    else:
+        loss_fn = CompoundVAELoss(data_format=args.data_format, spec=spec)
+        print('Loss: {} + 0.1 * l2 + 0.1 * kl.'.format(spec.describe()), flush=True)
     dice_fn = (RegionDiceCoefficient if targets == 'regions' else DiceCoefficient)(data_format=args.data_format)
     history = fit(model, optimizer, loss_fn, dice_fn, train_data, val_data, args.n_epochs, patience=args.patience,
                   save_folder=args.save_folder or None, log=lambda s: print(s, flush=True), compute_dtype=args.dtype,

@@ -1,5 +1,7 @@
 """DiceVAELoss, DiceCoefficient, ScheduledOptim -- drop-in for util.py of the reference (:7-24, :29-57, :60-84),
-plus train_step(), the body of the reference's training loop (train.py:140-152)."""
+plus train_step(), the body of the reference's training loop (train.py:140-152), and LossSpec / CompoundVAELoss: Dice plus a voxel-wise
+cross-entropy or focal term (no reference counterpart; csrc/loss_ce.hip)."""
+import collections
 import math
 
 import torch
@@ -43,6 +45,99 @@ class DiceVAELoss(object):
                 dyv = torch.empty(y_vae.shape, dtype=torch.float32, device=g.device)
                 dpr = torch.empty_like(proj)
                 ops.loss_bwd(y_pred.t, y.t, x.t, y_vae.t, proj, sums, g, dyp, dyv, dpr, through_sigmoid=False)
+                for src, d in ((y_pred, dyp), (y_vae, dyv)):
+                    if src.requires_grad:
+                        buf, acc = src.grad_slot()
+                        ops.add_strided(buf, d, acc)
+                ops.axpy(pbase.grad_full(), dpr, 1.0)
+            tape.record(backward)
+        return loss
+
+
+LOSS_KINDS = ('dice_ce', 'dice_focal')
+MAX_FOCAL_GAMMA = 8.0          # csrc/loss_ce.hip: SEG_MAX_GAMMA
+
+
+class LossSpec(collections.namedtuple('LossSpec', 'kind dice_weight ce_weight gamma alpha')):
+    """Which compound loss: loss = dice_weight * dice + ce_weight * CE + 0.1 * l2 + 0.1 * kl ("Compound loss").
+    kind 'dice_ce': CE is the binary cross-entropy of every output channel (gamma and alpha are ignored); 'dice_focal': the focal loss
+    with exponent gamma and, when alpha is given, the class weights alpha (target 1) and 1 - alpha (target 0).  A value object:
+    compares and hashes by its fields, validated when made."""
+    __slots__ = ()
+
+    def __new__(cls, kind='dice_ce', dice_weight=1.0, ce_weight=1.0, gamma=2.0, alpha=None):
+        if kind not in LOSS_KINDS:
+            raise ValueError('unknown loss kind %r: one of %s (the Dice loss alone is DiceVAELoss)' % (kind, ', '.join(LOSS_KINDS)))
+        dice_weight, ce_weight, gamma = float(dice_weight), float(ce_weight), float(gamma)
+        for name, v in (('dice_weight', dice_weight), ('ce_weight', ce_weight)):
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError('%s must be a finite number >= 0, got %r' % (name, v))
+        if not 0.0 <= gamma <= MAX_FOCAL_GAMMA:
+            raise ValueError('gamma must lie in [0, %g], got %r' % (MAX_FOCAL_GAMMA, gamma))
+        if alpha is not None:
+            alpha = float(alpha)
+            if not 0.0 < alpha < 1.0:
+                raise ValueError('alpha must lie in (0, 1), got %r' % (alpha,))
+        return super(LossSpec, cls).__new__(cls, kind, dice_weight, ce_weight, gamma, alpha)
+
+    @property
+    def kernel_args(self):
+        """(gamma, w_pos, w_neg) as csrc/loss_ce.hip takes them"""
+        if self.kind == 'dice_ce':
+            return 0.0, 1.0, 1.0
+        return (self.gamma, 1.0, 1.0) if self.alpha is None else (self.gamma, self.alpha, 1.0 - self.alpha)
+
+    def describe(self):
+        if self.kind == 'dice_ce':
+            return '%g * Dice + %g * binary cross-entropy' % (self.dice_weight, self.ce_weight)
+        return '%g * Dice + %g * focal (gamma %g, alpha %s)' % (self.dice_weight, self.ce_weight, self.gamma,
+                                                                'none' if self.alpha is None else '%g' % self.alpha)
+
+
+class CompoundVAELoss(object):
+    """DiceVAELoss with a voxel-wise cross-entropy or focal term on the sigmoid outputs: loss = dice_weight * dice + ce_weight * CE +
+    0.1 * l2 + 0.1 * kl, CE the mean over batch, voxels and channels (`spec`: a LossSpec).  DiceVAELoss' call signature, tape mechanics
+    and data-parallel rule: the raw sums (4 * out_ch + 5 doubles, the voxel count among them) are all-reduced, so every rank evaluates
+    the global-batch loss and its exact gradient.  .last_parts: dice, l2, kl, CE of the last call (device, 4 floats)."""
+
+    def __init__(self, name='compound_loss', data_format='channels_last', spec=None, **kwargs):
+        if data_format not in ('channels_last', 'channels_first'):
+            raise ValueError('unknown data_format %r' % (data_format,))
+        if spec is None:
+            spec = LossSpec()
+        if not isinstance(spec, LossSpec):
+            raise TypeError('spec must be a util.LossSpec, got %r' % (spec,))
+        self.data_format = data_format
+        self.axis = (0, 1, 2, 3) if data_format == 'channels_last' else (0, 2, 3, 4)
+        self.spec = spec
+        self.last_parts = None
+
+    def __call__(self, x, y, y_pred, y_vae, z_mean, z_logvar, sample_weight=None):
+        x, y = as_tensor(x, data_format=self.data_format), as_tensor(y, data_format=self.data_format)
+        y_pred, y_vae = as_tensor(y_pred, True), as_tensor(y_vae, True)
+        pbase = getattr(z_mean, 'base', None)
+        if pbase is None or pbase is not getattr(z_logvar, 'base', None):
+            raise ValueError('z_mean / z_logvar must be the two halves of the VAE projection returned by Model')
+        proj = pbase.t
+        c = y_pred.shape[-1]
+        spec = self.spec
+        gamma, w_pos, w_neg = spec.kernel_args
+        sums = ops.seg_loss_sums(y_pred.t, y.t, x.t, y_vae.t, proj, gamma, w_pos, w_neg)
+        parallel.all_reduce_sum(sums)                     # 4*out_ch + 5 doubles, no-op on one rank
+        lt, parts = ops.seg_loss_value(sums, c, True, spec.dice_weight, spec.ce_weight)
+        loss = Tensor(lt)
+        self.last_parts = parts
+        tape = current_tape()
+        if tape is not None:
+            def backward():
+                g = loss.grad
+                if g is None:
+                    return
+                dyp = torch.empty(y_pred.shape, dtype=torch.float32, device=g.device)
+                dyv = torch.empty(y_vae.shape, dtype=torch.float32, device=g.device)
+                dpr = torch.empty_like(proj)
+                ops.seg_loss_bwd(y_pred.t, y.t, x.t, y_vae.t, proj, sums, g, dyp, dyv, dpr, False, spec.dice_weight,
+                                 spec.ce_weight, gamma, w_pos, w_neg)
                 for src, d in ((y_pred, dyp), (y_vae, dyv)):
                     if src.requires_grad:
                         buf, acc = src.grad_slot()

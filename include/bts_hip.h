@@ -219,6 +219,24 @@ int bts_loss_value(const double* sums, float* loss, float* parts, int C, int has
 int bts_loss_bwd(const float* y_pred, const float* y, const float* x, const float* y_vae, const float* proj,
                  const double* sums, const float* gscale, float* dlogit, float* dyvae, float* dproj, int N, long V, int C,
                  int ldp, int ldy, int Cx, int ldx, int ldv, int Lz, int through_sigmoid, bts_stream_t stream);
+/* Compound loss (no reference counterpart): loss = w_dice * dice + w_ce * CE + 0.1 * l2 + 0.1 * kl with dice, l2, kl as above and
+ * CE = sum(e) / (N_global V C), e = w_pos t (1-q)^gamma (-log q) + w_neg (1-t) q^gamma (-log(1-q)), q = min(max(p, 2^-23), 1 - 2^-23):
+ * gamma = 0 is binary cross-entropy, gamma > 0 the focal loss, alpha is w_pos = alpha, w_neg = 1 - alpha.  Each entry point makes ONE pass.
+ * sums: 4C+5 doubles = the 3C+4 of bts_loss_sums, sum e per channel [C], this shard's N*V -- raw sums, all-reduce them for data parallel.
+ * parts[4] = dice, l2, kl, CE.  dlogit = w_dice * (the Dice gradient) + w_ce / (sums[4C+4] * C) * d sum(e), times *gscale; d e / d p is the
+ * clamped formula's (zero where p < 2^-23 or p > 1 - 2^-23); dyvae, dproj and the dense outputs as bts_loss_bwd.  BTS_ERR_SHAPE for C outside
+ * 1..8, N, V <= 0 or a voxel stride below its channel count; BTS_ERR_UNSUPPORTED for gamma outside [0, 8] or a negative / non-finite
+ * weight; BTS_ERR_WORKSPACE below bts_seg_loss_workspace() bytes. */
+long bts_seg_loss_workspace(void);
+int bts_seg_loss_sums(const float* y_pred, const float* y, const float* x, const float* y_vae, const float* proj, double* sums,
+                      void* workspace, long workspace_bytes, int N, long V, int C, int ldp, int ldy, int Cx, int ldx, int ldv,
+                      int Lz, float gamma, float w_pos, float w_neg, bts_stream_t stream);
+int bts_seg_loss_value(const double* sums, float* loss, float* parts, int C, int has_vae, float w_dice, float w_ce,
+                       bts_stream_t stream);
+int bts_seg_loss_bwd(const float* y_pred, const float* y, const float* x, const float* y_vae, const float* proj,
+                     const double* sums, const float* gscale, float* dlogit, float* dyvae, float* dproj, int N, long V, int C,
+                     int ldp, int ldy, int Cx, int ldx, int ldv, int Lz, int through_sigmoid, float w_dice, float w_ce, float gamma,
+                     float w_pos, float w_neg, bts_stream_t stream);
 /* table: (cells*C*3) doubles, cells = W if channels_last_axes else 1; labels: (N*V) uint8 or NULL */
 int bts_dice_metric_sums(const float* y_true, const float* y_pred, uint8_t* labels, double* table, int N, long V, int W,
                          int C, int ldt, int ldp, int channels_last_axes, bts_stream_t stream);
