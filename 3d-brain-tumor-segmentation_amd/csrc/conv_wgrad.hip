@@ -875,10 +875,14 @@ static int plan_wgrad(WgChoice& pl, int ntaps, int s, int neg, int N, int Dp, in
 // rows x = 0..15 (+2 unused).  A lane's four x inputs of a patch are two 8-byte reads at an 8-byte-aligned offset; the row
 // stride of 18 floats sends the 32 channels of a half wave to 32 distinct bank pairs ((9 c) mod 32 is a permutation):
 // conflict-free.  Staging slots run channel quad fastest, then x: a wave's 16-byte loads are contiguous in memory and its
-// transposing 4-byte LDS writes hit banks 8 cq + x (8 x 8 distinct).  The z combination is taken per wave in registers, then y
-// and x; xi = 3 of Q carries +q1 for the true -q1 on every axis, undone where G^T is applied (in the wave for y and x, across
-// the waves through LDS for z).  Every step is branch-free: the next sub-tile's loads go through a descriptor that is empty
-// behind the workgroup's last sub-tile.  Bias partials: the all-sum point of Q (xi = 1 on every axis, wave 1).
+// transposing 4-byte LDS writes hit banks 8 cq + x (8 x 8 distinct).  The z combination of P is taken on the way into LDS, as
+// w3_kernel's commit() does: a thread stages the four z rows of one column and writes the planes d0 - d2 | d1 + d2 | d2 - d1 |
+// d1 - d3 into the rows of the four z rows, a wave reads the plane of its own xi_z and transforms y and x.  Q stays raw (its
+// planes would not fit); xi = 3 of Q carries +q1 for the true -q1 on every axis, undone where G^T is applied (in the wave for y
+// and x, across the waves through LDS for z).  Every step is branch-free: the next sub-tile's loads go through descriptors that
+// are empty behind the workgroup's last sub-tile, and everything a step consumes was asked for two steps earlier (global loads
+// before their LDS writes, LDS reads before their matrix instructions).  Bias partials: the all-sum point of Q (xi = 1 on every
+// axis, wave 1).
 // ---------------------------------------------------------------------------------------------------------------------
 typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ wg_f32x2 wgw_pk_add(wg_f32x2 a, wg_f32x2 b) { wg_f32x2 d; asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
@@ -893,7 +897,8 @@ __device__ __forceinline__ float wgw_acc_rd(float a) { float v; asm volatile("v_
 #define WGW_PTILE (24 * 32 * WGW_RS)         /* 4 z-rows x 6 y-rows */
 #define WGW_QTILE (8 * 32 * WGW_RS)          /* 2 z-rows x 4 y-rows */
 #define WGW_BUF (WGW_PTILE + WGW_QTILE)      /* 18432 floats = 72 KB, double buffered; the two = the 4 x 9 tiles of the combine */
-#define WGW_NPS 14                           /* P slots per thread: 24 rows x 18 x x 8 channel quads = 3456 = 13.5 x 256 */
+#define WGW_PLANE (6 * 32 * WGW_RS)          /* one xi_z plane of the P tile: 6 y-rows */
+#define WGW_NPC 4                            /* P column slots per thread: 6 y-rows x 18 x x 8 channel quads = 864 = 3.375 x 256 */
 #define WGW_NQS 4                            /* Q slots per thread: 8 rows x 16 x x 8 channel quads = 1024 */
 
 __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p) {
@@ -906,27 +911,35 @@ __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p
   const float* pP = p.p + pct * 32;
   const float* pQ = p.q + qct * 32;
 
-  // ---- staging maps: slot id = tid + 256*i = ((row * XW) + x) * 8 + channel quad.  Byte offsets relative to the tile origin
-  //      are computed once; a slot outside the image gets a 2 GB offset = outside the buffer descriptor, the load returns
-  //      zeros (border tiles only: 6 face bits per slot against 6 per tile) ----
-  int p_lds[WGW_NPS];
-  unsigned poff[WGW_NPS], pfl[3] = {0u, 0u, 0u};
+  // ---- staging maps.  P: column id = tid + 256*i = ((y row * 18) + x) * 8 + channel quad; a thread loads the four z rows of its
+  //      column, each through the descriptor of that z row, and writes the four xi_z planes.  Byte offsets relative to the z row's
+  //      origin are computed once; a column on a y or x face of the image gets a 2 GB offset = outside the descriptor, the load
+  //      returns zeros (4 face bits per column against 4 per tile); a z row outside the image has an empty descriptor.
+  //      Q: slot id = tid + 256*i = ((row * 16) + x) * 8 + channel quad, raw. ----
+  int c_lds[WGW_NPC - 1], c3_lds[4];
+  unsigned coff[WGW_NPC], cfl = 0u;
 #pragma unroll
-  for (int i = 0; i < WGW_NPS; ++i) {
+  for (int i = 0; i < WGW_NPC; ++i) {
     const int id = tid + WGW_THREADS * i;
-    // (the half-filled last slot: its idle threads load nothing and write their zeros to the unused x = 16, 17 of the Q rows)
-    const int idle = id - 24 * 18 * 8;
-    p_lds[i] = WGW_PTILE + ((idle >> 4) * 32 + ((idle >> 1) & 7) * 4) * WGW_RS + 16 + (idle & 1);
-    poff[i] = 0x80000000u;
-    if (id < 24 * 18 * 8) {
+    int l = 0;
+    coff[i] = 0x80000000u;
+    if (id < 6 * 18 * 8) {
       const int cq = id & 7, vox = id >> 3;
-      const int row = vox / 18, xx = vox - row * 18;
-      const int zr = row / 6, yr = row - zr * 6;
-      p_lds[i] = (row * 32 + cq * 4) * WGW_RS + xx;
-      poff[i] = (unsigned)(((zr * p.Hp + yr) * p.Wp + xx) * p.ldp + cq * 4) * 4u;
-      const unsigned fl = (zr == 0 ? 1u : 0u) | (zr == 3 ? 2u : 0u) | (yr == 0 ? 4u : 0u) | (yr == 5 ? 8u : 0u) |
-                          (xx == 0 ? 16u : 0u) | (xx == 17 ? 32u : 0u);
-      pfl[i / 5] |= fl << (6 * (i % 5));
+      const int yr = vox / 18, xx = vox - yr * 18;
+      l = (yr * 32 + cq * 4) * WGW_RS + xx;
+      coff[i] = (unsigned)((yr * p.Wp + xx) * p.ldp + cq * 4) * 4u;
+      const unsigned fl = (yr == 0 ? 1u : 0u) | (yr == 5 ? 2u : 0u) | (xx == 0 ? 4u : 0u) | (xx == 17 ? 8u : 0u);
+      cfl |= fl << (4 * i);
+    }
+    if (i < WGW_NPC - 1) {
+      c_lds[i < WGW_NPC - 1 ? i : 0] = l;
+    } else {
+      // (the partly filled last slot: its idle threads load nothing and write their zeros to the unused x = 16, 17 of the Q rows,
+      // four channels of one row per plane)
+      const int idle = id - 6 * 18 * 8;
+#pragma unroll
+      for (int pl = 0; pl < 4; ++pl)
+        c3_lds[pl] = idle < 0 ? l + pl * WGW_PLANE : WGW_PTILE + 4 * (((idle >> 1) + 16 * pl) & 63) * WGW_RS + 16 + (idle & 1);
     }
   }
   int q_lds[WGW_NQS];
@@ -941,7 +954,8 @@ __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p
   const int t0 = blockIdx.x * p.sub_per_wg;
   int t1 = t0 + p.sub_per_wg;
   if (t1 > p.nsub) t1 = p.nsub;
-  // coordinates of the NEXT sub-tile to fetch (sub-tiles of a workgroup are consecutive: incremental, no division in the loop)
+  // coordinates and origins (P: the halo corner) of the NEXT sub-tile to fetch.  Sub-tiles of a workgroup are consecutive: the
+  // coordinates advance by carries and the origins by 32-bit byte strides, no division or 64-bit product in the loop
   int ftx, fty, ftz, fn;
   {
     int t = t0;
@@ -950,63 +964,100 @@ __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p
     ftz = t % p.ntz;
     fn = t / p.ntz;
   }
-  // The 18 slots of the next sub-tile are fetched in six groups of three (P 0-2 | 3-5 | 6-8 | 9-11 | P 12-13 + Q 0 | Q 1-3),
-  // group k issued at step k of the current sub-tile and written to the OTHER LDS buffer one step later.
-  f32x4 pre[WGW_NPS + WGW_NQS];
-  __amdgpu_buffer_rsrc_t f_pr, f_qr;
-  unsigned f_tm = 0;
+  const char* f_pb = reinterpret_cast<const char*>(pP + ((((long)fn * p.Dp + 2 * ftz - 1) * p.Hp + 4 * fty - 1) * p.Wp + 16 * ftx - 1) * p.ldp);
+  const char* f_qb = reinterpret_cast<const char*>(pQ + ((((long)fn * p.Dq + 2 * ftz) * p.Hq + 4 * fty) * p.Wq + 16 * ftx) * p.ldq);
+  const long zrow = (long)p.Hp * p.Wp * p.ldp;
+  // bytes to the next sub-tile along x; more to the first of the next y row; more to the first of the next z row (tiles are whole
+  // and samples contiguous: the next sample's first is one more z row on).  The launcher keeps five z rows of P and three of Q
+  // below 2 GB.
+  const unsigned pdx = 64u * p.ldp, pdy = 12u * p.Wp * p.ldp, pdz = (unsigned)zrow * 4u;
+  const unsigned qdx = 64u * p.ldq, qdy = 12u * p.Wq * p.ldq, qdz = (unsigned)p.Hq * p.Wq * p.ldq * 4u;
+  // The 20 requests of the next sub-tile go out in six groups (P column 0 | 1 | 2 | 3, four z rows each | Q 0-1 | Q 2-3).  Group k is
+  // written to the OTHER LDS buffer at step k and requested two steps before that -- groups 0 and 1 in the last two steps of the
+  // sub-tile before, where fetch_begin has just made its descriptors: a request has two steps to come back before the in-order
+  // wait of its write.
+  f32x4 pre[4 * WGW_NPC + WGW_NQS];
+  __amdgpu_buffer_rsrc_t f_pr[4], f_qr;
+  unsigned f_cm[WGW_NPC] = {0u, 0u, 0u, 0u};   // the tile's y / x face bits at the place of each column's
   auto fetch_begin = [&](bool live) {   // live = false: empty descriptors, every load returns zeros without traffic
-    const int z0 = 2 * ftz, y0 = 4 * fty, x0 = 16 * ftx;
-    const float* pb = pP + ((((long)fn * p.Dp + z0 - 1) * p.Hp + y0 - 1) * p.Wp + x0 - 1) * p.ldp;
-    const float* qb = pQ + ((((long)fn * p.Dq + z0) * p.Hq + y0) * p.Wq + x0) * p.ldq;
-    f_pr = __builtin_amdgcn_make_buffer_rsrc((void*)pb, 0, live ? 0x7fffffff : 0, 0x00020000);
+    const float* pb = reinterpret_cast<const float*>(f_pb);
+    const float* qb = reinterpret_cast<const float*>(f_qb);
+    f_pr[0] = __builtin_amdgcn_make_buffer_rsrc((void*)pb, 0, (live && ftz != 0) ? 0x7fffffff : 0, 0x00020000);
+    f_pr[1] = __builtin_amdgcn_make_buffer_rsrc((void*)(pb + zrow), 0, live ? 0x7fffffff : 0, 0x00020000);
+    f_pr[2] = __builtin_amdgcn_make_buffer_rsrc((void*)(pb + 2 * zrow), 0, live ? 0x7fffffff : 0, 0x00020000);
+    f_pr[3] = __builtin_amdgcn_make_buffer_rsrc((void*)(pb + 3 * zrow), 0, (live && ftz != p.ntz - 1) ? 0x7fffffff : 0, 0x00020000);
     f_qr = __builtin_amdgcn_make_buffer_rsrc((void*)qb, 0, live ? 0x7fffffff : 0, 0x00020000);
-    f_tm = (ftz == 0 ? 1u : 0u) | (ftz == p.ntz - 1 ? 2u : 0u) | (fty == 0 ? 4u : 0u) | (fty == p.nty - 1 ? 8u : 0u) |
-           (ftx == 0 ? 16u : 0u) | (ftx == p.ntx - 1 ? 32u : 0u);
+    const unsigned tm = (fty == 0 ? 1u : 0u) | (fty == p.nty - 1 ? 2u : 0u) | (ftx == 0 ? 4u : 0u) | (ftx == p.ntx - 1 ? 8u : 0u);
+#pragma unroll
+    for (int i = 0; i < WGW_NPC; ++i) f_cm[i] = tm << (4 * i);
     const int cx = (ftx + 1 == p.ntx) ? 1 : 0;   // (selects, no branches: the call sits inside a scheduled step)
     ftx = cx ? 0 : ftx + 1;
     const int cy = (fty + cx == p.nty) ? 1 : 0;
     fty = cy ? 0 : fty + cx;
     const int cz = (ftz + cy == p.ntz) ? 1 : 0;
     ftz = cz ? 0 : ftz + cy;
-    fn += cz;
+    f_pb += pdx + cx * pdy + cy * pdz;   // (cy implies cx)
+    f_qb += qdx + cx * qdy + cy * qdz;
   };
-  auto fetch_slot = [&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    if constexpr (i < WGW_NPS) {
-      const unsigned fl = ((pfl[i / 5] >> (6 * (i % 5))) & 63u) & f_tm;
-      pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_pr, fl ? 0x80000000u : poff[i], 0, 0));
-    } else {
-      pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_qr, qoff[i - WGW_NPS], 0, 0));
-    }
+  auto load4 = [](__amdgpu_buffer_rsrc_t r, unsigned off) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
   };
-  auto commit_slot = [&](float* buf, auto ic) {
-    constexpr int i = decltype(ic)::value;
-    if constexpr (i < WGW_NPS) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) buf[p_lds[i] + e * WGW_RS] = pre[i][e];
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) buf[q_lds[i - WGW_NPS] + e * WGW_RS] = pre[i][e];
-    }
+  auto sub4 = [](f32x4 a, f32x4 b) {
+    const wg_f32x2 lo = wgw_pk_sub(a.xy, b.xy), hi = wgw_pk_sub(a.zw, b.zw);
+    return f32x4{lo.x, lo.y, hi.x, hi.y};
+  };
+  auto add4 = [](f32x4 a, f32x4 b) {
+    const wg_f32x2 lo = wgw_pk_add(a.xy, b.xy), hi = wgw_pk_add(a.zw, b.zw);
+    return f32x4{lo.x, lo.y, hi.x, hi.y};
   };
   auto fetch_group = [&](auto kc) {
     constexpr int k = decltype(kc)::value;
-    fetch_slot(IC<3 * k>{}); fetch_slot(IC<3 * k + 1>{}); fetch_slot(IC<3 * k + 2>{});
+    if constexpr (k < WGW_NPC) {
+      const unsigned off = (cfl & f_cm[k]) ? 0x80000000u : coff[k];
+#pragma unroll
+      for (int zr = 0; zr < 4; ++zr) pre[4 * k + zr] = load4(f_pr[zr], off);
+    } else {
+      constexpr int i = 2 * (k - WGW_NPC);
+      pre[4 * WGW_NPC + i] = load4(f_qr, qoff[i]);
+      pre[4 * WGW_NPC + i + 1] = load4(f_qr, qoff[i + 1]);
+    }
   };
   auto commit_group = [&](float* buf, auto kc) {
     constexpr int k = decltype(kc)::value;
-    commit_slot(buf, IC<3 * k>{}); commit_slot(buf, IC<3 * k + 1>{}); commit_slot(buf, IC<3 * k + 2>{});
+    if constexpr (k < WGW_NPC) {   // xi_z planes d0 - d2 | d1 + d2 | d2 - d1 | d1 - d3 of the column, into the rows of the four z rows
+      const f32x4 d0 = pre[4 * k], d1 = pre[4 * k + 1], d2 = pre[4 * k + 2], d3 = pre[4 * k + 3];
+      const f32x4 pl[4] = {sub4(d0, d2), add4(d1, d2), sub4(d2, d1), sub4(d1, d3)};
+#pragma unroll
+      for (int z = 0; z < 4; ++z) {
+        float* o;
+        if constexpr (k < WGW_NPC - 1) o = buf + c_lds[k] + z * WGW_PLANE;
+        else o = buf + c3_lds[z];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e * WGW_RS] = pl[z][e];
+      }
+    } else {
+      constexpr int i0 = 2 * (k - WGW_NPC);
+#pragma unroll
+      for (int i = i0; i < i0 + 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) buf[q_lds[i] + e * WGW_RS] = pre[4 * WGW_NPC + i][e];
+    }
+  };
+  // the staging share of step s: write group s (steps 0-5: the barrier sits before step 6), request the group that is written two
+  // steps on.  The descriptors of the sub-tile after the next (live2: it exists) are made in step 6, which requests its group 0,
+  // behind the last request of the next (group 5, step 3)
+  auto stage = [&](float* buf, auto sc, bool live2) {
+    constexpr int s = decltype(sc)::value;
+    if constexpr (s <= 5) commit_group(buf, IC<s>{});
+    if constexpr (s == 6) fetch_begin(live2);
+    if constexpr (s + 2 <= 5) fetch_group(IC<s + 2>{});
+    else if constexpr (s >= 6) fetch_group(IC<s - 6>{});
   };
 
-  // ---- wave roles: xi_z of P: c = P[ra] + sp * P[rb]; of Q: a = X + sq * Y (xi_z = 3: +q1) ----
-  const int ra = (wave == 0) ? 0 : (wave == 2) ? 2 : 1;
-  const int rb = (wave == 0) ? 2 : (wave == 1) ? 2 : (wave == 2) ? 1 : 3;
-  const float sp = (wave == 1) ? 1.f : -1.f;
-  const wg_f32x2 sp2 = {sp, sp};
+  // ---- wave roles: xi_z of P: the wave's own plane; of Q: a = X + sq * Y (xi_z = 3: +q1) ----
   const float sq = (wave == 1) ? 1.f : (wave == 2) ? -1.f : 0.f;
   const wg_f32x2 sq2 = {sq, sq};
-  const int pA = (ra * 6 * 32 + ch) * WGW_RS + 2 * hh, pB = (rb * 6 * 32 + ch) * WGW_RS + 2 * hh;
+  const int pA = wave * WGW_PLANE + ch * WGW_RS + 2 * hh;
   const int qXa = WGW_PTILE + ((wave == 3 ? 4 : 0) * 32 + ch) * WGW_RS + 2 * hh;
   const int qYa = WGW_PTILE + (4 * 32 + ch) * WGW_RS + 2 * hh;
   const bool bias = p.want_bias && pct == 0 && wave == 1;
@@ -1022,23 +1073,30 @@ __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p
       for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.f;
 
   struct WgwOps { float v[4][4], t[4][4]; };
-  // operands of step st = (patch row py, x patch pair sx): this lane's patch is px = 2 sx + hh
-  auto form = [&](const float* cur, auto stc, WgwOps& o) {
+  struct WgwRaw { wg_f32x2 pl[4], px[4], qx[2], qy[2]; };
+  // LDS reads of step st = (patch row py, x patch pair sx): this lane's patch is px = 2 sx + hh.  They are issued two steps before
+  // the matrix instructions that use them and transformed one step before: a read has a whole step to come back
+  auto rd = [&](const float* cur, auto stc, WgwRaw& r) {
     constexpr int st = decltype(stc)::value;
     constexpr int py = st >> 2, sx = st & 3;
-    wg_f32x2 cl[4], cx[4];   // z-combined rows: x inputs 0,1 | 2,3
 #pragma unroll
-    for (int yr = 0; yr < 4; ++yr) {
+    for (int yr = 0; yr < 4; ++yr) {   // rows of the wave's xi_z plane: x inputs 0,1 | 2,3
       const float* a = cur + pA + (2 * py + yr) * 32 * WGW_RS + 4 * sx;
-      const float* b = cur + pB + (2 * py + yr) * 32 * WGW_RS + 4 * sx;
-      cl[yr] = wgw_pk_fma(*reinterpret_cast<const wg_f32x2*>(b), sp2, *reinterpret_cast<const wg_f32x2*>(a));
-      cx[yr] = wgw_pk_fma(*reinterpret_cast<const wg_f32x2*>(b + 2), sp2, *reinterpret_cast<const wg_f32x2*>(a + 2));
+      r.pl[yr] = *reinterpret_cast<const wg_f32x2*>(a);
+      r.px[yr] = *reinterpret_cast<const wg_f32x2*>(a + 2);
     }
+#pragma unroll
+    for (int yr = 0; yr < 2; ++yr) {
+      r.qx[yr] = *reinterpret_cast<const wg_f32x2*>(cur + qXa + (2 * py + yr) * 32 * WGW_RS + 4 * sx);
+      r.qy[yr] = *reinterpret_cast<const wg_f32x2*>(cur + qYa + (2 * py + yr) * 32 * WGW_RS + 4 * sx);
+    }
+  };
+  auto xf = [&](const WgwRaw& r, WgwOps& o) {
     wg_f32x2 vl[4], vx[4];
-    vl[0] = wgw_pk_sub(cl[0], cl[2]); vx[0] = wgw_pk_sub(cx[0], cx[2]);
-    vl[1] = wgw_pk_add(cl[1], cl[2]); vx[1] = wgw_pk_add(cx[1], cx[2]);
-    vl[2] = wgw_pk_sub(cl[2], cl[1]); vx[2] = wgw_pk_sub(cx[2], cx[1]);
-    vl[3] = wgw_pk_sub(cl[1], cl[3]); vx[3] = wgw_pk_sub(cx[1], cx[3]);
+    vl[0] = wgw_pk_sub(r.pl[0], r.pl[2]); vx[0] = wgw_pk_sub(r.px[0], r.px[2]);
+    vl[1] = wgw_pk_add(r.pl[1], r.pl[2]); vx[1] = wgw_pk_add(r.px[1], r.px[2]);
+    vl[2] = wgw_pk_sub(r.pl[2], r.pl[1]); vx[2] = wgw_pk_sub(r.px[2], r.px[1]);
+    vl[3] = wgw_pk_sub(r.pl[1], r.pl[3]); vx[3] = wgw_pk_sub(r.px[1], r.px[3]);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {   // x: e0 - e2 | e1 + e2 | e2 - e1 | e1 - e3
       const wg_f32x2 d = wgw_pk_sub(vl[a], vx[a]), m = wgw_pk_addsub(vx[a], vl[a]);
@@ -1047,13 +1105,7 @@ __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p
       o.v[a][2] = m.y;
       o.v[a][3] = d.y;
     }
-    wg_f32x2 qa[2];
-#pragma unroll
-    for (int yr = 0; yr < 2; ++yr) {
-      const wg_f32x2 X = *reinterpret_cast<const wg_f32x2*>(cur + qXa + (2 * py + yr) * 32 * WGW_RS + 4 * sx);
-      const wg_f32x2 Y = *reinterpret_cast<const wg_f32x2*>(cur + qYa + (2 * py + yr) * 32 * WGW_RS + 4 * sx);
-      qa[yr] = wgw_pk_fma(Y, sq2, X);
-    }
+    const wg_f32x2 qa[2] = {wgw_pk_fma(r.qy[0], sq2, r.qx[0]), wgw_pk_fma(r.qy[1], sq2, r.qx[1])};
     const wg_f32x2 ty[4] = {qa[0], wgw_pk_add(qa[0], qa[1]), wgw_pk_sub(qa[0], qa[1]), qa[1]};
 #pragma unroll
     for (int a = 0; a < 4; ++a) {   // x: e0 | e0 + e1 | e0 - e1 | + e1
@@ -1090,42 +1142,54 @@ __global__ __launch_bounds__(WGW_THREADS, 1) void wgw_kernel(const WgradParams p
   commit_group(lds, IC<4>{}); commit_group(lds, IC<5>{});
   __syncthreads();
   WgwOps opA, opB;
-  form(lds, IC<0>{}, opA);
+  WgwRaw rawA, rawB;
+  // (in the order of the loop's last two steps, so that the waits counted behind the loop's head are the same on both ways in)
+  rd(lds, IC<0>{}, rawA);
+  __builtin_amdgcn_sched_barrier(0);
   fetch_begin((t0 + 1) < t1);
+  fetch_group(IC<0>{});
+  __builtin_amdgcn_sched_barrier(0);
+  rd(lds, IC<1>{}, rawB);
+  __builtin_amdgcn_sched_barrier(0);
+  xf(rawA, opA);
+  __builtin_amdgcn_sched_barrier(0);
+  fetch_group(IC<1>{});
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_nop 3" ::: "memory");
+  // step s: the matrix instructions of step s, the transform of step s + 1, the LDS reads of step s + 2, the staging share
   for (int t = t0; t < t1; ++t) {
     const float* cur = lds + ((t - t0) & 1) * WGW_BUF;
     float* nxt = lds + ((t - t0 + 1) & 1) * WGW_BUF;
-    form(cur, IC<1>{}, opB); fetch_group(IC<0>{});
+    const bool live2 = (t + 2) < t1;
+    rd(cur, IC<2>{}, rawA); xf(rawB, opB); stage(nxt, IC<0>{}, live2);
     mfma16(opA);
     WGW_STEP_END();
-    form(cur, IC<2>{}, opA); commit_group(nxt, IC<0>{}); fetch_group(IC<1>{});
+    rd(cur, IC<3>{}, rawB); xf(rawA, opA); stage(nxt, IC<1>{}, live2);
     mfma16(opB);
     WGW_STEP_END();
-    form(cur, IC<3>{}, opB); commit_group(nxt, IC<1>{}); fetch_group(IC<2>{});
+    rd(cur, IC<4>{}, rawA); xf(rawB, opB); stage(nxt, IC<2>{}, live2);
     mfma16(opA);
     WGW_STEP_END();
-    form(cur, IC<4>{}, opA); commit_group(nxt, IC<2>{}); fetch_group(IC<3>{});
+    rd(cur, IC<5>{}, rawB); xf(rawA, opA); stage(nxt, IC<3>{}, live2);
     mfma16(opB);
     WGW_STEP_END();
-    form(cur, IC<5>{}, opB); commit_group(nxt, IC<3>{}); fetch_group(IC<4>{});
+    rd(cur, IC<6>{}, rawA); xf(rawB, opB); stage(nxt, IC<4>{}, live2);
     mfma16(opA);
     WGW_STEP_END();
-    form(cur, IC<6>{}, opA); commit_group(nxt, IC<4>{}); fetch_group(IC<5>{});
+    rd(cur, IC<7>{}, rawB); xf(rawA, opA); stage(nxt, IC<5>{}, live2);
     mfma16(opB);
     WGW_STEP_END();
-    form(cur, IC<7>{}, opB); commit_group(nxt, IC<5>{});
-    mfma16(opA);
-    WGW_STEP_END();
-    bsum += (double)bs;   // (step 0's share was added when it was formed, under the previous sub-tile's last step)
-    bs = 0.f;
-    // the barrier sits before the LAST step: step 0 of the next sub-tile is formed under this step's matrix instructions (behind
-    // the workgroup's last sub-tile the other buffer holds zeros or stale data and the operands formed from it are dropped)
+    // the barrier sits before step 6: the reads of the next sub-tile's steps 0 and 1 go out under this sub-tile's last two steps and
+    // its step 0 is formed under the last (behind the workgroup's last sub-tile the other buffer holds zeros or stale data and
+    // what is formed from it is dropped)
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
-    form(nxt, IC<0>{}, opA);
-    fetch_begin((t + 2) < t1);   // descriptors and face bits of the sub-tile after the next, fetched during the next
+    rd(nxt, IC<0>{}, rawA); xf(rawB, opB); stage(nxt, IC<6>{}, live2);
+    mfma16(opA);
+    WGW_STEP_END();
+    bsum += (double)bs;   // (step 0's share is added when it is formed, under the last step)
+    bs = 0.f;
+    rd(nxt, IC<1>{}, rawB); xf(rawA, opA); stage(nxt, IC<7>{}, live2);
     mfma16(opB);
     WGW_STEP_END();
   }
