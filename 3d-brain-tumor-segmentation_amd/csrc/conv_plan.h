@@ -33,8 +33,10 @@ struct UpmPlan { int lgTX, lgTY, TZ, ntz, nty, ntx, IZ, IY, IX, ksplit, kg_per; 
 // the tiled kernel: cfg ids 0:(2,1,4,1) M256 N32 | 1:(2,2,4,1) M256 N64 | 2:(1,2,2,2) M64 N128 | 3:(1,1,2,2) M64 N64 | 4:(1,1,4,1) M128 N32
 struct IgemmPlan { int cfg, lgTX, lgTY, TZ, ntz, nty, ntx, IZ, IY, IX, gridy, ksplit, kg_per, gn_zt; long need; };
 enum { CONV_DSC = 1, CONV_C2, CONV_W3, CONV_WINO, CONV_K1S, CONV_UPM, CONV_IGEMM };
-// profile symbols (bts_prof_begin; names: ops.kernel_symbol); the tiled kernel's is its cfg + SYM_IGEMM_K1 * (1x1x1 staging)
-enum { SYM_IGEMM_K1 = 8, SYM_UPM = 20, SYM_K1S = 21, SYM_DSC = 22, SYM_WINO = 23, SYM_C2 = 25, SYM_W3 = 27 };
+// profile symbols (bts_prof_begin; names: ops.kernel_symbol); the tiled kernel's is its cfg + SYM_IGEMM_K1 * (1x1x1 staging), the direct
+// weight-gradient kernel's (wgrad_plan.h) SYM_WGRAD + (MODE << 2 | FIXG) of wgrad_kernel<MODE, FIXG>
+enum { SYM_IGEMM_K1 = 8, SYM_UPM = 20, SYM_K1S = 21, SYM_DSC = 22, SYM_WINO = 23, SYM_WGW = 24, SYM_C2 = 25, SYM_K1W = 26, SYM_W3 = 27,
+       SYM_WGRAD = 100 };
 struct ConvChoice {
   int kernel;             // CONV_DSC | C2 | W3 | WINO | K1S | UPM | IGEMM
   int sym;                // its profile symbol (SYM_*)

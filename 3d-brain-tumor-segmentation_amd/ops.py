@@ -25,7 +25,7 @@ _workspaces = {}
 _CFG = {0: '2,1,4,1', 1: '2,2,4,1', 2: '1,2,2,2', 3: '1,1,2,2', 4: '1,1,4,1'}
 
 
-# profile symbol -> kernel name (fp32 conv engine: SYM_* of csrc/conv_plan.h; the weight-gradient and 16-bit kernels name theirs at the launch)
+# profile symbol -> kernel name (fp32 conv engine and its weight gradient: SYM_* of csrc/conv_plan.h; the 16-bit kernels name theirs at the launch)
 _SYMBOLS = {20: 'upm_kernel', 21: 'k1s_kernel', 22: 'dsc_kernel', 23: 'wino_kernel', 24: 'wgw_kernel', 25: 'c2_kernel', 26: 'k1w_kernel',
             27: 'w3_kernel', 30: 'lp_conv_s1_kernel', 31: 'lp_conv_gather_kernel', 32: 'lp_wgrad_kernel', 33: 'lp_s1d_kernel',
             34: 'lp_k1_kernel', 35: 'lp_up_kernel', 36: 'lp_wgs_kernel', 37: 'lp_wgd_kernel', 38: 'lp_s1z_kernel', 39: 'lp_s2t_kernel',

@@ -1,4 +1,4 @@
-"""-m gpu: the three-axis Winograd form F(2x2x2, 3x3x3) of the stride-1 3x3x3 weight gradient (wgw_kernel in csrc/conv_wgrad.hip)
+"""-m gpu: the three-axis Winograd form F(2x2x2, 3x3x3) of the stride-1 3x3x3 weight gradient (wgw_kernel in csrc/conv_wgw.hip)
 against the fp64 oracle, through bts_conv3d_bwd_weight.  Which form took a call is asked of the host
 query bts_conv3d_bwd_weight_form: 3 three-axis | 0 direct (BTS_WGW=0).  The two-axis form (2) it replaced lost at every layer shape
 and left with its switch, so no call can report it.

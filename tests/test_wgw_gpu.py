@@ -1,4 +1,4 @@
-"""-m gpu: the Winograd form of the stride-1 3x3x3 weight gradient (wgw_kernel in csrc/conv_wgrad.hip) against the fp64 oracle,
+"""-m gpu: the Winograd form of the stride-1 3x3x3 weight gradient (wgw_kernel in csrc/conv_wgw.hip) against the fp64 oracle,
 through bts_conv3d_bwd_weight.  The launcher uses it for whole 16x4x2 sub-tiles and 32-channel groups; every test asserts
 through the profiler that `wgw_kernel` really ran, and repeats the call on the direct kernel (BTS_WGW=0).
 

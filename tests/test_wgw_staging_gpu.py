@@ -1,4 +1,4 @@
-"""-m gpu: the staging of wgw_kernel (csrc/conv_wgrad.hip) at the smallest shapes where it can go wrong.  A thread stages the four
+"""-m gpu: the staging of wgw_kernel (csrc/conv_wgw.hip) at the smallest shapes where it can go wrong.  A thread stages the four
 z rows of one (y row, x, channel quad) column of the P halo tile, each z row through a descriptor of its own, and writes the four
 xi_z planes d0 - d2 | d1 + d2 | d2 - d1 | d1 - d3; every group of requests goes out two steps before its LDS write, groups 0 and
 1 of a sub-tile in the last two steps of the sub-tile before.  So: columns on every face (a plane must not come from the
