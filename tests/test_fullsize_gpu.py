@@ -5,8 +5,10 @@ it: tests/test_model_gpu.py::test_train_step_parity[cli_64]), so full size is co
   * form agreement: at 128^3 the dispatcher picks conv forms the small-grid oracle tests only reach by forcing thresholds
     (upm / k1s / dsc / c2 kernels, unsplit Winograd, the Winograd weight gradient, the streaming 1x1x1 weight gradient).
     One full step with the DEFAULT forms must agree with one step where every conv and weight gradient runs in DIRECT form
-    (BTS_WINO=0 BTS_WGW=0 BTS_K1W=0) -- two independent kernel families, the direct one being the family the oracle tests
-    pin at small sizes;
+    (BTS_WINO=0 BTS_WGW=0 BTS_K1W=0) -- two independent kernel families.  The direct convs are the tiled kernel, every config
+    and form of which that a layer runs with BTS_WINO=0 is held to the fp64 oracle by tests/test_tiled_configs_gpu.py (the
+    table tests/tiled_cases.py, kept complete by tests/test_tiled_configs_host.py); the direct weight gradients by
+    tests/test_wgrad_plan_gpu.py;
   * determinism: two default-form steps from the same state end bitwise identical (no float atomics, fixed-order reductions).
 
 Tolerances: loss <= 1e-5 relative, Dice <= 1e-4, y_pred max-abs <= 1e-4, label map identical outside counted

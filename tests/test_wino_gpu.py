@@ -252,7 +252,8 @@ def test_wino_is_deterministic():
 
 def test_wino_full_size_agrees_with_direct_form():
     """BASELINE size (32 -> 32 channels on 128^3, the layer the metric is dominated by): too big for the fp64 oracle, so the
-    Winograd form is held against the engine's own direct-form kernel (itself oracle-checked at small sizes) with the sum of
+    Winograd form is held against the engine's own direct-form kernel (cfg 0 of the tiled kernel with the fixed-geometry sweep, itself
+    held to the fp64 oracle on 16x64x128 by the row 's1 cfg0 fixed geometry 16->32' of tests/tiled_cases.py) with the sum of
     both bounds, the bound sum|a_i b_i| being evaluated by the direct kernel on |x|, |w|; plus linearity in x."""
     import os
     from bts_amd import ops
