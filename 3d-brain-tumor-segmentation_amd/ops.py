@@ -1651,6 +1651,75 @@ def case_norm(x, mask=None, clip=None, y=None, out=None):
     return (out, stats) if y is None else (out, yo, stats)
 
 
+# ---- rigid co-registration by mutual information ----
+def _check_bins(bins, who):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= 64:
+        raise ValueError('%s: bins must be an integer in 2..64, got %r' % (who, bins))
+    return int(bins)
+
+
+def quantize_bins(x, lo, hi, bins=32):
+    """dense float32 device tensor -> uint8 tensor of its shape: clamp(floor((double(x) - lo) * bins / (hi - lo)), 0, bins - 1), evaluated
+    in float64 (bts_quantize_bins); lo < hi finite, bins in 2..64"""
+    bins = _check_bins(bins, 'quantize_bins')
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
+        raise ValueError('quantize_bins: x must be a dense, non-empty float32 tensor on the GPU')
+    try:
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError('quantize_bins: lo and hi must be numbers, got %r and %r' % (lo, hi))
+    if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo and np.isfinite(hi - lo)):
+        raise ValueError('quantize_bins: lo < hi must be finite, got %r and %r' % (lo, hi))
+    q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    lib().call('bts_quantize_bins', _p(x), _p(q), x.numel(), lo, hi, bins, _stream())
+    return q
+
+
+def _int3(v, name, who):
+    try:
+        out = tuple(int(t) for t in v)
+        ok = len(out) == 3 and all(float(t) == int(t) for t in v)
+    except (TypeError, ValueError):
+        out, ok = (), False
+    if not ok:
+        raise ValueError('%s: %s must be three integers, got %r' % (who, name, v))
+    return out
+
+
+def joint_hist_pv(qf, qm, origin, stride, counts, matrices, bins=32):
+    """K joint histograms by partial-volume interpolation (bts_joint_hist_pv): qf (Df,Hf,Wf) and qm (Dm,Hm,Wm) dense uint8 device volumes of
+    bin numbers below `bins`; the lattice origin + l * stride, 0 <= l < counts, of the fixed grid; matrices (K,3,4) or (K,4,4) float64, fixed
+    voxel -> moving voxel, 1 <= K <= 32 -> (K,bins,bins) int64 on the device, [k][fixed bin][moving bin]; every counted lattice point adds
+    32768 to its candidate's histogram"""
+    who = 'joint_hist_pv'
+    bins = _check_bins(bins, who)
+    for t, name in ((qf, 'qf'), (qm, 'qm')):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 3 or not t.is_contiguous() \
+                or t.numel() < 1 or t.numel() >= 2 ** 31:
+            raise ValueError('%s: %s must be a dense, non-empty (D,H,W) uint8 volume on the GPU' % (who, name))
+    if qf.device != qm.device:
+        raise ValueError('%s: qf and qm live on different devices' % who)
+    o, s, n = _int3(origin, 'origin', who), _int3(stride, 'stride', who), _int3(counts, 'counts', who)
+    for a in range(3):
+        if o[a] < 0 or s[a] < 1 or n[a] < 1 or o[a] + (n[a] - 1) * s[a] > qf.shape[a] - 1:
+            raise ValueError('%s: the lattice origin %s stride %s counts %s does not lie inside the fixed extent %s'
+                             % (who, o, s, n, tuple(qf.shape)))
+    try:
+        m = np.asarray(matrices, dtype=np.float64)
+    except (TypeError, ValueError):
+        m = np.zeros(0)
+    if m.ndim == 3 and m.shape[1:] == (4, 4):
+        m = m[:, :3]
+    if m.ndim != 3 or m.shape[1:] != (3, 4) or not 1 <= m.shape[0] <= 32 or not np.all(np.isfinite(m)):
+        raise ValueError('%s: matrices must be 1..32 finite 3x4 or 4x4 arrays, got shape %s' % (who, np.shape(matrices)))
+    k = m.shape[0]
+    hist = torch.empty((k, bins, bins), dtype=torch.int64, device=qf.device)
+    m12 = (ctypes.c_double * (12 * k))(*[float(v) for v in m.reshape(-1)])
+    lib().call('bts_joint_hist_pv', _p(qf), qf.shape[0], qf.shape[1], qf.shape[2], _p(qm), qm.shape[0], qm.shape[1], qm.shape[2],
+               o[0], o[1], o[2], s[0], s[1], s[2], n[0], n[1], n[2], m12, k, bins, _p(hist), _stream())
+    return hist
+
+
 # ---- non-default samplers (SURVEY 8 f-4) ----
 def maxpool2_fwd(x):
     n, d, h, w, c = x.shape

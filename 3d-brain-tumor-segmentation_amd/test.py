@@ -5,7 +5,7 @@
                            [--min_component_voxels N] [--et_min_voxels N] [--component_connectivity 26] [--skull_largest_component]
                            [--lesionwise] [--lesion_dilation 3] [--lesion_min_voxels 50] [--lesion_penalty_mm 374]
                            [--window D,H,W|crop] [--window_overlap 0.5] [--window_mode gaussian] [--window_batch N]
-                           [--conform [CODE]]
+                           [--conform [CODE]] [--coregister] [--coregister_max_mm 30] [--coregister_max_deg 20] [--coregister_bins 32]
 
 This module is named after the reference's script and is NOT a pytest module: pytest's `test_*.py` pattern does not match `test.py`
 and `testpaths` points at tests/, so it is never collected.
@@ -49,10 +49,18 @@ is reported and skipped.  Scores act on that native grid, with its own voxel siz
 modality's affine, not a mean; one more line per case prints the native orientation code, the voxel size and the path taken.  Without
 --conform nothing changes.
 
+With --conform --coregister every modality after the first is first registered to the first one: `coreg.coregister_case` estimates one
+rigid motion per modality by normalised mutual information on the device (at most --coregister_max_mm and --coregister_max_deg per
+parameter, --coregister_bins intensity bins) and corrects that modality's affine, so the Conformer reads it where the anatomy is, not where
+the header says; one more line per case and modality prints the six parameters, the score before and after and the candidates evaluated.
+`mask.nii`, the truth check and every score are as with --conform alone: they belong to the first modality, which is not moved.  Without
+--conform the modalities are stacked voxel for voxel and there is no affine to correct: --coregister is then refused.
+
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
 accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
 --min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component, --lesionwise, --lesion_dilation,
---lesion_min_voxels, --lesion_penalty_mm, --window, --window_overlap, --window_mode, --window_batch, --conform.
+--lesion_min_voxels, --lesion_penalty_mm, --window, --window_overlap, --window_mode, --window_batch, --conform, --coregister,
+--coregister_max_mm, --coregister_max_deg, --coregister_bins.
 
 Deviations:
   * cases are visited in sorted order of their paths (the reference: the file system's order);
@@ -77,7 +85,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import nifti
+from . import coreg, nifti
 from .infer import (BRATS_REGIONS, WINDOW_MODES, Conformer, Interpolator, StageSpec, WindowSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
                     scores_from_confusion, segment_case, surface_scores, zoom_output_shape)
 from .preprocess import load_norm
@@ -92,6 +100,7 @@ LESION_COUNT_KEYS = tuple('lw_%s_%s' % (what, name) for what in ('lesions', 'fn'
 LESION_KEYS = LESION_SCORE_KEYS + LESION_COUNT_KEYS      # the columns --lesionwise appends to scores.csv, after the others
 LESION_DEFAULTS = {'lesion_dilation': 3, 'lesion_min_voxels': 50, 'lesion_penalty_mm': 374.0}
 WINDOW_DEFAULTS = {'window_overlap': 0.5, 'window_mode': 'gaussian', 'window_batch': None}
+COREGISTER_DEFAULTS = {'coregister_max_mm': 30.0, 'coregister_max_deg': 20.0, 'coregister_bins': 32}
 
 
 def _window_arg(text):
@@ -169,6 +178,15 @@ def arg_parser():
     # and --conform: absent, the namespace has no such attribute and nothing changes
     p.add_argument('--conform', type=_code_arg, nargs='?', const='LPS', default=argparse.SUPPRESS, metavar='CODE',
                    help='Bring every modality onto one 1 mm grid of this orientation by its affine (default code: LPS), and the labels back.')
+    # and --coregister with its bounds: `coregister_kwargs` supplies COREGISTER_DEFAULTS
+    p.add_argument('--coregister', action='store_true', default=argparse.SUPPRESS,
+                   help='With --conform: register every modality to the first by mutual information and correct its affine.')
+    p.add_argument('--coregister_max_mm', type=float, default=argparse.SUPPRESS,
+                   help='Largest translation searched per axis, mm (default: %g).' % COREGISTER_DEFAULTS['coregister_max_mm'])
+    p.add_argument('--coregister_max_deg', type=float, default=argparse.SUPPRESS,
+                   help='Largest rotation searched per axis, degrees (default: %g).' % COREGISTER_DEFAULTS['coregister_max_deg'])
+    p.add_argument('--coregister_bins', type=int, default=argparse.SUPPRESS,
+                   help='Intensity bins per modality of the joint histogram, 2..64 (default: %d).' % COREGISTER_DEFAULTS['coregister_bins'])
     return p
 
 
@@ -185,6 +203,16 @@ def parse_args(argv=None):
         parser.error('--window_overlap must lie in [0, 1)')
     if getattr(args, 'window_batch', 1) < 1:
         parser.error('--window_batch must be positive')
+    if hasattr(args, 'coregister') and not hasattr(args, 'conform'):
+        parser.error('--coregister needs --conform: without it the modalities are stacked voxel for voxel and there is no affine to correct')
+    if not hasattr(args, 'coregister') and any(hasattr(args, k) for k in COREGISTER_DEFAULTS):
+        parser.error('--coregister_max_mm, --coregister_max_deg and --coregister_bins need --coregister')
+    if not 0 < getattr(args, 'coregister_max_mm', 30.0) < float('inf'):
+        parser.error('--coregister_max_mm must be positive')
+    if not 0 < getattr(args, 'coregister_max_deg', 20.0) <= 180:
+        parser.error('--coregister_max_deg must lie in (0, 180]')
+    if not 2 <= getattr(args, 'coregister_bins', 32) <= 64:
+        parser.error('--coregister_bins must lie in 2..64')
     if args.skull_largest_component and not args.skull_model:
         parser.error('--skull_largest_component needs --skull_model')
     args.modalities = args.modalities.split(',')
@@ -344,6 +372,14 @@ def window_kwargs(args):
             'batch': getattr(args, 'window_batch', WINDOW_DEFAULTS['window_batch'])}
 
 
+def coregister_kwargs(args):
+    """None without --coregister, else the keyword arguments of coreg.coregister_case"""
+    if not getattr(args, 'coregister', False):
+        return None
+    v = {k: getattr(args, k, d) for k, d in COREGISTER_DEFAULTS.items()}
+    return {'bounds': (float(v['coregister_max_mm']), float(v['coregister_max_deg'])), 'bins': int(v['coregister_bins'])}
+
+
 def require_gpu():
     """-> the current device; no CPU path: without a GPU the command ends with the Interpolator's message"""
     Interpolator._device_volume(np.zeros((1, 1, 1, 1), dtype=np.float32))
@@ -419,6 +455,7 @@ def run(args):
     lesionwise = lesion is not None
     windowed = window_kwargs(args) is not None
     conf = Conformer(args.conform, (1.0, 1.0, 1.0), args.order) if getattr(args, 'conform', None) is not None else None
+    registering = coregister_kwargs(args)
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
     for (name, path), case in zip(cases, _decoded(cases, args)):
@@ -436,8 +473,13 @@ def run(args):
             pixdim = tuple(float(v) for v in case['pixdim'][1:4])
         else:
             vols, y = upload_conform_case(case, dev)
-            x, geometry, affine = None, (conf, vols, case['affines']), case['affines'][0]
-            plan = conf.plan([tuple(v.shape) for v in vols], case['affines'])
+            affines = case['affines']
+            if registering is not None:
+                affines, found = coreg.coregister_case(vols, affines, **registering)
+                for mod, r in zip(args.modalities[1:], found[1:]):
+                    print('{}. Coregistered {}'.format(name, coreg.format_result(mod, r)), flush=True)
+            x, geometry, affine = None, (conf, vols, affines), case['affines'][0]
+            plan = conf.plan([tuple(v.shape) for v in vols], affines)
             pixdim = plan['native_spacing']                      # the distances of the scores are taken on the native grid
             print('{}. Orientation {} -> {}, voxel size {:.4g} x {:.4g} x {:.4g} mm, {}'.format(
                 name, plan['code'], conf.orientation, pixdim[0], pixdim[1], pixdim[2],

@@ -628,6 +628,28 @@ int bts_case_norm(const float* xwin, long st0, long st1, const float* mask_or_nu
                   long yst0, long yst1, int T0, int T1, int T2, int C, int clip, double p_lo, double p_hi, float* xo, float* yo,
                   double* stats, void* workspace, long workspace_bytes, bts_stream_t stream);
 
+/* ===== rigid co-registration of a scan's modalities by mutual information (bts_amd.coreg; the reference stacks its modalities voxel
+ * for voxel, test.py:21-42, and so relies on files that were registered beforehand) =====
+ * q (n bytes, dense) = clamp(floor((double(x) - lo) * bins / (hi - lo)), 0, bins - 1) of the n dense fp32 values x, evaluated in fp64, each
+ * operation rounded once; a NaN gives bin 0.  lo < hi: host doubles; bins in 2..64.
+ * BTS_ERR_SHAPE, before any HIP call: n <= 0, hi <= lo or a bound that is not finite, bins outside 2..64, a NULL pointer. */
+int bts_quantize_bins(const float* x, uint8_t* q, long n, double lo, double hi, int bins, bts_stream_t stream);
+/* K joint histograms of the binned volumes qf (Df,Hf,Wf) and qm (Dm,Hm,Wm), dense bytes below `bins`, one per candidate map, by
+ * partial-volume interpolation (Collignon / Maes): hist, K x bins x bins device 64-bit counts, [k][fixed bin][moving bin], is overwritten
+ * completely and need not be set.  m12: a HOST array of 12 K doubles read during the call, K row-major 3 x 4 maps from a fixed voxel
+ * coordinate to a moving voxel coordinate (m12 of bts_affine_resample3d).  The lattice: points f = o + l * s of the fixed grid, 0 <= l_j < n_j,
+ * with o_j >= 0, s_j >= 1, n_j >= 1 and o_j + (n_j - 1) s_j <= extent_j - 1.  With Q = 32, per point and candidate, a = qf[f]:
+ *   c_j = ((m[j][0] f0 + m[j][1] f1) + m[j][2] f2) + m[j][3] in fp64, every operation rounded once (no fused multiply-add);
+ *   the point counts only if 0 <= c_j <= N_j - 1 on all three axes; then i_j = floor(c_j), r_j = (int)floor((c_j - i_j) Q + 0.5) in [0, Q];
+ *   the corner (d0,d1,d2) in {0,1}^3 holds b = qm[min(i_j + d_j, N_j - 1)], and hist[k][a][b] grows by prod_j (d_j ? r_j : Q - r_j).
+ * Every counted point adds exactly Q^3 = 32768, so the overlap of candidate k is sum(hist[k]) / 32768 points.  All sums are integers: the
+ * result is the same bits in every run.  No workspace.  A byte of qf / qm at or above `bins` counts as bins - 1.
+ * BTS_ERR_SHAPE, with nothing launched: a non-positive extent or a volume of 2^31 voxels or more, a lattice that is not as above, K outside
+ * 1..32, bins outside 2..64, a NULL qf, qm, m12 or hist. */
+int bts_joint_hist_pv(const uint8_t* qf, int Df, int Hf, int Wf, const uint8_t* qm, int Dm, int Hm, int Wm, int o0, int o1, int o2, int s0,
+                      int s1, int s2, int n0, int n1, int n2, const double* m12, int K, int bins, unsigned long long* hist,
+                      bts_stream_t stream);
+
 /* library identification */
 const char* bts_version(void);
 
