@@ -1720,6 +1720,154 @@ def joint_hist_pv(qf, qm, origin, stride, counts, matrices, bins=32):
     return hist
 
 
+# ---- N4 bias-field correction ----
+N4_MAX_BINS, N4_MAX_MESH, N4_MAX_AXIS = 1024, 64, 512
+
+
+def n4_lattice(shape, stride, who='n4'):
+    """-> the lattice counts per axis of the strided sub-grid origin stride // 2 (bts_n4_*); 1 <= stride <= extent per axis"""
+    shape, stride = _int3(shape, 'shape', who), _int3(stride, 'stride', who)
+    if min(shape) < 1 or shape[0] * shape[1] * shape[2] >= 2 ** 31:
+        raise ValueError('%s: the volume must have 1 .. 2^31 - 1 voxels, got shape %s' % (who, shape))
+    if any(not 1 <= s <= n for s, n in zip(stride, shape)):
+        raise ValueError('%s: stride %s must lie in 1..extent per axis of %s' % (who, stride, shape))
+    return tuple((n - 1 - s // 2) // s + 1 for n, s in zip(shape, stride))
+
+
+def _n4_mesh(mesh, who):
+    mesh = _int3(mesh, 'mesh', who)
+    if any(not 1 <= m <= N4_MAX_MESH for m in mesh):
+        raise ValueError('%s: mesh must lie in 1..%d per axis, got %s' % (who, N4_MAX_MESH, mesh))
+    return mesh
+
+
+def _n4_bins(bins, who):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= N4_MAX_BINS:
+        raise ValueError('%s: bins must be an integer in 2..%d, got %r' % (who, N4_MAX_BINS, bins))
+    return int(bins)
+
+
+def _n4_dense(t, dtype, shape, name, who):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError('%s: %s must be a dense %s tensor of shape %s on the GPU' % (who, name, str(dtype).replace('torch.', ''), tuple(shape)))
+    return t
+
+
+def _n4_points(t, name, who):
+    """a lattice array: dense, three-dimensional, non-empty"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.numel() < 1:
+        raise ValueError('%s: %s must be a non-empty (n0,n1,n2) lattice array' % (who, name))
+    return tuple(t.shape)
+
+
+def n4_log_lattice(x, mask=None, stride=(1, 1, 1)):
+    """dense float32 (D,H,W) device volume -> (v float64, lmask uint8) on the lattice of `stride`: v = log(x) and lmask = 1 where x > 0 and
+    finite and mask (uint8 or bool (D,H,W), non-zero = inside; None: everywhere) allows it, 0 and 0 elsewhere (bts_n4_log_lattice)"""
+    who = 'n4_log_lattice'
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError('%s: x must be a (D,H,W) volume' % who)
+    _n4_dense(x, torch.float32, x.shape, 'x', who)
+    n = n4_lattice(x.shape, stride, who)
+    s = _int3(stride, 'stride', who)
+    if mask is not None:
+        if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        _n4_dense(mask, torch.uint8, x.shape, 'mask', who)
+    v = torch.empty(n, dtype=torch.float64, device=x.device)
+    lm = torch.empty(n, dtype=torch.uint8, device=x.device)
+    lib().call('bts_n4_log_lattice', _p(x), _p(mask), x.shape[0], x.shape[1], x.shape[2], s[0], s[1], s[2], _p(v), _p(lm), _stream())
+    return v, lm
+
+
+def n4_hist(v, f, lmask, bins=200):
+    """-> (r, lohi, hist): r = v - f on the lattice mask (0 elsewhere), lohi = its exact (min, max) over the mask as 2 float64 on the device
+    ((+inf, -inf) for an empty mask), hist = `bins` int64 counts with linear two-bin weights, 2^24 per masked point (bts_n4_range_hist)"""
+    who = 'n4_hist'
+    bins = _n4_bins(bins, who)
+    n = _n4_points(v, 'v', who)
+    _n4_dense(v, torch.float64, n, 'v', who)
+    _n4_dense(f, torch.float64, n, 'f', who)
+    _n4_dense(lmask, torch.uint8, n, 'lmask', who)
+    r = torch.empty(n, dtype=torch.float64, device=v.device)
+    range4 = torch.empty(4, dtype=torch.float64, device=v.device)
+    hist = torch.empty(bins, dtype=torch.int64, device=v.device)
+    lib().call('bts_n4_range_hist', _p(v), _p(f), _p(lmask), v.numel(), bins, _p(r), _p(range4), _p(hist), _stream())
+    return r, range4[:2], hist
+
+
+def n4_residual(r, lmask, table, lo, sl):
+    """-> res = r - (E[i] (1 - o) + E[i+1] o) on the mask, 0 elsewhere: the table E (`bins` float64 on the device) looked up at
+    c = (r - lo) / sl, i = min(floor(c), bins - 2), o = c - i (bts_n4_residual); lo finite, sl >= 0 finite"""
+    who = 'n4_residual'
+    n = _n4_points(r, 'r', who)
+    _n4_dense(r, torch.float64, n, 'r', who)
+    _n4_dense(lmask, torch.uint8, n, 'lmask', who)
+    if not isinstance(table, torch.Tensor) or table.dim() != 1:
+        raise ValueError('%s: the table must be a vector of float64 on the GPU' % who)
+    bins = _n4_bins(int(table.numel()), who)
+    _n4_dense(table, torch.float64, (bins,), 'table', who)
+    lo, sl = float(lo), float(sl)
+    if not (np.isfinite(lo) and np.isfinite(sl) and sl >= 0.0):
+        raise ValueError('%s: lo must be finite and sl finite and not negative, got %r and %r' % (who, lo, sl))
+    res = torch.empty(n, dtype=torch.float64, device=r.device)
+    lib().call('bts_n4_residual', _p(r), _p(lmask), _p(table), r.numel(), bins, lo, sl, _p(res), _stream())
+    return res
+
+
+def _n4_geometry(shape, stride, mesh, lmask, who):
+    n = n4_lattice(shape, stride, who)
+    mesh = _n4_mesh(mesh, who)
+    _n4_dense(lmask, torch.uint8, n, 'lmask', who)
+    shape, stride = _int3(shape, 'shape', who), _int3(stride, 'stride', who)
+    return n, mesh, shape + stride + mesh
+
+
+def n4_fit(res, lmask, shape, stride, mesh, phi=None):
+    """one level of multilevel B-spline approximation of the residuals on the lattice of `stride` in a volume of `shape` -> (num, den,
+    dphi), float64 of shape mesh + 3: num = sum w^3 z / S, den = sum w^2 over the masked lattice points in each control point's support,
+    dphi = num / den, 0 where den == 0; phi (the same shape), when given, grows by dphi in place (bts_n4_fit)"""
+    who = 'n4_fit'
+    n, mesh, geo = _n4_geometry(shape, stride, mesh, lmask, who)
+    if max(n) > N4_MAX_AXIS:
+        raise ValueError('%s: at most %d lattice points per axis, got %s' % (who, N4_MAX_AXIS, n))
+    _n4_dense(res, torch.float64, n, 'res', who)
+    cp = tuple(m + 3 for m in mesh)
+    if phi is not None:
+        _n4_dense(phi, torch.float64, cp, 'phi', who)
+    num, den, dphi = (torch.empty(cp, dtype=torch.float64, device=res.device) for _ in range(3))
+    lib().call('bts_n4_fit', _p(res), _p(lmask), *(geo + (_p(num), _p(den), _p(dphi), _p(phi), _stream())))
+    return num, den, dphi
+
+
+def n4_eval(phi, lmask, f_old, shape, stride, mesh):
+    """-> (f_new, parts): the spline of phi (float64, mesh + 3) at every lattice point, and parts (B,2) float64, the sums of
+    e = exp(f_new - f_old) and e^2 over the masked points of each run of 1024 lattice points (bts_n4_eval)"""
+    who = 'n4_eval'
+    n, mesh, geo = _n4_geometry(shape, stride, mesh, lmask, who)
+    _n4_dense(phi, torch.float64, tuple(m + 3 for m in mesh), 'phi', who)
+    _n4_dense(f_old, torch.float64, n, 'f_old', who)
+    f_new = torch.empty(n, dtype=torch.float64, device=phi.device)
+    parts = torch.empty((lib().query('bts_n4_eval_parts', n[0] * n[1] * n[2]), 2), dtype=torch.float64, device=phi.device)
+    lib().call('bts_n4_eval', _p(phi), *(geo + (_p(f_old), _p(lmask), _p(f_new), _p(parts), _stream())))
+    return f_new, parts
+
+
+def n4_apply(x, phi, mesh, field=False):
+    """dense float32 (D,H,W) device volume -> float32(x / exp(spline of phi)) at every voxel; with field=True also float32(exp(spline))
+    (bts_n4_apply)"""
+    who = 'n4_apply'
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError('%s: x must be a (D,H,W) volume' % who)
+    _n4_dense(x, torch.float32, x.shape, 'x', who)
+    n4_lattice(x.shape, (1, 1, 1), who)
+    mesh = _n4_mesh(mesh, who)
+    _n4_dense(phi, torch.float64, tuple(m + 3 for m in mesh), 'phi', who)
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    fld = torch.empty(x.shape, dtype=torch.float32, device=x.device) if field else None
+    lib().call('bts_n4_apply', _p(x), x.shape[0], x.shape[1], x.shape[2], _p(phi), mesh[0], mesh[1], mesh[2], _p(out), _p(fld), _stream())
+    return (out, fld) if field else out
+
+
 # ---- non-default samplers (SURVEY 8 f-4) ----
 def maxpool2_fwd(x):
     n, d, h, w, c = x.shape

@@ -2,6 +2,8 @@
 
     python -m bts_amd.preprocess --in_locs a,b --modalities t1ce,flair --truth seg [--create_val] [--out_loc ./data]
                                  [--norm dataset|case] [--clip_percentiles LO,HI]
+                                 [--bias_correct [--bias_shrink 4] [--bias_levels 4] [--bias_iters 50] [--bias_threshold 0.001]
+                                  [--bias_fwhm 0.15]]
 
 The names, the argument order and the results are the reference's: `create_dataset` finds the bounding box of all non-zero voxels
 of all cases and crops every case to it, `compute_norm` gives the per-channel mean and standard deviation of the training cases,
@@ -28,7 +30,10 @@ Deviations:
   * examples are stored as `.npz` files with the arrays `x` and `y`, the form data.prepare_dataset reads, not as TFRecords;
   * --norm case (off by default) normalises every case on its own brain voxels instead, as the paper the model comes from does, with
     --clip_percentiles LO,HI after clamping them to robust percentiles (`normalize_case`, ops.case_norm, csrc/casenorm.hip); prepro.npy
-    then records the mode, and `python -m bts_amd.test` normalises each scan the same way (`load_norm`).
+    then records the mode, and `python -m bts_amd.test` normalises each scan the same way (`load_norm`);
+  * --bias_correct (off by default) removes the coil shading of every modality of every case by N4 (bts_amd.n4, csrc/n4.hip) right after
+    upload, before the bounding box, the statistics and the normalisation, on that modality's own positive voxels; prepro.npy then gains a
+    `bias` entry with the spec, and `python -m bts_amd.test` corrects each scan the same way (`load_bias`).
 """
 import argparse
 import collections
@@ -41,7 +46,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import nifti, ops
+from . import n4, nifti, ops
 
 
 def get_npy_image(path, name):
@@ -71,21 +76,24 @@ def _decode_case(path, names):
     return [np.ascontiguousarray(get_npy_image(path, name).T) for name in names]
 
 
-def _upload_case(vols, dev):
-    """the decoded volumes of one case (axes reversed, see `_decode_case`) -> resident x (h,w,d,c) and y (h,w,d,1)"""
+def _upload_case(vols, dev, bias=None):
+    """the decoded volumes of one case (axes reversed, see `_decode_case`) -> resident x (h,w,d,c) and y (h,w,d,1); bias: None or the
+    N4Spec every modality is corrected with on its own positive voxels before it is stored"""
     c = len(vols) - 1
     x = torch.empty(vols[0].shape[::-1] + (c,), dtype=torch.float32, device=dev)
     for ch in range(c):
-        x[..., ch].copy_(torch.from_numpy(vols[ch]).to(dev).permute(2, 1, 0))
+        v = torch.from_numpy(vols[ch]).to(dev).permute(2, 1, 0)
+        x[..., ch].copy_(v if bias is None else n4.correct(v.contiguous(), None, bias).out)
     y = torch.from_numpy(vols[c]).to(dev).permute(2, 1, 0).contiguous().unsqueeze(-1)
     return x, y
 
 
-def create_dataset(locs, modalities, truth, device=None, workers=8):
+def create_dataset(locs, modalities, truth, device=None, workers=8, bias=None):
     """-> (x, y, size): lists of device views (h,w,d,c) / (h,w,d,1) of the resident raw volumes, restricted to the bounding box
     common to all cases, and size = {'h','w','d','c'}   [preprocess.py:17-65]
     Every entry of every folder of `locs` is a case; folders and cases are visited in sorted order (the reference visits them in
-    the file system's order).  Files are decoded by `workers` threads.  `y` holds the labels as stored; see `remap_labels`."""
+    the file system's order).  Files are decoded by `workers` threads.  `y` holds the labels as stored; see `remap_labels`.
+    bias: None or the n4.N4Spec every modality is corrected with right after upload."""
     dev = _device(device)
     cases = [p for loc in locs for p in sorted(glob.glob(os.path.join(loc, '*')))]
     if not cases:
@@ -116,7 +124,7 @@ def create_dataset(locs, modalities, truth, device=None, workers=8):
                 occ = torch.zeros((len(cases), sum(shape)), dtype=torch.int32, device=dev)
             elif vols[0].shape[::-1] != shape:
                 raise ValueError('%s: shape %s differs from the %s of %s' % (path, vols[0].shape[::-1], shape, cases[0]))
-            x_, y_ = _upload_case(vols, dev)
+            x_, y_ = _upload_case(vols, dev, bias)
             ops.prepro_occupancy(x_, occ[k])
             xs.append(x_)
             ys.append(y_)
@@ -207,9 +215,22 @@ def _refuse_inputs_inside(out_loc, in_locs):
 
 
 NORM_MODES = ('dataset', 'case')
+BIAS_DEFAULTS = {'bias_shrink': 4, 'bias_levels': 4, 'bias_iters': 50, 'bias_threshold': 1e-3, 'bias_fwhm': 0.15}
+BIAS_FIELDS = {'bias_shrink': 'shrink', 'bias_levels': 'levels', 'bias_iters': 'iters', 'bias_threshold': 'threshold', 'bias_fwhm': 'fwhm'}
 
 
-def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=None, workers=8, norm='dataset', clip=None):
+def prepro_record(size, mean, std, norm='dataset', clip=None, bias=None):
+    """what prepro.npy holds: {'size', 'norm': {'mean', 'std'}} as the reference writes it; the mode and the clip percentiles with norm
+    'case'; and a `bias` entry (n4.spec_record) only where the examples were bias-corrected.  Without the new options the file is byte for
+    byte what it has always been"""
+    nd = {'mode': 'case', 'clip': clip, 'mean': mean, 'std': std} if norm == 'case' else {'mean': mean, 'std': std}
+    rec = {'size': size, 'norm': nd}
+    if bias is not None:
+        rec['bias'] = n4.spec_record(bias)
+    return rec
+
+
+def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=None, workers=8, norm='dataset', clip=None, bias=None):
     """the reference's main (preprocess.py:99-131): out_loc/train/{i}.npz, out_loc/val/{i}.npz (arrays x (h,w,d,c) and y (h,w,d,1),
     float32) and out_loc/prepro.npy -> {'size', 'mean', 'std', 'n_train', 'n_val'}
     An existing out_loc is REMOVED with everything in it and created anew before any scan is read, as the reference's argument
@@ -218,15 +239,17 @@ def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=Non
     norm: 'dataset' (the default: one mean and deviation per channel over the training cases, `compute_norm`, as the reference) |
     'case' (every case on its own brain voxels, `normalize_case`, as the paper the model comes from; `compute_norm` is not run and
     prepro.npy records the mode with an identity mean / std, so that every reader of the file keeps working).  clip: None or the
-    percentiles (lo, hi) of a case's brain voxels its intensities are clamped to first; 'case' only."""
+    percentiles (lo, hi) of a case's brain voxels its intensities are clamped to first; 'case' only.  bias: None or the n4.N4Spec of the
+    bias-field correction every modality gets first; prepro.npy then records it as `bias` (`prepro_record`)."""
     if norm not in NORM_MODES:
         raise ValueError('norm must be one of %s, got %r' % (NORM_MODES, norm))
     clip = ops.check_clip(clip)
     if clip is not None and norm != 'case':
         raise ValueError("clip needs norm='case'")
+    bias = n4.check_spec(bias) if bias is not None else None
     _refuse_inputs_inside(out_loc, in_locs)
     train_loc, val_loc = make_dirs(out_loc)
-    x_train, y_train, size = create_dataset(in_locs, modalities, truth, device=device, workers=workers)
+    x_train, y_train, size = create_dataset(in_locs, modalities, truth, device=device, workers=workers, bias=bias)
     x_val, y_val = [], []
     if create_val:
         split = len(x_train) // 11
@@ -238,11 +261,11 @@ def preprocess(in_locs, modalities, truth, out_loc, create_val=False, device=Non
         if not x_train:
             raise ValueError('preprocess needs at least one training case')
         mean, std = np.zeros((1, 1, 1, len(modalities))), np.ones((1, 1, 1, len(modalities)))
-        np.save(os.path.join(out_loc, 'prepro.npy'), {'size': size, 'norm': {'mode': 'case', 'clip': clip, 'mean': mean, 'std': std}})
+        np.save(os.path.join(out_loc, 'prepro.npy'), prepro_record(size, mean, std, norm, clip, bias))
         mean_d = std_d = None
     else:
         mean, std = compute_norm(x_train, len(modalities))
-        np.save(os.path.join(out_loc, 'prepro.npy'), {'size': size, 'norm': {'mean': mean, 'std': std}})
+        np.save(os.path.join(out_loc, 'prepro.npy'), prepro_record(size, mean, std, norm, clip, bias))
         dev = x_train[0].device
         mean_d, std_d = _stats_on(dev, mean), _stats_on(dev, std)
     _write(train_loc, x_train, y_train, mean_d, std_d, norm, clip)
@@ -261,6 +284,48 @@ def load_prepro(path):
     if mean.shape != (size[3],) or std.shape != (size[3],):
         raise ValueError('%s: mean / std of %d / %d values for %d channels' % (path, mean.size, std.size, size[3]))
     return size, mean, std
+
+
+def load_bias(path):
+    """prepro.npy -> the n4.N4Spec its examples were bias-corrected with, None where it records none"""
+    rec = np.load(path, allow_pickle=True).item().get('bias')
+    return n4.spec_from_record(rec) if rec is not None else None
+
+
+def add_bias_flags(p):
+    """--bias_correct and its sub-flags, shared with `python -m bts_amd.test`: in the namespace only where the command line gives them"""
+    p.add_argument('--bias_correct', action='store_true', default=argparse.SUPPRESS,
+                   help='Remove the coil shading of every modality by N4 bias-field correction on the device.')
+    p.add_argument('--bias_shrink', type=int, default=argparse.SUPPRESS,
+                   help='Stride of the lattice the field is estimated on (default: %d).' % BIAS_DEFAULTS['bias_shrink'])
+    p.add_argument('--bias_levels', type=int, default=argparse.SUPPRESS,
+                   help='Fitting levels, the spline mesh doubling from one to the next, 1..6 (default: %d).' % BIAS_DEFAULTS['bias_levels'])
+    p.add_argument('--bias_iters', type=int, default=argparse.SUPPRESS,
+                   help='Sweeps per level at most (default: %d).' % BIAS_DEFAULTS['bias_iters'])
+    p.add_argument('--bias_threshold', type=float, default=argparse.SUPPRESS,
+                   help='A level ends when the field changes by less than this coefficient of variation (default: %g).'
+                        % BIAS_DEFAULTS['bias_threshold'])
+    p.add_argument('--bias_fwhm', type=float, default=argparse.SUPPRESS,
+                   help='Width of the Gaussian the log histogram is deconvolved by (default: %g).' % BIAS_DEFAULTS['bias_fwhm'])
+
+
+def bias_spec(args, parser=None, recorded=None):
+    """-> the n4.N4Spec the flags ask for: None without --bias_correct (then `recorded`, a prepro.npy's own spec, stands as it is); with
+    it, the recorded spec or the defaults, each sub-flag given replacing its field.  A sub-flag without --bias_correct, or a value out of
+    range, ends in parser.error (ValueError without a parser)"""
+    def fail(msg):
+        if parser is not None:
+            parser.error(msg)
+        raise ValueError(msg)
+    given = {BIAS_FIELDS[k]: getattr(args, k) for k in BIAS_DEFAULTS if hasattr(args, k)}
+    if not hasattr(args, 'bias_correct'):
+        if given:
+            fail('--bias_shrink, --bias_levels, --bias_iters, --bias_threshold and --bias_fwhm need --bias_correct')
+        return recorded
+    try:
+        return n4.check_spec((recorded if recorded is not None else n4.N4Spec())._replace(**given))
+    except ValueError as e:
+        fail(str(e).replace('n4: ', '--bias_'))
 
 
 NormSpec = collections.namedtuple('NormSpec', ('mode', 'clip', 'mean', 'std'))
@@ -307,6 +372,7 @@ def arg_parser():
                         'brain voxels.')
     p.add_argument('--clip_percentiles', type=_clip_arg, default=argparse.SUPPRESS, metavar='LO,HI',
                    help='With --norm case: clamp the brain voxels of each case to these percentiles first, e.g. 0.5,99.5.')
+    add_bias_flags(p)
     return p
 
 
@@ -320,6 +386,7 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if hasattr(args, 'clip_percentiles') and getattr(args, 'norm', 'dataset') != 'case':
         parser.error('--clip_percentiles needs --norm case')
+    bias_spec(args, parser)
     args.in_locs = args.in_locs.split(',')
     args.modalities = args.modalities.split(',')
     return args
@@ -328,7 +395,7 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     print('Preprocess args: {}'.format(args))
-    r = preprocess(args.in_locs, args.modalities, args.truth, args.out_loc, create_val=args.create_val, **norm_kwargs(args))
+    r = preprocess(args.in_locs, args.modalities, args.truth, args.out_loc, create_val=args.create_val, bias=bias_spec(args), **norm_kwargs(args))
     print('mean {} std {}'.format(r['mean'].reshape(-1), r['std'].reshape(-1)))
     return 0
 

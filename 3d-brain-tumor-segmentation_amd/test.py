@@ -6,6 +6,7 @@
                            [--lesionwise] [--lesion_dilation 3] [--lesion_min_voxels 50] [--lesion_penalty_mm 374]
                            [--window D,H,W|crop] [--window_overlap 0.5] [--window_mode gaussian] [--window_batch N]
                            [--conform [CODE]] [--coregister] [--coregister_max_mm 30] [--coregister_max_deg 20] [--coregister_bins 32]
+                           [--bias_correct [--bias_shrink 4] [--bias_levels 4] [--bias_iters 50] [--bias_threshold 0.001] [--bias_fwhm 0.15]]
 
 This module is named after the reference's script and is NOT a pytest module: pytest's `test_*.py` pattern does not match `test.py`
 and `testpaths` points at tests/, so it is never collected.
@@ -56,11 +57,18 @@ the header says; one more line per case and modality prints the six parameters, 
 `mask.nii`, the truth check and every score are as with --conform alone: they belong to the first modality, which is not moved.  Without
 --conform the modalities are stacked voxel for voxel and there is no affine to correct: --coregister is then refused.
 
+Bias-field correction: where the tumour stage's prepro.npy records a `bias` spec (`python -m bts_amd.preprocess --bias_correct` wrote it),
+or with --bias_correct, every modality of every case is corrected once by N4 on its own positive voxels right after upload
+(`n4.correct`, csrc/n4.hip), before --coregister, --conform, the Interpolator and both model stages.  --bias_shrink, --bias_levels,
+--bias_iters, --bias_threshold and --bias_fwhm need --bias_correct and replace the recorded fields.  One line at the start says which
+rule applies, one more line per case prints the sweeps per level and the final cv per modality.  Without either nothing changes.
+
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
 accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
 --min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component, --lesionwise, --lesion_dilation,
 --lesion_min_voxels, --lesion_penalty_mm, --window, --window_overlap, --window_mode, --window_batch, --conform, --coregister,
---coregister_max_mm, --coregister_max_deg, --coregister_bins.
+--coregister_max_mm, --coregister_max_deg, --coregister_bins, --bias_correct, --bias_shrink, --bias_levels, --bias_iters,
+--bias_threshold, --bias_fwhm.
 
 Deviations:
   * cases are visited in sorted order of their paths (the reference: the file system's order);
@@ -85,10 +93,10 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import coreg, nifti
+from . import coreg, n4, nifti
 from .infer import (BRATS_REGIONS, WINDOW_MODES, Conformer, Interpolator, StageSpec, WindowSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
                     scores_from_confusion, segment_case, surface_scores, zoom_output_shape)
-from .preprocess import load_norm
+from .preprocess import add_bias_flags, bias_spec, load_bias, load_norm
 from .train import load_checkpoint, load_train_args
 
 N_CLASSES = 4        # background + the three BraTS labels 1, 2, 4 (4 counts as class 3, preprocess.py:36)
@@ -187,6 +195,8 @@ def arg_parser():
                    help='Largest rotation searched per axis, degrees (default: %g).' % COREGISTER_DEFAULTS['coregister_max_deg'])
     p.add_argument('--coregister_bins', type=int, default=argparse.SUPPRESS,
                    help='Intensity bins per modality of the joint histogram, 2..64 (default: %d).' % COREGISTER_DEFAULTS['coregister_bins'])
+    # and --bias_correct with its sub-flags, the ones of `python -m bts_amd.preprocess`
+    add_bias_flags(p)
     return p
 
 
@@ -213,6 +223,7 @@ def parse_args(argv=None):
         parser.error('--coregister_max_deg must lie in (0, 180]')
     if not 2 <= getattr(args, 'coregister_bins', 32) <= 64:
         parser.error('--coregister_bins must lie in 2..64')
+    bias_spec(args, parser)
     if args.skull_largest_component and not args.skull_model:
         parser.error('--skull_largest_component needs --skull_model')
     args.modalities = args.modalities.split(',')
@@ -380,6 +391,24 @@ def coregister_kwargs(args):
     return {'bounds': (float(v['coregister_max_mm']), float(v['coregister_max_deg'])), 'bins': int(v['coregister_bins'])}
 
 
+def bias_rule(args):
+    """-> the n4.N4Spec every modality of every case is corrected with right after upload, or None: the spec the tumour stage's
+    prepro.npy records (its examples were corrected, so its scans must be), or --bias_correct with its sub-flags, which replace the
+    recorded fields.  Says which rule applies in one line; silent where none does"""
+    recorded = load_bias(args.tumor_prepro) if os.path.isfile(args.tumor_prepro) else None      # a missing dump is load_stage's to report
+    spec = bias_spec(args, None, recorded)
+    if spec is not None:
+        why = ('--bias_correct' + (' over the record of %s' % args.tumor_prepro if recorded is not None else '')
+               if hasattr(args, 'bias_correct') else 'recorded by %s' % args.tumor_prepro)
+        print('Bias-field correction ({}): {}'.format(why, ', '.join('%s %s' % kv for kv in n4.spec_record(spec).items())), flush=True)
+    return spec
+
+
+def print_bias(name, modalities, results):
+    """the one line per case of the bias-field correction: sweeps per level and final cv per modality"""
+    print('{}. Bias-corrected {}'.format(name, '; '.join(n4.format_result(m, r) for m, r in zip(modalities, results))), flush=True)
+
+
 def require_gpu():
     """-> the current device; no CPU path: without a GPU the command ends with the Interpolator's message"""
     Interpolator._device_volume(np.zeros((1, 1, 1, 1), dtype=np.float32))
@@ -456,6 +485,7 @@ def run(args):
     windowed = window_kwargs(args) is not None
     conf = Conformer(args.conform, (1.0, 1.0, 1.0), args.order) if getattr(args, 'conform', None) is not None else None
     registering = coregister_kwargs(args)
+    bias = bias_rule(args)
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
     for (name, path), case in zip(cases, _decoded(cases, args)):
@@ -470,9 +500,17 @@ def run(args):
         geometry, affine = None, case['affine']
         if conf is None:
             x, y = upload_case(case, dev)
+            if bias is not None:
+                corrected = [n4.correct(x[..., ch].contiguous(), None, bias) for ch in range(x.shape[3])]
+                for ch, r in enumerate(corrected):
+                    x[..., ch].copy_(r.out)
+                print_bias(name, args.modalities, corrected)
             pixdim = tuple(float(v) for v in case['pixdim'][1:4])
         else:
             vols, y = upload_conform_case(case, dev)
+            if bias is not None:
+                vols, corrected = n4.correct_case([v.contiguous() for v in vols], bias)
+                print_bias(name, args.modalities, corrected)
             affines = case['affines']
             if registering is not None:
                 affines, found = coreg.coregister_case(vols, affines, **registering)

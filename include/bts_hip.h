@@ -650,6 +650,45 @@ int bts_joint_hist_pv(const uint8_t* qf, int Df, int Hf, int Wf, const uint8_t* 
                       int s1, int s2, int n0, int n1, int n2, const double* m12, int K, int bins, unsigned long long* hist,
                       bts_stream_t stream);
 
+/* ===== N4 bias-field correction of one MRI volume (bts_amd.n4; Tustison et al. 2010.  The reference has no such stage:
+ * preprocess.py and test.py take the scans as they come) =====
+ * The volume x is dense fp32 (D,H,W).  The bias field is exp of a cubic B-spline with M_a mesh elements and M_a + 3 control points per axis,
+ * phi: (M0+3)(M1+3)(M2+3) device doubles, last axis fastest.  Along an axis of extent N a voxel of index p has u = (p + 0.5) / N * M,
+ * cell i = min(floor(u), M - 1), t = u - i, and the uniform cubic B-spline weights of t, (1-t)^3/6, (3t^3-6t^2+4)/6, (-3t^3+3t^2+3t+1)/6,
+ * t^3/6, multiply the control points i .. i+3.  The working lattice is the strided sub-grid p = s_a / 2 + l s_a, 0 <= l < n_a =
+ * (N_a - 1 - s_a / 2) / s_a + 1, with 1 <= s_a <= N_a; a lattice array is n0 n1 n2 values, last axis fastest.  All arithmetic is fp64, every
+ * operation rounded once (no fused multiply-add), no floating-point atomics, fixed summation orders: the same bits in every run.
+ * Every entry point returns BTS_ERR_SHAPE with nothing launched for a non-positive extent, a volume of 2^31 voxels or more, a stride
+ * outside 1..extent, a mesh outside 1..64, bins outside 2..1024, npts outside 1..2^31-1, or a NULL pointer that is not marked _or_null. */
+/* v = log(double(x)) and lmask = 1 at the lattice points where x > 0 and finite and mask_or_null (D,H,W bytes, non-zero = inside; NULL: all)
+ * allows it; v = 0, lmask = 0 elsewhere. */
+int bts_n4_log_lattice(const float* x, const uint8_t* mask_or_null, int D, int H, int W, int s0, int s1, int s2, double* v, uint8_t* lmask,
+                       bts_stream_t stream);
+/* r = v - f on the mask (0 elsewhere); range4[0], range4[1] = the exact min lo and max hi of r over the mask (+inf, -inf for an empty mask),
+ * range4[2..3] are the call's own scratch; hist: `bins` 64-bit counts, overwritten.  With sl = (hi - lo) / (bins - 1), a masked point has
+ * c = (r - lo) / sl, i = min(floor(c), bins - 2), o = c - i, q = rint(o 2^24), and adds 2^24 - q to bin i and q to bin i + 1; with hi == lo
+ * every point adds 2^24 to bin 0.  Three launches. */
+int bts_n4_range_hist(const double* v, const double* f, const uint8_t* lmask, long npts, int bins, double* r, double* range4,
+                      long long* hist, bts_stream_t stream);
+/* res = r - (E[i] (1 - o) + E[i+1] o) on the mask with i, o as above from the host doubles lo and sl >= 0 (0 elsewhere); E: `bins` device
+ * doubles, the sharpened table. */
+int bts_n4_residual(const double* r, const uint8_t* lmask, const double* E, long npts, int bins, double lo, double sl, double* res,
+                    bts_stream_t stream);
+/* one level of multilevel B-spline approximation (Lee, Wolberg, Shin 1997) in gather form.  A masked lattice point with residual z and
+ * tensor weight w_c at control point c has S = the product over the axes of the sum of its four squared weights; num[c] = sum w_c^3 z / S,
+ * den[c] = sum w_c^2 over the lattice points whose cell lies in the 4-cell support of c, dphi[c] = num / den, 0 where den == 0;
+ * phi_or_null[c] += dphi[c].  One workgroup per control point; at most 512 lattice points per axis. */
+int bts_n4_fit(const double* res, const uint8_t* lmask, int D, int H, int W, int s0, int s1, int s2, int M0, int M1, int M2, double* num,
+               double* den, double* dphi, double* phi_or_null, bts_stream_t stream);
+/* f_new = the spline at every lattice point; parts: bts_n4_eval_parts(npts) pairs of doubles, the sums of e = exp(f_new - f_old) and of
+ * e^2 over the masked points of each run of 1024 lattice points, to be added up in order by the caller. */
+long bts_n4_eval_parts(long npts);
+int bts_n4_eval(const double* phi, int D, int H, int W, int s0, int s1, int s2, int M0, int M1, int M2, const double* f_old,
+                const uint8_t* lmask, double* f_new, double* parts, bts_stream_t stream);
+/* out = float(double(x) / exp(spline)) at every voxel; field_or_null = float(exp(spline)).  x is read once and out written once. */
+int bts_n4_apply(const float* x, int D, int H, int W, const double* phi, int M0, int M1, int M2, float* out, float* field_or_null,
+                 bts_stream_t stream);
+
 /* library identification */
 const char* bts_version(void);
 
