@@ -4,9 +4,10 @@ tests/test_poison_gpu.py; imported the way lowp_ref and norm_ref are).
 Every buffer the host side hands to the C ABI -- outputs, saved activations, gradient buffers, partial-sum scratch and each `*_workspace`
 buffer, sized EXACTLY by its query -- is carved out of a larger allocation pre-filled with one byte value, PAD bytes of it on either side.
 `Guarded` stands in for the `torch` module inside the package: `empty` and `empty_like` return the fill, `zeros`, `zeros_like` and `full`
-their defined contents; `check()` asserts that every band still holds the fill.  `install()` swaps it in for every bts_amd module and
-replaces `ops.workspace` (which normally hands out a grow-only buffer of at least 1 MB, i.e. would hide an over-run of the queried size
-and keep an earlier call's contents).
+their defined contents; `check()` asserts that every band still holds the fill.  `install()` swaps it in for every bts_amd module -- the
+subject modules of the `ops` package included, which `ops/__init__.py` imports eagerly -- and replaces `ops._core.workspace`, the one
+binding every wrapper looks up and `ops.workspace` reads (it normally hands out a grow-only buffer of at least 1 MB, i.e. would hide an over-run of the queried
+size and keep an earlier call's contents).
 
 The fill byte decides what an unwritten element reads as:
   0xA5  the out-of-bounds pattern: -2.9e-16 as fp32 / bf16, -0.022 as fp16, -2.5e-127 as fp64 -- close to zero, so a kernel that adds in
@@ -25,8 +26,11 @@ PAD = 4096
 FILL = 0xA5
 POISON = 0xFF
 
-MODULES = ('model', 'util', 'tape', 'ops', 'lowp', 'lowp_train', 'parallel', 'data', 'infer', 'train', 'layers._base', 'layers.resnet',
-           'layers.group_norm', 'layers.downsample', 'layers.upsample', 'layers.vae', 'layers.encoder', 'layers.decoder')
+OPS = ('_core', 'streams', 'profile', 'conv', 'norm', 'pointwise', 'loss', 'volume', 'window', 'score', 'augment', 'regions', 'prepro', 'coreg',
+       'n4')
+MODULES = ('model', 'util', 'tape', 'ops') + tuple('ops.' + m for m in OPS) + (
+    'lowp', 'lowp_train', 'parallel', 'data', 'infer', 'train', 'layers._base', 'layers.resnet', 'layers.group_norm', 'layers.downsample',
+    'layers.upsample', 'layers.vae', 'layers.encoder', 'layers.decoder')
 
 
 class Guarded(object):
@@ -126,8 +130,8 @@ class Guarded(object):
 
 
 def install(monkeypatch, fill=FILL):
-    """swap a Guarded(fill) in for `torch` in every bts_amd module and an exact-size, filled buffer for ops.workspace; undone with the
-    monkeypatch.  -> the Guarded"""
+    """swap a Guarded(fill) in for `torch` in every bts_amd module and an exact-size, filled buffer for ops._core.workspace; undone with
+    the monkeypatch.  -> the Guarded"""
     import bts_amd  # noqa: F401
     from bts_amd import ops
     g = Guarded(fill)
@@ -137,8 +141,13 @@ def install(monkeypatch, fill=FILL):
     for m in mods:
         if getattr(m, 'torch', None) is torch:
             monkeypatch.setattr(m, 'torch', g)
+    for name in OPS:                           # every subject module that allocates does so from the Guarded
+        m = sys.modules['bts_amd.ops.' + name]
+        assert getattr(m, 'torch', g) is g, 'bts_amd.ops.%s still allocates from torch' % name
 
     def exact_workspace(nbytes, device):       # exactly what the *_workspace query asked for -- no 1 MB floor, no reuse
         return g._alloc((max(int(nbytes), 1),), torch.uint8, device)
-    monkeypatch.setattr(ops, 'workspace', exact_workspace)
+    monkeypatch.setattr(ops._core, 'workspace', exact_workspace)
+    # one binding: the callers of ops.workspace outside the package (lowp.py, the tests' own raw calls) get the guarded one too
+    assert ops.workspace is ops._core.workspace is exact_workspace and 'workspace' not in vars(ops)
     return g

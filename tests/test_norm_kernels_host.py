@@ -437,7 +437,7 @@ def test_block_bwd_workspace_declines_exactly_where_block_bwd_takes_says_no(monk
     import bts_amd  # noqa: F401
     from bts_amd import ops
     from bts_amd._lib import lib
-    monkeypatch.setattr(ops, '_check', lambda *a, **k: None)      # (the tensors are never touched: CPU stand-ins)
+    monkeypatch.setattr(ops._core, '_check', lambda *a, **k: None)      # (the tensors are never touched: CPU stand-ins; patched where the wrappers look it up)
     L = lib()
     took = 0
     for n in (1, 3):
