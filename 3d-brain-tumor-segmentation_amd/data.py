@@ -222,6 +222,71 @@ def draw_intensity(gen, cfg, c):
     return IntensityDraw(params, (int(key[0]), int(key[1])))
 
 
+class ForegroundConfig(object):
+    """foreground oversampling of the training crops (the nnU-Net / batchgenerators recipe): with probability `prob`, in (0, 1], an
+    example's crop is centred on a voxel drawn from its class-location table (ops.class_locations: at most `samples` evenly spaced
+    voxels per class, built on the device once per file) instead of being placed uniformly.  classes: the classes c (label c + 1) to
+    choose from, a subset of range(out_ch); None: all.  A class without a voxel in the example is never chosen, and an example without
+    any voxel of the allowed classes keeps its uniform crop."""
+
+    def __init__(self, prob, samples=10000, classes=None):
+        try:
+            self.prob = float(prob)
+        except (TypeError, ValueError):
+            self.prob = float('nan')
+        if not 0.0 < self.prob <= 1.0:
+            raise ValueError('ForegroundConfig: prob must be in (0, 1], got %r' % (prob,))
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or not 1 <= int(samples) < 2 ** 31:
+            raise ValueError('ForegroundConfig: samples must be an integer >= 1, got %r' % (samples,))
+        self.samples = int(samples)
+        if classes is not None:
+            try:
+                cl = [int(c) for c in classes]
+                ok = len(cl) > 0 and all(float(c) == int(c) for c in classes)
+            except (TypeError, ValueError):
+                cl, ok = [], False
+            if not ok or len(set(cl)) != len(cl) or min(cl) < 0 or max(cl) >= ops.CLASS_LOCATIONS_MAX_CLASSES:
+                raise ValueError('ForegroundConfig: classes must be distinct integers in range(out_ch), got %r' % (classes,))
+            classes = tuple(sorted(cl))
+        self.classes = classes
+
+    def allowed(self, out_ch):
+        """the ascending classes to choose from for `out_ch` output classes; ValueError for a class outside range(out_ch)"""
+        if self.classes is None:
+            return list(range(int(out_ch)))
+        if self.classes[-1] >= int(out_ch):
+            raise ValueError('ForegroundConfig: classes %r must lie in range(out_ch) = range(%d)' % (self.classes, int(out_ch)))
+        return list(self.classes)
+
+
+def draw_foreground(gen, cfg, counts, loc, vol_size, crop_size, offsets):
+    """The foreground draw of one example, taken right after draw() (and before draw_spatial()) on the same generator -> its three crop
+    offsets.  counts: the out_ch voxel counts n_c, loc: the (out_ch, K) table of ops.class_locations, both on the host; offsets: what
+    draw() placed.  The same three values are consumed in every branch, so the position in the stream never depends on a draw.  Order:
+    torch.rand(3, float64) = [u_on, u_class, u_voxel] with on = (u_on < prob).  present = the ascending allowed classes with n_c > 0; if
+    on and present is not empty: c = present[min(int(u_class len(present)), len(present) - 1)], j = min(int(u_voxel m_c), m_c - 1) with
+    m_c = ceil(n_c / max(1, ceil(n_c / K))) the entries the table holds for c, p = the voxel of linear index loc[c][j], and
+    offset_k = min(max(p_k - crop_k // 2, 0), vol_k - crop_k).  Otherwise `offsets` is returned as it came.
+
+    Where the voxel ends up: p sits at index crop_k // 2 of the crop unless an offset was clamped at a face of the volume, and then it
+    sits nearer that face.  Flips act on the crop's own index and keep it inside.  The spatial transform (bts_augment_spatial_batch) fixes
+    the crop's geometric centre (crop_k - 1) / 2, so an unclamped p lies half a voxel (even crop_k) or no distance (odd crop_k) from the
+    fixed point and a rotation or zoom moves it by a fraction of a voxel; a clamped p can lie up to crop_k / 2 from the fixed point, and a
+    rotation, a zoom above 1 or the elastic field can then move it out of the crop."""
+    u = torch.rand(3, generator=gen, dtype=torch.float64).tolist()
+    k = len(loc[0])
+    present = [c for c in cfg.allowed(len(counts)) if int(counts[c]) > 0]
+    if not (u[0] < cfg.prob and present):
+        return list(offsets)
+    c = present[min(int(u[1] * len(present)), len(present) - 1)]
+    n = int(counts[c])
+    stride = max(1, -(-n // k))
+    m = -(-n // stride)
+    p = int(loc[c][min(int(u[2] * m), m - 1)])
+    pk = (p // (vol_size[1] * vol_size[2]), (p // vol_size[2]) % vol_size[1], p % vol_size[2])
+    return [min(max(pk[a] - crop_size[a] // 2, 0), vol_size[a] - crop_size[a]) for a in range(3)]
+
+
 TARGETS = ('labels', 'regions')
 
 
@@ -252,12 +317,18 @@ class _Dataset(object):
 
     targets ('labels': nothing below happens): with 'regions' the label batch goes through bts_region_targets right after the augment
     launch (before the intensity stage, which does not touch y), so y holds the nested BraTS regions (WT, TC, ET) in place of the
-    disjoint one-hot labels.  No value is drawn for it: x and the generator states are those of 'labels'."""
+    disjoint one-hot labels.  No value is drawn for it: x and the generator states are those of 'labels'.
+
+    foreground (a ForegroundConfig, or None: nothing below happens and not one extra value is drawn): draw_foreground() follows every
+    draw(), before draw_spatial(), on the same generator, and replaces the crop offsets; nothing else of the draws changes, so spatial,
+    intensity and targets compose as they are.  It reads the example's class-location table (ops.class_locations on the labels, copied to
+    the host once), which is built where the variance is and kept next to (x, y, var): a property of the file, never rebuilt for a
+    resident example, rebuilt per read for a streamed one.  The host tables do not count against resident_bytes."""
 
     channels_first = False
 
     def __init__(self, files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, device, rank=0, world=1,
-                 resident_bytes=0, workers=0, spatial=None, intensity=None, targets='labels'):
+                 resident_bytes=0, workers=0, spatial=None, intensity=None, targets='labels', foreground=None):
         if targets not in TARGETS:
             raise ValueError('unknown targets %r: one of %s' % (targets, TARGETS))
         if targets == 'regions' and int(out_ch) != 3:
@@ -270,9 +341,13 @@ class _Dataset(object):
         self.gen = torch.Generator().manual_seed(seed + 7919 * (self.rank + 1))
         self.device = device
         self.resident_bytes, self.workers = max(0, int(resident_bytes)), max(0, int(workers))
-        self._resident, self._resident_used = {}, 0           # file index -> (x, y, var) on the device; bytes of their x + y
+        # file index -> (x, y, var) on the device and the host class-location table (None without foreground); bytes of their x + y
+        self._resident, self._resident_used = {}, 0
         self.spatial = spatial
         self.intensity = intensity
+        self.foreground = foreground
+        if foreground is not None:
+            foreground.allowed(self.out_ch)                     # (a class outside range(out_ch) is refused here, not at the first batch)
 
     def _per_rank(self):
         return len(self.files) // self.world if self.world > 1 else len(self.files)
@@ -304,6 +379,21 @@ class _Dataset(object):
         return (np.ascontiguousarray(z['x'], dtype=np.float32).reshape(h, w, d, c),
                 np.ascontiguousarray(z['y'], dtype=np.float32).reshape(h, w, d, 1))
 
+    def _table(self, y):
+        """the class-location table of an example's device labels, copied to the host: (counts, loc); None without foreground oversampling"""
+        if self.foreground is None:
+            return None
+        counts, loc = ops.class_locations(y, self.out_ch, self.foreground.samples)
+        return counts.cpu().tolist(), loc.cpu().numpy()
+
+    def _draw(self, table):
+        """draw() of one example, its crop moved by draw_foreground() where that is on"""
+        h, w, d, c = self.prepro_size
+        dr = draw(self.gen, c, (h, w, d), self.crop_size)
+        if self.foreground is not None:
+            dr.offsets = draw_foreground(self.gen, self.foreground, table[0], table[1], (h, w, d), self.crop_size, dr.offsets)
+        return dr
+
     def __iter__(self):
         if self.resident_bytes == 0 and self.workers == 0:
             return self._iter_per_example()
@@ -316,7 +406,7 @@ class _Dataset(object):
         for i in order:
             xh, yh = self._read(i)
             x, y = torch.from_numpy(xh).to(self.device), torch.from_numpy(yh).to(self.device)
-            dr = draw(self.gen, c, (h, w, d), self.crop_size)
+            dr = self._draw(self._table(y))
             if self.spatial is None:
                 xa, ya = augment_example(x, y, self.crop_size, self.out_ch, dr)
             else:
@@ -365,13 +455,13 @@ class _Dataset(object):
                 xh, yh = next(host)
                 # (uploads run on the current stream, like everything that reads them: a yielded batch is ordered behind them)
                 x, y = torch.from_numpy(xh).to(self.device), torch.from_numpy(yh).to(self.device)
-                ex = (x, y, ops.channel_moments(x)[1])
+                ex = (x, y, ops.channel_moments(x)[1], self._table(y))
                 nbytes = (x.numel() + y.numel()) * 4
                 if self._resident_used + nbytes <= self.resident_bytes:
                     self._resident[i] = ex
                     self._resident_used += nbytes
             batch.append(ex)
-            draws.append(draw(self.gen, c, (h, w, d), self.crop_size))
+            draws.append(self._draw(ex[3]))
             if self.spatial is not None:
                 sdraws.append(draw_spatial(self.gen, self.spatial, self.crop_size))
             if self.intensity is not None:
@@ -420,7 +510,7 @@ class _ChannelsFirstDataset(_Dataset):
 
 def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=True, data_format='channels_last', seed=0,
                     device=None, rank=None, world=None, resident_bytes=0, workers=0, spatial=None, intensity=None,
-                    targets='labels'):
+                    targets='labels', foreground=None):
     """-> (re-iterable dataset of (x, y) device batches, number of examples)   [train.py:12-64]
     rank / world default to the process group's (one shard of the examples per rank, see _Dataset).
     resident_bytes: budget of example bytes kept on the device after their first read; workers: host threads reading ahead
@@ -428,7 +518,9 @@ def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=Tru
     crops, on the device in the same launch) or None, which leaves every draw and every batch as it was.  intensity: an
     IntensityConfig (noise, blur, brightness, contrast and gamma on the augmented batch, on the device) or None, likewise.
     targets: 'labels' (y = one-hot labels minus the background, as the reference trains) or 'regions' (y = the nested BraTS regions
-    WT, TC, ET: bts_region_targets on the label batch; out_ch must be 3); x and every draw are the same in both."""
+    WT, TC, ET: bts_region_targets on the label batch; out_ch must be 3); x and every draw are the same in both.  foreground: a
+    ForegroundConfig (a share of the crops centred on a foreground voxel of the example, from a class-location table built on the device
+    once per file) or None, which leaves every draw and every batch as it was."""
     if data_format not in ('channels_last', 'channels_first'):
         raise ValueError('unknown data_format %r' % (data_format,))
     from . import parallel
@@ -438,4 +530,4 @@ def prepare_dataset(loc, batch_size, prepro_size, crop_size, out_ch, shuffle=Tru
     dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
     cls = _Dataset if data_format == 'channels_last' else _ChannelsFirstDataset
     return cls(files, batch_size, prepro_size, crop_size, out_ch, shuffle, seed, dev, rank, world, resident_bytes, workers, spatial,
-               intensity, targets), len(files)
+               intensity, targets, foreground), len(files)

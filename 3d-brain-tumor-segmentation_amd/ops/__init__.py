@@ -34,9 +34,9 @@ from .volume import affine_resample3d, flip_affine, reorient3d, skull_strip, spl
 from .window import window_accumulate, window_batch_max, window_gather, window_occupancy      # noqa: F401
 from .score import (component_boxes, component_largest, component_sizes, components3d, components_apply, dilate3d, edt3d_sq,      # noqa: F401
                     label_confusion, lesion_crop, lesion_pairs, lesion_pairs_capacity, masked_select, region_relabel, region_surface)
-from .augment import (INTENSITY_BLUR, INTENSITY_BRIGHT, INTENSITY_CONTRAST, INTENSITY_GAMMA, INTENSITY_INVERT, INTENSITY_NOISE,      # noqa: F401
+from .augment import (CLASS_LOCATIONS_MAX_CLASSES, INTENSITY_BLUR, INTENSITY_BRIGHT, INTENSITY_CONTRAST, INTENSITY_GAMMA, INTENSITY_INVERT, INTENSITY_NOISE,      # noqa: F401
                       augment_batch, augment_batch_max, augment_crop, augment_spatial_batch, augment_spatial_batch_max, channel_moments,
-                      intensity_batch, intensity_blur_weights)
+                      class_locations, intensity_batch, intensity_blur_weights)
 from .regions import REGION_CHANNELS, region_dice_sums, region_finish, region_targets      # noqa: F401
 from .prepro import case_norm, check_clip, prepro_crop_norm, prepro_occupancy, prepro_sums      # noqa: F401
 from .coreg import joint_hist_pv, quantize_bins      # noqa: F401

@@ -21,6 +21,38 @@ def channel_moments(x):
     return mean, var
 
 
+CLASS_LOCATIONS_MAX_CLASSES = 8
+
+
+def class_locations(y, out_ch, k):
+    """the class-location table of a label volume (bts_class_locations), for foreground-oversampled crops.  y: dense float32 labels on
+    the GPU as the dataset stores them, (S0,S1,S2) or (S0,S1,S2,1), label c+1 = class c (the convention of augment_crop's one-hot); out_ch
+    in 1..8; k >= 1 the table's capacity per class -> (counts int64 (out_ch,), loc int32 (out_ch, k)) on the device: counts[c] = n_c, the
+    voxels whose label is exactly c+1; loc[c, j] the linear index of the class's voxel of rank j * s_c in ascending index order,
+    s_c = max(1, ceil(n_c / k)), for j < ceil(n_c / s_c), and -1 from there on.  Bit-identical from call to call.  Every refusal is a
+    ValueError raised before the library is reached."""
+    who = 'class_locations'
+    if not isinstance(y, torch.Tensor):
+        raise ValueError('%s: y must be a dense float32 tensor on the GPU' % who)
+    try:
+        _core._check(y, who + ': y')
+    except RuntimeError as e:      # (_check speaks RuntimeError for the training step's wrappers; this one refuses with ValueError throughout)
+        raise ValueError(str(e))
+    if y.dim() not in (3, 4) or (y.dim() == 4 and y.shape[3] != 1) or not y.is_contiguous():
+        raise ValueError('%s: y must be a dense (S0,S1,S2) or (S0,S1,S2,1) volume, got shape %s' % (who, tuple(y.shape)))
+    for name, v, lo, hi in (('out_ch', out_ch, 1, CLASS_LOCATIONS_MAX_CLASSES), ('k', k, 1, 2 ** 31 - 1)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError('%s: %s must be an integer in %d..%d, got %r' % (who, name, lo, hi, v))
+    nvox = y.numel()
+    if not 1 <= nvox < 2 ** 31:
+        raise ValueError('%s: y must hold between 1 and 2^31 - 1 voxels, got %d' % (who, nvox))
+    counts = torch.empty(out_ch, dtype=torch.int64, device=y.device)
+    loc = torch.empty((out_ch, k), dtype=torch.int32, device=y.device)
+    ws, nb = _core.scratch('bts_class_locations_workspace', y.device, nvox, out_ch)
+    _core.lib().call('bts_class_locations', _core._p(y), _core._p(counts), _core._p(loc), _core._p(ws), nb, nvox, out_ch, k, _core._stream())
+    return counts, loc
+
+
 def augment_crop(x, y, var, crop, offsets, flip_mask, shift, scale, out_ch):
     """x: (S0,S1,S2,C), y: (S0,S1,S2) or (S0,S1,S2,1) float labels, var: (C,) device tensor; shift/scale: C python floats
     -> (x_out (T0,T1,T2,C), y_out (T0,T1,T2,out_ch))"""

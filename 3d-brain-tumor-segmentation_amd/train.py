@@ -23,7 +23,9 @@ accepted and implied: there is no CPU path.  Added: --dtype (training AND valida
 the spatial augmentation of the TRAINING examples (add_spatial_arguments: --spatial_prob, --rotate_deg, --zoom_range, --elastic_sigma,
 --elastic_spacing; off by default, never applied to --val_loc; data.SpatialConfig), and their intensity augmentation
 (add_intensity_arguments: --intensity_aug and the --noise_*, --blur_*, --brightness_*, --contrast_* and --gamma_* flags; off by
-default, never applied to --val_loc; data.IntensityConfig), and --targets (add_target_arguments: `labels`, the default, trains the
+default, never applied to --val_loc; data.IntensityConfig), the foreground oversampling of their crops (add_foreground_arguments:
+--foreground_prob, --foreground_samples, --foreground_classes; off by default, never applied to --val_loc; data.ForegroundConfig;
+stored in train_args.pkl and restored by --load_folder, an older pickle meaning off), and --targets (add_target_arguments: `labels`, the default, trains the
 output channels on the disjoint labels as the reference does; `regions` trains them on the nested BraTS regions WT, TC, ET, for both
 datasets, and the Dice columns of train.log are then util.RegionDiceCoefficient's; the mode is stored in train_args.pkl, restored by
 --load_folder and read by `python -m bts_amd.test`), and the training loss (add_loss_arguments: --loss `dice`, the default, is the
@@ -467,6 +469,22 @@ def add_intensity_arguments(p):
     return p
 
 
+FOREGROUND_KEYS = ('foreground_prob', 'foreground_samples', 'foreground_classes')
+
+
+def add_foreground_arguments(p):
+    """the flags of the foreground oversampling of the training crops (data.ForegroundConfig), a group of their own like the augmentation
+    ones"""
+    g = p.add_argument_group('foreground oversampling of the training crops')
+    g.add_argument('--foreground_prob', type=float, default=0.0,
+                   help='Probability that a training crop is centred on a random voxel of a random foreground class of its example; 0: off.')
+    g.add_argument('--foreground_samples', type=int, default=10000,
+                   help='Voxels kept per class in an example\'s class-location table (evenly spaced over the class).')
+    g.add_argument('--foreground_classes', type=str, default='',
+                   help='Classes to choose from, as c0,c1,... out of 0..out_ch-1 (class c is label c+1); empty: all.')
+    return p
+
+
 def add_target_arguments(p):
     """the flag of the target encoding (data.TARGETS), a group of its own like the augmentation ones"""
     g = p.add_argument_group('target encoding')
@@ -496,8 +514,8 @@ def add_loss_arguments(p):
 
 
 def full_parser():
-    """what the command parses: arg_parser() and the spatial augmentation, intensity augmentation, target and loss groups"""
-    return add_loss_arguments(add_target_arguments(add_intensity_arguments(add_spatial_arguments(arg_parser()))))
+    """what the command parses: arg_parser() and the spatial augmentation, intensity augmentation, foreground, target and loss groups"""
+    return add_loss_arguments(add_target_arguments(add_foreground_arguments(add_intensity_arguments(add_spatial_arguments(arg_parser())))))
 
 
 def _floats(text, counts, flag):
@@ -532,6 +550,18 @@ def intensity_config(args):
                            gamma_prob=a['gamma_prob'], gamma=a['gamma_range'], gamma_invert_prob=a['gamma_invert_prob'])
 
 
+def foreground_config(args):
+    """the data.ForegroundConfig of the parsed (or unpickled) arguments, None when foreground_prob is 0 or absent; a class outside
+    range(out_ch) is refused here"""
+    a = args if isinstance(args, dict) else vars(args)
+    if not a.get('foreground_prob'):
+        return None
+    from .data import ForegroundConfig
+    cfg = ForegroundConfig(a['foreground_prob'], samples=a.get('foreground_samples', 10000), classes=a.get('foreground_classes') or None)
+    cfg.allowed(a['model_args']['out_ch'])
+    return cfg
+
+
 def loss_spec(args):
     """the util.LossSpec of the parsed (or unpickled) arguments, None for `dice` (or no `loss` key: an older pickle) -- the reference's
     loss, which has no weights: a non-default --dice_weight / --ce_weight is refused with it"""
@@ -562,6 +592,10 @@ def parse_args(argv=None):
     args.zoom_range = _floats(args.zoom_range, (2,), '--zoom_range')
     for key in _INTENSITY_RANGES:
         setattr(args, key, _floats(getattr(args, key), (2,), '--' + key))
+    try:
+        args.foreground_classes = [int(v) for v in args.foreground_classes.split(',')] if args.foreground_classes else None
+    except ValueError:
+        raise ValueError('--foreground_classes: expected comma-separated integers, got %r' % (args.foreground_classes,))
     args.model_args = {}
     for key in [k for k in vars(args) if k.startswith('model_args.')]:                                    # args.py:24-38
         args.model_args[key.split('.', 1)[1]] = getattr(args, key)
@@ -596,12 +630,17 @@ def parse_args(argv=None):
         for key in INTENSITY_KEYS[1:]:
             if key in chkpt_args:
                 setattr(args, key, chkpt_args[key])
+        args.foreground_prob = chkpt_args.get('foreground_prob', 0.0)                                      # (an older pickle: off)
+        for key in FOREGROUND_KEYS[1:]:
+            if key in chkpt_args:
+                setattr(args, key, chkpt_args[key])
         args.targets = chkpt_args.get('targets', 'labels')                                                 # (an older pickle: labels)
         args.loss = chkpt_args.get('loss', 'dice')                                                         # (an older pickle: dice)
         for key in LOSS_KEYS[1:]:
             setattr(args, key, chkpt_args.get(key, LOSS_DEFAULTS[key]))
     spatial_config(args)                      # (a bad range or probability is refused here, not at the first batch)
     intensity_config(args)
+    foreground_config(args)
     loss_spec(args)
     if args.targets == 'regions' and int(args.model_args['out_ch']) != 3:
         raise ValueError('--targets regions trains the three BraTS regions WT, TC, ET: --out_ch must be 3, got %r' %
@@ -630,6 +669,9 @@ def run(args):
     train_extra = {} if spatial is None else {'spatial': spatial}
     if intensity is not None:
         train_extra['intensity'] = intensity
+    foreground = foreground_config(args)
+    if foreground is not None:
+        train_extra['foreground'] = foreground
     for loc, shuffle, extra in ((args.train_loc, True, train_extra), (args.val_loc, False, {})):
         sets.append(data.prepare_dataset(loc, args.batch_size, args.prepro_size, args.crop_size, args.model_args['out_ch'],
                                          shuffle=shuffle, data_format=args.data_format, seed=args.seed, device=dev,

@@ -521,6 +521,20 @@ int bts_augment_spatial_batch(const float* const* x, const float* const* y, cons
                               const float* scale, const int* spatial, const float* M, const float* const* phi, const int* spacing,
                               const float* fill, int out_ch, int layout, bts_stream_t stream);
 
+/* Class-location table of a label volume, for foreground-oversampled crops (no reference counterpart: train.py:26 crops uniformly; the
+ * recipe is nnU-Net's).  y: V = S0*S1*S2 dense fp32 labels as the dataset stores them, label k in 1..out_ch = class k-1 (the convention
+ * of bts_augment_crop's one-hot).  counts (out_ch int64): n_c = the voxels whose label is EXACTLY c+1 -- 0, a value above out_ch and a
+ * non-integer value are in no class.  loc (out_ch x K int32): with s_c = max(1, ceil(n_c / K)) and m_c = ceil(n_c / s_c), entry j < m_c
+ * is the linear index of the class's voxel of rank j s_c, ranks counting the class's voxels in ascending linear index; entries j >= m_c
+ * are -1.  All out_ch*K entries and all counts are written on every call.  A pure function of the input, bit-identical from run to run:
+ * a slot follows from the voxel's rank (count per workgroup, exclusive scan, second sweep), never from an atomic cursor; integer arithmetic
+ * and plain stores only.  y is read twice.  BTS_ERR_SHAPE, before any HIP call: V < 1 or V >= 2^31, out_ch outside 1..8, K < 1, a NULL
+ * y, counts or loc; BTS_ERR_WORKSPACE: a NULL workspace or one smaller than bts_class_locations_workspace() (itself BTS_ERR_SHAPE for a
+ * V or out_ch the call refuses). */
+long bts_class_locations_workspace(long V, int out_ch);
+int bts_class_locations(const float* y, long* counts, int* loc, void* workspace, long workspace_bytes, long V, int out_ch, int K,
+                        bts_stream_t stream);
+
 /* Intensity augmentation of the batch that bts_augment_batch / bts_augment_spatial_batch wrote: Gaussian noise, Gaussian blur,
  * brightness, contrast and gamma (the nnU-Net / batchgenerators set; train.py:19-20 has only the shift and scale).  x: dense fp32
  * (N,T0,T1,T2,C) (layout 0) or (N,C,T0,T1,T2) (layout 1), 1 <= C <= 16, changed IN PLACE; labels are not touched.  The unit is one
