@@ -51,10 +51,17 @@ Where the script is not functional (README.md:70 says so) the evident intent is 
     a stated orientation and spacing by the affines (nifti.best_affine) -- an exact reorientation copy where the map is a signed
     permutation, a spline resample with a general matrix otherwise (bts_reorient3d, bts_affine_resample3d) -- and the prediction back;
     `segment_case(geometry=...)` uses it in place of the Interpolator, off by default.
+  * the reference runs one tumour checkpoint (test.py:185-221) and says of a voxel its label and nothing else, although the paper it
+    implements won BraTS 2018 with an ensemble of ten models.  A `StageEnsemble` stands wherever the tumour `StageSpec` does: every
+    member runs its own TestTimeAugmentor on the same input and the unmasked means are averaged on the device by Welford's recurrence
+    (bts_ensemble_update), which also keeps the members' spread; with `uncertainty` = 'entropy' or 'std' `segment_case` adds a map of
+    levels 0..100 per voxel and channel on the scan's own grid (bts_uncertainty_finish), and `uncertainty_scores` gives the
+    uncertainty-filtered Dice and the filtered true positives and negatives of the BraTS uncertainty task from one table counted on the
+    device (bts_uncertainty_confusion); off by default.
 All tensor work is on the device through the C ABI (bts_flip_affine, bts_tta_finish, bts_region_finish, bts_spline_prefilter3d, bts_zoom3d,
 bts_skull_strip, bts_label_confusion, bts_region_surface, bts_edt3d_sq, bts_masked_select, bts_components3d, bts_component_sizes,
 bts_component_largest, bts_components_apply, bts_region_relabel, bts_dilate3d, bts_lesion_pairs, bts_component_boxes, bts_lesion_crop,
-bts_reorient3d, bts_affine_resample3d, the model forward).
+bts_reorient3d, bts_affine_resample3d, bts_ensemble_update, bts_uncertainty_finish, bts_uncertainty_confusion, the model forward).
 """
 import glob
 import os
@@ -359,13 +366,19 @@ def segment_volume(model, x, mask, mean, std, spatial_res, spatial_tta=True, thr
     x (D,H,W,C), mask (D,H,W,1) channels_last (test.py:109) -> (probabilities, uint8 labels (D,H,W)); the probabilities are
     (D,H,W,out_ch), or (out_ch,D,H,W) for a model built with data_format='channels_first'.  window: a WindowSpec -> the padded volume
     is predicted in blended windows of that extent; targets: 'labels' | 'regions', the decode of the label map (TestTimeAugmentor);
-    norm: None | a NormSpec, how the volume is normalised (TestTimeAugmentor); in case mode over the voxels of `mask`"""
+    norm: None | a NormSpec, how the volume is normalised (TestTimeAugmentor); in case mode over the voxels of `mask`.
+    model may be a StageEnsemble: its members carry their own statistics and settings, so of the other arguments only x, mask, window
+    and norm are read, and the probabilities are the members' mean, channels last"""
+    ensemble = isinstance(model, StageEnsemble)
+    if ensemble:
+        spatial_res = model.spatial_res
     if window is not None:
         window.check_resolution(spatial_res)
     xp, mp, orig = pad_to_spatial_res(spatial_res, x, mask)
     df = getattr(model, 'data_format', 'channels_last')
-    tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch, window=window, targets=targets, norm=norm)
+    tta = model.augmentor(window, norm) if ensemble else TestTimeAugmentor(
+        mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype, tta_batch=tta_batch, window=window,
+        targets=targets, norm=norm)
     y = tta(xp, mp)
     lab = tta.labels()
     y = y[:, :orig[0], :orig[1], :orig[2]] if df == 'channels_first' else y[:orig[0], :orig[1], :orig[2]]
@@ -444,26 +457,31 @@ class Interpolator(object):
         self.affine = np.mean(affine, axis=0, dtype=np.float32)
         return self.resample(np.stack(image, axis=-1), self.pixdim[1:4], pad_res=pad_res)
 
-    def reverse(self, prob, mask=None, path=None, threshold=0.5, targets='labels'):
+    def reverse(self, prob, mask=None, path=None, threshold=0.5, targets='labels', extra=None, native=False):
         """prob (D1,H1,W1,K): cropped probability map on the 1 mm^3 grid, mask (D1,H1,W1,1) (default: the last resample's)
         -> (probabilities (D,H,W,K), uint8 labels (D,H,W)) on the scan's native grid; with `path`, writes mask.nii there
         (test.py:69-70) with the affine averaged in __call__ (identity if the scan came through resample()).  targets: 'labels' (the
-        arg-max of bts_tta_finish) | 'regions' (K == 3, the decode of bts_region_finish), taken on the native grid either way"""
+        arg-max of bts_tta_finish) | 'regions' (K == 3, the decode of bts_region_finish), taken on the native grid either way.
+        extra: one more (D1,H1,W1,J) volume that rides the same way back at order 1 (a variance: linear interpolation keeps it inside
+        its range); with it, or with native=True, a third value is returned: (the probabilities before the mask multiplies them, the
+        mask (D,H,W,1), extra or None), all on the native grid"""
         finish = _finish_of(targets)
         if self.native_shape is None:
             raise RuntimeError('Interpolator.reverse: no scan has been resampled yet')
         mask = self.mask if mask is None else mask
         p = prob.to(torch.float32).contiguous()
         m = mask.to(torch.float32).contiguous()
+        e = None if extra is None else extra.to(torch.float32).contiguous()
         if not all(f == 1.0 for f in self.factors):
             p = self._zoom(p, self.native_shape, self.order)
             m = self._zoom(m, self.native_shape, 0)
+            e = None if e is None else self._zoom(e, self.native_shape, 1)
         y, lab = finish(p.unsqueeze(0), m.unsqueeze(0), threshold)
         y, lab = y[0], lab[0]
         if path is not None:
             from . import nifti
             nifti.save(os.path.join(path, 'mask.nii'), lab.cpu().numpy(), np.eye(4) if self.affine is None else self.affine)
-        return y, lab
+        return (y, lab, (p, m, e)) if native or extra is not None else (y, lab)
 
 
 def _grid_corners(shape):
@@ -641,34 +659,38 @@ class Conformer(object):
         """did the reference modality of the last scan already lie on the target grid, array axes included?"""
         return self.last is not None and self.last['reorient'][0] == IDENTITY_REORIENTATION
 
-    def reverse(self, prob, mask=None, path=None, threshold=0.5, targets='labels'):
+    def reverse(self, prob, mask=None, path=None, threshold=0.5, targets='labels', extra=None, native=False):
         """prob (D1,H1,W1,K): cropped probability map on the target grid, mask (D1,H1,W1,1) (default: the last forward's)
         -> (probabilities (D,H,W,K), uint8 labels (D,H,W)) on the reference modality's own grid, as Interpolator.reverse: the
         probabilities at the configured order and the mask at order 0 through the inverse map (the exact copy where the forward was a
         reorientation), the labels taken there ('labels' | 'regions'); with `path`, writes mask.nii there with the reference modality's
-        own affine"""
+        own affine.  extra, native: as Interpolator.reverse -- one more volume through the inverse map at order 1 (the exact copy where
+        the forward was a reorientation), and the third value (unmasked probabilities, mask, extra or None) on the native grid"""
         finish = _finish_of(targets)
         if self.last is None:
             raise RuntimeError('Conformer.reverse: no scan has been conformed yet')
         mask = self.mask if mask is None else mask
         p = prob.to(torch.float32).contiguous()
         m = mask.to(torch.float32).contiguous()
+        e = None if extra is None else extra.to(torch.float32).contiguous()
         ro = self.last['reorient'][0]
         if ro is None:
             inv = np.linalg.inv(self.last['voxel_map'])[:3]
             p = self._gather(p, inv, self.native_shape, self.order)
             m = self._gather(m, inv, self.native_shape, 0)
+            e = None if e is None else self._gather(e, inv, self.native_shape, 1)
         elif ro != IDENTITY_REORIENTATION:
             perm, flip = ro
             back = tuple(perm.index(b) for b in range(3))                     # native axis b is the target's axis back[b]
             p = ops.reorient3d(p, back, tuple(flip[a] for a in back))
             m = ops.reorient3d(m, back, tuple(flip[a] for a in back))
+            e = None if e is None else ops.reorient3d(e, back, tuple(flip[a] for a in back))
         y, lab = finish(p.unsqueeze(0), m.unsqueeze(0), threshold)
         y, lab = y[0], lab[0]
         if path is not None:
             from . import nifti
             nifti.save(os.path.join(path, 'mask.nii'), lab.cpu().numpy(), self.affine)
-        return y, lab
+        return (y, lab, (p, m, e)) if native or extra is not None else (y, lab)
 
 
 def _conformed(geometry, pad_res):
@@ -690,7 +712,11 @@ def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True,
     segment_volume with the reference's mask, bit for bit.  window: a WindowSpec, targets: 'labels' | 'regions', norm: None | a NormSpec, as
     in segment_volume (in case mode the voxels of the resampled brain mask).
     geometry: (Conformer, one (D,H,W) volume per modality, their 4x4 affines) -> the Conformer takes the Interpolator's place, forward and
-    back; `image`, `pixdim` and `order` are not read, and the result lies on the first modality's own grid."""
+    back; `image`, `pixdim` and `order` are not read, and the result lies on the first modality's own grid.
+    model may be a StageEnsemble, as in segment_volume: mean, std, spatial_res and the TTA arguments are then its members' own."""
+    ensemble = isinstance(model, StageEnsemble)
+    if ensemble:
+        spatial_res, threshold, targets = model.spatial_res, model.threshold, model.targets
     if window is not None:
         window.check_resolution(spatial_res)
     if geometry is None:
@@ -701,8 +727,9 @@ def segment_scan(model, image, pixdim, mean, std, spatial_res, spatial_tta=True,
         interp, xp, mp, orig = _conformed(geometry, spatial_res)
         same_grid = interp.identity
     df = getattr(model, 'data_format', 'channels_last')
-    tta = TestTimeAugmentor(mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype,
-                            tta_batch=tta_batch, window=window, targets=targets, norm=norm)
+    tta = model.augmentor(window, norm) if ensemble else TestTimeAugmentor(
+        mean, std, model, df, spatial_tta=spatial_tta, threshold=threshold, compute_dtype=compute_dtype, tta_batch=tta_batch, window=window,
+        targets=targets, norm=norm)
     y = tta(xp, mp)
     if same_grid:
         lab = tta.labels()
@@ -767,6 +794,100 @@ class StageSpec(object):
         return self._tta
 
 
+UNCERTAINTY_MODES = ops.UNCERTAINTY_MODES        # ('entropy', 'std')
+
+
+class EnsembleAugmentor(object):
+    """what `StageEnsemble.augmentor` hands out: a TestTimeAugmentor's call and `labels()` over the mean of the members.  After a call
+    `_prob` is the unmasked mean probability (1,D,H,W,C) of the members, channels last, `_mask` the brain mask it was called with and,
+    in 'std' mode, `_m2` the sum of the members' squared deviations from that mean (ops.ensemble_update)"""
+
+    def __init__(self, ensemble, window=None, norm=None):
+        self.ensemble, self.window, self.norm = ensemble, window, norm
+        self._finish = _finish_of(ensemble.targets)
+        self.threshold, self.targets = ensemble.threshold, ensemble.targets
+        self._prob = self._mask = self._m2 = None
+
+    def __call__(self, x, bmask):
+        """x: (D,H,W,C) raw intensities, bmask: (D,H,W,1) -> masked mean probability map (D,H,W,out_ch) of the members, channels last.
+        Every member runs its own augmentor (its own statistics, NormSpec and window) on the same input; its unmasked mean over the
+        augmented copies is folded into the running mean, so one member's volume is held at a time"""
+        ens = self.ensemble
+        mean = m2 = None
+        for k, member in enumerate(ens.members, 1):
+            tta = member.augmentor(self.window, self.norm)
+            tta(x, bmask)
+            p = tta._prob.contiguous()
+            if k == 1:
+                mean = torch.empty_like(p)
+                m2 = torch.empty_like(p) if ens.uncertainty == 'std' else None
+            elif tuple(p.shape) != tuple(mean.shape):
+                raise ValueError('StageEnsemble: member %d gives probabilities of shape %s, the members before it %s' %
+                                 (k - 1, tuple(p.shape), tuple(mean.shape)))
+            ops.ensemble_update(p, mean, m2, k)
+            self._mask = tta._mask
+        self._prob, self._m2 = mean, m2
+        y, _ = self._finish(mean, self._mask, self.threshold, want_probabilities=True, want_labels=False)
+        return y[0]
+
+    def labels(self):
+        """uint8 label map (D,H,W) of the last call, decoded from the members' mean as TestTimeAugmentor.labels decodes one model's"""
+        _, lab = self._finish(self._prob, self._mask, self.threshold, want_probabilities=False, want_labels=True)
+        return lab[0]
+
+    def uncertainty(self, mean, mask, spread=None):
+        """the ensemble's map from a mean (and, in 'std' mode, a VARIANCE) volume and a mask on one grid -> uint8 (D,H,W,C)"""
+        if self.ensemble.uncertainty == 'std':
+            return ops.uncertainty_finish(mean, mask, 'std', spread=spread, scale=1.0)
+        return ops.uncertainty_finish(mean, mask, 'entropy')
+
+
+class StageEnsemble(object):
+    """several tumour models in the place of one StageSpec: the probabilities `segment_case` decodes, resamples and hands back are the
+    mean over the members of each member's mean over its augmented copies.  members: a non-empty list of StageSpec that agree in
+    spatial_res, decoder out_ch, targets, threshold and compute_dtype (anything else -- statistics, NormSpec, window, data format, TTA
+    settings -- is each member's own); uncertainty: None | 'entropy' | 'std', the voxel-wise map `segment_case(return_stages=True)` adds
+    as stages['uncertainty']: the binary entropy of the mean per channel, or the population deviation of the members' probabilities
+    (two members at least), as levels 0..100 (ops.uncertainty_finish).  The ensemble hands over channels last whatever the members are."""
+
+    data_format = 'channels_last'
+
+    def __init__(self, members, uncertainty=None):
+        members = list(members) if isinstance(members, (list, tuple)) else None
+        if not members or not all(isinstance(m, StageSpec) for m in members):
+            raise ValueError('StageEnsemble: members must be a non-empty list of StageSpec')
+        if uncertainty is not None and uncertainty not in UNCERTAINTY_MODES:
+            raise ValueError('StageEnsemble: uncertainty must be None or one of %s, got %r' % (UNCERTAINTY_MODES, uncertainty))
+        if uncertainty == 'std' and len(members) < 2:
+            raise ValueError("StageEnsemble: uncertainty 'std' is the spread between members and needs two at least, got %d" % len(members))
+
+        def facts(m):
+            return (('spatial_res', m.spatial_res), ('out_ch', getattr(getattr(m.model, 'decoder', None), 'out_ch', None)),
+                    ('targets', m.targets), ('threshold', m.threshold), ('compute_dtype', m.compute_dtype))
+        first = facts(members[0])
+        for i, m in enumerate(members[1:], 1):
+            for (what, a), (_, b) in zip(first, facts(m)):
+                if a != b:
+                    raise ValueError('StageEnsemble: member %d has %s = %r, member 0 has %r' % (i, what, b, a))
+        self.members, self.uncertainty = members, uncertainty
+        self.spatial_res, self.out_ch, self.targets, self.threshold, self.compute_dtype = (v for _, v in first)
+        self._tta = None
+
+    @property
+    def window_counts(self):
+        """(windows run, windows skipped as empty) summed over the members' last windowed calls, None where none was windowed"""
+        counts = [m.window_counts for m in self.members if m.window_counts is not None]
+        return (sum(c[0] for c in counts), sum(c[1] for c in counts)) if counts else None
+
+    def augmentor(self, window=None, norm=None):
+        """the ensemble's EnsembleAugmentor; window, norm: for this call in place of every member's own, as StageSpec.augmentor"""
+        check_norm(norm)
+        if window is not None:
+            window.check_resolution(self.spatial_res)
+        self._tta = EnsembleAugmentor(self, window, norm)
+        return self._tta
+
+
 def remove_components(lab, class_mask, K=4, connectivity=26, min_voxels=0, largest_only=False, fill=0):
     """clean one region of a dense uint8 label map (D,H,W) on the GPU, IN PLACE: the region (classes min(label, K-1) whose bit is set in
     class_mask) is split into its connected components (6 | 18 | 26 neighbours), and every voxel of a component of fewer than
@@ -823,7 +944,12 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
     ops.skull_strip multiplies.
     geometry: (Conformer, one (D,H,W) volume per modality, their 4x4 affines) -> the Conformer takes the Interpolator's place for the forward
     and the reverse: `image`, `pixdim` and `order` are not read, 'x1mm' is the conformed scan, and probabilities and labels lie on the
-    first modality's own grid.  None: as before."""
+    first modality's own grid.  None: as before.
+    tumor may be a StageEnsemble: its members' mean probabilities take the place of one model's, everything after is the same.  One built
+    with `uncertainty` adds two keys: 'uncertainty', uint8 (D,H,W,C) levels 0..100 on the scan's own grid, channels last, 0 outside the
+    brain mask, and 'uncertainty_mask', that mask (D,H,W,1) float32.  Where the scan was resampled the mean goes back at the configured
+    order and the mask at order 0, as for the labels, in 'std' mode the members' variance m2 / M rides the same inverse map at order 1, and
+    ops.uncertainty_finish runs on the native grid.  Post-processing changes the labels only, never the map."""
     if window is not None:
         for stage in (tumor, skull):
             if stage is not None:
@@ -864,10 +990,24 @@ def segment_case(tumor, image, pixdim, skull=None, order=3, return_stages=False,
         y = y.permute(1, 2, 3, 0)
     y = y[:orig[0], :orig[1], :orig[2]]
     stages['prob_1mm'] = y
-    if same_grid:
-        lab = tta.labels()[:orig[0], :orig[1], :orig[2]]
+    mode = getattr(tumor, 'uncertainty', None)                       # a StageEnsemble that was asked for its map
+    if mode is None:
+        if same_grid:
+            lab = tta.labels()[:orig[0], :orig[1], :orig[2]]
+        else:
+            y, lab = interp.reverse(y, threshold=tumor.threshold, targets=tumor.targets)
     else:
-        y, lab = interp.reverse(y, threshold=tumor.threshold, targets=tumor.targets)
+        var = None
+        if mode == 'std':                                            # the population variance of the members, on the 1 mm^3 grid
+            var = (tta._m2[0, :orig[0], :orig[1], :orig[2]] * (1.0 / len(tumor.members))).contiguous()
+        if same_grid:
+            lab = tta.labels()[:orig[0], :orig[1], :orig[2]]
+            mean = tta._prob[0, :orig[0], :orig[1], :orig[2]].contiguous()
+            mask = tta._mask[0, :orig[0], :orig[1], :orig[2]].contiguous()
+        else:                                                        # the map is taken where the labels are: on the scan's own grid
+            y, lab, (mean, mask, var) = interp.reverse(y, threshold=tumor.threshold, targets=tumor.targets, extra=var, native=True)
+        stages['uncertainty'] = tta.uncertainty(mean, mask, var)
+        stages['uncertainty_mask'] = mask
     if postprocess is not None:
         lab = lab.contiguous()
         stages['postprocess'] = postprocess_labels(lab, **postprocess)
@@ -938,6 +1078,72 @@ def region_rates_from_confusion(confusion):
         tn, neg = total - t - p + tp, total - t
         out['sens_' + name] = tp / t if t else float('nan')
         out['spec_' + name] = tn / neg if neg else float('nan')
+    return out
+
+
+UNCERTAINTY_SCORE_KEYS = ('qu_score', 'qu_dice_auc', 'qu_ftp_auc', 'qu_ftn_auc')
+
+
+def uncertainty_channels(targets='labels', n_classes=4):
+    """-> ((name, classes), ...) of an uncertainty map's channels over min(label, K-1): BRATS_REGIONS for 'regions', the single classes
+    ('class_1', (1,)), ... for 'labels'"""
+    if targets not in TARGETS:
+        raise ValueError('unknown targets %r: one of %s' % (targets, TARGETS))
+    return BRATS_REGIONS if targets == 'regions' else tuple(('class_%d' % c, (c,)) for c in range(1, int(n_classes)))
+
+
+def uncertainty_scores_from_counts(table):
+    """(101, 4) counts [level, (TN, FP, FN, TP)] of one channel -> (score, dice_auc, ftp_auc, ftn_auc), float64 on the host.  See
+    `uncertainty_scores` for the definition"""
+    t = np.asarray(table)
+    if t.shape != (101, 4):
+        raise ValueError('table must be (101, 4): one row per level, cells TN, FP, FN, TP; got shape %s' % (t.shape,))
+    kept = np.cumsum(t.astype(np.int64), axis=0).astype(np.float64)          # at threshold tau: the voxels with level <= tau
+    tn, fp, fn, tp = kept[:, 0], kept[:, 1], kept[:, 2], kept[:, 3]
+    den = 2.0 * tp + fp + fn
+    dice = np.where(den > 0, 2.0 * tp / np.where(den > 0, den, 1.0), 1.0)
+    ftp = (tp[100] - tp) / tp[100] if tp[100] > 0 else np.zeros(101)
+    ftn = (tn[100] - tn) / tn[100] if tn[100] > 0 else np.zeros(101)
+
+    def auc(v):                                                              # the trapezoid over tau = 0..100, divided by 100
+        return float((v[0] / 2.0 + v[1:100].sum() + v[100] / 2.0) / 100.0)
+    a_dice, a_ftp, a_ftn = auc(dice), auc(ftp), auc(ftn)
+    return (a_dice + (1.0 - a_ftp) + (1.0 - a_ftn)) / 3.0, a_dice, a_ftp, a_ftn
+
+
+def uncertainty_scores(truth, pred, unc, mask=None, targets='labels', n_classes=4):
+    """the uncertainty-filtered scores of the BraTS uncertainty task (QU-BraTS, Mehta et al. 2022) of a map `unc`, uint8 (D,H,W,C) levels
+    0..100 channels last, for the label maps truth and pred, uint8 (D,H,W) (device tensors or numpy); mask: uint8 (D,H,W) or None, only
+    voxels with mask != 0 count.  Channels: wt, tc, et with the class sets BRATS_REGIONS for targets 'regions', class_1.. with single
+    classes for 'labels' (`uncertainty_channels`); labels >= K-1 count as class K-1.
+    -> {'qu_score_<name>', 'qu_dice_auc_<name>', 'qu_ftp_auc_<name>', 'qu_ftn_auc_<name>'} per channel.  Per channel, with thresholds
+    tau = 0, 1, ..., 100 and the voxels of level <= tau KEPT at tau:
+      Dice(tau) = 2 TP / (2 TP + FP + FN) over the kept voxels, 1 where the denominator is 0;
+      FTP(tau) = (TP_100 - TP_tau) / TP_100, the true positives filtered out, and FTN(tau) likewise of the true negatives, each 0 where
+      its denominator is 0;
+      AUC = the trapezoid over tau, divided by 100;
+      score = (AUC_Dice + (1 - AUC_FTP) + (1 - AUC_FTN)) / 3.
+    Where published code differs in a detail, this definition holds.  The device counts the table (ops.uncertainty_confusion: one pass,
+    integer counts), the host reduces it in float64 (`uncertainty_scores_from_counts`)."""
+    chans = uncertainty_channels(targets, n_classes)
+    tmap, pmap = _label_maps(truth, pred, 'uncertainty_scores')
+    if tuple(unc.shape) != tuple(tmap.shape) + (len(chans),):
+        raise ValueError('uncertainty_scores: the map must have shape %s, got %s' % (tuple(tmap.shape) + (len(chans),), tuple(unc.shape)))
+    maps = []
+    for t in (unc, mask):
+        if isinstance(t, np.ndarray):
+            if t.dtype != np.uint8:
+                raise ValueError('uncertainty_scores: the map and the mask must be uint8, got %s' % t.dtype)
+            t = torch.from_numpy(np.ascontiguousarray(t)).to(tmap.device)
+        maps.append(None if t is None else t.contiguous())
+    if maps[1] is not None and tuple(maps[1].shape) != tuple(tmap.shape):
+        raise ValueError('uncertainty_scores: the mask must have shape %s, got %s' % (tuple(tmap.shape), tuple(maps[1].shape)))
+    table = ops.uncertainty_confusion(tmap, pmap, maps[0], [sum(1 << int(c) for c in set(sel)) for _, sel in chans], mask=maps[1],
+                                      n_classes=int(n_classes)).cpu().numpy()                 # the one read
+    out = {}
+    for (name, _), counts in zip(chans, table):
+        for key, v in zip(UNCERTAINTY_SCORE_KEYS, uncertainty_scores_from_counts(counts)):
+            out['%s_%s' % (key, name)] = v
     return out
 
 

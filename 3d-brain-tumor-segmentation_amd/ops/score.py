@@ -23,6 +23,32 @@ def label_confusion(truth, pred, n_classes=4, counts=None):
     return counts
 
 
+UNCERTAINTY_LEVELS = 101      # levels 0..100 of an uncertainty map
+
+
+def uncertainty_confusion(truth, pred, unc, class_masks, mask=None, n_classes=4, table=None):
+    """truth, pred: dense uint8 label maps of V voxels on the GPU; unc: dense uint8 levels (V, C), channels last (a level above 100 counts
+    as 100); class_masks: C host integers, channel c's region = the classes min(label, K-1) whose bit is set in class_masks[c]; mask:
+    dense uint8 of V voxels or None, only voxels with mask != 0 count
+    -> table (C, 101, 4) int64 on the GPU with table[c, unc[v, c], 2 t + pr] += 1 (cells TN, FP, FN, TP).  table: a zeroed (or partly
+    filled) buffer to add into; a new one otherwise   [csrc/ensemble.hip]"""
+    k = int(n_classes)
+    masks = [int(m) for m in class_masks]
+    c = len(masks)
+    _core.dense(truth, u8, 'uncertainty_confusion: truth')
+    _core.dense(pred, u8, 'uncertainty_confusion: pred', numel=truth.numel())
+    _core.dense(unc, u8, 'uncertainty_confusion: unc', numel=truth.numel() * c)
+    if mask is not None:
+        _core.dense(mask, u8, 'uncertainty_confusion: mask', numel=truth.numel())
+    if any(m < 0 or m >> max(k, 0) for m in masks):
+        raise ValueError('uncertainty_confusion: class masks must lie in [0, 2^%d), got %r' % (k, masks))
+    table = _core.out_or_new(table, (c, UNCERTAINTY_LEVELS, 4), i64, truth.device, 'uncertainty_confusion: table',
+                             numel=c * UNCERTAINTY_LEVELS * 4, zero=True)
+    _core.lib().call('bts_uncertainty_confusion', _core._p(truth), _core._p(pred), _core._p(unc), _core._p(mask), truth.numel(), c, k,
+                     _core.carray(ctypes.c_uint, masks), _core._p(table), _core._stream())
+    return table
+
+
 def region_surface(lab, n_classes=4, class_mask=0b1110, out=None, count=None):
     """lab: dense uint8 label map (D,H,W) on the GPU; the region is the set of classes min(label, K-1) whose bit is set in class_mask
     -> (surf uint8 (D,H,W): 1 on the region's surface voxels (a face neighbour outside the region or the volume), 0 elsewhere;

@@ -31,6 +31,52 @@ def tta_finish(prob, bmask, threshold=0.5, want_probabilities=True, want_labels=
     return y, labels
 
 
+def ensemble_update(p, mean, m2, k):
+    """member k (counted from 1) of an ensemble, in place: d = p - mean; mean += d / k; m2 += d * (p - mean) over dense float32 tensors of
+    one size (Welford's recurrence, the float32 numpy expression bit for bit).  k == 1 writes mean = p and m2 = 0 without reading them.
+    mean None (k == 1 only): a new tensor of p's shape; m2 None: only the mean is kept  -> (mean, m2)   [csrc/ensemble.hip]"""
+    f32 = torch.float32
+    _core.dense(p, f32, 'ensemble_update: p')
+    k = int(k)
+    if k < 1:
+        raise ValueError('ensemble_update: k counts the members from 1, got %r' % (k,))
+    if mean is None and k != 1:
+        raise ValueError('ensemble_update: member %d needs the mean of the members before it' % k)
+    mean = _core.out_or_new(mean, p.shape, f32, p.device, 'ensemble_update: mean', numel=p.numel())
+    if m2 is not None:
+        _core.dense(m2, f32, 'ensemble_update: m2', numel=p.numel())
+    _core.lib().call('bts_ensemble_update', _core._p(p), _core._p(mean), _core._p(m2), p.numel(), k, _core._stream())
+    return mean, m2
+
+
+UNCERTAINTY_MODES = ('entropy', 'std')
+
+
+def uncertainty_finish(mean, bmask, mode='entropy', spread=None, scale=1.0, out=None):
+    """-> uint8 levels 0..100 of `mean`'s shape (..., C), channels last, 0 where bmask (one float per voxel) == 0.
+    'entropy': of p = clamp(mean, 0, 1), h = -(p log2 p + (1 - p) log2(1 - p)), level = min(100, floor(100 h + 0.5)).
+    'std': level = min(100, floor(200 sqrt(max(spread, 0) * scale) + 0.5)); spread (of mean's shape) = ensemble_update's m2 with
+    scale = 1 / members, or a variance with scale = 1; only the shape of `mean` is read.  out: a dense uint8 tensor of that many
+    values to write into   [csrc/ensemble.hip]"""
+    f32 = torch.float32
+    if mode not in UNCERTAINTY_MODES:
+        raise ValueError('uncertainty_finish: mode must be one of %s, got %r' % (UNCERTAINTY_MODES, mode))
+    _core.dense(mean, f32, 'uncertainty_finish: mean')
+    if mean.dim() < 1 or mean.numel() == 0:
+        raise ValueError('uncertainty_finish: mean must have shape (..., C), got %s' % (tuple(mean.shape),))
+    c = int(mean.shape[-1])
+    nvox = mean.numel() // c
+    _core.dense(bmask, f32, 'uncertainty_finish: bmask', numel=nvox)
+    if mode == 'std':
+        if spread is None:
+            raise ValueError("uncertainty_finish: mode 'std' needs the spread")
+        _core.dense(spread, f32, 'uncertainty_finish: spread', numel=mean.numel())
+    out = _core.out_or_new(out, mean.shape, torch.uint8, mean.device, 'uncertainty_finish: out', numel=mean.numel())
+    _core.lib().call('bts_uncertainty_finish', _core._p(mean), _core._p(spread if mode == 'std' else None), _core._p(bmask), _core._p(out), nvox,
+                     c, UNCERTAINTY_MODES.index(mode), float(scale), _core._stream())
+    return out
+
+
 def spline_prefilter3d(x, out=None):
     """cubic B-spline coefficients of a dense (D,H,W,C) volume along D, H and W (the spline_filter half of
     scipy.ndimage.zoom(order=3, mode='reflect')); C <= 8, spatial extents >= 4"""

@@ -1,6 +1,7 @@
 """Segment folders of scans end to end: the reference's test.py main() (test.py:181-270) on the device.
 
-    python -m bts_amd.test --in_locs a,b --modalities t1ce,flair --tumor_model DIR --tumor_prepro DIR/prepro.npy
+    python -m bts_amd.test --in_locs a,b --modalities t1ce,flair --tumor_model DIR[,DIR...] --tumor_prepro DIR/prepro.npy[,FILE...]
+                           [--uncertainty entropy|std]
                            [--skull_model DIR --skull_prepro FILE] [--truth seg] [--out_loc DIR] [--dtype float16]
                            [--min_component_voxels N] [--et_min_voxels N] [--component_connectivity 26] [--skull_largest_component]
                            [--lesionwise] [--lesion_dilation 3] [--lesion_min_voxels 50] [--lesion_penalty_mm 374]
@@ -63,8 +64,20 @@ or with --bias_correct, every modality of every case is corrected once by N4 on 
 --bias_iters, --bias_threshold and --bias_fwhm need --bias_correct and replace the recorded fields.  One line at the start says which
 rule applies, one more line per case prints the sweeps per level and the final cv per modality.  Without either nothing changes.
 
+Ensembles and uncertainty: --tumor_model A,B,C runs every checkpoint folder of the list as a member of one `infer.StageEnsemble` (its own
+statistics, normalisation and crop size each; --tumor_prepro takes one dump for all of them or one per member) and decodes the mean of
+their probabilities; the members must agree in resolution, output channels, `targets` and the flags here make them agree in the rest,
+and a refusal names the member.  With --uncertainty entropy|std each case also gets `unc_<name>.nii` beside `mask.nii`, uint8 levels
+0..100 with the same affine, one file per channel of the tumour stage (wt, tc, et for a stage trained on regions, else 1, 2, 4): the
+binary entropy of the mean probability, or (two models at least) the deviation between the members.  A labelled case prints one more line
+and gets twelve more columns at the end of its scores.csv row, the scores of `infer.uncertainty_scores` (qu_score_*, qu_dice_auc_*,
+qu_ftp_auc_*, qu_ftn_auc_*: uncertainty-filtered Dice and the filtered true positives and negatives of the BraTS uncertainty task),
+counted inside the brain mask on the scan's grid; the `total` row holds the mean of the finite values.  Post-processing changes the
+labels, never the map.  One line at the start lists the members and what each decodes.  One model and no --uncertainty is the code path
+there has always been.
+
 The flags and defaults are the reference's TestArgParser (args.py:199-235), its two checks included (args.py:243-246).  --gpu is
-accepted and implied: there is no CPU path.  Added: --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
+accepted and implied: there is no CPU path.  Added: --uncertainty, the comma lists of --tumor_model and --tumor_prepro, --dtype, --tta_batch, --workers, --out_loc, --surface_metrics,
 --min_component_voxels, --et_min_voxels, --component_connectivity, --skull_largest_component, --lesionwise, --lesion_dilation,
 --lesion_min_voxels, --lesion_penalty_mm, --window, --window_overlap, --window_mode, --window_batch, --conform, --coregister,
 --coregister_max_mm, --coregister_max_deg, --coregister_bins, --bias_correct, --bias_shrink, --bias_levels, --bias_iters,
@@ -94,8 +107,9 @@ import numpy as np
 import torch
 
 from . import coreg, n4, nifti
-from .infer import (BRATS_REGIONS, WINDOW_MODES, Conformer, Interpolator, StageSpec, WindowSpec, label_scores, lesionwise_scores, region_rates_from_confusion,
-                    scores_from_confusion, segment_case, surface_scores, zoom_output_shape)
+from .infer import (BRATS_REGIONS, UNCERTAINTY_MODES, UNCERTAINTY_SCORE_KEYS, WINDOW_MODES, Conformer, Interpolator, StageEnsemble, StageSpec, WindowSpec,
+                    label_scores, lesionwise_scores, region_rates_from_confusion, scores_from_confusion, segment_case, surface_scores,
+                    uncertainty_channels, uncertainty_scores, zoom_output_shape)
 from .preprocess import add_bias_flags, bias_spec, load_bias, load_norm
 from .train import load_checkpoint, load_train_args
 
@@ -109,6 +123,25 @@ LESION_KEYS = LESION_SCORE_KEYS + LESION_COUNT_KEYS      # the columns --lesionw
 LESION_DEFAULTS = {'lesion_dilation': 3, 'lesion_min_voxels': 50, 'lesion_penalty_mm': 374.0}
 WINDOW_DEFAULTS = {'window_overlap': 0.5, 'window_mode': 'gaussian', 'window_batch': None}
 COREGISTER_DEFAULTS = {'coregister_max_mm': 30.0, 'coregister_max_deg': 20.0, 'coregister_bins': 32}
+
+
+UNCERTAINTY_FILE_NAMES = {'regions': ('wt', 'tc', 'et'), 'labels': ('1', '2', '4')}      # unc_<name>.nii per channel of the map
+
+
+def tumor_models(args):
+    """--tumor_model A,B,C -> the checkpoint folders of the ensemble's members, one for a single model"""
+    return [m for m in args.tumor_model.split(',') if m]
+
+
+def tumor_prepros(args):
+    """--tumor_prepro: one dump for every member, or one per member -> one per member"""
+    files, n = [f for f in args.tumor_prepro.split(',') if f], len(tumor_models(args))
+    return files * n if len(files) == 1 else files
+
+
+def uncertainty_keys(targets):
+    """the columns --uncertainty appends to scores.csv for a tumour stage that decodes `targets`"""
+    return tuple('%s_%s' % (key, name) for key in UNCERTAINTY_SCORE_KEYS for name, _ in uncertainty_channels(targets, N_CLASSES))
 
 
 def _window_arg(text):
@@ -195,6 +228,10 @@ def arg_parser():
                    help='Largest rotation searched per axis, degrees (default: %g).' % COREGISTER_DEFAULTS['coregister_max_deg'])
     p.add_argument('--coregister_bins', type=int, default=argparse.SUPPRESS,
                    help='Intensity bins per modality of the joint histogram, 2..64 (default: %d).' % COREGISTER_DEFAULTS['coregister_bins'])
+    # and --uncertainty: absent, no map is computed and no file written
+    p.add_argument('--uncertainty', type=str, choices=UNCERTAINTY_MODES, default=argparse.SUPPRESS,
+                   help='Also write unc_<name>.nii, levels 0..100 per voxel: the entropy of the mean probability, or the deviation '
+                        'between the models of --tumor_model A,B,C.')
     # and --bias_correct with its sub-flags, the ones of `python -m bts_amd.preprocess`
     add_bias_flags(p)
     return p
@@ -224,6 +261,13 @@ def parse_args(argv=None):
     if not 2 <= getattr(args, 'coregister_bins', 32) <= 64:
         parser.error('--coregister_bins must lie in 2..64')
     bias_spec(args, parser)
+    models, prepros = tumor_models(args), [f for f in args.tumor_prepro.split(',') if f]
+    if not models:
+        parser.error('--tumor_model names no checkpoint folder')
+    if len(prepros) not in (1, len(models)):
+        parser.error('--tumor_prepro takes one file for all models or one per model: %d files for %d models' % (len(prepros), len(models)))
+    if getattr(args, 'uncertainty', None) == 'std' and len(models) < 2:
+        parser.error('--uncertainty std is the deviation between models and needs two at least in --tumor_model A,B')
     if args.skull_largest_component and not args.skull_model:
         parser.error('--skull_largest_component needs --skull_model')
     args.modalities = args.modalities.split(',')
@@ -395,11 +439,12 @@ def bias_rule(args):
     """-> the n4.N4Spec every modality of every case is corrected with right after upload, or None: the spec the tumour stage's
     prepro.npy records (its examples were corrected, so its scans must be), or --bias_correct with its sub-flags, which replace the
     recorded fields.  Says which rule applies in one line; silent where none does"""
-    recorded = load_bias(args.tumor_prepro) if os.path.isfile(args.tumor_prepro) else None      # a missing dump is load_stage's to report
+    prepro = tumor_prepros(args)[0]                           # of an ensemble: the first member's
+    recorded = load_bias(prepro) if os.path.isfile(prepro) else None      # a missing dump is load_stage's to report
     spec = bias_spec(args, None, recorded)
     if spec is not None:
-        why = ('--bias_correct' + (' over the record of %s' % args.tumor_prepro if recorded is not None else '')
-               if hasattr(args, 'bias_correct') else 'recorded by %s' % args.tumor_prepro)
+        why = ('--bias_correct' + (' over the record of %s' % prepro if recorded is not None else '')
+               if hasattr(args, 'bias_correct') else 'recorded by %s' % prepro)
         print('Bias-field correction ({}): {}'.format(why, ', '.join('%s %s' % kv for kv in n4.spec_record(spec).items())), flush=True)
     return spec
 
@@ -486,6 +531,7 @@ def run(args):
     conf = Conformer(args.conform, (1.0, 1.0, 1.0), args.order) if getattr(args, 'conform', None) is not None else None
     registering = coregister_kwargs(args)
     bias = bias_rule(args)
+    unc_mode, unc_keys = getattr(args, 'uncertainty', None), ()
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
     for (name, path), case in zip(cases, _decoded(cases, args)):
@@ -528,16 +574,27 @@ def run(args):
                 shape_1mm = plan['shape']
             else:
                 shape_1mm = tuple(x.shape[:3]) if unit else zoom_output_shape(tuple(x.shape[:3]), pixdim)
-            tumor = load_stage(args.tumor_model, args.tumor_prepro, args, shape_1mm)
+            members = [load_stage(folder, prepro, args, shape_1mm) for folder, prepro in zip(tumor_models(args), tumor_prepros(args))]
+            tumor = members[0]
+            if len(members) > 1 or unc_mode is not None:             # one model and no map: the code path there has always been
+                print('Ensemble of {}: {}'.format(len(members), ', '.join(
+                    '%s (%s)' % (f, m.targets) for f, m in zip(tumor_models(args), members))), flush=True)
+                tumor = StageEnsemble(members, unc_mode)
+                unc_keys = uncertainty_keys(tumor.targets)
             if args.skull_strip:
                 skull = load_stage(args.skull_model, args.skull_prepro, args, shape_1mm)
                 if largest:
                     skull.largest_component = True
         geo = {} if geometry is None else {'geometry': geometry}          # without --conform the call is the one it has always been
-        if post is None and not largest:
+        unc = None
+        if post is None and not largest and unc_mode is None:
             _, lab = segment_case(tumor, x, pixdim, skull=skull, order=args.order, **geo)
+        elif post is None and not largest:
+            _, lab, st = segment_case(tumor, x, pixdim, skull=skull, order=args.order, return_stages=True, **geo)
+            unc = st['uncertainty']
         else:
             _, lab, st = segment_case(tumor, x, pixdim, skull=skull, order=args.order, return_stages=True, postprocess=post, **geo)
+            unc = st.get('uncertainty')
             counts = dict(st.get('postprocess') or {})
             counts.update({'brain_' + k: v for k, v in (st.get('brain_counts') or {}).items()})
             cleaned.append((name, counts))
@@ -556,9 +613,16 @@ def run(args):
                 s.update(region_rates_from_confusion(s['confusion']))
             if lesionwise:
                 s.update(lesion_columns(lesionwise_scores(y, lab, pixdim, N_CLASSES, **lesion)))
+            if unc is not None:                                      # counted inside the brain mask the map was taken with
+                brain = (st['uncertainty_mask'] > 0).to(torch.uint8).reshape(tuple(lab.shape)).contiguous()
+                s.update(uncertainty_scores(y, lab.contiguous(), unc, brain, tumor.targets, N_CLASSES))
         where = os.path.join(args.out_loc, name) if args.out_loc else path
         os.makedirs(where, exist_ok=True)
         nifti.save(os.path.join(where, 'mask.nii'), lab.cpu().numpy(), affine)
+        if unc is not None:
+            levels = unc.cpu().numpy()
+            for ch, fname in enumerate(UNCERTAINTY_FILE_NAMES[tumor.targets]):
+                nifti.save(os.path.join(where, 'unc_%s.nii' % fname), np.ascontiguousarray(levels[..., ch]), affine)
         done += 1
         if s is not None:
             scores.append((name, s))
@@ -570,6 +634,8 @@ def run(args):
                       'Lesions (missed, false positives) WT: {:d} ({:d}, {:d}). TC: {:d} ({:d}, {:d}). ET: {:d} ({:d}, {:d})'.format(
                           name, *([s[k] for k in LESION_SCORE_KEYS] +
                                   [s['lw_%s_%s' % (what, r)] for r, _ in BRATS_REGIONS for what in ('lesions', 'fn', 'fp')])), flush=True)
+            if unc is not None:
+                print('{}. Uncertainty ({}) {}'.format(name, unc_mode, '. '.join('%s: %1.4f' % (k, s[k]) for k in unc_keys)), flush=True)
     overall = scores_from_confusion(total) if scores else None
     n_inf = 0
     if args.surface_metrics:
@@ -580,6 +646,8 @@ def run(args):
     if lesionwise and overall is not None:
         overall.update({k: mean_finite([s[k] for _, s in scores]) for k in LESION_SCORE_KEYS})
         overall.update({k: sum(s[k] for _, s in scores) for k in LESION_COUNT_KEYS})
+    if unc_keys and overall is not None:
+        overall.update({k: mean_finite([s[k] for _, s in scores]) for k in unc_keys})
     if args.out_loc:
         head = ['case', 'macro', 'micro'] + ['dice_%d' % c for c in range(1, N_CLASSES)] + ['wt', 'tc', 'et']
         rows = [head] + [score_row(n, s) for n, s in scores]
@@ -590,6 +658,10 @@ def run(args):
             rows = [r + e for r, e in zip(rows, extra)]
         if lesionwise:
             extra = [list(LESION_KEYS)] + [lesion_row(s) for _, s in scores] + ([lesion_row(overall)] if overall is not None else [])
+            rows = [r + e for r, e in zip(rows, extra)]
+        if unc_keys:
+            extra = [list(unc_keys)] + [[_fmt(s[k]) for k in unc_keys] for _, s in scores] + (
+                [[_fmt(overall[k]) for k in unc_keys]] if overall is not None else [])
             rows = [r + e for r, e in zip(rows, extra)]
         with open(os.path.join(args.out_loc, 'scores.csv'), 'w') as f:
             f.write(''.join(','.join(r) + '\n' for r in rows))

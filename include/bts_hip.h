@@ -601,6 +601,29 @@ int bts_region_dice_sums(const float* y_true, const float* y_pred, uint8_t* labe
 int bts_region_finish(const float* prob, const float* bmask, float* y, uint8_t* labels, long nvox, int C, float threshold,
                       bts_stream_t stream);
 
+/* ===== ensembles of tumour models and voxel-wise uncertainty maps (bts_amd.infer.StageEnsemble, uncertainty_scores; DESIGN section 37.
+ * The reference runs one checkpoint, test.py:185-221, and reports a label per voxel) =====
+ * Welford's recurrence over the n floats of member k's mean probabilities (k counts from 1): d = p - mean; mean += d / k;
+ * m2 += d * (p - mean), every operation rounded once, so the float32 numpy recurrence bit for bit.  k == 1 writes mean = p and m2 = 0 and
+ * does not read the accumulators.  m2 may be NULL: only the mean is kept.  After M members mean is their mean and m2 the sum of their
+ * squared deviations from it.  BTS_ERR_SHAPE for n <= 0, k < 1 or a missing p or mean; BTS_ERR_UNSUPPORTED when two of the buffers are
+ * the same. */
+int bts_ensemble_update(const float* p, float* mean, float* m2, long n, int k, bts_stream_t stream);
+/* unc (nvox, C) uint8, channels last = one level 0..100 per voxel and channel, 0 where bmask (one float per voxel) == 0.
+ * mode 0, entropy: p = clamp(mean, 0, 1), h = -(p log2 p + (1 - p) log2(1 - p)), 0 at p in {0, 1}; level = min(100, floor(100 h + 0.5));
+ * spread is not read.  mode 1, deviation: level = min(100, floor(200 sqrt(max(spread, 0) * scale) + 0.5)), spread = bts_ensemble_update's
+ * m2 with scale = 1 / M, or a variance with scale = 1; the population deviation of values in [0, 1] is at most 0.5; mean is not read.
+ * BTS_ERR_UNSUPPORTED for another mode; BTS_ERR_SHAPE for nvox <= 0, C outside 1..1024, a negative scale or a missing buffer. */
+int bts_uncertainty_finish(const float* mean, const float* spread, const float* bmask, uint8_t* unc, long nvox, int C, int mode,
+                           float scale, bts_stream_t stream);
+/* table (C, 101, 4) uint64 on the device, accumulated across calls: per voxel with mask != 0 (mask may be NULL: every voxel) and per
+ * channel c, table[c][min(unc[v C + c], 100)][2 t + pr] += 1 with t = bit min(truth[v], K-1) of class_masks[c] and pr the same of
+ * pred[v] (cells TN, FP, FN, TP).  truth, pred, mask: dense uint8 label maps; class_masks: C HOST values below 2^K; C in 1..4, K in 2..8.
+ * Integer atomics only: exact and bit-reproducible.  BTS_ERR_UNSUPPORTED for C outside 1..4; BTS_ERR_SHAPE for K outside 2..8, nvox
+ * outside [0, 2^31 - 1) or a class mask outside its range; nvox == 0 launches nothing. */
+int bts_uncertainty_confusion(const uint8_t* truth, const uint8_t* pred, const uint8_t* unc, const uint8_t* mask, long nvox, int C, int K,
+                              const unsigned* class_masks, unsigned long long* table, bts_stream_t stream);
+
 /* ===== dataset preprocessing on the device (preprocess.py:17-131: create_dataset, compute_norm, main) =====
  * Dense fp32 (S0,S1,S2,C) volumes, C innermost, 1 <= C <= 16.  A crop window (T0,T1,T2,C) of such a volume is addressed in place:
  * `xwin` points at its origin, st0 / st1 are the element strides of the two outer axes, the voxel stride is C. */
