@@ -10,6 +10,9 @@
 //   bts_affine_resample3d   one thread per output voxel, all C channels in registers: the source coordinate M (o0,o1,o2,1) in fp64 (so
 //                           integer-valued maps are exact), then the taps of bts_zoom3d (resample_taps.h; order 1 summed in fp64); 0 outside the source's
 //                           field of view [-0.5, n - 0.5] and in the padding; written to channels c0 .. c0+C-1 of a wider destination.
+//   bts_label_resample3d    a label map (C = 1) through the same map: the 8 taps of order 1 vote with their fp64 weights, the value with
+//                           the largest total wins, of equal totals the smallest (preprocess --conform; nnU-Net's per-class linear
+//                           interpolation and arg-max, in one gather).
 #include "common.h"
 #include "bts_internal.h"
 #include "resample_taps.h"
@@ -297,4 +300,83 @@ extern "C" int bts_affine_resample3d(const float* coef, int Ds, int Hs, int Ws, 
     case 7: return cf_affine_launch<7>(p, order, (int)blocks, stream);
     default: return cf_affine_launch<8>(p, order, (int)blocks, stream);
   }
+}
+
+struct LabelParams {
+  const float* lab;
+  float* dst;
+  int Ds, Hs, Ws, Do, Ho, Wo, Dp, Hp, Wp;
+  double m[12];  // as AffineParams
+};
+
+// A label map through the same map: the coordinate, the field of view and the 8 taps (indices, fp64 weights (wd * wh) * ww, row-major
+// order) of cf_affine_kernel<1, 2> / cf_trilinear, but the taps vote instead of being summed.  A label value's weight is the sum, in tap
+// order, of the weights of the taps that hold it; every tap's value gets its total by comparing it with all 8 (taps of one value get the
+// same sum, term for term), the largest total wins and of equal totals the smallest value.  All in registers, for any values.
+__global__ __launch_bounds__(256) void cf_label_kernel(const LabelParams p) {
+  const long total = (long)p.Dp * p.Hp * p.Wp;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+    long v = i;
+    const int w = (int)(v % p.Wp); v /= p.Wp;
+    const int h = (int)(v % p.Hp);
+    const int d = (int)(v / p.Hp);
+    float res = 0.f;
+    if (d < p.Do && h < p.Ho && w < p.Wo) {
+      const double od = (double)d, oh = (double)h, ow = (double)w;
+      const double sd = fma(p.m[2], ow, fma(p.m[1], oh, p.m[0] * od)) + p.m[3];
+      const double sh = fma(p.m[6], ow, fma(p.m[5], oh, p.m[4] * od)) + p.m[7];
+      const double sw = fma(p.m[10], ow, fma(p.m[9], oh, p.m[8] * od)) + p.m[11];
+      if (sd >= -0.5 && sd <= (double)p.Ds - 0.5 && sh >= -0.5 && sh <= (double)p.Hs - 0.5 && sw >= -0.5 && sw <= (double)p.Ws - 0.5) {
+        const double fd = floor(sd), fh = floor(sh), fw = floor(sw);
+        const int id[2] = {rs_reflect((int)fd, p.Ds), rs_reflect((int)fd + 1, p.Ds)};
+        const int ih[2] = {rs_reflect((int)fh, p.Hs), rs_reflect((int)fh + 1, p.Hs)};
+        const int iw[2] = {rs_reflect((int)fw, p.Ws), rs_reflect((int)fw + 1, p.Ws)};
+        const double wd[2] = {1.0 - (sd - fd), sd - fd}, wh[2] = {1.0 - (sh - fh), sh - fh}, ww[2] = {1.0 - (sw - fw), sw - fw};
+        float val[8];
+        double wt[8];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const float* row = p.lab + ((long)id[a] * p.Hs + ih[b]) * p.Ws;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              val[4 * a + 2 * b + k] = row[iw[k]];
+              wt[4 * a + 2 * b + k] = wd[a] * wh[b] * ww[k];
+            }
+          }
+        double best = -1.0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          double sum = 0.0;
+#pragma unroll
+          for (int u = 0; u < 8; ++u) sum += val[u] == val[t] ? wt[u] : 0.0;
+          if (sum > best || (sum == best && val[t] < res)) {
+            best = sum;
+            res = val[t];
+          }
+        }
+      }
+    }
+    p.dst[i] = res;
+  }
+}
+
+extern "C" int bts_label_resample3d(const float* lab, int Ds, int Hs, int Ws, float* dst, int Do, int Ho, int Wo, int Dp, int Hp, int Wp,
+                                    const double* m12, hipStream_t stream) {
+  if (Ds < 1 || Hs < 1 || Ws < 1 || Do < 1 || Ho < 1 || Wo < 1) return BTS_ERR_SHAPE;
+  if (Dp < Do || Hp < Ho || Wp < Wo) return BTS_ERR_SHAPE;
+  if (lab == nullptr || dst == nullptr || m12 == nullptr || lab == dst) return BTS_ERR_SHAPE;
+  if (((uintptr_t)lab | (uintptr_t)dst) & 3) return BTS_ERR_ALIGN;
+  LabelParams p;
+  p.lab = lab; p.dst = dst;
+  p.Ds = Ds; p.Hs = Hs; p.Ws = Ws; p.Do = Do; p.Ho = Ho; p.Wo = Wo; p.Dp = Dp; p.Hp = Hp; p.Wp = Wp;
+  for (int k = 0; k < 12; ++k) p.m[k] = m12[k];
+  const long total = (long)Dp * Hp * Wp;
+  long blocks = (total + 255) / 256;
+  if (blocks > 262144) blocks = 262144;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(cf_label_kernel, dim3(blocks), dim3(256), 0, stream, p);
+  BTS_LAUNCH_CHECK();
+  return BTS_OK;
 }

@@ -30,8 +30,8 @@ from .pointwise import (add_strided, axpy, dense_bwd, dense_fwd, dropout_apply, 
                         normal, relu_bwd, scalar_lincomb, sigmoid_bwd, upsample2_bwd, upsample2_fwd, vae_sample_bwd, vae_sample_fwd)
 from .loss import (adam_tf_step, dice_metric_sums, dice_metric_value, grad_nonfinite, l2_reg_bwd, l2_reg_fwd, loss_bwd, loss_sums,      # noqa: F401
                    loss_value, seg_loss_bwd, seg_loss_sums, seg_loss_value)
-from .volume import (UNCERTAINTY_MODES, affine_resample3d, ensemble_update, flip_affine, reorient3d, skull_strip, spline_prefilter3d,      # noqa: F401
-                     tta_finish, uncertainty_finish, zoom3d)
+from .volume import (UNCERTAINTY_MODES, affine_resample3d, ensemble_update, flip_affine, label_resample3d, reorient3d, skull_strip,      # noqa: F401
+                     spline_prefilter3d, tta_finish, uncertainty_finish, zoom3d)
 from .window import window_accumulate, window_batch_max, window_gather, window_occupancy      # noqa: F401
 from .score import (UNCERTAINTY_LEVELS, component_boxes, component_largest, component_sizes, components3d, components_apply, dilate3d, edt3d_sq,      # noqa: F401
                     label_confusion, lesion_crop, lesion_pairs, lesion_pairs_capacity, masked_select, region_relabel, region_surface,

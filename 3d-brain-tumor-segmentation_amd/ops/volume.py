@@ -155,6 +155,27 @@ def affine_resample3d(coef, matrix, out_shape, order=3, pad_to=None, out=None, c
     return (out, mask) if want_mask else out
 
 
+def label_resample3d(y, matrix, out_shape, pad_to=None, out=None):
+    """a label map through `matrix` (as affine_resample3d takes it): y, dense float32 (D,H,W) or (D,H,W,1) of label values (any finite
+    values), read at the source voxel coordinate matrix @ (o0, o1, o2, 1) of every voxel of a grid of extent out_shape.  The 8 taps of
+    order 1 vote with their float64 weights: the value with the largest summed weight wins, of exactly equal weights the smallest value
+    -- the arg-max over classes of each class indicator interpolated linearly, in one gather.  0 outside the source's field of view
+    [-0.5, n - 0.5] and in the padding of pad_to >= out_shape.  out: a dense float32 (pad_to, 1) volume to write into
+    -> (pad_to or out_shape) + (1,) float32   [csrc/conform.hip]"""
+    f32 = torch.float32
+    _core.dense(y, f32, 'label_resample3d: y')
+    if y.dim() not in (3, 4) or (y.dim() == 4 and y.shape[3] != 1) or y.numel() == 0:
+        raise ValueError('label_resample3d: y must have shape (D,H,W) or (D,H,W,1), got %s' % (tuple(y.shape),))
+    (do, ho, wo), (dp, hp, wp) = _core.grid('label_resample3d', out_shape, pad_to, 0)
+    m12, _ = _core.matrix12(matrix, 'label_resample3d: matrix')
+    d, h, w = (int(v) for v in y.shape[:3])
+    given, out = out is not None, _core.out_or_new(out, (dp, hp, wp, 1), f32, y.device, 'label_resample3d: out')
+    if given and out.data_ptr() == y.data_ptr():
+        raise ValueError('label_resample3d: out must not be y')
+    _core.lib().call('bts_label_resample3d', _core._p(y), d, h, w, _core._p(out), do, ho, wo, dp, hp, wp, m12, _core._stream())
+    return out
+
+
 def skull_strip(x, p, m, orig, pad_to, out=None):
     """x (Da,Ha,Wa,C), p and m (Da,Ha,Wa,1) dense float32; orig = the unpadded extent (D,H,W); pad_to = (Db,Hb,Wb) >= orig
     -> (xo (Db,Hb,Wb,C) = x * (1 - p) inside orig, 0 outside; mo (Db,Hb,Wb,1) = m inside, 0 outside)   [test.py:244-254]

@@ -58,6 +58,13 @@ the header says; one more line per case and modality prints the six parameters, 
 `mask.nii`, the truth check and every score are as with --conform alone: they belong to the first modality, which is not moved.  Without
 --conform the modalities are stacked voxel for voxel and there is no affine to correct: --coregister is then refused.
 
+Recorded geometry: where the tumour stage's prepro.npy records a `geometry` (`python -m bts_amd.preprocess --conform` wrote it: the examples
+the model was trained on were conformed by their headers), every scan is conformed to the recorded orientation code without any flag
+here, and co-registered first with the recorded bounds where it records them (`geometry_rule`, `preprocess.load_geometry`); one line at
+the start says so.  --conform CODE and --coregister with its bounds win over the record, a code other than the recorded one gets one
+warning line, and the dumps of an ensemble must record the same geometry (a refusal names the member).  The truth rule of --conform is
+the same either way.  A prepro.npy without the entry changes nothing.
+
 Bias-field correction: where the tumour stage's prepro.npy records a `bias` spec (`python -m bts_amd.preprocess --bias_correct` wrote it),
 or with --bias_correct, every modality of every case is corrected once by N4 on its own positive voxels right after upload
 (`n4.correct`, csrc/n4.hip), before --coregister, --conform, the Interpolator and both model stages.  --bias_shrink, --bias_levels,
@@ -110,7 +117,8 @@ from . import coreg, n4, nifti
 from .infer import (BRATS_REGIONS, UNCERTAINTY_MODES, UNCERTAINTY_SCORE_KEYS, WINDOW_MODES, Conformer, Interpolator, StageEnsemble, StageSpec, WindowSpec,
                     label_scores, lesionwise_scores, region_rates_from_confusion, scores_from_confusion, segment_case, surface_scores,
                     uncertainty_channels, uncertainty_scores, zoom_output_shape)
-from .preprocess import add_bias_flags, bias_spec, load_bias, load_norm
+from .preprocess import (COREGISTER_DEFAULTS, add_bias_flags, add_geometry_flags, bias_spec, check_geometry_flags,      # noqa: F401
+                         code_arg as _code_arg, coregister_kwargs, load_bias, load_geometry, load_norm, truth_grid_shift)
 from .train import load_checkpoint, load_train_args
 
 N_CLASSES = 4        # background + the three BraTS labels 1, 2, 4 (4 counts as class 3, preprocess.py:36)
@@ -122,7 +130,6 @@ LESION_COUNT_KEYS = tuple('lw_%s_%s' % (what, name) for what in ('lesions', 'fn'
 LESION_KEYS = LESION_SCORE_KEYS + LESION_COUNT_KEYS      # the columns --lesionwise appends to scores.csv, after the others
 LESION_DEFAULTS = {'lesion_dilation': 3, 'lesion_min_voxels': 50, 'lesion_penalty_mm': 374.0}
 WINDOW_DEFAULTS = {'window_overlap': 0.5, 'window_mode': 'gaussian', 'window_batch': None}
-COREGISTER_DEFAULTS = {'coregister_max_mm': 30.0, 'coregister_max_deg': 20.0, 'coregister_bins': 32}
 
 
 UNCERTAINTY_FILE_NAMES = {'regions': ('wt', 'tc', 'et'), 'labels': ('1', '2', '4')}      # unc_<name>.nii per channel of the map
@@ -155,15 +162,6 @@ def _window_arg(text):
     if len(roi) != 3 or min(roi) < 1:
         raise argparse.ArgumentTypeError("expected D,H,W (three positive integers) or 'crop', got %r" % (text,))
     return roi
-
-
-def _code_arg(text):
-    """--conform: an orientation code, one letter from each of R/L, A/P, S/I"""
-    try:
-        nifti.reorientation(text.upper(), text.upper())
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text.upper()
 
 
 def arg_parser():
@@ -216,18 +214,9 @@ def arg_parser():
                    help='Importance of a voxel inside its window (default: %s).' % WINDOW_DEFAULTS['window_mode'])
     p.add_argument('--window_batch', type=int, default=argparse.SUPPRESS,
                    help='Windows and augmented copies per forward (default: as --tta_batch).')
-    # and --conform: absent, the namespace has no such attribute and nothing changes
-    p.add_argument('--conform', type=_code_arg, nargs='?', const='LPS', default=argparse.SUPPRESS, metavar='CODE',
-                   help='Bring every modality onto one 1 mm grid of this orientation by its affine (default code: LPS), and the labels back.')
-    # and --coregister with its bounds: `coregister_kwargs` supplies COREGISTER_DEFAULTS
-    p.add_argument('--coregister', action='store_true', default=argparse.SUPPRESS,
-                   help='With --conform: register every modality to the first by mutual information and correct its affine.')
-    p.add_argument('--coregister_max_mm', type=float, default=argparse.SUPPRESS,
-                   help='Largest translation searched per axis, mm (default: %g).' % COREGISTER_DEFAULTS['coregister_max_mm'])
-    p.add_argument('--coregister_max_deg', type=float, default=argparse.SUPPRESS,
-                   help='Largest rotation searched per axis, degrees (default: %g).' % COREGISTER_DEFAULTS['coregister_max_deg'])
-    p.add_argument('--coregister_bins', type=int, default=argparse.SUPPRESS,
-                   help='Intensity bins per modality of the joint histogram, 2..64 (default: %d).' % COREGISTER_DEFAULTS['coregister_bins'])
+    # and --conform, and --coregister with its bounds, the ones of `python -m bts_amd.preprocess`: absent, the namespace has no such
+    # attribute and nothing changes; `coregister_kwargs` supplies COREGISTER_DEFAULTS
+    add_geometry_flags(p)
     # and --uncertainty: absent, no map is computed and no file written
     p.add_argument('--uncertainty', type=str, choices=UNCERTAINTY_MODES, default=argparse.SUPPRESS,
                    help='Also write unc_<name>.nii, levels 0..100 per voxel: the entropy of the mean probability, or the deviation '
@@ -250,16 +239,7 @@ def parse_args(argv=None):
         parser.error('--window_overlap must lie in [0, 1)')
     if getattr(args, 'window_batch', 1) < 1:
         parser.error('--window_batch must be positive')
-    if hasattr(args, 'coregister') and not hasattr(args, 'conform'):
-        parser.error('--coregister needs --conform: without it the modalities are stacked voxel for voxel and there is no affine to correct')
-    if not hasattr(args, 'coregister') and any(hasattr(args, k) for k in COREGISTER_DEFAULTS):
-        parser.error('--coregister_max_mm, --coregister_max_deg and --coregister_bins need --coregister')
-    if not 0 < getattr(args, 'coregister_max_mm', 30.0) < float('inf'):
-        parser.error('--coregister_max_mm must be positive')
-    if not 0 < getattr(args, 'coregister_max_deg', 20.0) <= 180:
-        parser.error('--coregister_max_deg must lie in (0, 180]')
-    if not 2 <= getattr(args, 'coregister_bins', 32) <= 64:
-        parser.error('--coregister_bins must lie in 2..64')
+    check_geometry_flags(args, parser)
     bias_spec(args, parser)
     models, prepros = tumor_models(args), [f for f in args.tumor_prepro.split(',') if f]
     if not models:
@@ -330,17 +310,6 @@ def decode_case(path, modalities, truth, conform=False):
     if conform:
         out['affines'] = best
     return out
-
-
-def truth_grid_shift(shape, affine, truth_shape, truth_affine):
-    """how far, in voxels along any axis, the truth volume's affine moves a corner of the reference grid from where the reference's own
-    puts it; None when the shapes differ"""
-    if tuple(int(v) for v in shape) != tuple(int(v) for v in truth_shape):
-        return None
-    n = [float(int(v) - 1) for v in shape]
-    corners = np.array([[a, b, c, 1.0] for a in (0.0, n[0]) for b in (0.0, n[1]) for c in (0.0, n[2])], dtype=np.float64).T
-    moved = np.linalg.inv(np.asarray(affine, dtype=np.float64)) @ np.asarray(truth_affine, dtype=np.float64) @ corners
-    return float(np.abs(moved[:3] - corners[:3]).max())
 
 
 def upload_conform_case(case, dev):
@@ -427,14 +396,6 @@ def window_kwargs(args):
             'batch': getattr(args, 'window_batch', WINDOW_DEFAULTS['window_batch'])}
 
 
-def coregister_kwargs(args):
-    """None without --coregister, else the keyword arguments of coreg.coregister_case"""
-    if not getattr(args, 'coregister', False):
-        return None
-    v = {k: getattr(args, k, d) for k, d in COREGISTER_DEFAULTS.items()}
-    return {'bounds': (float(v['coregister_max_mm']), float(v['coregister_max_deg'])), 'bins': int(v['coregister_bins'])}
-
-
 def bias_rule(args):
     """-> the n4.N4Spec every modality of every case is corrected with right after upload, or None: the spec the tumour stage's
     prepro.npy records (its examples were corrected, so its scans must be), or --bias_correct with its sub-flags, which replace the
@@ -447,6 +408,40 @@ def bias_rule(args):
                if hasattr(args, 'bias_correct') else 'recorded by %s' % prepro)
         print('Bias-field correction ({}): {}'.format(why, ', '.join('%s %s' % kv for kv in n4.spec_record(spec).items())), flush=True)
     return spec
+
+
+def geometry_rule(args):
+    """-> (orientation code or None, keyword arguments of coreg.coregister_case or None): how every case is conformed.  Where the tumour
+    stage's prepro.npy records a geometry (`python -m bts_amd.preprocess --conform` wrote it: its examples were conformed, so its scans must
+    be), that code and, where it records one, that co-registration apply without any flag, and one line says so.  --conform CODE and
+    --coregister with its bounds win over the record; a code that differs from the recorded one gets one warning line.  The dumps of an
+    ensemble must record the same geometry: ValueError naming the member.  No record and no flag: (None, None), and nothing changes"""
+    prepros, models = tumor_prepros(args), tumor_models(args)
+    records = [load_geometry(f) if os.path.isfile(f) else None for f in prepros]      # a missing dump is load_stage's to report
+    for folder, f, rec in zip(models[1:], prepros[1:], records[1:]):
+        if rec != records[0]:
+            raise ValueError('%s: %s records the geometry %s, the first member\'s %s records %s: the members of an ensemble must see '
+                             'the scan on one grid' % (folder, f, _geometry_text(rec), prepros[0], _geometry_text(records[0])))
+    recorded = records[0]
+    code = getattr(args, 'conform', None)
+    if recorded is None:
+        return code, coregister_kwargs(args)
+    registering = coregister_kwargs(args, recorded.coregister)
+    if code is None:
+        print('Geometry (recorded by {}): {}'.format(prepros[0], _geometry_text(recorded._replace(coregister=registering))), flush=True)
+        return recorded.orientation, registering
+    if code != recorded.orientation:
+        print('Warning: --conform {} over the record of {}, whose examples were conformed to {}'.format(code, prepros[0], recorded.orientation),
+              flush=True)
+    return code, registering
+
+
+def _geometry_text(spec):
+    if spec is None:
+        return 'none'
+    reg = spec.coregister
+    return 'conform to %s at 1 mm%s' % (spec.orientation, '' if reg is None else ', co-register within %g mm and %g degrees on %d bins' % (
+        reg['bounds'][0], reg['bounds'][1], reg['bins']))
 
 
 def print_bias(name, modalities, results):
@@ -494,9 +489,11 @@ def mean_finite(values):
     return float(np.mean(vals)) if vals else float('nan')
 
 
-def _decoded(cases, args):
-    """the decoded cases in order; with workers > 0 a bounded number of them is decoded ahead by host threads"""
-    conform = getattr(args, 'conform', None) is not None
+def _decoded(cases, args, conform=None):
+    """the decoded cases in order; with workers > 0 a bounded number of them is decoded ahead by host threads.  conform: do the headers
+    decide (default: as --conform says)"""
+    if conform is None:
+        conform = getattr(args, 'conform', None) is not None
     if args.workers <= 0:
         for _, path in cases:
             yield decode_case(path, args.modalities, args.truth, conform)
@@ -528,13 +525,13 @@ def run(args):
     lesion = lesion_kwargs(args)
     lesionwise = lesion is not None
     windowed = window_kwargs(args) is not None
-    conf = Conformer(args.conform, (1.0, 1.0, 1.0), args.order) if getattr(args, 'conform', None) is not None else None
-    registering = coregister_kwargs(args)
+    code, registering = geometry_rule(args)
+    conf = Conformer(code, (1.0, 1.0, 1.0), args.order) if code is not None else None
     bias = bias_rule(args)
     unc_mode, unc_keys = getattr(args, 'uncertainty', None), ()
     total = np.zeros((N_CLASSES, N_CLASSES), dtype=np.int64)
     t0 = time.time()
-    for (name, path), case in zip(cases, _decoded(cases, args)):
+    for (name, path), case in zip(cases, _decoded(cases, args, conf is not None)):
         if 'missing' in case:
             print('{}: no *{}*.nii* file, case skipped'.format(name, case['missing']), flush=True)
             skipped.append((name, case['missing']))

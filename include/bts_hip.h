@@ -338,6 +338,16 @@ int bts_reorient3d(const float* src, float* dst, int D, int H, int W, int C, int
  * present, with nothing launched. */
 int bts_affine_resample3d(const float* coef, int Ds, int Hs, int Ws, int C, float* dst, int ld_dst, int c0, float* bmask, int Do, int Ho,
                           int Wo, int Dp, int Hp, int Wp, const double* m12, int order, bts_stream_t stream);
+/* A label map through a general affine (python -m bts_amd.preprocess --conform): lab is a dense fp32 (Ds,Hs,Ws) volume of label values
+ * (any finite values), dst a dense fp32 (Dp,Hp,Wp) one.  Per output voxel inside (Do,Ho,Wo): s = m12 (o0,o1,o2,1) as
+ * bts_affine_resample3d forms it; 0 where s lies outside [-0.5, n - 0.5] on any axis or is not finite; else the 8 taps of order 1
+ * (floor(s), floor(s) + 1 per axis, reflected; fp64 weights (wd * wh) * ww, row-major tap order) vote: a value's weight is the sum, in
+ * tap order, of the weights of the taps that hold it, the value with the largest weight wins and, of exactly equal weights, the smallest
+ * value.  This is the arg-max over classes of each class indicator interpolated linearly, in one gather, for any set of values.  The
+ * voxels outside (Do,Ho,Wo) are 0.  No atomics, no workspace: deterministic.  BTS_ERR_SHAPE for an extent < 1, Dp < Do (and so on), a
+ * NULL lab, dst or m12, or lab == dst; BTS_ERR_ALIGN for a pointer off a float's alignment; with nothing launched. */
+int bts_label_resample3d(const float* lab, int Ds, int Hs, int Ws, float* dst, int Do, int Ho, int Wo, int Dp, int Hp, int Wp,
+                         const double* m12, bts_stream_t stream);
 
 /* ===== segmenting a folder of scans end to end (test.py:181-270: main) =====
  * The skull-stripping hand-over between the two models (test.py:244-254: invert, multiply, slice, pad again) in one pass.
